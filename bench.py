@@ -12,7 +12,11 @@ ccsd_amd.loader.load_sampling_fn, i.e. prior draw (ccsd_init_state), K PC steps,
 all-gather of the samples, device-synchronised.  Checkpoint load, plan creation and quantisation are outside,
 as they are in the reference.
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--workload qm9_CC|community_small_CC|...]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--workload qm9_CC|community_small_CC|...] [--dump-outputs DIR] [--full]
+A plain run sets up, warms up, times the K steps and prints the result line; `--full` adds what the headline figure does not
+need: the kernel-event pass (the `roofline*` objects) and the CPU baseline.  `--dump-outputs DIR` writes the samples the timed
+region's last sampler call returned (DIR/x.npy, adj.npy[, rank2.npy], float32; a fixed seeded sample of the complexes when the
+whole batch exceeds the size cap); with the same arguments the inputs are the same in every run.
 `--gpus N` (N > 1) without a launcher starts N fresh worker processes itself (torch.distributed.run on
 127.0.0.1, before this process touches a GPU) and relays rank 0's JSON line; under torch.distributed.run it
 is a rank.  The batch dimension is sharded (weak scaling, 1024 complexes per rank, per-shard Langevin norms
@@ -83,6 +87,8 @@ VALU_ISSUE_CYCLES = 2.65
 KERNEL_NAMES = ["k_xa", "k_r2", "k_hf_score", "k_gemm_h", "k_gemm_p", "k_langevin_apply", "k_s4_apply", "k_ew1"]
 MFMA_F32_FLOP_PER_BUSY_CYCLE = 64                         # 2048 FLOP / 32 cycles (16x16x4) = 512 FLOP / 8 cycles (4x4x1 16B): both fp32 shapes
 WARMUP_MIN_SECONDS = 0.25                                 # the warm-up call is repeated until the device has been busy this long
+DUMP_BUDGET_BYTES = 60_000_000                            # --dump-outputs: all arrays together stay below 64 MB
+DUMP_SAMPLE_SEED = 0                                      # --dump-outputs: seed of the complex sample taken above the budget
 
 
 def pmc_files():
@@ -361,7 +367,42 @@ def parse_args(argv=None):
     ap.add_argument("--emulate", action="store_true",
                     help="TEST ONLY: run the product code over the host emulation of the kernels on the CPU with gloo (exercises the launcher / "
                          "sharding / reporting path on a GPU-less box; the numbers mean nothing)")
-    return ap.parse_args(argv)
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline figure does not need: the kernel-event pass after the timed region (roofline "
+                         "objects; --no-kernel-events drops it) and, on one GPU, the CPU baseline (--no-cpu-baseline drops it)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the samples of the timed region's last sampler call to DIR/<name>.npy (float32; a fixed seeded sample "
+                         f"of the complexes when the whole batch exceeds {DUMP_BUDGET_BYTES // 10**6} MB)")
+    args = ap.parse_args(argv)
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
+
+
+def dump_outputs(out_dir: str, names, tensors):
+    """Write the sampler's output tensors as <out_dir>/<name>.npy (float32, or float64 where the tensor is).  When the whole
+    batch exceeds DUMP_BUDGET_BYTES, the same fixed seeded sample of complexes (batch rows, in batch order) is taken from every
+    tensor.  Returns what the result line reports about the dump."""
+    import numpy as np
+    import torch
+
+    os.makedirs(out_dir, exist_ok=True)
+    total = tensors[0].shape[0]
+    per_complex = sum(t[0].numel() * (8 if t.dtype == torch.float64 else 4) for t in tensors)
+    keep = min(total, DUMP_BUDGET_BYTES // per_complex)
+    idx = None
+    if keep < total:
+        idx = np.sort(np.random.RandomState(DUMP_SAMPLE_SEED).choice(total, keep, replace=False))
+    shapes = {}
+    for name, t in zip(names, tensors):
+        if idx is not None:
+            t = t[torch.from_numpy(idx).to(t.device)]
+        a = t.detach().cpu().numpy()
+        a = a.astype(np.float64 if a.dtype == np.float64 else np.float32, copy=False)
+        np.save(os.path.join(out_dir, f"{name}.npy"), a)
+        shapes[name] = list(a.shape)
+    return {"dir": out_dir, "arrays": shapes, "complexes": keep, "of": total,
+            "sample": None if idx is None else f"np.random.RandomState({DUMP_SAMPLE_SEED}).choice({total}, {keep}, replace=False), sorted"}
 
 
 def main():
@@ -486,6 +527,9 @@ def _main(real_stdout):
     MERGED_R2 = bool(eng.query("merged_r2"))
     if world > 1:
         sampling_fn.timing, sampling_fn.gather_seconds = True, 0.0   # split [local loop | final all-gather] per rank (diagnostic)
+    # the closure keys its Philox draws by its call count, and the number of warm-up calls depends on how fast they ran: counting
+    # from 0 again gives the timed region the same priors and noise in every run with the same arguments
+    inner.calls = 0
     # ---- the timed region: exactly K steps, un-instrumented (no HIP events between the dispatches)
     sync()
     t0 = time.perf_counter()
@@ -495,10 +539,15 @@ def _main(real_stdout):
     dt_local = time.perf_counter() - t0                              # this rank's own time, before it waits for the others
     sync()
     dt = time.perf_counter() - t0
-    # ---- kernel-event pass, AFTER the timed region (an event record between two dispatches breaks back-to-back issue: dense
-    # bracketing costs ~6 % of the step): the same steps again (at most 200) with every n-th launch of a kernel bracketed
+    nt = 3 if is_cc else 2
+    dump = None
+    if args.dump_outputs and rank == 0:
+        dump = dump_outputs(args.dump_outputs, names, outs[:nt])
+    # ---- kernel-event pass (--full), AFTER the timed region (an event record between two dispatches breaks back-to-back issue:
+    # dense bracketing costs ~6 % of the step): the same steps again (at most 200) with every n-th launch of a kernel bracketed
+    kernel_events = args.full and not args.no_kernel_events
     ksteps = 0
-    if not args.no_kernel_events:
+    if kernel_events:
         for kname in KERNEL_NAMES:                   # HIP events around those kernels' launches, on their stream
             eng.profile_kernel(kname)
         ksteps = min(args.steps, 200)
@@ -526,13 +575,12 @@ def _main(real_stdout):
             f"{sampling_fn.gather_seconds * 1e3:.2f} ms")
     log(f"timed region: {args.steps} steps in {dt:.3f} s")
     ktimes = {}
-    if not args.no_kernel_events:
+    if kernel_events:
         for k in KERNEL_NAMES:
             tot = eng.profile_launches(k)
             n, ms = eng.profile_read(k)
             ktimes[k] = (n, ms, tot, ksteps)
         eng.profile_kernel(None)
-    nt = 3 if is_cc else 2
     ok = all(torch.isfinite(t).all().item() for t in outs[:nt]) and all(t.shape[0] == total for t in outs[:nt])
 
     if rank == 0:
@@ -558,6 +606,8 @@ def _main(real_stdout):
         }
         if per_rank is not None:     # per-rank split of the timed region: PC-step time without the final all-gather, and the all-gather
             line["per_rank"] = per_rank
+        if dump is not None:
+            line["dump_outputs"] = dump
         if args.emulate:
             line["data"] = "EMULATION (host CPU, test of the launcher path only): " + line["data"]
         for k in live[1:]:
@@ -565,7 +615,7 @@ def _main(real_stdout):
         if wl["flop_x"] is not None:
             line["achieved_model_tflops"] = evals * (wl["flop_x"] + wl["flop_a"] + wl["flop_f"]) * units_per_s / 1e12
         line["achieved_state_gbps"] = 2 * evals * state_floats * 4 * units_per_s / 1e9
-        if world == 1 and not args.no_cpu_baseline and not args.emulate:
+        if args.full and world == 1 and not args.no_cpu_baseline and not args.emulate:
             line["cpu_baseline"] = cpu_baseline(wname, B)
             line["speedup_vs_cpu_baseline"] = value / line["cpu_baseline"]["value"]
         print(json.dumps(line), file=real_stdout, flush=True)

@@ -5,12 +5,12 @@ pair the reference's load_model_from_ckpt builds a model from (ccsd/src/utils/lo
 * duck-typed stand-ins (always run): plain objects that carry exactly the attributes the reference constructors store
   (ScoreNetwork_X.py:47-51, ScoreNetwork_A_CC.py:83-106, ScoreNetwork_F.py:64-76) and a state_dict(), inside a
   DataParallel-like wrapper;
-* the real thing (build container only, skipped where /root/reference is absent): modules built by the reference's own
-  load_model_from_ckpt, handed unchanged to this package's get_pc_sampler.
+* the reference's own description: torch.nn.Modules with the class names, constructor attributes and state_dict keys that
+  the reference's load_model_from_ckpt gives them (recorded in tests/golden/reference_module_objects.json), the adjacency
+  network inside torch.nn.DataParallel, handed unchanged to this package's get_pc_sampler.
 Both run the product code over the host emulation of the kernels and must reproduce the reference goldens."""
 import json
 import os
-import sys
 
 import numpy as np
 import pytest
@@ -103,25 +103,40 @@ def test_sampler_accepts_duck_typed_reference_modules():
                         lambda meta, parts, names: [_stand_in(meta[f"params_{p}"], parts[p]) for p in names])
 
 
-@pytest.mark.skipif(not os.path.isdir("/root/reference/ccsd"), reason="the upstream reference is only present in the build container")
+def _reference_module(desc, weights):
+    """A torch.nn.Module as the reference's load_model_from_ckpt returns it (tests/golden/reference_module_objects.json, recorded
+    from that function by tools/make_golden.py::reference_module_objects): the reference's class name, the plain attributes its
+    constructor stores, and the checkpoint's weights as parameters under the reference's state_dict keys."""
+    m = type(desc["class"], (torch.nn.Module,), {})()
+    for a, v in desc["attributes"].items():
+        setattr(m, a, v)
+    for key, kind in desc["state_dict"]:
+        assert kind == "parameter", (key, kind)
+        owner, *path = [m] + key.split(".")
+        for part in path[:-1]:
+            if not hasattr(owner, part):
+                owner.add_module(part, torch.nn.Module())
+            owner = getattr(owner, part)
+        owner.register_parameter(path[-1], torch.nn.Parameter(weights[key].detach().clone()))
+    assert list(m.state_dict()) == [k for k, _ in desc["state_dict"]]
+    return m
+
+
 def test_sampler_accepts_the_reference_own_modules():
-    sys.path.insert(0, os.path.join(ROOT, "tools"))
-    import refshim
+    """torch.nn.Modules of the reference's own description, the adjacency network inside torch.nn.DataParallel."""
+    with open(os.path.join(ROOT, "tests", "golden", "reference_module_objects.json")) as f:
+        recorded = json.load(f)
 
-    refshim.install()
-    from ccsd.src.utils import cc_utils as ref_cc
-    from ccsd.src.utils import loader as ref_loader
+    def make_for(ckpt):
+        def make(meta, parts, names):
+            ms = []
+            for p in names:
+                m = _reference_module(recorded[ckpt][p], parts[p])
+                assert not hasattr(m, "params")
+                ms.append(m)
+            ms[1] = torch.nn.DataParallel(ms[1])   # loader.py:649-650 wraps on multi-GPU hosts
+            return ms
+        return make
 
-    def make(meta, parts, names):
-        ref_cc.default_mask.cache_clear()      # see tools/make_golden.py::build_models
-        ms = []
-        for p in names:
-            sd = {k: v.detach() for k, v in parts[p].items()}
-            m = ref_loader.load_model_from_ckpt(refshim.EasyDict(meta[f"params_{p}"]), sd, "cpu")
-            assert isinstance(m, torch.nn.Module) and not hasattr(m, "params")
-            ms.append(m)
-        ms[1] = torch.nn.DataParallel(ms[1])   # loader.py:649-650 wraps on multi-GPU hosts
-        return ms
-
-    _run_against_golden("ccsd_qm9_CC", "ccsd_qm9_CC", "k10", make)
-    _run_against_golden("ccsd_qm9_Base_CC", "ccsd_qm9_Base_CC", "n1000_first3", make)
+    _run_against_golden("ccsd_qm9_CC", "ccsd_qm9_CC", "k10", make_for("ccsd_qm9_CC"))
+    _run_against_golden("ccsd_qm9_Base_CC", "ccsd_qm9_Base_CC", "n1000_first3", make_for("ccsd_qm9_Base_CC"))

@@ -662,6 +662,33 @@ def reference_variant_status():
         print("variant", k, v["result"], v.get("type", ""), v.get("message", v.get("shape")))
 
 
+def reference_module_objects():
+    """What the reference's own load_model_from_ckpt (loader.py:619-657) returns for the checkpoints the seam test feeds it
+    (tests/test_seam_modules.py): per model the class name, the plain attributes its constructor stores, and the state_dict
+    keys with the kind of tensor behind each.  The test rebuilds torch.nn.Modules of that description around the checkpoint's
+    weights, so it runs without the reference."""
+    out = {}
+    for name in ("ccsd_qm9_CC", "ccsd_qm9_Base_CC"):
+        with open(os.path.join(CKPT, name + ".json")) as f:
+            meta = json.load(f)
+        z = np.load(os.path.join(CKPT, name + ".npz"))
+        out[name] = {}
+        for p in ("x", "adj", "rank2"):
+            sd = {k.split("/", 1)[1]: torch.from_numpy(z[k]) for k in z.files if k.startswith(p + "/")}
+            ref_cc.default_mask.cache_clear()          # see build_models
+            m = ref_loader.load_model_from_ckpt(refshim.EasyDict(meta[f"params_{p}"]), sd, "cpu")
+            params, buffers = dict(m.named_parameters()), dict(m.named_buffers())
+            out[name][p] = {
+                "class": type(m).__name__,
+                "attributes": {k: v for k, v in vars(m).items()
+                               if not k.startswith("_") and k != "training" and isinstance(v, (bool, int, float, str))},
+                "state_dict": [[k, "parameter" if k in params else "buffer" if k in buffers else "other"] for k in m.state_dict()],
+            }
+    with open(os.path.join(GOLD, "reference_module_objects.json"), "w") as f:
+        json.dump(out, f, indent=1)
+    print("reference_module_objects", {n: {p: d["class"] for p, d in v.items()} for n, v in out.items()})
+
+
 def kat_reference_held():
     """The known-answer vectors the REFERENCE'S OWN TESTS hold for the path (tests/models/test_ScoreNetwork_A_CC.py:119-162,
     test_ScoreNetwork_A_Base_CC.py:115-158, test_ScoreNetwork_F.py:69-106, test_hodge_attention.py:96-209, test_hodge_layers.py:143-375)
@@ -872,6 +899,8 @@ def main():
         kat_reference_held()
     if not only or "variants" in only:
         reference_variant_status()
+    if not only or "modules" in only:
+        reference_module_objects()
 
 
 if __name__ == "__main__":
