@@ -690,11 +690,13 @@ def get_pc_sampler(sde_x: SDE, sde_adj: SDE, shape_x, shape_adj, predictor="Eule
                    snr=0.1, scale_eps=1.0, n_steps=1, probability_flow=False, continuous=False, denoise=True,
                    eps=1e-3, is_cc=False, sde_rank2: Optional[SDE] = None, shape_rank2=None,
                    d_min=None, d_max=None, noise: Optional[NoiseSource] = None, keep_traj=True,
-                   n_diff_steps: Optional[int] = None, prior=None, trace: Optional[list] = None):
+                   n_diff_steps: Optional[int] = None, prior=None, trace: Optional[list] = None,
+                   final: Optional[list] = None):
     """Functional restatement of get_pc_sampler.  `nets` passed to the closure are callables
     net(x, adj[, rank2], flags) -> Tensor.  Extra test hooks (not in the reference): `noise`
     (draw source), `n_diff_steps` (stop after that many of the sde_adj.N steps), `prior`
-    (explicit initial state), `trace` (per-step Langevin scalars)."""
+    (explicit initial state), `trace` (per-step Langevin scalars), `final` (a list that receives
+    the sampled state after the last step, whatever `denoise` returns)."""
     if predictor not in ("Reverse", "Euler"):
         raise NotImplementedError(f"Predictor {predictor} not yet supported. Select from [Reverse, Euler].")
     if corrector not in ("Langevin", "None"):
@@ -744,6 +746,8 @@ def get_pc_sampler(sde_x: SDE, sde_adj: SDE, shape_x, shape_adj, predictor="Eule
                     trace.append(tr)
                 if keep_traj:
                     traj.append([(m if denoise else s)[0].detach().clone() for m, s in zip(means, state)])
+            if final is not None:
+                final[:] = state
             out = means if denoise else state
             return (*out, diff_steps * (n_steps + 1), traj)
 
@@ -756,11 +760,13 @@ def get_pc_sampler(sde_x: SDE, sde_adj: SDE, shape_x, shape_adj, predictor="Eule
 def S4_solver(sde_x: SDE, sde_adj: SDE, shape_x, shape_adj, predictor="None", corrector="None", snr=0.1, scale_eps=1.0,
               n_steps=1, probability_flow=False, continuous=False, denoise=True, eps=1e-3, is_cc=False,
               sde_rank2: Optional[SDE] = None, shape_rank2=None, d_min=None, d_max=None,
-              noise: Optional[NoiseSource] = None, keep_traj=True, n_diff_steps: Optional[int] = None):
+              noise: Optional[NoiseSource] = None, keep_traj=True, n_diff_steps: Optional[int] = None, prior=None,
+              final: Optional[list] = None):
     """Functional restatement of S4_solver: per step one joint score evaluation, Sdrift = -g(t)^2 score
     (solver.py:1290-1294, 1436-1444), a Langevin-style correction per target with the alpha index taken from sde_x
     (:1296-1334, :1446-1510), transition(v, t, dt/2) + noise, v += Sdrift*dt, transition(v, t + dt/2, dt/2) + noise
-    (:1337-1352, :1512-1529).  predictor / corrector / n_steps / probability_flow are unused, as in the reference."""
+    (:1337-1352, :1512-1529).  predictor / corrector / n_steps / probability_flow are unused, as in the reference.
+    Test hooks as in get_pc_sampler: `noise`, `n_diff_steps`, `prior` (explicit initial state), `final`."""
     if not continuous:
         raise NotImplementedError("Discrete not supported")
     src = noise or NoiseSource()
@@ -773,9 +779,12 @@ def S4_solver(sde_x: SDE, sde_adj: SDE, shape_x, shape_adj, predictor="None", co
         assert len(nets) == len(sdes)
         fns = [make_score_fn(s, n) for s, n in zip(sdes, nets)]
         with torch.no_grad():
-            state = [sde_x.prior(shape_x), sde_adj.prior_sym(shape_adj)]
-            if is_cc:
-                state.append(sde_rank2.prior(shape_rank2))
+            if prior is not None:
+                state = [p.clone() for p in prior]
+            else:
+                state = [sde_x.prior(shape_x), sde_adj.prior_sym(shape_adj)]
+                if is_cc:
+                    state.append(sde_rank2.prior(shape_rank2))
             flags = init_flags
             state[0] = mask_x(state[0], flags)
             state[1] = mask_adjs(state[1], flags)
@@ -812,6 +821,8 @@ def S4_solver(sde_x: SDE, sde_adj: SDE, shape_x, shape_adj, predictor="None", co
                     means[k] = trans[k][0]
                 if keep_traj:
                     traj.append([(m if denoise else v)[0].detach().clone() for m, v in zip(means, state)])
+            if final is not None:
+                final[:] = state
             out = means if denoise else state
             return (*out, 0, traj)
 

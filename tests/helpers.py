@@ -8,6 +8,8 @@ import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GOLDEN = os.path.join(ROOT, "tests", "golden")
 CKPT = os.path.join(ROOT, "ccsd_amd", "checkpoints")
+# shipped checkpoints the package does not carry: converted weights kept as test fixtures only
+GOLDEN_CKPT = os.path.join(GOLDEN, "ckpt")
 
 
 def load_golden(name):
@@ -15,12 +17,17 @@ def load_golden(name):
 
 
 def load_ckpt_np(name):
-    """Neutral-format checkpoint -> (meta dict, {part: {key: torch tensor}})."""
-    with open(os.path.join(CKPT, name + ".json")) as f:
+    """Neutral-format checkpoint -> (meta dict, {part: {key: torch tensor}}): ccsd_amd/checkpoints/ first, then
+    tests/golden/ckpt/."""
+    d = CKPT if os.path.exists(os.path.join(CKPT, name + ".json")) else GOLDEN_CKPT
+    with open(os.path.join(d, name + ".json")) as f:
         meta = json.load(f)
-    z = np.load(os.path.join(CKPT, name + ".npz"))
+    z = {}
+    for fname in meta.get("files", [name + ".npz"]):          # fixtures: the state dict split into files of at most 1 MiB
+        f = np.load(os.path.join(d, fname))
+        z.update({k: f[k] for k in f.files})
     parts = {}
-    for k in z.files:
+    for k in z:
         part, key = k.split("/", 1)
         # requires_grad mirrors nn.Parameter: ATen's linear() picks the same (non-XNNPACK) CPU kernel as
         # the reference's modules do, which makes the oracle bit-identical to it under torch.no_grad()

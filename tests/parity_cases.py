@@ -85,6 +85,44 @@ def case_forward_vs_reference_golden(name, lib, device):
                 assert_close(out, g[f"unit/score_{p}_t1"], f"{name} score_{p} t=0.5")
 
 
+def _oracle_nets(meta, parts, is_cc, names):
+    if is_cc:
+        return [(lambda x, a, r, f, p=p: O.run_network(meta[f"params_{p}"], parts[p], x, a, r, f)) for p in names]
+    return [(lambda x, a, f, p=p: O.run_network(meta[f"params_{p}"], parts[p], x, a, None, f)) for p in names]
+
+
+def case_forward_vs_oracle(name, lib, device):
+    """G1 for checkpoints whose rank-2 goldens are too large to store whole (ego_small_CC: E = 153, K = 12444; the fixture keeps a
+    hash, a subsample and row sums, which the CPU suite pins the oracle to bit for bit): each network's forward and the score
+    scaling at t = 0.5 on the g1 inputs, against the oracle computed here from the committed weights."""
+    g = load_golden(f"g1_{name}.npz")
+    assert rng_matches(g)
+    eng, meta, parts = engine_from_ckpt(name, lib, device)
+    cfg, is_cc = meta["config"], meta["is_cc"]
+    N, Fd = cfg["data"]["max_node_num"], cfg["data"]["max_feat_num"]
+    d_min, d_max = (cfg["data"]["d_min"], cfg["data"]["d_max"]) if is_cc else (0, 0)
+    names = ["x", "adj"] + (["rank2"] if is_cc else [])
+    nets = _oracle_nets(meta, parts, is_cc, names)
+    flags = torch.from_numpy(g["flags"])
+    B = flags.shape[0]
+    dv = lambda t: None if t is None else t.to(device)
+    for tag, scale in (("unit", 1.0), ("small", 0.3)):
+        x, adj, rank2 = masked_state(int(g["seed"]), B, N, Fd, is_cc, d_min, d_max, flags, scale)
+        assert np.array_equal(x.numpy(), g[f"{tag}/x"]) and np.array_equal(adj.numpy(), g[f"{tag}/adj"])
+        args = (x, adj, rank2, flags) if is_cc else (x, adj, flags)
+        for t, (p, net) in enumerate(zip(names, nets)):
+            with torch.no_grad():
+                want = net(*args)
+            assert_close(eng.score(t, dv(x), dv(adj), dv(rank2), dv(flags)), want, f"{name} {tag} net_{p}")
+            if tag == "unit":
+                sde = loader.load_sde(cfg["sde"][p])
+                tt = torch.ones(B) * 0.5
+                with torch.no_grad():
+                    want = O.make_score_fn(O.load_sde(cfg["sde"][p]), net)(*args, tt)
+                ss = 1.0 if sde.kind == "VE" else float(-1.0 / sde.marginal_prob(torch.zeros(1, 1, 1), tt[:1])[1])
+                assert_close(eng.score(t, dv(x), dv(adj), dv(rank2), dv(flags), ss), want, f"{name} score_{p} t=0.5")
+
+
 def case_model_objects_forward(lib, device):
     """The nn.Module-like objects: ctor kwargs, load_state_dict, forward (reference loader.py:619-657)."""
     meta, parts = load_ckpt_np("ccsd_qm9_CC")
@@ -176,7 +214,15 @@ def sampler_from_golden(g, ckpt, case, lib, device, rng="torch_cpu", shape_overr
 # float64 trajectory between 0.6e-4 and 3.0e-4 at random): the difference is chaotic amplification, not a biased sum.
 # Cross-check in float64 (case_fp64_arbiter / test_fp64_arbiter_*): against the same trajectory computed in float64 the
 # reference's fp32 golden is off by 2.3e-4 (k4) / 1.0e-4 (k20) and the product by 1.5e-4 / 1.3e-4.
-TRAJ_RTOL = {("s4_ccsd_enzymes_small_CC", "k20"): 2e-4, ("s4_ccsd_enzymes_small_CC", "k4"): 5e-4}
+# ccsd_enzymes_small_Base_CC under S4 at 6 scales (its own sample_enzymes_small_Base_CC.yaml settings) is the same mechanism, more
+# strongly amplified: the ScoreNetworkF of the checkpoint is the same cubic form and the A-network's HodgeBaselineLayer feeds the
+# rank-2 state back through tanh(MLP(hodge_adj)) @ rank2.  Measured with the same test: the reference's one-ulp sensitivity on rank2
+# is 5.8e-4 .. 7.8e-4 (median 6.8e-4), so TRAJ_RTOL = 2 x 6.8e-4 ~ 1.4e-3; the product differs from the golden by 1.16e-3.  The
+# float64 arbiter (test_fp64_arbiter_s4_enzymes_base_cc): the fp32 reference is 8.6e-4 from the float64 trajectory on rank2 and
+# the product 7.4e-4 (x: 4.8e-4 both) -- the product is not the further one.  3 of the 94380 rank-2 cells quantise the other way,
+# all within the tolerance of the 0.5 threshold.  Its 1000-scale case agrees to RTOL.
+TRAJ_RTOL = {("s4_ccsd_enzymes_small_CC", "k20"): 2e-4, ("s4_ccsd_enzymes_small_CC", "k4"): 5e-4,
+             ("ccsd_enzymes_small_Base_CC", "k6"): 1.4e-3}
 
 
 @contextlib.contextmanager
@@ -271,7 +317,59 @@ def case_pc_sampler_identical_seed(gname, ckpt, case, lib, device):
     assert np.array_equal(eng.quantize(res[1], -1.0).cpu().numpy(), g[f"{case}/quantize_mol_adj"])
     assert np.array_equal(eng.quantize(res[1], 0.5).cpu().numpy(), g[f"{case}/quantize_adj"].astype(np.int64))
     if "rank2" in names:
-        assert np.array_equal(eng.quantize(res[2], 0.5).cpu().numpy().astype(np.uint8), g[f"{case}/quantize_rank2"])
+        q = eng.quantize(res[2], 0.5).cpu().numpy().astype(np.uint8)
+        if rtol > RTOL and not np.array_equal(q, g[f"{case}/quantize_rank2"]):
+            # a TRAJ_RTOL case: the measured tolerance also bounds which cells may flip -- only those whose reference value lies
+            # within rtol * scale of the 0.5 threshold, and few of them
+            ref = g[f"{case}/rank2"]
+            near = np.abs(ref - 0.5) <= rtol * np.abs(ref).max()
+            diff = q != g[f"{case}/quantize_rank2"]
+            assert not (diff & ~near).any(), f"{gname} {case}: quantize_rank2 differs away from the threshold"
+            assert diff.sum() <= max(2, 1e-4 * diff.size), f"{gname} {case}: {diff.sum()} rank-2 cells flip at the threshold"
+        else:
+            assert np.array_equal(q, g[f"{case}/quantize_rank2"])
+
+
+def case_pc_sampler_vs_oracle(gname, ckpt, case, lib, device):
+    """G5 for checkpoints whose rank-2 goldens are stored as summaries (ego_small_CC): the closure with every draw from torch's
+    CPU generator against the oracle run here through the same seed (the CPU suite pins that oracle run to the fixture's hash,
+    subsample and row sums); the quantised adjacency bit for bit against the reference's."""
+    rtol = TRAJ_RTOL.get((gname, case), RTOL)
+    g = load_golden(f"g5_{gname}.npz")
+    assert rng_matches(g)
+    meta, parts = load_ckpt_np(ckpt)
+    cfg, is_cc = meta["config"], meta["is_cc"]
+    sm = json.loads(str(g["sampler"]))
+    N, Fd = cfg["data"]["max_node_num"], cfg["data"]["max_feat_num"]
+    flags = torch.from_numpy(g["flags"])
+    B = flags.shape[0]
+    names = ["x", "adj"] + (["rank2"] if is_cc else [])
+    num_scales, max_steps = parse_case(case)
+    sdes = []
+    for p in names:
+        c = dict(cfg["sde"][p])
+        if num_scales is not None:
+            c["num_scales"] = num_scales
+        sdes.append(O.load_sde(c))
+    kw = dict(sde_x=sdes[0], sde_adj=sdes[1], shape_x=(B, N, Fd), shape_adj=(B, N, N), predictor=sm["predictor"],
+              corrector=sm["corrector"], snr=sm["snr"], scale_eps=sm["scale_eps"], n_steps=sm["n_steps"], probability_flow=False,
+              continuous=True, denoise=True, eps=1e-4, n_diff_steps=max_steps)
+    if is_cc:
+        d_min, d_max = cfg["data"]["d_min"], cfg["data"]["d_max"]
+        kw.update(is_cc=True, sde_rank2=sdes[2], shape_rank2=(B, *O.get_rank2_dim(N, d_min, d_max)), d_min=d_min, d_max=d_max)
+    ofn = (O.S4_solver if sm["predictor"] == "S4" else O.get_pc_sampler)(**kw)
+    torch.manual_seed(int(g["seed"]))
+    want = ofn(*_oracle_nets(meta, parts, is_cc, names), flags)
+    fn, models, _, _ = sampler_from_golden(g, ckpt, case, lib, device, keep_traj=True)
+    torch.manual_seed(int(g["seed"]))
+    res = fn(*models, flags.to(device))
+    for p, v, w in zip(names, res, want):
+        assert_close(v, w, f"{gname} {case} {p}", rtol)
+    assert int(res[len(names)]) == int(g[f"{case}/nfe"]) and len(res[-1]) == int(g[f"{case}/traj_len"])
+    assert_close(res[-1][-1][1], g[f"{case}/traj_last_adj"], "diff_traj[-1] adj", rtol)
+    adj = res[1].cpu()
+    assert np.array_equal(O.quantize_mol(adj), g[f"{case}/quantize_mol_adj"])
+    assert np.array_equal(O.quantize(adj).numpy(), g[f"{case}/quantize_adj"])
 
 
 def case_philox_properties(lib, device, B=6, steps=3):
@@ -420,14 +518,35 @@ def case_one_step_vs_oracle_large(name, lib, device, B, counts, predictor, corre
         assert_close(g_, w_, f"{name} B={B} one step {p}")
 
 
+def loop_phases(predictor, corrector, n_steps=1):
+    """The half-step phases of one step whose draws the production loop consumes, in the oracle's draw order (ccsd_noise_draws's
+    phase numbering, ccsd_api.h draw_base): Langevin 0..n_steps-1 corrector iterations then the predictor at n_steps; a
+    corrector-free plan only the predictor's phase n_steps (phase 0 is a slot it never uses); S4 the correction draw, then the
+    two transition draws (S4_solver's order, solver.py:1299-1350)."""
+    if predictor == "S4":
+        return (0, 1, 2)
+    if corrector == "Langevin":
+        return tuple(range(n_steps + 1))
+    return (n_steps,)
+
+
 def case_production_loop_vs_oracle(name, lib, device, B, counts, steps, predictor, corrector, snr, seps, seed=5, expect_fused=None,
-                                   source=None):
+                                   source=None, keep_traj=False, subset=None, expect_route=None, stepwise=True):
     """The PRODUCTION loop -- one ccsd_sampler_run call: in-kernel Philox noise, the Langevin apply fused into the predictor
-    kernels' prologues where the plan supports it -- against the oracle, value for value.  ccsd_noise_draws exports the masked
-    draws the kernels consume for every (step, half-step); the oracle replays them as its noise stream (RecordedNoise) from the
-    same prior.  Also: the Python-driven step-wise loop (ccsd_corrector_norms + ccsd_corrector_apply + ccsd_predictor, the path
-    the golden cases exercise) must reproduce the single call bit for bit.  (solver.py:1123-1147.)"""
-    assert corrector == "Langevin"
+    kernels' prologues where the plan supports it -- against the oracle, value for value, in each of its four step forms (S4,
+    Langevin fused, Langevin unfused, predictor only).  ccsd_noise_draws exports the masked draws the kernels consume for every
+    (step, phase) the plan draws (loop_phases); the oracle replays them as its noise stream (RecordedNoise) from the same prior
+    and must consume exactly them.  Checked: the denoised mean the closure returns, the sampled state after the last step, and
+    (keep_traj) the trajectory.  Also: the Python-driven step-wise loop (ccsd_corrector_norms + ccsd_corrector_apply /
+    ccsd_s4_apply + ccsd_predictor, the path the golden cases exercise) must reproduce the single call bit for bit.
+
+    `subset`: batch rows the oracle replays (draws and prior are sliced on the device before the copy to the host).  Only for the
+    corrector-free predictor loop: with corrector None every update of a complex reads that complex's state, score and draws alone
+    -- no batch-mean norm couples the complexes, as the Langevin corrector's and S4's step sizes do -- so the rows of a subset
+    evolve exactly as they do inside the full batch.  `expect_route`: {plan query: value} the plan must have selected."""
+    s4 = predictor == "S4"
+    if subset is not None:
+        assert corrector == "None" and not s4, "a subset replay needs complexes that do not couple through batch-mean norms"
     if source is None:
         meta, parts = load_ckpt_np(name)
     else:                                  # networks that are not a shipped checkpoint: (meta in the checkpoint layout, weights)
@@ -437,37 +556,70 @@ def case_production_loop_vs_oracle(name, lib, device, B, counts, steps, predicto
     names = ["x", "adj"] + (["rank2"] if is_cc else [])
     nt = len(names)
     flags = make_flags(B, N, counts)
-    kw = dict(shape_x=(B, N, Fd), shape_adj=(B, N, N), predictor=predictor, corrector=corrector, snr=snr, scale_eps=seps,
-              n_steps=1, probability_flow=False, continuous=True, denoise=True, eps=1e-4)
-    if is_cc:
-        d_min, d_max = cfg["data"]["d_min"], cfg["data"]["d_max"]
-        kw.update(is_cc=True, shape_rank2=(B, *rank2_dim(N, d_min, d_max)), d_min=d_min, d_max=d_max)
+    rows = list(range(B)) if subset is None else list(subset)
+    Bo = len(rows)
+
+    def kwargs(nb):
+        kw = dict(shape_x=(nb, N, Fd), shape_adj=(nb, N, N), predictor=predictor, corrector=corrector, snr=snr, scale_eps=seps,
+                  n_steps=1, probability_flow=False, continuous=True, denoise=True, eps=1e-4)
+        if is_cc:
+            d_min, d_max = cfg["data"]["d_min"], cfg["data"]["d_max"]
+            kw.update(is_cc=True, shape_rank2=(nb, *rank2_dim(N, d_min, d_max)), d_min=d_min, d_max=d_max)
+        return kw
+
     sd = [loader.load_sde(cfg["sde"][p]) for p in names]
     ms = [loader.load_model_from_ckpt(meta[f"params_{p}"], parts[p], device) for p in names]
     skw = dict(sde_x=sd[0], sde_adj=sd[1])
     if is_cc:
         skw["sde_rank2"] = sd[2]
+    make = solver.S4_solver if s4 else solver.get_pc_sampler
     dflags = flags.to(device)
-    fn = solver.get_pc_sampler(device=device, rng="philox", seed=seed, max_steps=steps, lib=lib, **skw, **kw)
+    fn = make(device=device, rng="philox", seed=seed, max_steps=steps, lib=lib, keep_traj=keep_traj, **skw, **kwargs(B))
     got = fn(*ms, dflags)
     eng = fn.engine()
     if expect_fused is not None:
         assert eng.query("fused_loop") == int(expect_fused), "the plan did not take the expected loop form"
+    for what, v in (expect_route or {}).items():
+        assert eng.query(what) == v, f"{name}: plan query {what} = {eng.query(what)}, expected {v}"
+    pick = lambda t: (t if subset is None else t[torch.tensor(rows, device=t.device)]).cpu().clone()
+    # the sampled state after the last step (the closure returns the denoised mean): the same single call on buffers of our own
+    state, scratch, result = (eng.alloc_state(B) for _ in range(3))
+    eng.init_and_run(dflags, state, scratch, result, seed, 0, 0, steps)
+    for p, a, b in zip(names, got[:nt], result[:nt]):
+        assert torch.equal(a, b), f"{name} B={B}: two identical ccsd_sampler_run calls differ in {p}"
+    got_state = [pick(t) for t in state[:nt]]
+    got_mean = [pick(t) for t in got[:nt]]
+    got_traj = got[-1]
+    del state, scratch, result
     # step-wise driver == the single C call, bit for bit, at this batch
-    fn_s = solver.get_pc_sampler(device=device, rng="philox", seed=seed, max_steps=steps, lib=lib, group=_FakeGroup(), **skw, **kw)
-    got_s = fn_s(*ms, dflags)
-    for p, a, b in zip(names, got[:nt], got_s[:nt]):
-        assert torch.equal(a, b), f"{name} B={B}: step-wise loop != ccsd_sampler_run for {p}"
+    if stepwise:
+        fn_s = make(device=device, rng="philox", seed=seed, max_steps=steps, lib=lib, group=_FakeGroup(), **skw, **kwargs(B))
+        got_s = fn_s(*ms, dflags)
+        for p, a, b in zip(names, got[:nt], got_s[:nt]):
+            assert torch.equal(a, b), f"{name} B={B}: step-wise loop != ccsd_sampler_run for {p}"
+        del fn_s, got_s
+    del got
     # the draws the kernels consumed
     buf = eng.alloc_state(B)
     eng.init_state(dflags, buf, None, seed, 0)
-    prior = [t.cpu().clone() for t in buf[:nt]]
+    prior = [pick(t) for t in buf[:nt]]
+    phases = loop_phases(predictor, corrector)
     draws = []
     for step in range(steps):
-        for phase in (0, 1):                       # corrector (inner iteration 0), predictor
+        for phase in phases:
             eng.noise_draws(dflags, step, phase, buf, seed, 0)
-            draws += [t.cpu().clone() for t in buf[:nt]]
-    assert not torch.equal(draws[0], draws[nt]) and not torch.equal(draws[0], prior[0])
+            draws += [pick(t) for t in buf[:nt]]
+    unused = None
+    if not s4 and corrector == "None":     # the slot a corrector would draw from: real draws, never consumed by this plan
+        unused = []
+        for step in range(steps):
+            eng.noise_draws(dflags, step, 0, buf, seed, 0)
+            unused += [pick(t) for t in buf[:nt]]
+        assert not any(torch.equal(u, d) for u, d in zip(unused, draws))
+    del buf
+    assert not torch.equal(draws[0], prior[0])
+    if len(draws) > nt:
+        assert not torch.equal(draws[0], draws[nt])
     so = [O.load_sde(cfg["sde"][p]) for p in names]
     okw = dict(sde_x=so[0], sde_adj=so[1])
     if is_cc:
@@ -475,12 +627,29 @@ def case_production_loop_vs_oracle(name, lib, device, B, counts, steps, predicto
         nets = [(lambda x, a, r, f, p=p: O.run_network(meta[f"params_{p}"], parts[p], x, a, r, f)) for p in names]
     else:
         nets = [(lambda x, a, f, p=p: O.run_network(meta[f"params_{p}"], parts[p], x, a, None, f)) for p in names]
+    omake = O.S4_solver if s4 else O.get_pc_sampler
+    oflags = flags[rows] if subset is not None else flags
     rec = O.RecordedNoise(draws)
-    ofn = O.get_pc_sampler(n_diff_steps=steps, keep_traj=False, noise=rec, prior=prior, **okw, **kw)
-    want = ofn(*nets, flags)
+    final = []
+    ofn = omake(n_diff_steps=steps, keep_traj=keep_traj, noise=rec, prior=prior, final=final, **okw, **kwargs(Bo))
+    want = ofn(*nets, oflags)
     assert rec.i == len(draws), "the oracle consumed a different number of draws"
-    for p, g_, w_ in zip(names, got, want):
-        assert_close(g_, w_, f"{name} B={B} production loop, {steps} steps, {p}")
+    tag = f"{name} {predictor}+{corrector} B={B}{'' if subset is None else f' rows {rows}'} production loop, {steps} steps"
+    for p, g_, w_ in zip(names, got_mean, want):
+        assert_close(g_, w_, f"{tag}, result {p}")
+    for p, g_, w_ in zip(names, got_state, final):
+        assert_close(g_, w_, f"{tag}, state {p}")
+    if keep_traj:
+        assert len(got_traj) == steps == len(want[-1])
+        for i, (gs, ws) in enumerate(zip(got_traj, want[-1])):
+            for p, g_, w_ in zip(names, gs, ws):
+                assert_close(g_, w_, f"{tag}, traj[{i}] {p}")
+    if unused is not None:
+        # the kernels are not keyed at the unused slot: a replay of phase 0 in the predictor's place misses them
+        ofn = omake(n_diff_steps=steps, keep_traj=False, noise=O.RecordedNoise(unused), prior=prior, **okw, **kwargs(Bo))
+        off = ofn(*nets, oflags)
+        assert any((g_ - w_).abs().max() > 10 * RTOL * max(w_.abs().max().item(), 1e-6) for g_, w_ in zip(got_mean, off)), \
+            f"{tag}: the unused phase-0 draws reproduce the result too -- the replay does not tell the slots apart"
 
 
 def case_zinc5b_production_loop(lib, device):

@@ -10,6 +10,9 @@ from tests.emu_util import emu_library
 
 torch.set_num_threads(8)
 DEV = "cpu"
+# shipped checkpoints the package does not carry: weights under tests/golden/ckpt/, reference goldens stored whole
+SHIPPED = ["ccsd_enzymes_small_Base_CC", "gdss_qm9", "gdss_qm9_retrained", "gdss_ego_small", "gdss_ego_small_retrained",
+           "gdss_enzymes_small_retrained"]
 
 
 @pytest.fixture(scope="module")
@@ -27,11 +30,23 @@ def test_forward_community_small_cc(lib, name):
     pc.case_forward_vs_reference_golden(name, lib, DEV)
 
 
-@pytest.mark.parametrize("name", ["ccsd_enzymes_small_CC", "gdss_zinc250k"])
+@pytest.mark.parametrize("name", ["ccsd_enzymes_small_CC", "gdss_zinc250k", *SHIPPED])
 def test_forward_large_nets(lib, name):
     """ENZYMES_small_CC (E = 66 > 64: tiled rank-2 kernels, 2-linear hodge MLPs) and zinc250k (N = 38: channel stack in
     the HBM workspace)."""
     pc.case_forward_vs_reference_golden(name, lib, DEV)
+
+
+@pytest.mark.parametrize("name", ["ccsd_ego_small_CC", "ccsd_ego_small_CC_v2"])
+def test_forward_vs_oracle_ego_small_cc(lib, name):
+    """ego_small_CC / _v2 (E = 153, K = 12444: the tiled rank-2 kernels) against the oracle computed in the test."""
+    pc.case_forward_vs_oracle(name, lib, DEV)
+
+
+@pytest.mark.parametrize("name", ["ccsd_ego_small_CC", "ccsd_ego_small_CC_v2"])
+def test_pc_sampler_vs_oracle_ego_small_cc(lib, name):
+    """Two steps of the 1000-scale Euler + None run against the oracle (the k6 case takes ~50 s here: GPU suite only)."""
+    pc.case_pc_sampler_vs_oracle(name, name, "n1000_first2", lib, DEV)
 
 
 def test_model_objects(lib):
@@ -65,6 +80,9 @@ def test_kat_small_general_paths(lib):
     ("ccsd_qm9_CC_pflow", "ccsd_qm9_CC", "k6"),
     ("gdss_community_small_pflow", "gdss_community_small", "k5"),
     ("ccsd_qm9_CC_subvp_mixed", "ccsd_qm9_CC", "k4"),
+    # shipped checkpoints the package does not carry (weights under tests/golden/ckpt/), at their own sample_*.yaml settings
+    # (S4 on ccsd_enzymes_small_Base_CC at 6 scales: parity_cases.TRAJ_RTOL, test_fp64_arbiter_s4_enzymes_base_cc)
+    *[(n, n, c) for n in SHIPPED for c in ("k6", "n1000_first2")],
 ])
 def test_pc_sampler_identical_seed(lib, gname, ckpt, case):
     pc.case_pc_sampler_identical_seed(gname, ckpt, case, lib, DEV)
@@ -75,6 +93,14 @@ def test_fp64_arbiter_s4_enzymes(lib, case):
     """The two cases whose tolerance against the fp32 reference golden is wider than 1e-4 (parity_cases.TRAJ_RTOL), judged
     against the float64 trajectory: the product may not be further from it than the reference is."""
     r = pc.case_fp64_arbiter("s4_ccsd_enzymes_small_CC", "ccsd_enzymes_small_CC", case, lib, DEV)
+    e_ref, e_mine, e_mut = r["rank2"]
+    assert e_mut <= e_ref + e_mine + 1e-7
+    assert e_ref > 0.9e-4, "the reference itself is no longer > 1e-4 from the exact trajectory: tighten TRAJ_RTOL"
+
+
+def test_fp64_arbiter_s4_enzymes_base_cc(lib):
+    """The third TRAJ_RTOL case (S4 on ccsd_enzymes_small_Base_CC, 6 scales) judged against the float64 trajectory."""
+    r = pc.case_fp64_arbiter("ccsd_enzymes_small_Base_CC", "ccsd_enzymes_small_Base_CC", "k6", lib, DEV)
     e_ref, e_mine, e_mut = r["rank2"]
     assert e_mut <= e_ref + e_mine + 1e-7
     assert e_ref > 0.9e-4, "the reference itself is no longer > 1e-4 from the exact trajectory: tighten TRAJ_RTOL"
@@ -150,6 +176,37 @@ def test_production_loop_vs_oracle(lib):
     pc.case_production_loop_vs_oracle("ccsd_qm9_CC", lib, DEV, 5, [9, 7, 8, 0, 4], 2, "Reverse", "Langevin", 0.2, 0.7, expect_fused=True)
     pc.case_production_loop_vs_oracle("gdss_community_small", lib, DEV, 3, [20, 12, 16], 2, "Euler", "Langevin", 0.05, 0.7,
                                       expect_fused=False)
+
+
+def test_production_loop_corrector_free_vs_oracle(lib):
+    """ccsd_sampler_run's predictor-only branch (corrector None: the ego_small YAMLs' Euler + None) against the oracle on the exported
+    predictor draws, with the trajectory; the plan's unused phase-0 slot must not reproduce the result."""
+    pc.case_production_loop_vs_oracle("ccsd_qm9_CC", lib, DEV, 5, [9, 7, 8, 0, 4], 3, "Euler", "None", 0.0, 0.0, seed=43,
+                                      expect_fused=False, keep_traj=True)
+    pc.case_production_loop_vs_oracle("gdss_community_small", lib, DEV, 3, [20, 12, 16], 2, "Reverse", "None", 0.0, 0.0, seed=47,
+                                      expect_fused=False)
+
+
+def test_production_loop_corrector_free_subset_replay(lib):
+    """Corrector None couples no complexes: the oracle replaying a subset of the rows (first, last, mixed node counts) sees exactly
+    what the full batch computed for them."""
+    pc.case_production_loop_vs_oracle("ccsd_qm9_CC", lib, DEV, 9, [9, 3, 8, 0, 9, 5, 2, 7, 6], 2, "Euler", "None", 0.0, 0.0, seed=53,
+                                      subset=[0, 2, 5, 8], keep_traj=True)
+
+
+def test_production_loop_s4_vs_oracle(lib):
+    """ccsd_sampler_run's S4 branch (the ENZYMES_small YAMLs' sampler) against the oracle's S4_solver on the exported draws (three
+    per target and step, in S4_solver's order), with the trajectory."""
+    pc.case_production_loop_vs_oracle("ccsd_qm9_CC", lib, DEV, 5, [9, 7, 8, 0, 4], 3, "S4", "None", 0.15, 0.7, seed=59,
+                                      expect_fused=False, keep_traj=True)
+    pc.case_production_loop_vs_oracle("ccsd_enzymes_small_CC", lib, DEV, 3, [12, 9, 5], 2, "S4", "None", 0.15, 0.7, seed=61)
+
+
+def test_production_loop_langevin_unfused_vs_oracle(lib, monkeypatch):
+    """The Langevin branch with the apply pass as a launch of its own (CCSD_NO_FUSED_APPLY) on a plan that would fuse it."""
+    monkeypatch.setenv("CCSD_NO_FUSED_APPLY", "1")
+    pc.case_production_loop_vs_oracle("ccsd_qm9_CC", lib, DEV, 5, [9, 7, 8, 0, 4], 2, "Reverse", "Langevin", 0.2, 0.7, seed=67,
+                                      expect_fused=False, keep_traj=True)
 
 
 def test_production_loop_edge_flags(lib):

@@ -9,6 +9,9 @@ from tests import parity_cases as pc
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
+# shipped checkpoints the package does not carry: weights under tests/golden/ckpt/, reference goldens stored whole
+SHIPPED = ["ccsd_enzymes_small_Base_CC", "gdss_qm9", "gdss_qm9_retrained", "gdss_ego_small", "gdss_ego_small_retrained",
+           "gdss_enzymes_small_retrained"]
 
 
 @pytest.fixture(scope="module")
@@ -23,9 +26,26 @@ def lib():
 
 @pytest.mark.parametrize("name", ["ccsd_qm9_CC", "ccsd_community_small_CC", "gdss_community_small",
                                   "ccsd_enzymes_small_CC", "gdss_zinc250k", "ccsd_qm9_Base_CC",
-                                  "ccsd_community_small_Base_CC"])
+                                  "ccsd_community_small_Base_CC", *SHIPPED])
 def test_forward_vs_reference_golden(lib, name):
     pc.case_forward_vs_reference_golden(name, lib, DEV)
+
+
+EGO_CC = ["ccsd_ego_small_CC", "ccsd_ego_small_CC_v2"]
+
+
+@pytest.mark.parametrize("name", EGO_CC)
+def test_forward_vs_oracle_ego_small_cc(lib, name):
+    """ego_small_CC / _v2 (E = 153, K = 12444): forwards and score scaling against the oracle computed in the test (their rank-2
+    goldens are summaries, pinned to the oracle by the CPU suite)."""
+    pc.case_forward_vs_oracle(name, lib, DEV)
+
+
+@pytest.mark.parametrize("name", EGO_CC)
+@pytest.mark.parametrize("case", ["k6", "n1000_first2"])
+def test_pc_sampler_vs_oracle_ego_small_cc(lib, name, case):
+    """Short sampler runs of ego_small_CC / _v2 at sample_ego_small_CC.yaml's settings (Euler + None) against the oracle."""
+    pc.case_pc_sampler_vs_oracle(name, name, case, lib, DEV)
 
 
 def test_model_objects(lib):
@@ -65,6 +85,9 @@ def test_kat_small_general_paths(lib):
     ("ccsd_qm9_CC_subvp_mixed", "ccsd_qm9_CC", "k4"),
     # the metric's own length: the shipped 1000-scale qm9_CC set-up from the prior to the last step, every draw from the CPU generator
     ("ccsd_qm9_CC_full1000", "ccsd_qm9_CC", "n1000"),
+    # shipped checkpoints the package does not carry (weights under tests/golden/ckpt/), at their own sample_*.yaml settings
+    # (S4 on ccsd_enzymes_small_Base_CC at 6 scales: parity_cases.TRAJ_RTOL, test_fp64_arbiter_s4_enzymes_base_cc)
+    *[(n, n, c) for n in SHIPPED for c in ("k6", "n1000_first2")],
 ])
 def test_pc_sampler_identical_seed(lib, gname, ckpt, case):
     pc.case_pc_sampler_identical_seed(gname, ckpt, case, lib, DEV)
@@ -75,6 +98,14 @@ def test_fp64_arbiter_s4_enzymes(lib, case):
     """The two cases whose tolerance against the fp32 reference golden is wider than 1e-4 (parity_cases.TRAJ_RTOL), judged
     against the float64 trajectory: the product may not be further from it than the reference is."""
     r = pc.case_fp64_arbiter("s4_ccsd_enzymes_small_CC", "ccsd_enzymes_small_CC", case, lib, DEV)
+    e_ref, e_mine, e_mut = r["rank2"]
+    assert e_mut <= e_ref + e_mine + 1e-7
+    assert e_ref > 0.9e-4, "the reference itself is no longer > 1e-4 from the exact trajectory: tighten TRAJ_RTOL"
+
+
+def test_fp64_arbiter_s4_enzymes_base_cc(lib):
+    """The third TRAJ_RTOL case (S4 on ccsd_enzymes_small_Base_CC, 6 scales) judged against the float64 trajectory."""
+    r = pc.case_fp64_arbiter("ccsd_enzymes_small_Base_CC", "ccsd_enzymes_small_Base_CC", "k6", lib, DEV)
     e_ref, e_mine, e_mut = r["rank2"]
     assert e_mut <= e_ref + e_mine + 1e-7
     assert e_ref > 0.9e-4, "the reference itself is no longer > 1e-4 from the exact trajectory: tighten TRAJ_RTOL"
@@ -316,6 +347,61 @@ def test_production_loop_edge_flags(lib):
     # the one-workgroup-per-complex rank-2 kernels (B >= 256) with empty and near-empty complexes among full ones
     pc.case_production_loop_vs_oracle("ccsd_community_small_CC", lib, DEV, 256, [0, 1, 2, 20, 12, 3, 20, 16], 1, "Euler", "Langevin", 0.05, 0.7,
                                       seed=41, expect_fused=True)
+
+
+QM9_MIX = [9, 9, 8, 9, 7, 9, 9, 6, 9, 5, 9, 9, 4, 9, 8, 9, 3, 9, 7, 2, 9, 1]
+ENZ_MIX = [12, 11, 12, 9, 10, 12, 8, 12, 6, 12, 11, 5, 12, 10, 3, 12, 7]
+EGO_MIX = [18, 17, 18, 12, 18, 9, 16, 18, 5, 18, 14, 2, 18, 11, 18, 7]
+# the route the ego_small_CC plan takes (ccsd_plan_query): the tiled rank-2 kernels (k_gemm_h*, k_gemm_p*, k_hf_score), not k_r2 / k_ew1
+EGO_ROUTE = {"fused_r2": 0, "ew1": 0, "fused_loop": 0}
+
+
+def test_production_loop_corrector_free_qm9_full_batch(lib):
+    """ccsd_sampler_run's predictor-only branch (corrector None) at the headline geometry (qm9_CC, B = 1024) against the oracle on the
+    exported predictor draws: result, final state, and bit equality with the step-wise loop."""
+    pc.case_production_loop_vs_oracle("ccsd_qm9_CC", lib, DEV, 1024, QM9_MIX, 4, "Euler", "None", 0.0, 0.0, seed=71, expect_fused=False)
+
+
+def test_production_loop_corrector_free_traj(lib):
+    """The same branch on a short run with the trajectory kept (ccsd_sampler_run's traj slots)."""
+    pc.case_production_loop_vs_oracle("ccsd_qm9_CC", lib, DEV, 9, [9, 7, 8, 0, 4, 9, 1, 2, 6], 3, "Euler", "None", 0.0, 0.0, seed=73,
+                                      keep_traj=True)
+    pc.case_production_loop_vs_oracle("ccsd_qm9_CC", lib, DEV, 9, [9, 7, 8, 0, 4, 9, 1, 2, 6], 3, "S4", "None", 0.15, 0.7, seed=79,
+                                      keep_traj=True)
+
+
+def test_production_loop_s4_enzymes_small_cc_chunk(lib):
+    """ccsd_sampler_run's S4 branch at the ENZYMES_small_CC YAML's chunk batch (cc_nb_eval 1000 / divide_batch 4 = 250)."""
+    pc.case_production_loop_vs_oracle("ccsd_enzymes_small_CC", lib, DEV, 250, ENZ_MIX, 2, "S4", "None", 0.15, 0.7, seed=83, expect_fused=False)
+
+
+def test_production_loop_s4_enzymes_small_base_cc(lib):
+    """S4 with the ScoreNetworkA_Base_CC checkpoint of the same dataset (sample_enzymes_small_Base_CC.yaml)."""
+    pc.case_production_loop_vs_oracle("ccsd_enzymes_small_Base_CC", lib, DEV, 250, ENZ_MIX, 2, "S4", "None", 0.15, 0.7, seed=89)
+
+
+def test_production_loop_corrector_free_gdss_ego_small_retrained(lib):
+    """Euler + None (sample_ego_small_retrained.yaml) on the graph-only ego_small checkpoint, N = 18."""
+    pc.case_production_loop_vs_oracle("gdss_ego_small_retrained", lib, DEV, 250, EGO_MIX, 3, "Euler", "None", 0.0, 0.0, seed=97)
+
+
+def test_production_loop_ego_small_cc_chunk(lib):
+    """ego_small_CC (N = 18, d 3..5: E = 153, K = 12444, 7.6 MB of rank-2 state per complex) at its YAML's chunk batch, B = 250, Euler +
+    None.  The oracle replays eight rows (b = 0, b = B - 1, mixed node counts): with corrector None no batch-mean norm couples the
+    complexes, so each row of the batch evolves from its own prior, score and draws alone."""
+    pc.case_production_loop_vs_oracle("ccsd_ego_small_CC", lib, DEV, 250, EGO_MIX, 2, "Euler", "None", 0.0, 0.0, seed=101,
+                                      subset=[0, 3, 5, 8, 11, 100, 131, 249], expect_route=EGO_ROUTE)
+
+
+def test_production_loop_ego_small_cc_beyond_4gib(lib):
+    """The same loop at B = 600: one rank-2 state tensor is 4.6 GB, so every per-batch byte offset of the rank-2 kernels, the Philox
+    draw kernels and the state copies passes 2^32 for the last complexes.  The oracle replays the last rows, rows just below and
+    straddles the 2^32-byte boundary (b = 563; b = 564 is the first whose rank-2 block starts past it) and a middle one."""
+    B = 600
+    per = 153 * 12444 * 4
+    assert 563 * per < 2 ** 32 < 564 * per
+    pc.case_production_loop_vs_oracle("ccsd_ego_small_CC", lib, DEV, B, EGO_MIX, 2, "Euler", "None", 0.0, 0.0, seed=103,
+                                      subset=[0, 300, 562, 563, 564, 598, 599], expect_route=EGO_ROUTE, stepwise=False)
 
 
 def test_fused_r2_serves_nonaffine_shapes(lib):

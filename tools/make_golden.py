@@ -65,8 +65,25 @@ def plain(o):
     return o
 
 
-def export_checkpoint(name):
-    rel, is_cc = CHECKPOINTS[name]
+# Shipped checkpoints within the N <= 38 envelope that the product does not package: their converted weights are test
+# fixtures only (tests/golden/ckpt/, found there by tests/helpers.load_ckpt_np).  `python tools/make_golden.py shipped`
+# writes these files and nothing else.
+SHIPPED = {
+    "ccsd_ego_small_CC": ("checkpoints/ego_small_CC/ccsd_ego_small_CC.pth", True),
+    "ccsd_ego_small_CC_v2": ("checkpoints/ego_small_CC/ccsd_ego_small_CC_v2.pth", True),
+    "ccsd_enzymes_small_Base_CC": ("checkpoints/ENZYMES_small_CC/ccsd_enzymes_small_Base_CC.pth", True),
+    "gdss_qm9": ("checkpoints/QM9/gdss_qm9.pth", False),
+    "gdss_qm9_retrained": ("checkpoints/QM9/gdss_qm9_retrained.pth", False),
+    "gdss_ego_small": ("checkpoints/ego_small/gdss_ego_small.pth", False),
+    "gdss_ego_small_retrained": ("checkpoints/ego_small/gdss_ego_small_retrained.pth", False),
+    "gdss_enzymes_small_retrained": ("checkpoints/ENZYMES_small/gdss_enzymes_small_retrained.pth", False),
+}
+SHIPPED_CKPT = os.path.join(GOLD, "ckpt")
+MAX_FIXTURE = 1 << 20                # no committed file exceeds 1 MiB
+
+
+def export_checkpoint(name, table=CHECKPOINTS, dest=CKPT):
+    rel, is_cc = table[name]
     ck = refshim.load_reference_ckpt(rel)
     arrays = {}
     meta = {"name": name, "source": rel, "is_cc": is_cc, "config": plain(ck["model_config"])}
@@ -84,8 +101,29 @@ def export_checkpoint(name):
             assert len(names) == len(shadow)
             for n, v in zip(names, shadow):
                 arrays[f"ema_{part}/{n}"] = v.detach().cpu().numpy().astype(np.float32)
-    np.savez_compressed(os.path.join(CKPT, name + ".npz"), **arrays)
-    with open(os.path.join(CKPT, name + ".json"), "w") as f:
+    os.makedirs(dest, exist_ok=True)
+    if dest == CKPT:
+        np.savez_compressed(os.path.join(dest, name + ".npz"), **arrays)
+    else:
+        # fixture files stay under MAX_FIXTURE: the state-dict weights (what every parity run uses) in <name>.npz (+ <name>.<i>.npz),
+        # listed in meta["files"] for tests/helpers.load_ckpt_np.  The EMA shadow weights are not kept: no test reads them
+        keys = [k for k in arrays if not k.startswith("ema_")]
+        shards, cur, size = [], [], 0
+        for k in keys:
+            if cur and size + arrays[k].nbytes > MAX_FIXTURE - (64 << 10):
+                shards.append(cur)
+                cur, size = [], 0
+            cur.append(k)
+            size += arrays[k].nbytes
+        if cur:
+            shards.append(cur)
+        meta["files"] = []
+        for i, ks in enumerate(shards):
+            fname = name + (".npz" if i == 0 else f".{i}.npz")
+            np.savez_compressed(os.path.join(dest, fname), **{k: arrays[k] for k in ks})
+            assert os.path.getsize(os.path.join(dest, fname)) <= MAX_FIXTURE, fname
+            meta["files"].append(fname)
+    with open(os.path.join(dest, name + ".json"), "w") as f:
         json.dump(meta, f, indent=1, sort_keys=True)
     return ck
 
@@ -129,7 +167,35 @@ def masked_state(seed, B, N, Fdim, is_cc, d_min, d_max, flags, scale=1.0):
     return x, adj, rank2
 
 
-def g1_network_forwards(name, ck, is_cc, B, counts, seed=1234):
+SUMMARY_BYTES = 1 << 20      # arrays above this size are stored as a summary (summarize) in the shipped-checkpoint fixtures
+SUMMARY_SAMPLES = 1 << 16
+
+
+def summarize(key, a):
+    """An array too large for a fixture -> {key}/sha256 of its bytes, a fixed subsample ({key}/idx, {key}/val: seeded flat
+    indices that include every row's first and last entry) and its float64 row sums ({key}/rowsum, over the last axis)."""
+    import hashlib
+
+    a = np.ascontiguousarray(a)
+    n, last = a.size, a.shape[-1]
+    rows = np.arange(n // last, dtype=np.int64) * last
+    rng = np.random.default_rng(20261016)
+    idx = np.unique(np.concatenate([rows, rows + last - 1, rng.choice(n, SUMMARY_SAMPLES, replace=False)]))
+    return {f"{key}/sha256": np.array(hashlib.sha256(a.tobytes()).hexdigest()), f"{key}/idx": idx,
+            f"{key}/val": a.reshape(-1)[idx], f"{key}/rowsum": a.astype(np.float64).sum(axis=-1)}
+
+
+def save_golden(fname, out, summarize_large=False):
+    if summarize_large:
+        for k in [k for k, v in out.items() if isinstance(v, np.ndarray) and v.nbytes > SUMMARY_BYTES]:
+            out.update(summarize(k, out.pop(k)))
+    path = os.path.join(GOLD, fname)
+    np.savez_compressed(path, **out)
+    if summarize_large:
+        assert os.path.getsize(path) <= MAX_FIXTURE, (fname, os.path.getsize(path))
+
+
+def g1_network_forwards(name, ck, is_cc, B, counts, seed=1234, summarize_large=False):
     """G1/G2: per-network forward + score-fn scaling at three t."""
     cfg = ck["model_config"]
     N, Fd = cfg["data"]["max_node_num"], cfg["data"]["max_feat_num"]
@@ -155,7 +221,7 @@ def g1_network_forwards(name, ck, is_cc, B, counts, seed=1234):
                         continue
                     fn = (ref_losses.get_score_fn_cc if is_cc else ref_losses.get_score_fn)(s, m, train=False, continuous=True)
                     out[f"{tag}/score_{part}_t{ti}"] = fn(*args, t).numpy()
-    np.savez_compressed(os.path.join(GOLD, f"g1_{name}.npz"), **out)
+    save_golden(f"g1_{name}.npz", out, summarize_large)
     print("g1", name, {k: v.shape for k, v in out.items() if hasattr(v, "shape") and v.ndim > 1 and "net" in k})
 
 
@@ -247,18 +313,18 @@ def g7_init_flags():
     print("wrote g7_init_flags", {k: v["n_train"] for k, v in meta.items()})
 
 
-def g5_pc_runs(name, ck, is_cc, B, counts, sampler_cfg, cases, seed, min_dist=0.0):
+def g5_pc_runs(name, ck, is_cc, B, counts, sampler_cfg, cases, seed, min_dist=0.0, summarize_large=False):
     """Wrapper: when `min_dist` is given, the seed is advanced (by 100) until every case's final adjacency stays at least
     that far from every quantisation threshold, so that the bit-exact integer comparison has a margin."""
     for attempt in range(20):
-        d = _g5_pc_runs(name, ck, is_cc, B, counts, sampler_cfg, cases, seed + 100 * attempt)
+        d = _g5_pc_runs(name, ck, is_cc, B, counts, sampler_cfg, cases, seed + 100 * attempt, summarize_large)
         if d >= min_dist:
             return
         print("g5", name, "seed", seed + 100 * attempt, "too close to a threshold:", d)
     raise RuntimeError("no seed with the requested threshold margin")
 
 
-def _g5_pc_runs(name, ck, is_cc, B, counts, sampler_cfg, cases, seed):
+def _g5_pc_runs(name, ck, is_cc, B, counts, sampler_cfg, cases, seed, summarize_large=False):
     """G4/G5: end-to-end sampler runs; inputs are regenerated from the seed by the consumer
     (prior + every in-loop draw come from torch's global CPU generator in reference order).
     sampler_cfg may carry `probability_flow` (default False) and `sde_override` = {part: sde dict} replacing the
@@ -314,8 +380,9 @@ def _g5_pc_runs(name, ck, is_cc, B, counts, sampler_cfg, cases, seed):
         thr = torch.tensor([0.5, 1.5, 2.5])
         out[f"{case}/min_thr_dist"] = np.array((res[1][..., None] - thr).abs().min().item())
         print("g5", name, case, "adj absmax", float(res[1].abs().max()), "min thr dist", float(out[f"{case}/min_thr_dist"]))
-    np.savez_compressed(os.path.join(GOLD, f"g5_{name}.npz"), **out)
-    return min(float(out[f"{case}/min_thr_dist"]) for case in cases)
+    dist = min(float(out[f"{case}/min_thr_dist"]) for case in cases)
+    save_golden(f"g5_{name}.npz", out, summarize_large)
+    return dist
 
 
 def kat_small_models():
@@ -801,8 +868,38 @@ def reference_kat_status():
     print("reference KATs:", r.returncode, tail)
 
 
+def shipped():
+    """The eight shipped checkpoints of SHIPPED: converted weights under tests/golden/ckpt/, g1 forwards at the full node count
+    and a smaller one, g5 short runs at the sampler settings of each checkpoint's own sample_*.yaml (a sibling's where it has
+    none).  ego_small_CC-sized rank-2 tensors are stored as summaries (summarize)."""
+    pc = dict(predictor="Reverse", corrector="Langevin", snr=0.2, scale_eps=0.7, n_steps=1)       # sample_qm9*.yaml
+    ego = dict(predictor="Euler", corrector="None", snr=0.0, scale_eps=0.0, n_steps=1)            # sample_ego_small*.yaml
+    enz = dict(predictor="S4", corrector="None", snr=0.15, scale_eps=0.7, n_steps=1)              # sample_enzymes_small*.yaml
+    runs = {                      # name -> (g1 counts, g5 sampler, g5 counts)
+        "gdss_qm9": ([9, 6], pc, [9, 7]),
+        "gdss_qm9_retrained": ([9, 6], pc, [9, 7]),
+        "gdss_ego_small": ([18, 11], ego, [18, 9]),
+        "gdss_ego_small_retrained": ([18, 11], ego, [18, 9]),
+        "gdss_enzymes_small_retrained": ([12, 8], enz, [12, 9]),
+        "ccsd_enzymes_small_Base_CC": ([12, 8], enz, [12, 9]),
+        "ccsd_ego_small_CC": ([18, 11], ego, [18, 9]),
+        "ccsd_ego_small_CC_v2": ([18, 11], ego, [18, 9]),
+    }
+    for name, (g1c, smp, g5c) in runs.items():
+        _, is_cc = SHIPPED[name]
+        ck = export_checkpoint(name, SHIPPED, SHIPPED_CKPT)
+        big = name.startswith("ccsd_ego_small")
+        g1_network_forwards(name, ck, is_cc, 2, g1c, summarize_large=big)
+        g5_pc_runs(name, ck, is_cc, 2, g5c, smp, {"k6": (6, None), "n1000_first2": (None, 2)}, seed=42, min_dist=5e-3,
+                   summarize_large=big)
+        print("shipped", name)
+
+
 def main():
     only = set(sys.argv[1:])
+    if only == {"shipped"}:
+        shipped()
+        return
     cks = {}
     for name in CHECKPOINTS:
         cks[name] = export_checkpoint(name)
