@@ -97,6 +97,9 @@ struct ccsd_plan {
     // mlp_value, or no fused rank-2 kernel for the geometry): R_l is materialised layer by layer (k_hodge_value) from the dense hodge
     // adjacencies k_xa<., XA_GEN> dumps (launch_xa); CCSD_HODGE_GENERAL forces it for any plan with more than two layers (diagnostic)
     int h_general = 0;
+    // tiled graph-network route (ccsd_k_lg.h): graph-only plans k_xa cannot place (N > 64, or no LDS layout), or any eligible plan
+    // when CCSD_LARGE_GRAPH=1 was set at plan creation; launch_xa hands such plans to launch_lg
+    int lg = 0;
     // diagnostic knobs, read from the environment ONCE at plan creation (never on the launch path):
     // CCSD_OLD_GEMM_P, CCSD_XA_THREADS, CCSD_NO_FUSED_APPLY (CCSD_NO_FUSED_R2 / CCSD_XA_PASS / CCSD_XA_GCH / CCSD_NO_CHAIN shape the plan itself)
     int opt_old_gemm_p = 0, opt_xa_threads = 0, opt_no_fused_apply = 0;   // opt_xa_threads: 0 = by batch (launch_xa)
@@ -289,8 +292,10 @@ extern "C" int ccsd_plan_create(const ccsd_config_t* cfg, const float* weights, 
     if (const char* sg = getenv("CCSD_R2_STAGGER")) sscanf(sg, "%d,%d", &pl->opt_r2_stagger_mask, &pl->opt_r2_stagger_sleep);
     if (const char* xt = getenv("CCSD_XA_THREADS")) { const int v = atoi(xt); if (v >= 64 && v <= 1024 && v % 64 == 0) pl->opt_xa_threads = v; }
     PlanBuilder pb;
+    if (const char* lgv = getenv("CCSD_LARGE_GRAPH")) pb.lg_force = atoi(lgv) == 1;
     pl->nweights = ccsd_build_plan(cfg, &pl->h, pb);
     if (pb.status != CCSD_OK) { delete pl; return set_err(pb.status, pb.err); }
+    pl->lg = pb.lg;
     pl->h.geo_off = getenv("CCSD_NO_GEO") ? 1 : getenv("CCSD_NO_BAKE") ? 2 : 0;      // 2: geometry instances yes, baked-plan instances no
     pl->npacked = (size_t)pb.pcur;
     if (pl->nweights != n_weights) {
@@ -420,6 +425,7 @@ extern "C" int ccsd_plan_create(const ccsd_config_t* cfg, const float* weights, 
     if (pl->fused_r2 && pl->r2_lds > 64 * 1024) {
         PC(rt_set_max_dyn_smem(r2_kernel(pl), pl->r2_lds));
     }
+    if (pl->lg && lg_nmlp_lds(pl->h) > 64 * 1024) PC(rt_set_max_dyn_smem((const void*)k_lg_nmlp, lg_nmlp_lds(pl->h)));
     if (pl->h.is_cc && pl->h.E == 190 && pl->h.K == 1140) {      // k_hp_full: 66.6 KB of dynamic LDS
         const size_t lds = (size_t)(2 * 192 * H_LD + 2 * 16 * H_LD) * 4;
         PC(rt_set_max_dyn_smem((const void*)k_hp_full<190, 1140, 1>, lds));
@@ -474,6 +480,11 @@ struct Workspace {
     const float* hg_rank2;          // (the rank2 launch_p saw: launch_xa continues from it)
     int h_done;                     // H of this pass is already in w.H (k_hp_full produced it beside P_0): launch_h returns at once
     int p1_raw;     // who filled P1 last: k_r2 with the raw factors (1, see k_r2) or k_gemm_p with the finished projections (0)
+    // tiled graph-network route (launch_lg): channel stack [B][a_fdim][N][N]; attention [B][cin][N][N]; D^-1/2 [B][cin][N]; X W and the
+    // GCN output [B][cin][N][cp] (Q | K | V side by side); node features (ping-pong) [B][N][max(F, nhid)]; ScoreNetworkX's concatenation
+    // [B][N][x_fdim], its X W [B][N][nhid], its masked net [B][N][F]; k_lg_fin's per-tile norm partials [B][lg_tiles][2]
+    float *lg_S, *lg_att, *lg_dis, *lg_Y, *lg_QKV, *lg_x[2], *lg_xcat, *lg_xY, *lg_xnet, *lg_part;
+    int lg_tiles;
     size_t bytes;
 };
 static Workspace carve_ws(const ccsd_plan* pl, int B, void* base) {
@@ -519,6 +530,27 @@ static Workspace carve_ws(const ccsd_plan* pl, int B, void* base) {
     w.part2 = (float*)take((size_t)B * 2 * 4);
     w.sums = (float*)take(64);
     w.chan = (float*)take(p.chan_global ? (size_t)B * p.chan_rows * p.N * p.N * 4 : 0);
+    if (pl->lg) {
+        const size_t N = p.N, NN = N * N;
+        int cin = 1, cp = 1, fx = p.F > p.x_nhid ? p.F : p.x_nhid;
+        for (int l = 0; l < p.a_L; ++l) {
+            if (p.al[l].cin > cin) cin = p.al[l].cin;
+            if (p.al[l].cp > cp) cp = p.al[l].cp;
+            if (p.al[l].fout > fx) fx = p.al[l].fout;
+        }
+        w.lg_tiles = (int)((NN + CCSD_LG_FIN_ROWS - 1) / CCSD_LG_FIN_ROWS);
+        w.lg_S = (float*)take((size_t)B * p.a_fdim * NN * 4);
+        w.lg_att = (float*)take((size_t)B * cin * NN * 4);
+        w.lg_dis = (float*)take((size_t)B * cin * N * 4);
+        w.lg_Y = (float*)take((size_t)B * cin * N * cp * 4);
+        w.lg_QKV = (float*)take((size_t)B * cin * N * cp * 4);
+        w.lg_x[0] = (float*)take((size_t)B * N * fx * 4);
+        w.lg_x[1] = (float*)take((size_t)B * N * fx * 4);
+        w.lg_xcat = (float*)take((size_t)B * N * p.x_fdim * 4);
+        w.lg_xY = (float*)take((size_t)B * N * p.x_nhid * 4);
+        w.lg_xnet = (float*)take((size_t)B * N * p.F * 4);
+        w.lg_part = (float*)take((size_t)B * w.lg_tiles * 2 * 4);
+    }
     w.bytes = o;
     return w;
 }
@@ -547,6 +579,7 @@ static int check_state(const ccsd_plan* pl, const ccsd_state_t* s, const char* w
 }
 
 static int launch_flagbits(const ccsd_plan* pl, int B, const float* flags, Workspace& w, void* stream) {
+    if (pl->lg) return CCSD_OK;       // (64-bit node masks feed only the rank-2 tables; the tiled route is graph-only and goes past 64 nodes)
     CCSD_LAUNCH(k_flagbits, dim3(grid_for(B, 256)), dim3(CCSD_NTHREADS), 0, stream, flags, w.offbits, B, pl->h.N);
     LAUNCH_CHECK();
     if (pl->h.is_cc) {      // (consumers: k_ew1, k_langevin_apply, k_noise_norm; the fused rank-2 kernel builds its own masks in LDS)
@@ -719,7 +752,9 @@ static int launch_p(const ccsd_plan* pl, int B, const float* adj, const float* r
     }
     return CCSD_OK;
 }
+static int launch_lg(const ccsd_plan* pl, int B, XaArgs& xa, NoiseArgs& na, Workspace& w, void* stream);
 static int launch_xa(const ccsd_plan* pl, int B, XaArgs& xa, NoiseArgs& na, Workspace& w, void* stream, bool set_b = false) {
+    if (pl->lg) return launch_lg(pl, B, xa, na, w, stream);
     xa.P0 = set_b ? w.P0b : w.P0; xa.P1 = set_b ? w.P1b : w.P1; xa.U1 = set_b ? w.U1b : w.U1; xa.chan_ws = w.chan;
     xa.p1_raw = w.p1_raw; xa.dbg = pl->dbg ? pl->dbg + 32 : nullptr;
     xa.stagger_mask = pl->opt_xa_stagger_mask; xa.stagger_sleep = pl->opt_xa_stagger_sleep; xa.prio_mode = pl->opt_xa_prio;
@@ -796,6 +831,69 @@ static int launch_xa(const ccsd_plan* pl, int B, XaArgs& xa, NoiseArgs& na, Work
     LAUNCH_CHECK();
     return CCSD_OK;
 }
+// Tiled graph-network route (ccsd_k_lg.h): ScoreNetworkX on (xX, adjX) and ScoreNetworkA on (xA, adjA) as a sequence of launches over
+// the workspace (LgWs fields of Workspace), then the epilogues of k_xa's contract (mode, coefficients, mean pointers, norm2[b][4]).
+// Graph-only plans never fuse the corrector apply into this pass (fused_apply_ok), so a CorrFuse here is an error.
+static int launch_lg(const ccsd_plan* pl, int B, XaArgs& xa, NoiseArgs& na, Workspace& w, void* stream) {
+    const PlanD& p = pl->h;
+    if (xa.cf.on) return set_err(CCSD_ERR_RUNTIME, "tiled graph-network route: no fused corrector apply");
+    const int N = p.N, F = p.F, NN = N * N, H = p.x_nhid, XF = p.x_fdim;
+    const int rt = (N + 15) / 16, gt = (N + CCSD_LG_GT - 1) / CCSD_LG_GT, at = (N + CCSD_LG_AT - 1) / CCSD_LG_AT;
+    const dim3 blk(CCSD_NTHREADS);
+    auto cdiv = [](int a, int b_) { return (a + b_ - 1) / b_; };
+    prof_mark(const_cast<ccsd_plan*>(pl), KID_XA, stream);
+    if (xa.do_x) {
+        // ScoreNetworkX (ScoreNetwork_X.py:102-132): depth x tanh(DenseGCNConv) on adjX, concatenated behind x, final MLP per node
+        CCSD_LAUNCH(k_lg_dis, dim3(grid_for(N, 256), B), blk, 0, stream, xa.adjX, (long long)NN, 0, 1, N, w.lg_dis);
+        CCSD_LAUNCH(k_lg_put, dim3(grid_for((long long)B * N * F, 256)), blk, 0, stream, xa.xX, F, w.lg_xcat, XF, B * N);
+        for (int l = 0; l < p.x_depth; ++l) {
+            const int fin = l ? H : F;
+            const float* src = l ? w.lg_xcat + F + (l - 1) * H : xa.xX;
+            CCSD_LAUNCH(k_lg_xw, dim3(grid_for((long long)N * H, 256), B), blk, 0, stream, src, (long long)N * (l ? XF : F), l ? XF : F, fin,
+                        (const float*)pl->w + p.x_gw[l], 0, H, 1, N, (const float*)w.lg_dis, w.lg_xY);
+            CCSD_LAUNCH(k_lg_gcn, dim3(gt * cdiv(H, CCSD_LG_GT), 1, B), blk, 0, stream, xa.adjX, (long long)NN, 0, (const float*)w.lg_xY,
+                        (const float*)w.lg_dis, (const float*)pl->w + p.x_gb[l], 0, H, H, 1, N, w.lg_xcat, (long long)N * XF, 0, XF, F + l * H, 1);
+        }
+        CCSD_LAUNCH(k_lg_nmlp, dim3(rt, B), blk, lg_nmlp_lds_of(p.x_fin), stream, p.x_fin, (const float*)pl->w,
+                    (LgGather{w.lg_xcat, (long long)N * XF, 0, XF, 0, XF}), N, xa.flags, 0, w.lg_xnet);
+        LAUNCH_CHECK();
+    }
+    if (xa.do_a) {
+        // ScoreNetworkA (ScoreNetwork_A.py:505-541): channel stack [A, A^2, ..] + every AttentionLayer's output channels, final MLP per entry
+        const long long ss = (long long)p.a_fdim * NN;
+        for (int c = 0; c < p.a_cinit; ++c)
+            CCSD_LAUNCH(k_lg_pow, dim3(grid_for(NN, 256), B), blk, 0, stream, xa.adjA, w.lg_S, ss, N, c);
+        for (int l = 0; l < p.a_L; ++l) {
+            const AttnLayerD& L = p.al[l];
+            const float* xin = l ? w.lg_x[(l - 1) & 1] : xa.xA;
+            const float* wq = pl->wp + L.qkvp;                  // per channel [fin][cp] weights + [cp] biases (ccsd_pack_qkv)
+            const int wcs = L.fin * L.cp + L.cp;
+            CCSD_LAUNCH(k_lg_dis, dim3(grid_for((long long)L.cin * N, 256), B), blk, 0, stream, (const float*)w.lg_S, ss, L.ci0, L.cin, N, w.lg_dis);
+            CCSD_LAUNCH(k_lg_xw, dim3(grid_for((long long)L.cin * N * L.cp, 256), B), blk, 0, stream, xin, (long long)N * L.fin, L.fin, L.fin,
+                        wq, wcs, L.cp, L.cin, N, (const float*)w.lg_dis, w.lg_Y);
+            CCSD_LAUNCH(k_lg_gcn, dim3(gt * cdiv(L.cp, CCSD_LG_GT), L.cin, B), blk, 0, stream, (const float*)w.lg_S, ss, L.ci0, (const float*)w.lg_Y,
+                        (const float*)w.lg_dis, wq + L.fin * L.cp, wcs, L.cp, L.cp, L.cin, N, w.lg_QKV, (long long)L.cin * N * L.cp, N * L.cp, L.cp, 0, 0);
+            // node update: tanh(mask_x(multi_channel(cat_c V_c)))
+            CCSD_LAUNCH(k_lg_nmlp, dim3(rt, B), blk, lg_nmlp_lds_of(L.mc), stream, L.mc, (const float*)pl->w,
+                        (LgGather{w.lg_QKV, (long long)L.cin * N * L.cp, N * L.cp, L.cp, 2 * L.adim, L.fout}), N, xa.flags, 1, w.lg_x[l & 1]);
+            const float inv_scale = (float)sqrt((double)L.fout);     // attention.py:121: / math.sqrt(out_dim)
+            CCSD_LAUNCH(k_lg_att, dim3(at * at, L.cin, B), blk, 0, stream, (const float*)w.lg_QKV, L.cp, L.adim, L.nchunk, L.dsplit, 1.0f / inv_scale,
+                        0.5f / (float)L.nchunk, L.cin, N, w.lg_att);
+            CCSD_LAUNCH(k_lg_edge, dim3(w.lg_tiles, B), blk, 0, stream, L.mlp, (const float*)pl->wp, (const float*)w.lg_att, w.lg_S, ss, L.ci0, L.co0,
+                        L.cin, N);
+            CCSD_LAUNCH(k_lg_sym, dim3(grid_for((long long)L.cout * NN, 256), B), blk, 0, stream, w.lg_S, ss, L.co0, L.cout, N, xa.flags);
+            LAUNCH_CHECK();
+        }
+        CCSD_LAUNCH(k_lg_fin, dim3(w.lg_tiles, B), blk, 0, stream, p.a_fin, (const float*)pl->wp, (const float*)w.lg_S, ss, N, xa.flags, xa.adjA,
+                    xa, na, w.lg_part);
+        LAUNCH_CHECK();
+    }
+    CCSD_LAUNCH(k_lg_epi, dim3(B), blk, 0, stream, (const float*)w.lg_xnet, xa.xX, xa.flags, xa, na, (const float*)w.lg_part, w.lg_tiles, N, F);
+    prof_mark(const_cast<ccsd_plan*>(pl), KID_XA, stream);
+    LAUNCH_CHECK();
+    return CCSD_OK;
+}
+
 static int launch_hf(const ccsd_plan* pl, int B, const float* rank2, RankEpi& ep, NoiseArgs& na, Workspace& w, void* stream) {
     const PlanD& p = pl->h;
     dim3 g(xcd_grid(B, ((p.K + T_BN - 1) / T_BN) * ((p.E + T_BM - 1) / T_BM)));
@@ -979,7 +1077,7 @@ static int draws_to_state(ccsd_plan* pl, int32_t B, const float* flags, const cc
         pl->init_off_cap = (size_t)B;
     }
     unsigned long long* offbits = pl->init_off;
-    CCSD_LAUNCH(k_flagbits, dim3(grid_for(B, 256)), dim3(CCSD_NTHREADS), 0, stream, flags, offbits, B, p.N);
+    if (!pl->lg) CCSD_LAUNCH(k_flagbits, dim3(grid_for(B, 256)), dim3(CCSD_NTHREADS), 0, stream, flags, offbits, B, p.N);   // (graph-only on the tiled route: no rank-2 draws read it)
     NoiseArgs na = make_noise(raw, seed, sample_offset, base, flat_r);
     const long long total = (long long)B * (p.N * p.F + p.N * p.N) +
                             (p.is_cc ? (flat_r ? (long long)B * (((long long)p.E * p.K + 3) / 4) : (long long)B * ((p.E + 3) / 4) * p.K) : 0);
@@ -1020,6 +1118,7 @@ extern "C" int ccsd_plan_query(const ccsd_plan_t* pl, int32_t what, int64_t* val
         case CCSD_QUERY_MERGED_R2: *value = (pl->cfg.predictor != CCSD_PRED_S4 && pl->cfg.corrector == CCSD_CORR_LANGEVIN && pl->cfg.n_corr_steps == 1 &&
                                              fused_apply_ok(pl) && merge_ok(pl)) ? 1 : 0; break;
         case CCSD_QUERY_EW1: *value = pl->ew1; break;
+        case CCSD_QUERY_LARGE_GRAPH: *value = pl->lg; break;
         default: return set_err(CCSD_ERR_INVALID, "unknown query");
     }
     return CCSD_OK;

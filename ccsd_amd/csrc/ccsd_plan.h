@@ -15,6 +15,8 @@
 #define CCSD_SMALLW 8     // widest per-thread MLP in the hodge branch
 #define CCSD_FW 16        // widest per-thread MLP in ScoreNetworkF's general path (fused kernel; hodge baseline mlp_hodge)
 #define CCSD_FWMAX 32     // ... in the tiled k_hf_score path
+#define CCSD_XA_MAXN 64   // k_xa: one graph per workgroup, its working set in one CU's LDS (node masks: one 64-bit word per graph)
+#define CCSD_LG_MAXN 512  // tiled graph-network route (ccsd_k_lg.h): ceiling on N (a graph's channel stack, fdim N^2 floats, is indexed in 32 bits)
 
 struct MlpD {
     int n, in, hid, out;
@@ -172,6 +174,8 @@ struct PlanBuilder {
     }
     std::string err;
     int status = CCSD_OK;
+    int lg_force = 0;   // in: CCSD_LARGE_GRAPH=1 (read once by ccsd_plan_create) -- the tiled route for any eligible plan
+    int lg = 0;         // out: the plan takes the tiled graph-network route (ccsd_k_lg.h) instead of k_xa
     int take(int64_t n) {
         int o = cur;
         cur += (int)n;
@@ -269,11 +273,42 @@ static inline int round_ld(int rows) {  // node-row stride of the feature-major 
     return r;
 }
 
+// Why the tiled graph-network route (ccsd_k_lg.h) cannot serve a plan whose networks `p` holds (nullptr: it can).  It covers graph-only
+// plans with the plain ScoreNetworkX and a GCN-conv ScoreNetworkA whose edge MLPs are the 16-wide MFMA chains and whose final MLP is a
+// chained shape (fdim <= 64); ScoreNetworkX_GMH, conv = "MLP" and the combinatorial-complex networks stay with k_xa (N <= 64).
+// dynamic LDS of the route's per-node MLP kernel k_lg_nmlp for one MLP: 16 rows of its input and of two activations (bytes)
+static inline size_t lg_nmlp_lds_of(const MlpD& m) {
+    const int wmax = m.hid > m.out ? m.hid : m.out;
+    return (size_t)16 * ((m.in > wmax ? m.in : wmax) + wmax) * 4;
+}
+static inline size_t lg_nmlp_lds(const PlanD& p) {
+    size_t v = lg_nmlp_lds_of(p.x_fin);
+    for (int l = 0; l < p.a_L; ++l) if (lg_nmlp_lds_of(p.al[l].mc) > v) v = lg_nmlp_lds_of(p.al[l].mc);
+    return v;
+}
+static inline const char* ccsd_lg_ineligible(const ccsd_config_t* c, const PlanD* p) {
+    if (c->is_cc || p->a_is_cc) return "combinatorial-complex plans";
+    if (p->x_gmh) return "ScoreNetworkX_GMH";
+    for (int l = 0; l < p->a_L; ++l) {
+        const AttnLayerD& a = p->al[l];
+        if (a.conv_mlp) return "conv = \"MLP\" attention";
+        if (a.mlp.chain != 1) return "edge MLPs wider than 16 features";
+        if (a.adim > 64) return "attention dimensions above 64";
+    }
+    if (!p->a_fin.chain) return "final MLPs wider than 64 input channels";
+    if (lg_nmlp_lds(*p) > 160 * 1024) return "per-node MLPs whose 16-row activations exceed the 160 KB LDS of a CU";
+    return nullptr;
+}
+
 // Fills `p` (except the affine fold, which needs the weights) and returns the blob size.
 static inline size_t ccsd_build_plan(const ccsd_config_t* c, PlanD* p, PlanBuilder& pb) {
     memset(p, 0, sizeof(*p));
     if (!c || c->abi_version != CCSD_ABI_VERSION) { pb.fail(CCSD_ERR_INVALID, "abi_version mismatch"); return 0; }
-    if (c->N < 2 || c->N > 64 || c->F < 1) { pb.fail(CCSD_ERR_UNSUPPORTED, "need 2 <= N <= 64 and F >= 1"); return 0; }
+    if (c->N < 2 || c->F < 1) { pb.fail(CCSD_ERR_UNSUPPORTED, "need 2 <= N <= 512 and F >= 1"); return 0; }
+    if (c->N > CCSD_LG_MAXN) { pb.fail(CCSD_ERR_UNSUPPORTED, "N = " + std::to_string(c->N) + " exceeds the ceiling of the tiled graph-network route (N <= 512)"); return 0; }
+    // above 64 nodes only the tiled route serves (checked once the networks are known: lg_reason below)
+    const bool big = c->N > CCSD_XA_MAXN;
+    if (big && c->is_cc) { pb.fail(CCSD_ERR_UNSUPPORTED, "combinatorial-complex plans need N <= 64 (the tiled route above 64 nodes is graph-only)"); return 0; }
     int E; int64_t K64;
     ccsd_dims(c, &E, &K64);
     if (c->is_cc && (c->d_min < 1 || c->d_max < c->d_min || c->d_max > c->N)) { pb.fail(CCSD_ERR_INVALID, "bad d_min/d_max"); return 0; }
@@ -449,6 +484,17 @@ static inline size_t ccsd_build_plan(const ccsd_config_t* c, PlanD* p, PlanBuild
         if (ok) p->f_blk = (int)((nweights + 15) & ~(size_t)15);
     }
 
+    // ---- route: tiled graph-network kernels (ccsd_k_lg.h) when k_xa cannot place the plan (N > 64, or no LDS layout below) or when forced
+    const char* lg_reason = ccsd_lg_ineligible(c, p);
+    if (big) {
+        if (lg_reason) { pb.fail(CCSD_ERR_UNSUPPORTED, std::string("N > 64 needs the tiled graph-network route, which does not serve ") + lg_reason); return 0; }
+        pb.lg = 1;
+        p->ldn = round_ld(N);
+        p->chan_rows = p->a_fdim;
+        return nweights;            // (no k_xa layout: its LDS fields stay zero)
+    }
+    if (pb.lg_force && !lg_reason) pb.lg = 1;
+
     // ---- k_xa LDS carve-up
     const int NN = N * N;
     p->ldn = round_ld(N);
@@ -612,8 +658,10 @@ static inline size_t ccsd_build_plan(const ccsd_config_t* c, PlanD* p, PlanBuild
     }
     if (getenv("CCSD_VERBOSE"))
         fprintf(stderr, "[ccsd] k_xa LDS %d B (cg=%d pch=%d/%d pchp=%d/%d stage=%d floats, channel stack in %s)\n", best_total * 4, p->cg, p->pch, p->ldp, p->pchp, p->ldpp, p->wst_floats, p->chan_global ? "HBM" : "LDS");
-    if (best_total < 0 || (size_t)best_total * 4 > 160 * 1024)
-        pb.fail(CCSD_ERR_UNSUPPORTED, "graph-network working set exceeds the 160 KB LDS of a CU");
+    if (best_total < 0 || (size_t)best_total * 4 > 160 * 1024) {
+        if (!lg_reason) pb.lg = 1;         // no k_xa layout: the tiled route serves the plan
+        else pb.fail(CCSD_ERR_UNSUPPORTED, "graph-network working set exceeds the 160 KB LDS of a CU");
+    }
     return nweights;
 }
 

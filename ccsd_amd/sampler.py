@@ -20,6 +20,9 @@ whose files the reference repository does not ship (.MISSING_LARGE_BLOBS).  When
 are read from it in the reference's order (mol_train_node_counts: same indices, same flags for the same numpy seed); otherwise
 the flags come from a shipped histogram -- QM9: the node counts of the shipped test graphs (data/qm9_test_nx.pkl), ZINC250k: a
 discretised normal fit of the dataset's published heavy-atom statistics (node_counts.json notes) -- and the run says so.
+Generic datasets without shipped counts (ENZYMES, grid): the training graphs of the user's <folder>/<data.dir>/<data>.pkl, the file
+the reference loads (graph_train_node_counts, reference order; its test split sets the number of sampling rounds); without it,
+sample(node_counts=...) supplies them.
 """
 from __future__ import annotations
 
@@ -142,6 +145,30 @@ def mol_train_node_counts(config, configt):
     return None
 
 
+def graph_train_node_counts(config, configt):
+    """Node counts of the TRAINING graphs of a generic dataset that node_counts.json does not cover (ENZYMES, grid), from the user's own
+    copy of the dataset -- the file the reference itself loads (data_loader.py:76-81): <folder>/<data.dir>/<data>.pkl, a pickled list of
+    networkx graphs; test_size = int(test_split * len(graph_list)), training split = graph_list[test_size:] in file order.  Returns
+    (counts, test_size), or (None, 0) when the file is not there.  networkx is imported only here (the pickled graphs are its objects)."""
+    data = _get(configt, "data")
+    name = str(_get(data, "data"))
+    folder = _get(configt, "folder", None) or _get(config, "folder", "./")
+    dirs = [_get(data, "dir", "./data"), _get(_get(config, "data"), "dir", None), "data"]
+    for base in dict.fromkeys(os.path.join(folder, d) for d in dirs if d):
+        path = os.path.join(base, f"{name}.pkl")
+        if not os.path.exists(path):
+            continue
+        import pickle
+
+        import networkx  # noqa: F401
+
+        with open(path, "rb") as f:
+            graphs = pickle.load(f)
+        test_size = int(_get(data, "test_split", 0.2) * len(graphs))
+        return np.array([g.number_of_nodes() for g in graphs[test_size:]], dtype=np.int64), test_size
+    return None, 0
+
+
 class Sampler:
     """Common body of the four reference samplers.  The subclasses below carry the reference's per-class differences:
     `IS_MOL` (molecule datasets: one sampling round of sample.n_samples, quantize_mol + relabelling) and `APPLIES_EMA`
@@ -187,7 +214,8 @@ class Sampler:
         return f"{self.__class__.__name__}(is_cc={self.is_cc}, data={_get(_get(self.config, 'data'), 'data')})"
 
     # -- pieces of sample(), reusable on their own
-    def load(self):
+    def load(self, node_counts=None):
+        """`node_counts`: the caller's node counts (sample(node_counts=...)); they stand in when no dataset source is found."""
         cfg = self.config
         self.ckpt_dict = loader.load_ckpt(cfg, self.device, is_cc=self.is_cc)
         self.configt = self.ckpt_dict["config"]
@@ -218,6 +246,12 @@ class Sampler:
                                                        divide_batch=self.divide_batch, **extra)
         counts, self.n_test = train_node_counts(self.configt, with_test_size=True)
         self.node_counts_source = "shipped per-graph node counts of the training split (ccsd_amd/data/node_counts.json)"
+        if counts is None and not self.is_mol:
+            # generic datasets without shipped counts (ENZYMES, grid): the training graphs of the user's dataset copy, reference order
+            counts, n_test = graph_train_node_counts(cfg, self.configt)
+            if counts is not None:
+                self.n_test = n_test
+                self.node_counts_source = "training graphs of the dataset under <folder>/<data.dir> (reference order)"
         if counts is None and self.is_mol:
             # molecule datasets: the training molecules of the user's own dataset copy, as the reference draws them (sampler.py:1162-1194)
             counts = mol_train_node_counts(cfg, self.configt)
@@ -226,18 +260,23 @@ class Sampler:
             with open(_COUNTS) as f:
                 entry = json.load(f).get(_dataset_key(_get(_get(self.configt, "data"), "data")), {})
             counts = entry.get("test_histogram") or entry.get("fallback_histogram")
-            if counts is None:
-                raise FileNotFoundError(f"no node counts for dataset {_get(_get(self.configt, 'data'), 'data')}: pass "
+            if counts is None and node_counts is None:
+                name = _get(_get(self.configt, "data"), "data")
+                raise FileNotFoundError(f"no node counts for dataset {name}: put the dataset's {name}.pkl under <folder>/<data.dir> or pass "
                                         "`node_counts=` to sample()")
-            self.node_counts_source = entry.get("note", "shipped node-count histogram")
-            if self.rank == 0:
+            if counts is None:
+                counts = node_counts
+                self.node_counts_source = "node_counts= of the caller"
+            else:
+                self.node_counts_source = entry.get("note", "shipped node-count histogram")
+            if self.rank == 0 and counts is not node_counts:
                 print(f"init_flags: dataset files not found under {_get(cfg, 'folder', './')}/data -- node counts are drawn from the shipped "
                       f"histogram ({self.node_counts_source})")
         self.node_counts = counts
 
     def sample(self, save: bool = False, node_counts=None, rounds: Optional[int] = None) -> Dict[str, torch.Tensor]:
         cfg = self.config
-        self.load()
+        self.load(node_counts)
         if node_counts is not None:
             self.node_counts = node_counts
         loader.load_seed(_get(_get(cfg, "sample"), "seed", 42))

@@ -164,7 +164,9 @@ enum {
     CCSD_QUERY_FUSED_LOOP = 4,    /* 1: ccsd_sampler_run fuses the Langevin apply into the predictor launches */
     CCSD_QUERY_MERGED_R2 = 5,     /* 1: ... and k_r2 runs the predictor half-step of step i and the rank-2 side of the norms pass of step i + 1
                                      in one launch (one block load per PC step) */
-    CCSD_QUERY_EW1 = 6            /* 1: element-wise rank-2 kernel k_ew1 (affine ScoreNetworkF without a Hodge Laplacian term, cnum = 1) */
+    CCSD_QUERY_EW1 = 6,           /* 1: element-wise rank-2 kernel k_ew1 (affine ScoreNetworkF without a Hodge Laplacian term, cnum = 1) */
+    CCSD_QUERY_LARGE_GRAPH = 7    /* 1: the tiled graph-network kernels k_lg_* serve the graph networks instead of k_xa (graph-only plans above
+                                     64 nodes or without a k_xa LDS layout, up to N = 512; CCSD_LARGE_GRAPH=1 at plan creation forces it) */
 };
 int ccsd_plan_query(const ccsd_plan_t* plan, int32_t what, int64_t* value);
 

@@ -77,6 +77,9 @@ SHIPPED = {
     "gdss_ego_small": ("checkpoints/ego_small/gdss_ego_small.pth", False),
     "gdss_ego_small_retrained": ("checkpoints/ego_small/gdss_ego_small_retrained.pth", False),
     "gdss_enzymes_small_retrained": ("checkpoints/ENZYMES_small/gdss_enzymes_small_retrained.pth", False),
+    # above 64 nodes: the tiled graph-network route (`python tools/make_golden.py large`)
+    "gdss_enzymes": ("checkpoints/ENZYMES/gdss_enzymes.pth", False),
+    "gdss_grid": ("checkpoints/grid/gdss_grid.pth", False),
 }
 SHIPPED_CKPT = os.path.join(GOLD, "ckpt")
 MAX_FIXTURE = 1 << 20                # no committed file exceeds 1 MiB
@@ -187,7 +190,8 @@ def summarize(key, a):
 
 def save_golden(fname, out, summarize_large=False):
     if summarize_large:
-        for k in [k for k, v in out.items() if isinstance(v, np.ndarray) and v.nbytes > SUMMARY_BYTES]:
+        limit = SUMMARY_BYTES if summarize_large is True else int(summarize_large)      # (an int: a lower threshold)
+        for k in [k for k, v in out.items() if isinstance(v, np.ndarray) and v.nbytes > limit]:
             out.update(summarize(k, out.pop(k)))
     path = os.path.join(GOLD, fname)
     np.savez_compressed(path, **out)
@@ -895,10 +899,28 @@ def shipped():
         print("shipped", name)
 
 
+def large_graph():
+    """The two generic-graph checkpoints above 64 nodes (the tiled graph-network route): converted weights under tests/golden/ckpt/,
+    g1 forwards of ENZYMES at B = 3, g5 first steps (arrays above 256 KB as summaries) of the shipped 1000-scale samplers:
+    ENZYMES S4 (sample_enzymes.yaml), grid Reverse + Langevin (sample_grid.yaml)."""
+    enz = dict(predictor="S4", corrector="None", snr=0.15, scale_eps=0.7, n_steps=1)
+    grid = dict(predictor="Reverse", corrector="Langevin", snr=0.1, scale_eps=0.7, n_steps=1)
+    # (grid: no g1 file -- two 361 x 361 inputs alone exceed MAX_FIXTURE; its forward tests take the oracle on the committed weights)
+    for name, g1c, smp, g5c in (("gdss_enzymes", [125, 37, 1], enz, [125, 60]), ("gdss_grid", None, grid, [361, 144])):
+        ck = export_checkpoint(name, SHIPPED, SHIPPED_CKPT)
+        if g1c:
+            g1_network_forwards(name, ck, False, len(g1c), g1c, summarize_large=True)
+        g5_pc_runs(name, ck, False, 2, g5c, smp, {"n1000_first3": (None, 3)}, seed=42, summarize_large=1 << 18)
+        print("large graph", name)
+
+
 def main():
     only = set(sys.argv[1:])
     if only == {"shipped"}:
         shipped()
+        return
+    if only == {"large"}:
+        large_graph()
         return
     cks = {}
     for name in CHECKPOINTS:
