@@ -1,9 +1,17 @@
-// ccsd_api.h -- host side of the C ABI declared in include/ccsd_hip.h: plan construction,
-// workspace carve-up and the launch sequences of one corrector / predictor half-step.
-// Included once by ccsd_hip.hip (product) and by tests/emu/ccsd_emu.cpp (CPU emulation of the same
-// kernels, test infrastructure only).
+// ccsd_api.h -- host side of the C ABI declared in include/ccsd_hip.h: plan construction, workspace carve-up and the launch
+// sequences of one corrector / predictor half-step.  Included once by ccsd_hip.hip (product) and by tests/emu/ccsd_emu.cpp (CPU
+// emulation of the same kernels, test infrastructure only).
+//
+// Which kernel serves a plan is decided ONCE, by resolve_route() at the end of ccsd_plan_create, from (config, the weights'
+// architecture, the Knobs read from the environment at creation): the k_xa / k_r2 instance and its launch entry out of the tables
+// of ccsd_instances.h, the rank-2 family, the compiled-in geometry of the general-path kernels, the form of ccsd_sampler_run's loop.
+// The launchers read the plan's Route; nothing on a launch path compares plans or tests a geometry.  What also depends on the
+// batch of the CALL (threads per graph of k_xa, k_gemm_h_full / k_hp_full at >= 256 complexes, k_normsum's block) is a function of
+// (route, B) next to resolve_route.  ccsd_plan_query reports the Route, on the product and on the emulation alike.
 #pragma once
 #include "ccsd_kernels.h"
+#define CCSD_INST_TABLES
+#include "ccsd_instances.h"
 #include <stdio.h>
 #include <stdlib.h>
 #include <string>
@@ -11,55 +19,6 @@
 
 static thread_local std::string g_last_error;
 static int set_err(int st, const std::string& m) { g_last_error = m; return st; }
-
-// the k_xa variant a plan needs, and its instantiation (for hipFuncSetAttribute)
-static inline bool plan_is_baked(const PlanD& p, const unsigned char* baked, size_t baked_size) {
-    if (baked_size != sizeof(PlanD) || p.geo_off != 0) return false;
-    unsigned char bytes[sizeof(PlanD)];
-    ccsd_plan_arch_bytes(p, bytes);
-    return memcmp(bytes, baked, sizeof(PlanD)) == 0;
-}
-static inline int xa_variant_sem(const PlanD& p) {          // what the network needs: XA_PLAIN / XA_HB / XA_GMH / XA_GEN
-    bool conv_mlp = false;
-    for (int l = 0; l < p.a_L; ++l) conv_mlp = conv_mlp || p.al[l].conv_mlp;
-    if (p.x_gmh) for (int l = 0; l < p.x_depth; ++l) conv_mlp = conv_mlp || p.gl[l].conv_mlp;
-    if (conv_mlp || (p.hb_L && p.x_gmh) || p.h_L > 2) return XA_GEN;
-    // the small-graph XA_PLAIN / XA_GMH variants are compiled without the two widest final-MLP chain shapes (ccsd_k_xa.h: they cost
-    // them their registers -- 30 VGPRs spilled around the final MLP of every launch); the HodgeBaseline networks need them
-    if (!p.chan_global && !p.hb_L && p.a_fin.chain >= 5) return XA_GEN;
-    if (p.hb_L) return XA_HB;
-    if (p.x_gmh) return XA_GMH;
-    return XA_PLAIN;
-}
-static inline int xa_variant(const PlanD& p) {
-    const int sem = xa_variant_sem(p);
-    // instances with the WHOLE plan as a compile-time constant: only for a plan whose architecture bytes equal a baked one's
-    // (tools/bake_plan.py; ccsd_baked_*.h), and only in the instantiation the bake was made for
-    if (sem == XA_PLAIN && !p.chan_global && plan_is_baked(p, CCSD_BAKED_QM9_PLAN, CCSD_BAKED_QM9_SIZE)) return XA_BAKED9;
-    if (sem == XA_PLAIN && p.chan_global && plan_is_baked(p, CCSD_BAKED_CS_PLAN, CCSD_BAKED_CS_SIZE)) return XA_BAKED20;
-    if (sem == XA_PLAIN && p.chan_global && plan_is_baked(p, CCSD_BAKED_Z_PLAN, CCSD_BAKED_Z_SIZE)) return XA_BAKED38;
-    if (sem == XA_GEN && !p.chan_global && plan_is_baked(p, CCSD_BAKED_ENZ_PLAN, CCSD_BAKED_ENZ_SIZE)) return XA_BAKEDENZ;
-    if (sem != XA_PLAIN || p.geo_off == 1) return sem;
-    // instances with the dataset geometry compiled in
-    if (!p.chan_global && p.N == 9 && p.F == 4 && p.E == 36 && p.ldn == 16) return XA_PLAIN9;
-    if (p.chan_global && p.N == 20 && p.E == 190 && p.ldn == 24) return XA_PLAIN20;
-    if (p.chan_global && p.N == 38 && p.E == 703 && p.ldn == 40) return XA_PLAIN38;
-    return XA_PLAIN;
-}
-static inline const void* xa_kernel(const PlanD& p) {
-    const int v = xa_variant(p);
-#define XA_FN(G_) (v == XA_HB ? (const void*)k_xa<G_, XA_HB> : v == XA_GMH ? (const void*)k_xa<G_, XA_GMH> : \
-                   v == XA_GEN ? (const void*)k_xa<G_, XA_GEN> : (const void*)k_xa<G_, XA_PLAIN>)
-    if (v == XA_PLAIN9) return (const void*)k_xa<false, XA_PLAIN9>;
-    if (v == XA_BAKED9) return (const void*)k_xa<false, XA_BAKED9>;
-    if (v == XA_BAKEDENZ) return (const void*)k_xa<false, XA_BAKEDENZ>;
-    if (v == XA_PLAIN20) return (const void*)k_xa<true, XA_PLAIN20>;
-    if (v == XA_BAKED20) return (const void*)k_xa<true, XA_BAKED20>;
-    if (v == XA_PLAIN38) return (const void*)k_xa<true, XA_PLAIN38>;
-    if (v == XA_BAKED38) return (const void*)k_xa<true, XA_BAKED38>;
-    return p.chan_global ? XA_FN(true) : XA_FN(false);
-#undef XA_FN
-}
 
 // widest layer of ScoreNetworkF's per-element MLPs
 static inline int fnet_width(const PlanD& p) {
@@ -72,6 +31,89 @@ static inline int fnet_width(const PlanD& p) {
     if (p.f_fin.n > 1 && p.f_fin.hid > fw) fw = p.f_fin.hid;
     return fw;
 }
+
+// Every switch the library takes from the environment; read_knobs() is the only reader and runs first in ccsd_plan_create.
+//   variable             field                 effect                                                          set by
+//   CCSD_NO_FUSED_R2     no_fused_r2           no LDS-resident k_r2: the tiled / element-wise rank-2 kernels   tests (emu + gpu)
+//   CCSD_HODGE_GENERAL   hodge_general         general hodge stack for any plan with > 2 hodge layers          tests
+//   CCSD_NO_GEO          geo_off = 1           no instance with a geometry or plan compiled in                 tests (emu + gpu)
+//   CCSD_NO_BAKE         geo_off = 2           geometry instances yes, baked-plan instances no                 tests (gpu), tools/dev
+//   CCSD_NO_FUSED_APPLY  no_fused_apply        Langevin apply as a launch of its own in ccsd_sampler_run       tests (emu + gpu)
+//   CCSD_NO_H_FULL       no_h_full             k_gemm_h's 64 x 64 tiles instead of k_gemm_h_full / k_hp_full   tests (gpu)
+//   CCSD_NO_HP_FULL      no_hp_full            k_gemm_p0 + k_gemm_h_full instead of the one k_hp_full pass     tests (gpu)
+//   CCSD_HP_FULL_NORMS   hp_full_norms         k_hp_full in the norms pass too (slower: A/B only)              tests (gpu)
+//   CCSD_SPLIT_BF16=3    split_bf16            EXPERIMENT: split-precision k_gemm_h_full, NOT bit-identical    tests (gpu), bench.py, tools/dev
+//   CCSD_XA_THREADS      xa_threads            threads per graph of k_xa (64 .. 1024; 0 = by batch)            tests (gpu)
+//   CCSD_XA_PRIO         xa_prio               k_xa issue-priority scheme     } their other half is kernel     tools/dev
+//   CCSD_XA_STAGGER      xa_stagger_*          "mask,sleep" start stagger     } code: removing them is a       tools/dev
+//   CCSD_R2_STAGGER      r2_stagger_*          "mask,sleep" start stagger     } follow-up with the kernels     nobody
+//   CCSD_LARGE_GRAPH=1   lg_force              tiled graph-network route for any eligible plan  (PlanBuilder)  tests (emu + gpu)
+//   CCSD_XA_PASS=<n>     xa_pass               first k_xa LDS budget candidate tried            (PlanBuilder)  tests (emu + gpu)
+//   CCSD_XA_GCH          xa_gch                channel stack in the HBM workspace first         (PlanBuilder)  tests (emu + gpu)
+//   CCSD_NO_MLP_WT       no_mlp_wt             no transposed copies of the non-chained MLPs     (PlanBuilder)  tests (gpu)
+//   CCSD_VERBOSE         verbose               print the k_xa LDS layout                        (PlanBuilder)  by hand
+//   CCSD_DUMP_PLAN[_NAME] dump_plan[_name]     write the plan's architecture bytes as a C header               tools/bake_plan.py
+struct Knobs {
+    int no_fused_r2 = 0, hodge_general = 0, geo_off = 0, no_fused_apply = 0, no_h_full = 0, no_hp_full = 0, hp_full_norms = 0, split_bf16 = 0;
+    int xa_threads = 0, xa_prio = 0, xa_stagger_mask = 0, xa_stagger_sleep = 0, r2_stagger_mask = 0, r2_stagger_sleep = 0;
+    int lg_force = 0, xa_pass = -1, xa_gch = 0, no_mlp_wt = 0, verbose = 0;
+    const char *dump_plan = nullptr, *dump_plan_name = nullptr;
+};
+static Knobs read_knobs() {
+    Knobs k;
+    auto on = [](const char* name) { return getenv(name) != nullptr; };
+    k.no_fused_r2 = on("CCSD_NO_FUSED_R2"); k.hodge_general = on("CCSD_HODGE_GENERAL");
+    k.geo_off = on("CCSD_NO_GEO") ? 1 : on("CCSD_NO_BAKE") ? 2 : 0;
+    k.no_fused_apply = on("CCSD_NO_FUSED_APPLY"); k.no_h_full = on("CCSD_NO_H_FULL"); k.no_hp_full = on("CCSD_NO_HP_FULL");
+    k.hp_full_norms = on("CCSD_HP_FULL_NORMS");
+    if (const char* v = getenv("CCSD_SPLIT_BF16")) k.split_bf16 = atoi(v) == 3 ? 3 : 0;
+    if (const char* v = getenv("CCSD_XA_THREADS")) { const int t = atoi(v); if (t >= 64 && t <= 1024 && t % 64 == 0) k.xa_threads = t; }
+    if (const char* v = getenv("CCSD_XA_PRIO")) k.xa_prio = atoi(v);
+    if (const char* v = getenv("CCSD_XA_STAGGER")) sscanf(v, "%d,%d", &k.xa_stagger_mask, &k.xa_stagger_sleep);
+    if (const char* v = getenv("CCSD_R2_STAGGER")) sscanf(v, "%d,%d", &k.r2_stagger_mask, &k.r2_stagger_sleep);
+    if (const char* v = getenv("CCSD_LARGE_GRAPH")) k.lg_force = atoi(v) == 1;
+    if (const char* v = getenv("CCSD_XA_PASS")) k.xa_pass = atoi(v);
+    k.xa_gch = on("CCSD_XA_GCH"); k.no_mlp_wt = on("CCSD_NO_MLP_WT"); k.verbose = on("CCSD_VERBOSE");
+    k.dump_plan = getenv("CCSD_DUMP_PLAN"); k.dump_plan_name = getenv("CCSD_DUMP_PLAN_NAME");
+    return k;
+}
+
+// Which kernels serve a plan: fixed by (config, the weights' architecture, knobs), resolved once by resolve_route().
+enum { R2_NONE = 0, R2_FUSED = 1, R2_EW1 = 2, R2_TILED = 3 };       // rank-2 family: graph-only / k_r2 / k_ew1 / k_gemm_h + k_hf_score
+// form of ccsd_sampler_run's loop (LOOP_STEPWISE: Langevin with n_corr_steps != 1, which the call refuses)
+enum { LOOP_PRED_ONLY = 0, LOOP_LANGEVIN = 1, LOOP_LANGEVIN_FUSED = 2, LOOP_S4 = 3, LOOP_STEPWISE = 4 };
+struct Route {
+    // graph-network side
+    int lg = 0;                     // tiled route (ccsd_k_lg.h) instead of k_xa: graph-only plans k_xa cannot place (N > 64, no LDS layout), or
+                                    // any eligible plan under CCSD_LARGE_GRAPH=1; launch_xa hands such plans to launch_lg
+    int xa_variant = 0;             // XA_* (what CCSD_QUERY_XA_VARIANT reports)
+    const XaEntry* xa = nullptr;    // its instance, and the run-time-geometry twin that serves launches of a fixed-256 instance with
+    const XaEntry* xa_twin = nullptr;   // another (diagnostic) thread count
+    int xa_threads = 0;             // CCSD_XA_THREADS (0: by batch, xa_launch)
+    // rank-2 side
+    int r2_family = R2_NONE;
+    const R2Entry* r2 = nullptr;    // R2_FUSED: the k_r2 instance
+    int r2_ldk = 0, r2_ldh = 0;     // ... and its LDS geometry
+    size_t r2_lds = 0;
+    // general hodge stack: more than two HodgeAdjAttentionLayers whose later projections cannot be folded into rank2's (a non-affine
+    // mlp_value, or no fused rank-2 kernel for the geometry): R_l is materialised layer by layer (k_hodge_value) from the dense hodge
+    // adjacencies k_xa<., XA_GEN> dumps (launch_xa); CCSD_HODGE_GENERAL forces it for any plan with more than two layers
+    int h_general = 0;
+    int geo = 0;                    // index of the plan's (E, K) in CCSD_GEO_LIST (0: run-time values)
+    int p0 = -1;                    // index of the narrow layer-0 projection's k_gemm_p0 in CCSD_P0_LIST (-1: wide, k_gemm_p)
+    int h_full = 0;                 // launch_h's H = F F^T may come from k_gemm_h_full (use_h_full)
+    unsigned hp_full_modes = 0;     // P0Fuse modes whose pass k_hp_full may serve, one bit each (use_hp_full)
+    // ccsd_sampler_run
+    int loop = LOOP_PRED_ONLY;
+    int merged = 0;                 // LOOP_LANGEVIN_FUSED: k_r2 runs predictor i and the rank-2 side of norms pass i + 1 in one launch
+    int tiled_fuse = 0;             // tiled rank-2 path, ONE hodge layer: the corrector's rank2 work rides on the layer-0 projection pass
+    int ew1_fuse = 0;               // k_ew1 plans, ONE hodge layer: the whole rank-2 side of a half-step rides on it (P0Fuse modes 3 / 4)
+    // The Langevin corrector's rank2 draws are keyed by flat groups of four consecutive elements (NoiseArgs::flat_r): they are
+    // generated where rank2 streams through registers in 16-byte pieces (k_r2's block load, k_langevin_apply, k_noise_norm).
+    // Priors, predictor draws and the three draws of an S4 step keep the 4-row groups of the MFMA epilogues -- except on k_ew1
+    // plans, whose kernel streams 16-byte pieces for every draw.
+    int corrector_flat = 0, predictor_flat = 0;
+};
 
 struct ccsd_plan {
     ccsd_config_t cfg;
@@ -88,33 +130,8 @@ struct ccsd_plan {
     long long* dbg = nullptr;   // diagnostic cycle stamps (ccsd_debug_stamps)
     unsigned long long* init_off = nullptr;   // device: off-bit table of ccsd_init_state (which takes no workspace), grown on demand
     size_t init_off_cap = 0;
-    // fused rank-2 kernel (k_r2): eligibility and LDS geometry
-    int fused_r2 = 0, r2_ldk = 0, r2_ldh = 0;
-    size_t r2_lds = 0;
-    // element-wise rank-2 side (k_ew1): affine ScoreNetworkF without a Hodge Laplacian term (cnum = 1), tiled path, PC samplers
-    int ew1 = 0;
-    // general hodge stack: more than two HodgeAdjAttentionLayers whose later projections cannot be folded into rank2's (a non-affine
-    // mlp_value, or no fused rank-2 kernel for the geometry): R_l is materialised layer by layer (k_hodge_value) from the dense hodge
-    // adjacencies k_xa<., XA_GEN> dumps (launch_xa); CCSD_HODGE_GENERAL forces it for any plan with more than two layers (diagnostic)
-    int h_general = 0;
-    // tiled graph-network route (ccsd_k_lg.h): graph-only plans k_xa cannot place (N > 64, or no LDS layout), or any eligible plan
-    // when CCSD_LARGE_GRAPH=1 was set at plan creation; launch_xa hands such plans to launch_lg
-    int lg = 0;
-    // diagnostic knobs, read from the environment ONCE at plan creation (never on the launch path):
-    // CCSD_OLD_GEMM_P, CCSD_XA_THREADS, CCSD_NO_FUSED_APPLY (CCSD_NO_FUSED_R2 / CCSD_XA_PASS / CCSD_XA_GCH / CCSD_NO_CHAIN shape the plan itself)
-    int opt_old_gemm_p = 0, opt_xa_threads = 0, opt_no_fused_apply = 0;   // opt_xa_threads: 0 = by batch (launch_xa)
-    int opt_r2_stagger_mask = 0, opt_r2_stagger_sleep = 0;     // CCSD_R2_STAGGER="mask,sleep" (diagnostic)
-    int opt_xa_prio = 0;                                       // CCSD_XA_PRIO (diagnostic: k_xa issue-priority scheme)
-    int opt_xa_stagger_mask = 0, opt_xa_stagger_sleep = 0;     // CCSD_XA_STAGGER="mask,sleep" (diagnostic)
-    int opt_no_merge = 0;                                      // CCSD_NO_MERGE (diagnostic: separate norms / predictor k_r2 launches)
-    int opt_hp_full_norms = 0;                                 // CCSD_HP_FULL_NORMS (diagnostic: k_hp_full in the norms pass too)
-    int opt_no_hp_full = 0;                                    // CCSD_NO_HP_FULL (diagnostic: k_gemm_p0<., ., 1 / 2> + k_gemm_h_full instead of the one fused pass)
-    // EXPERIMENT, never the default (CCSD_SPLIT_BF16=3): split-precision ("bf16 x 3") MFMA contraction in k_gemm_h_full, the norms pass's
-    // H = F F^T of the community_small geometry (split_frag / split_mma, ccsd_k_rank2.h); results are NOT bit-identical to fp32
-    int opt_split_bf16 = 0;
-    int opt_no_h_full = 0;                                     // CCSD_NO_H_FULL (diagnostic: k_gemm_h's 64 x 64 tiles for the community_small geometry too)
-    int opt_no_tiled_fuse = 0;                                 // CCSD_NO_TILED_FUSE (diagnostic: k_noise_norm / k_langevin_apply as launches of their own on the tiled path)
-    int opt_r2_masked = 1;                                     // CCSD_NO_R2_MASKED clears it (diagnostic: the loop's k_r2 launches re-mask rank2 in the Q_1 loader)
+    Knobs knobs;                // the environment, read ONCE at plan creation (read_knobs)
+    Route rt;                   // which kernels serve the plan (resolve_route)
     // optional per-kernel timing with HIP events on the launch stream (bench.py roofline leg)
     unsigned prof_mask = 0;
     size_t prof_used[8] = {0, 0, 0, 0, 0, 0, 0, 0};
@@ -155,53 +172,136 @@ static void prof_mark(ccsd_plan* pl, int kid, void* stream) {
         if (_e != RT_OK) return set_err(CCSD_ERR_RUNTIME, std::string("kernel launch: ") + rt_error_string(_e)); \
     } while (0)
 
-// Instantiation of the fused rank-2 kernel for a plan: (MT, RS) from E -- MT = ceil(E / 16) row tiles, RS = plain MFMA steps
-// covering E mod 16 behind the full 16-wide blocks of phase 2's contraction index (0: last block taken whole) --, AFFINE
-// ScoreNetworkF, general hodge mlp_value.  RS only shapes the affine phase 2; the non-affine kernels are instantiated with RS = 0.
-static inline void r2_shape(const ccsd_plan* pl, int* MT, int* RS, bool* aff, bool* gen1) {
-    const int E = pl->h.E, rem = E & 15;
-    *MT = (E + 15) / 16;
-    *aff = pl->h.f_affine != 0;
-    *gen1 = pl->h.h_L > 1 && pl->h.hl[0].mval.n > 1;
-    *RS = (!*aff || rem == 0 || rem > 12) ? 0 : (rem + 3) / 4;
-}
-// X(MT, RS, AFFINE, GEN1) is expanded for the plan's combination
-#define R2_CASE(MT_, RS_, X) \
-    if (mt_ == MT_ && rs_ == RS_) { \
-        if (aff_ && !gen1_) { X(MT_, RS_, true, false); } else if (aff_) { X(MT_, RS_, true, true); } \
-        else if (!gen1_) { X(MT_, 0, false, false); } else { X(MT_, 0, false, true); } \
-    }
-// non-affine ScoreNetworkF: RS is always 0 (r2_shape), every MT has its instance (CCSD_R2_GEN)
-#define R2_CASE_GEN(MT_, X) \
-    if (!aff_ && mt_ == MT_) { if (!gen1_) { X(MT_, 0, false, false); } else { X(MT_, 0, false, true); } }
-#define R2_DISPATCH(pl_, X) \
-    do { \
-        int mt_, rs_; bool aff_, gen1_; \
-        r2_shape(pl_, &mt_, &rs_, &aff_, &gen1_); \
-        /* E = N (N - 1) / 2 <= 64, i.e. E in {1, 3, 6, 10, 15, 21, 28, 36, 45, 55}: the (MT, RS) pairs that occur */ \
-        R2_CASE_GEN(1, X) else R2_CASE_GEN(2, X) else R2_CASE_GEN(3, X) else R2_CASE_GEN(4, X) \
-        else R2_CASE(1, 0, X) else R2_CASE(1, 1, X) else R2_CASE(1, 2, X) else R2_CASE(1, 3, X) \
-        else R2_CASE(2, 2, X) else R2_CASE(2, 3, X) else R2_CASE(3, 0, X) else R2_CASE(3, 1, X) else R2_CASE(4, 2, X) \
-    } while (0)
-// the instances with the qm9 geometry compiled in: 1 = k_r2<3, 1, true, false, 1> (geometry only), 2 = <..., 2> (the whole baked plan:
-// only when the plan's architecture bytes equal ccsd_baked_qm9.h), 0 = the run-time-geometry instances
-static inline int r2_qm9(const ccsd_plan* pl) {
+// ---------------- route ----------------
+// Decides every field of pl->rt (but rt.lg, the planner's verdict) and nothing else; runs once, at the end of ccsd_plan_create.
+static int resolve_route(ccsd_plan* pl) {
     const PlanD& p = pl->h;
-    const bool gen1 = p.h_L > 1 && p.hl[0].mval.n > 1;
-    if (p.geo_off == 1 || gen1 || p.E != 36 || p.K != 466 || p.N != 9 || pl->r2_ldk != 488 || pl->r2_ldh != 36) return 0;
-    if (!p.f_affine) return 3;                           // k_r2<3, 0, false, false, 1>: the non-affine network on the qm9 geometry
-    return plan_is_baked(p, CCSD_BAKED_QM9_PLAN, CCSD_BAKED_QM9_SIZE) ? 2 : 1;
+    const ccsd_config_t& c = pl->cfg;
+    const Knobs& k = pl->knobs;
+    Route& r = pl->rt;
+    const int E = p.E, K = p.K;
+    const bool s4 = c.predictor == CCSD_PRED_S4, langevin = c.corrector == CCSD_CORR_LANGEVIN;
+    // instances with the WHOLE plan as a compile-time constant: only for a plan whose architecture bytes equal a baked one's
+    // (tools/bake_plan.py; ccsd_baked_*.h), and only in the instantiation the bake was made for
+    unsigned char arch[sizeof(PlanD)];
+    ccsd_plan_arch_bytes(p, arch);
+    auto baked = [&](const unsigned char* plan, size_t size) { return size == sizeof(PlanD) && p.geo_off == 0 && memcmp(arch, plan, size) == 0; };
+
+    // ---- graph-network side: what the network needs (XA_PLAIN / XA_HB / XA_GMH / XA_GEN), then the instance that has it compiled in
+    bool conv_mlp = false;
+    for (int l = 0; l < p.a_L; ++l) conv_mlp = conv_mlp || p.al[l].conv_mlp;
+    if (p.x_gmh) for (int l = 0; l < p.x_depth; ++l) conv_mlp = conv_mlp || p.gl[l].conv_mlp;
+    int v = p.hb_L ? XA_HB : p.x_gmh ? XA_GMH : XA_PLAIN;
+    // the small-graph XA_PLAIN / XA_GMH variants are compiled without the two widest final-MLP chain shapes (ccsd_k_xa.h: they cost
+    // them their registers -- 30 VGPRs spilled around the final MLP of every launch); the HodgeBaseline networks need them
+    if (conv_mlp || (p.hb_L && p.x_gmh) || p.h_L > 2 || (!p.chan_global && !p.hb_L && p.a_fin.chain >= 5)) v = XA_GEN;
+    if (v == XA_PLAIN && !p.chan_global && baked(CCSD_BAKED_QM9_PLAN, CCSD_BAKED_QM9_SIZE)) v = XA_BAKED9;
+    else if (v == XA_PLAIN && p.chan_global && baked(CCSD_BAKED_CS_PLAN, CCSD_BAKED_CS_SIZE)) v = XA_BAKED20;
+    else if (v == XA_PLAIN && p.chan_global && baked(CCSD_BAKED_Z_PLAN, CCSD_BAKED_Z_SIZE)) v = XA_BAKED38;
+    else if (v == XA_GEN && !p.chan_global && baked(CCSD_BAKED_ENZ_PLAN, CCSD_BAKED_ENZ_SIZE)) v = XA_BAKEDENZ;
+    else if (v == XA_PLAIN && p.geo_off != 1)
+        for (const auto& g : XA_GEO_TABLE)
+            if ((p.chan_global != 0) == (g.gch != 0) && p.N == g.N && (!g.F || p.F == g.F) && E == g.E && p.ldn == g.ldn) v = g.var;
+    r.xa_variant = v;
+    r.xa_threads = k.xa_threads;
+    for (const XaEntry& e : XA_TABLE) {
+        if ((e.gch != 0) != (p.chan_global != 0)) continue;
+        if (e.var == v) r.xa = &e;
+        if (e.var == XA_PLAIN) r.xa_twin = &e;
+    }
+    if (!r.xa || !r.xa_twin) return set_err(CCSD_ERR_RUNTIME, "k_xa variant " + std::to_string(v) + " has no instance in CCSD_XA_LIST");
+    if (!r.xa->fixed256) r.xa_twin = nullptr;
+
+    // ---- rank-2 side.  Fused path: one complex's rank2 block (E x K) LDS-resident, E <= 64
+    const bool aff = p.f_affine != 0, gen1 = p.h_L > 1 && p.hl[0].mval.n > 1;
+    const int mt = (E + 15) / 16, rem = E & 15, rs = (!aff || rem == 0 || rem > 12) ? 0 : (rem + 3) / 4;
+    auto r2_find = [&](int qm9) -> const R2Entry* {
+        for (const R2Entry& e : R2_TABLE)
+            if (e.mt == mt && e.rs == rs && (e.affine != 0) == aff && (e.gen1 != 0) == gen1 && e.qm9 == qm9) return &e;
+        return nullptr;
+    };
+    bool fused = false;
+    if (c.is_cc && E <= 64 && !k.no_fused_r2) {
+        const int Kp4 = (K + 31) & ~31, Ep4 = (E + 3) & ~3;   // K zero-padded to whole 8-step MFMA batches
+        int ldk = Kp4; while ((ldk & 31) != 8 && (ldk & 31) != 24) ldk += 4;   // conflict-free ds_read_b128 fragment reads (16 rows x 4 k-quads)
+        const int ldh = Ep4;                                                 // 16-byte aligned rows: phase 2 re-reads H's fragments per column tile as ds_read_b128
+        const size_t fl = (size_t)E * ldk + (size_t)E * ldh + 64 * 2 + (size_t)p.a_cinit * E + 3 * c.N * c.N + 64 + (Kp4 + 3) / 4 + 4;
+        // (the fused kernel's per-element MLPs are padded to <= 16; more Hodge powers than two: tiled kernels)
+        if (fl * 4 + 64 <= 160 * 1024 && fnet_width(p) <= CCSD_FW && r2_find(0) && p.f_cnum <= 2) {
+            fused = true; r.r2_ldk = ldk; r.r2_ldh = ldh; r.r2_lds = fl * 4;
+            // the instances with the qm9 geometry compiled in (QM9 = 1), or the whole baked plan (2: affine ScoreNetworkF only)
+            const bool qm9 = p.geo_off != 1 && !gen1 && E == CCSD_R2_QM9_E && K == CCSD_R2_QM9_K && p.N == CCSD_R2_QM9_N &&
+                             ldk == CCSD_R2_QM9_LDK && ldh == CCSD_R2_QM9_LDH;
+            r.r2 = r2_find(!qm9 ? 0 : aff && baked(CCSD_BAKED_QM9_PLAN, CCSD_BAKED_QM9_SIZE) ? 2 : 1);
+            if (!r.r2) return set_err(CCSD_ERR_RUNTIME, "k_r2: the qm9-geometry instance is missing from CCSD_R2_LIST_*");
+        }
+    }
+    if (p.h_L > 2) {
+        bool affine_values = true;
+        for (int l = 0; l + 1 < p.h_L; ++l) affine_values = affine_values && ccsd_hl(p, l).mval.n == 1;
+        // (the folded route -- k_r2 hands over one consolidated projection, k_xa chains the M_j -- is built and tested for up to four layers;
+        // r2_lds keeps reporting what the fused kernel would have taken)
+        if (!affine_values || !fused || p.h_L > 4 || k.hodge_general) { r.h_general = 1; fused = false; r.r2 = nullptr; }
+    }
+    // element-wise rank-2 side (k_ew1): affine ScoreNetworkF without a Hodge Laplacian term (cnum = 1), tiled path, PC samplers
+    const bool ew1 = c.is_cc && !fused && aff && p.f_cnum == 1 && !s4;
+    r.r2_family = !c.is_cc ? R2_NONE : fused ? R2_FUSED : ew1 ? R2_EW1 : R2_TILED;
+    if (p.geo_off != 1) for (const GeoEntry& g : GEO_TABLE) if (E == g.E && K == g.K) r.geo = g.idx;
+    if (p.h_L >= 1) {       // narrow layer-0 projection (at most four 16-column tiles): no 64-column padding, K compiled in where listed
+        auto p0_find = [&](int kc) {
+            for (int i = 0; i < (int)(sizeof(P0_TABLE) / sizeof(P0_TABLE[0])); ++i)
+                if (P0_TABLE[i].nt == (p.hl[0].wc + 15) / 16 && P0_TABLE[i].kc == kc) return i;
+            return -1;
+        };
+        if (p.geo_off != 1) r.p0 = p0_find(K);
+        if (r.p0 < 0) r.p0 = p0_find(0);
+    }
+    // tiled rank-2 path (k_gemm_h / k_gemm_p0 / k_hf_score: community_small_CC) with ONE hodge layer: the corrector's rank2 work rides on
+    // the layer-0 projection pass (P0Fuse) -- flat-keyed corrector draws, K a multiple of 4 (a Philox group = one 16-byte piece of a row)
+    r.tiled_fuse = r.r2_family == R2_TILED && p.h_L == 1 && (K & 3) == 0 && !s4 && langevin;
+    // k_ew1 plans with ONE hodge layer: one read of rank2 per norms pass, one read + one write per predictor pass (P0Fuse modes 3 / 4)
+    r.ew1_fuse = ew1 && p.h_L == 1 && (K & 3) == 0 && langevin;
+    // community_small geometry: one workgroup per complex, F streamed once (k_gemm_h_full; bit-identical), and ONE fused pass per
+    // half-step (k_hp_full) instead of k_gemm_p0<., ., 1 / 2> + k_gemm_h_full.  In the norms pass (mode 1, whose only extra is the
+    // noise norm) the fused pass is slower -- 370 us against 129 + 213, the eight waves of the one workgroup a CU holds run in
+    // lockstep --: CCSD_HP_FULL_NORMS turns it on for A/B
+    const bool full_geo = c.is_cc && E == CCSD_FULL_E && K == CCSD_FULL_K && p.geo_off != 1 && !k.no_h_full;
+    r.h_full = full_geo && r.r2_family == R2_TILED && p.f_cnum >= 2;
+
+    // ---- ccsd_sampler_run.  The Langevin apply fuses into the predictor launches of k_r2 plans, of k_ew1 plans whose hodge
+    // projections do not depend on the adjacency (at most one hodge layer) and of tiled plans with one hodge layer
+    const bool fused_apply = (fused || (ew1 && p.h_L <= 1) || r.tiled_fuse) && !k.no_fused_apply;
+    r.loop = s4 ? LOOP_S4 : !langevin ? LOOP_PRED_ONLY : c.n_corr_steps != 1 ? LOOP_STEPWISE : fused_apply ? LOOP_LANGEVIN_FUSED : LOOP_LANGEVIN;
+    // merged k_r2 launches (predictor of step i + rank-2 side of the norms pass of step i + 1): the row-strip instantiation of the
+    // kernel (E = 33..36, affine ScoreNetworkF, linear mlp_value), pair-wise block load (K even, E K a multiple of 4)
+    // (k_hp_full's mode 2 is the fused apply: only the fused loop's predictor pass carries it)
+    if (full_geo && r.tiled_fuse && p.hl[0].wc <= 16 && p.f_cnum == 2 && !k.no_hp_full)
+        r.hp_full_modes = (r.loop == LOOP_LANGEVIN_FUSED ? 1u << 2 : 0u) | (k.hp_full_norms ? 1u << 1 : 0u);
+    r.merged = r.loop == LOOP_LANGEVIN_FUSED && fused && mt == 3 && rs == 1 && aff && !gen1 && (K & 1) == 0 && ((E * K) & 3) == 0;
+    r.corrector_flat = !s4;
+    r.predictor_flat = ew1;
+    return CCSD_OK;
 }
-static inline const void* r2_kernel(const ccsd_plan* pl) {
-    if (r2_qm9(pl) == 2) return (const void*)k_r2<3, 1, true, false, 2>;
-    if (r2_qm9(pl) == 1) return (const void*)k_r2<3, 1, true, false, 1>;
-    if (r2_qm9(pl) == 3) return (const void*)k_r2<3, 0, false, false, 1>;
-    const void* fn = nullptr;
-#define R2_PTR(MT_, RS_, A_, G_) fn = (const void*)k_r2<MT_, RS_, A_, G_>
-    R2_DISPATCH(pl, R2_PTR);
-#undef R2_PTR
-    return fn;
+// ---- what also depends on the batch of the call
+static inline bool use_h_full(const Route& r, int B) { return r.h_full && B >= 256; }      // at least one complex per CU
+static inline bool use_hp_full(const Route& r, int B, int mode) { return B >= 256 && ((r.hp_full_modes >> mode) & 1u); }
+#define HP_FULL_LDS ((size_t)(2 * 192 * H_LD + 2 * 16 * H_LD) * 4)       /* dynamic LDS of k_hp_full */
+// Threads per graph of k_xa, and the instance that takes them.  256 (four waves) is right when the batch fills the chip -- 1024 graphs =
+// four co-resident workgroups per CU -- and k_xa is bound by the latency of one graph's critical path either way; when the batch leaves
+// a CU with one or two workgroups (B <= 256 / <= 512) the same graph runs on sixteen / eight waves: every per-pair, per-tile and
+// per-element loop of the kernel strides by the workgroup's thread count (zinc250k B = 256: 419 -> 293 us per launch;
+// community_small_CC B = 512: 418 -> 349 us; ENZYMES_small_CC B = 64: 236 -> 180 us).  Only the instances compiled for 4 waves per SIMD
+// without a fixed thread count take more than 256 (CCSD_XA_LIST); CCSD_XA_THREADS overrides the choice (diagnostic) and moves a plan
+// off an instance that has its 256 compiled in, to the run-time-geometry twin.
+static inline const XaEntry* xa_launch(const Route& r, int B, int* threads) {
+    const XaEntry* e = r.xa;
+    int t = r.xa_threads;
+    if (t == 0) t = e->max_threads == 256 ? 256 : B <= 256 ? 1024 : B <= 512 ? 512 : 256;
+    if (e->fixed256 && t != 256) e = r.xa_twin;
+    *threads = t > e->max_threads ? e->max_threads : t;
+    return e;
 }
+static inline int normsum_threads(int B) { return B > 512 ? 1024 : B > 256 ? 512 : 256; }
 
 extern "C" const char* ccsd_last_error(void) { return g_last_error.c_str(); }
 
@@ -278,25 +378,13 @@ extern "C" int ccsd_plan_create(const ccsd_config_t* cfg, const float* weights, 
     *out = nullptr;
     ccsd_plan* pl = new ccsd_plan();
     pl->cfg = *cfg;
-    pl->opt_old_gemm_p = getenv("CCSD_OLD_GEMM_P") != nullptr;
-    pl->opt_no_fused_apply = getenv("CCSD_NO_FUSED_APPLY") != nullptr;
-    pl->opt_no_merge = getenv("CCSD_NO_MERGE") != nullptr;
-    pl->opt_r2_masked = getenv("CCSD_NO_R2_MASKED") == nullptr;
-    pl->opt_no_tiled_fuse = getenv("CCSD_NO_TILED_FUSE") != nullptr;
-    pl->opt_no_h_full = getenv("CCSD_NO_H_FULL") != nullptr;
-    if (const char* sp = getenv("CCSD_SPLIT_BF16")) pl->opt_split_bf16 = atoi(sp) == 3 ? 3 : 0;
-    pl->opt_no_hp_full = getenv("CCSD_NO_HP_FULL") != nullptr;
-    pl->opt_hp_full_norms = getenv("CCSD_HP_FULL_NORMS") != nullptr;
-    if (const char* pr = getenv("CCSD_XA_PRIO")) pl->opt_xa_prio = atoi(pr);
-    if (const char* sg = getenv("CCSD_XA_STAGGER")) sscanf(sg, "%d,%d", &pl->opt_xa_stagger_mask, &pl->opt_xa_stagger_sleep);
-    if (const char* sg = getenv("CCSD_R2_STAGGER")) sscanf(sg, "%d,%d", &pl->opt_r2_stagger_mask, &pl->opt_r2_stagger_sleep);
-    if (const char* xt = getenv("CCSD_XA_THREADS")) { const int v = atoi(xt); if (v >= 64 && v <= 1024 && v % 64 == 0) pl->opt_xa_threads = v; }
+    const Knobs& k = pl->knobs = read_knobs();
     PlanBuilder pb;
-    if (const char* lgv = getenv("CCSD_LARGE_GRAPH")) pb.lg_force = atoi(lgv) == 1;
+    pb.lg_force = k.lg_force; pb.xa_pass = k.xa_pass; pb.xa_gch = k.xa_gch; pb.no_mlp_wt = k.no_mlp_wt; pb.verbose = k.verbose;
     pl->nweights = ccsd_build_plan(cfg, &pl->h, pb);
     if (pb.status != CCSD_OK) { delete pl; return set_err(pb.status, pb.err); }
-    pl->lg = pb.lg;
-    pl->h.geo_off = getenv("CCSD_NO_GEO") ? 1 : getenv("CCSD_NO_BAKE") ? 2 : 0;      // 2: geometry instances yes, baked-plan instances no
+    pl->rt.lg = pb.lg;
+    pl->h.geo_off = k.geo_off;
     pl->npacked = (size_t)pb.pcur;
     if (pl->nweights != n_weights) {
         delete pl;
@@ -396,46 +484,26 @@ extern "C" int ccsd_plan_create(const ccsd_config_t* cfg, const float* weights, 
     PC(rt_h2d(pl->edges, edges.data(), edges.size()));
     PC(rt_malloc((void**)&pl->cells, cells.size() * sizeof(unsigned long long)));
     PC(rt_h2d(pl->cells, cells.data(), cells.size() * sizeof(unsigned long long)));
-    // fused rank-2 path: one complex's rank2 block (E x K) LDS-resident, E <= 64
-    if (cfg->is_cc && E <= 64 && getenv("CCSD_NO_FUSED_R2") == nullptr) {
-        const PlanD& p = pl->h;
-        const int Kp4 = (K + 31) & ~31, Ep4 = (E + 3) & ~3;   // K zero-padded to whole 8-step MFMA batches
-        int ldk = Kp4; while ((ldk & 31) != 8 && (ldk & 31) != 24) ldk += 4;   // conflict-free ds_read_b128 fragment reads (16 rows x 4 k-quads)
-        int ldh = Ep4;                                                     // 16-byte aligned rows: phase 2 re-reads H's fragments per column tile as ds_read_b128
-        const size_t fl = (size_t)E * ldk + (size_t)E * ldh + 64 * 2 + (size_t)p.a_cinit * E + 3 * N * N + 64 + (Kp4 + 3) / 4 + 4;
-        const bool wc_ok = fnet_width(p) <= CCSD_FW;        // the fused kernel's per-element MLPs are padded to <= 16
-        if (fl * 4 + 64 <= 160 * 1024 && wc_ok && r2_kernel(pl) != nullptr && p.f_cnum <= 2) {   // more Hodge powers: tiled kernels
-            pl->fused_r2 = 1; pl->r2_ldk = ldk; pl->r2_ldh = ldh; pl->r2_lds = fl * 4;
+    if (int st = resolve_route(pl)) { ccsd_plan_destroy(pl); return st; }
+    {
+        const Route& r = pl->rt;
+        const size_t xlds = (size_t)pl->h.xa_lds_floats * 4;
+        if (xlds > 64 * 1024) {
+            PC(rt_set_max_dyn_smem((const void*)r.xa->fn, xlds));
+            if (r.xa_twin) PC(rt_set_max_dyn_smem((const void*)r.xa_twin->fn, xlds));
         }
-    }
-    if (pl->h.h_L > 2) {
-        bool affine_values = true;
-        for (int l = 0; l + 1 < pl->h.h_L; ++l) affine_values = affine_values && ccsd_hl(pl->h, l).mval.n == 1;
-        // (the folded route -- k_r2 hands over one consolidated projection, k_xa chains the M_j -- is built and tested for up to four layers)
-        if (!affine_values || !pl->fused_r2 || pl->h.h_L > 4 || getenv("CCSD_HODGE_GENERAL") != nullptr) { pl->h_general = 1; pl->fused_r2 = 0; }
-    }
-    pl->ew1 = cfg->is_cc && !pl->fused_r2 && pl->h.f_affine && pl->h.f_cnum == 1 && cfg->predictor != CCSD_PRED_S4 &&
-              getenv("CCSD_NO_EW1") == nullptr;
+        if (r.r2 && r.r2_lds > 64 * 1024) PC(rt_set_max_dyn_smem((const void*)r.r2->fn, r.r2_lds));
+        if (r.lg && lg_nmlp_lds(pl->h) > 64 * 1024) PC(rt_set_max_dyn_smem((const void*)k_lg_nmlp, lg_nmlp_lds(pl->h)));
 #ifndef CCSD_EMU
-    if ((size_t)pl->h.xa_lds_floats * 4 > 64 * 1024) {
-        PC(rt_set_max_dyn_smem(xa_kernel(pl->h), (size_t)pl->h.xa_lds_floats * 4));
-        if (xa_variant(pl->h) == XA_PLAIN9 || xa_variant(pl->h) == XA_BAKED9)     // (its run-time-geometry twin serves launches with a diagnostic thread count)
-            PC(rt_set_max_dyn_smem((const void*)k_xa<false, XA_PLAIN>, (size_t)pl->h.xa_lds_floats * 4));
-    }
-    if (pl->fused_r2 && pl->r2_lds > 64 * 1024) {
-        PC(rt_set_max_dyn_smem(r2_kernel(pl), pl->r2_lds));
-    }
-    if (pl->lg && lg_nmlp_lds(pl->h) > 64 * 1024) PC(rt_set_max_dyn_smem((const void*)k_lg_nmlp, lg_nmlp_lds(pl->h)));
-    if (pl->h.is_cc && pl->h.E == 190 && pl->h.K == 1140) {      // k_hp_full: 66.6 KB of dynamic LDS
-        const size_t lds = (size_t)(2 * 192 * H_LD + 2 * 16 * H_LD) * 4;
-        PC(rt_set_max_dyn_smem((const void*)k_hp_full<190, 1140, 1>, lds));
-        PC(rt_set_max_dyn_smem((const void*)k_hp_full<190, 1140, 2>, lds));
-    }
+        if (r.hp_full_modes) {      // k_hp_full: 66.6 KB of dynamic LDS
+            PC(rt_set_max_dyn_smem((const void*)k_hp_full<CCSD_FULL_E, CCSD_FULL_K, 1>, HP_FULL_LDS));
+            PC(rt_set_max_dyn_smem((const void*)k_hp_full<CCSD_FULL_E, CCSD_FULL_K, 2>, HP_FULL_LDS));
+        }
 #endif
+    }
 #undef PC
-    if (const char* path = getenv("CCSD_DUMP_PLAN")) {     // tools/bake_plan.py: the plan's architecture bytes as a C header
-        const char* nm = getenv("CCSD_DUMP_PLAN_NAME");      // QM9 (default), CS
-        if (!nm) nm = "QM9";
+    if (const char* path = k.dump_plan) {     // tools/bake_plan.py: the plan's architecture bytes as a C header
+        const char* nm = k.dump_plan_name ? k.dump_plan_name : "QM9";
         std::vector<unsigned char> bytes(sizeof(PlanD));
         ccsd_plan_arch_bytes(pl->h, bytes.data());
         if (FILE* f = fopen(path, "w")) {
@@ -453,16 +521,6 @@ extern "C" int ccsd_plan_create(const ccsd_config_t* cfg, const float* weights, 
     return CCSD_OK;
 }
 
-// (E, K) of the shipped geometries the general-path kernels have instances for: X(EC, KC) is expanded with the plan's pair as
-// compile-time constants when it is one of them (loop bounds, row strides and divisions fold), with (0, 0) = run-time values otherwise
-#define GEO_EK(p_, X) \
-    do { \
-        if ((p_).geo_off == 1) { X(0, 0); } \
-        else if ((p_).E == 190 && (p_).K == 1140) { X(190, 1140); }    /* community_small (d_min 2 .. d_max) */ \
-        else if ((p_).E == 703 && (p_).K == 8436) { X(703, 8436); }    /* N = 38 (zinc250k), the 5b substitute's cells */ \
-        else if ((p_).E == 66 && (p_).K == 715) { X(66, 715); }        /* ENZYMES_small */ \
-        else { X(0, 0); } \
-    } while (0)
 
 #define CCSD_P_SPLITS 8     /* most K slices k_gemm_p is split into when its row tiles cannot fill the chip */
 
@@ -477,9 +535,6 @@ struct Workspace {
     int ntiles, nchunk;
     float *hgH, *hgR[2], *hgP[CCSD_MAXHL + CCSD_MAXHLX - 1];   // general hodge stack: dumped H^l, R_l (two alternating), P_l of the layers >= 1
     size_t hg_hstride;
-    const float* hg_rank2;          // (the rank2 launch_p saw: launch_xa continues from it)
-    int h_done;                     // H of this pass is already in w.H (k_hp_full produced it beside P_0): launch_h returns at once
-    int p1_raw;     // who filled P1 last: k_r2 with the raw factors (1, see k_r2) or k_gemm_p with the finished projections (0)
     // tiled graph-network route (launch_lg): channel stack [B][a_fdim][N][N]; attention [B][cin][N][N]; D^-1/2 [B][cin][N]; X W and the
     // GCN output [B][cin][N][cp] (Q | K | V side by side); node features (ping-pong) [B][N][max(F, nhid)]; ScoreNetworkX's concatenation
     // [B][N][x_fdim], its X W [B][N][nhid], its masked net [B][N][F]; k_lg_fin's per-tile norm partials [B][lg_tiles][2]
@@ -487,6 +542,12 @@ struct Workspace {
     int lg_tiles;
     size_t bytes;
 };
+// What one pass (a norms pass, a predictor pass, one ccsd_score) hands from launcher to launcher.
+struct Pass {
+    const float* h_src = nullptr;   // the rank2 block w.H was computed from in this pass (k_hp_full leaves H beside P_0): launch_h skips for it
+    int p1_raw = 0;                 // who filled P1 last: k_r2 with the raw factors (1, see k_r2) or k_gemm_p with the finished projections (0)
+};
+static inline int r2_p1_raw(const PlanD& p) { return p.h_L > 1 && p.hl[0].mval.n == 1; }
 static Workspace carve_ws(const ccsd_plan* pl, int B, void* base) {
     const PlanD& p = pl->h;
     Workspace w{};
@@ -504,12 +565,12 @@ static Workspace carve_ws(const ccsd_plan* pl, int B, void* base) {
     // K slices of k_gemm_p (always split: batch-invariant summation order; the step-wise score / norms calls of fused-rank-2 plans use k_gemm_p too)
     w.psplit_floats = p.h_L > 1 ? (size_t)CCSD_P_SPLITS * B * E * p.h_pw : 0;
     w.psplit = (float*)take(w.psplit_floats * 4);
-    const bool two = pl->fused_r2 != 0;
+    const bool two = pl->rt.r2_family == R2_FUSED;
     w.P0b = (float*)take(two && p.h_L > 0 ? (size_t)B * E * p.hl[0].wc * 4 : 0);
     w.P1b = (float*)take(two && p.h_L > 1 ? (size_t)B * E * p.h_pw * 4 : 0);
     w.U1b = (float*)take(two && p.h_L > 1 ? (size_t)B * p.h_pw * 4 : 0);
     w.acoef = (float*)take(p.h_L > 1 ? (size_t)B * p.a_cinit * E * 4 : 0);
-    if (pl->h_general) {
+    if (pl->rt.h_general) {
         int cmax = 1;
         for (int l = 0; l + 1 < p.h_L; ++l) cmax = ccsd_hl(p, l).cout > cmax ? ccsd_hl(p, l).cout : cmax;
         w.hg_hstride = (size_t)cmax * E * E;
@@ -530,7 +591,7 @@ static Workspace carve_ws(const ccsd_plan* pl, int B, void* base) {
     w.part2 = (float*)take((size_t)B * 2 * 4);
     w.sums = (float*)take(64);
     w.chan = (float*)take(p.chan_global ? (size_t)B * p.chan_rows * p.N * p.N * 4 : 0);
-    if (pl->lg) {
+    if (pl->rt.lg) {
         const size_t N = p.N, NN = N * N;
         int cin = 1, cp = 1, fx = p.F > p.x_nhid ? p.F : p.x_nhid;
         for (int l = 0; l < p.a_L; ++l) {
@@ -579,7 +640,7 @@ static int check_state(const ccsd_plan* pl, const ccsd_state_t* s, const char* w
 }
 
 static int launch_flagbits(const ccsd_plan* pl, int B, const float* flags, Workspace& w, void* stream) {
-    if (pl->lg) return CCSD_OK;       // (64-bit node masks feed only the rank-2 tables; the tiled route is graph-only and goes past 64 nodes)
+    if (pl->rt.lg) return CCSD_OK;       // (64-bit node masks feed only the rank-2 tables; the tiled route is graph-only and goes past 64 nodes)
     CCSD_LAUNCH(k_flagbits, dim3(grid_for(B, 256)), dim3(CCSD_NTHREADS), 0, stream, flags, w.offbits, B, pl->h.N);
     LAUNCH_CHECK();
     if (pl->h.is_cc) {      // (consumers: k_ew1, k_langevin_apply, k_noise_norm; the fused rank-2 kernel builds its own masks in LDS)
@@ -591,31 +652,24 @@ static int launch_flagbits(const ccsd_plan* pl, int B, const float* flags, Works
     return CCSD_OK;
 }
 
-static inline bool tiled_fuse_ok(const ccsd_plan* pl);
-// one fused pass per half-step (k_hp_full) instead of k_gemm_p0<., ., 1 / 2> + k_gemm_h_full
-static inline bool hp_full_ok(const ccsd_plan* pl, int B) {
-    const PlanD& p = pl->h;
-    return tiled_fuse_ok(pl) && p.E == 190 && p.K == 1140 && p.geo_off != 1 && B >= 256 && p.hl[0].wc <= 16 && p.f_cnum == 2 &&
-           !pl->opt_no_h_full && !pl->opt_no_hp_full;
-}
 // H = F F^T (ScoreNetworkF) from `rank2`
-static int launch_h(const ccsd_plan* pl, int B, const float* rank2, Workspace& w, void* stream) {
+static int launch_h(const ccsd_plan* pl, int B, const float* rank2, Pass& ps, Workspace& w, void* stream) {
     const PlanD& p = pl->h;
     if (!p.is_cc || p.f_cnum < 2) return CCSD_OK;
-    if (w.h_done) { w.h_done = 0; return CCSD_OK; }
+    if (ps.h_src == rank2) return CCSD_OK;
+    const bool full = use_h_full(pl->rt, B);        // (a GPU-only kernel: the emulation launches k_gemm_h)
     const int nth_ = (p.E + T_BM - 1) / T_BM;
     dim3 g(xcd_grid(B, nth_ * (nth_ + 1) / 2));
     prof_mark(const_cast<ccsd_plan*>(pl), KID_GEMM_H, stream);
 #ifndef CCSD_EMU
-    // community_small geometry, at least one complex per CU: one workgroup per complex, F streamed once (k_gemm_h_full; bit-identical)
-    if (p.E == 190 && p.K == 1140 && p.geo_off != 1 && B >= 256 && !pl->opt_no_h_full) {
-        if (pl->opt_split_bf16 == 3) hipLaunchKernelGGL((k_gemm_h_full<190, 1140, 2>), dim3(B), dim3(256), 0, (hipStream_t)stream, rank2, w.H, p.f_hmask);
-        else hipLaunchKernelGGL((k_gemm_h_full<190, 1140>), dim3(B), dim3(256), 0, (hipStream_t)stream, rank2, w.H, p.f_hmask);
-    } else
+    if (full && pl->knobs.split_bf16 == 3) hipLaunchKernelGGL((k_gemm_h_full<CCSD_FULL_E, CCSD_FULL_K, 2>), dim3(B), dim3(256), 0, (hipStream_t)stream, rank2, w.H, p.f_hmask);
+    else if (full) hipLaunchKernelGGL((k_gemm_h_full<CCSD_FULL_E, CCSD_FULL_K>), dim3(B), dim3(256), 0, (hipStream_t)stream, rank2, w.H, p.f_hmask);
+    else
 #endif
     {
+        (void)full;
 #define H_GO(EC_, KC_) CCSD_LAUNCH((k_gemm_h<EC_, KC_>), g, dim3(CCSD_NTHREADS), 0, stream, rank2, w.H, p.E, p.K, p.f_hmask, B)
-    GEO_EK(p, H_GO);
+        GEO_EK(pl->rt.geo, H_GO);
 #undef H_GO
     }
     prof_mark(const_cast<ccsd_plan*>(pl), KID_GEMM_H, stream);
@@ -631,47 +685,46 @@ static int launch_h(const ccsd_plan* pl, int B, const float* rank2, Workspace& w
 }
 struct RankEpi;
 static int launch_r2(const ccsd_plan* pl, int B, const float* rank2, const float* adj, const float* flags, int want_p,
-                     RankEpi& ep, NoiseArgs& na, Workspace& w, void* stream, const CorrFuse* cf, int merge_draw);
+                     RankEpi& ep, NoiseArgs& na, Pass& ps, Workspace& w, void* stream, const CorrFuse* cf, int merge_draw);
 // hodge projections for ScoreNetworkA_CC from (adj, rank2)
-// fuse (tiled path, h_L == 1; tiled_fuse_ok): the Langevin corrector's element-wise work on rank2 rides on the layer-0 projection
+// fuse (tiled path, h_L == 1; Route::tiled_fuse): the Langevin corrector's element-wise work on rank2 rides on the layer-0 projection
 // pass -- mode 1: the noise norm of the corrector's draw per row (-> fuse->zrow), mode 2: the corrector apply (corrected rank2 -> fuse->f1,
 // which the projection is then taken of).  See P0Fuse (ccsd_k_rank2.h).
-static int launch_p(const ccsd_plan* pl, int B, const float* adj, const float* rank2, Workspace& w, void* stream, const P0Fuse* fuse = nullptr) {
+static int launch_p(const ccsd_plan* pl, int B, const float* adj, const float* rank2, Pass& ps, Workspace& w, void* stream, const P0Fuse* fuse = nullptr) {
     const PlanD& p = pl->h;
+    const Route& rt = pl->rt;
     if (p.h_L < 1) return CCSD_OK;
-    w.hg_rank2 = rank2;
-    if (p.h_L > 2 && !pl->h_general) {
+    if (p.h_L > 2 && !rt.h_general) {
         // more than two hodge layers: k_xa's general layer loop consumes the factors only the fused rank-2 kernel produces
         // (plan creation guarantees it exists); its ScoreNetworkF output lands in the net_r scratch, which every caller
         // of launch_p overwrites afterwards
         RankEpi ep{};
         ep.mode = MODE_SCORE; ep.sscale = 0.f; ep.out = w.net_r;
         NoiseArgs na0{};
-        return launch_r2(pl, B, rank2, adj, nullptr, 1, ep, na0, w, stream, nullptr, -1);
+        return launch_r2(pl, B, rank2, adj, nullptr, 1, ep, na0, ps, w, stream, nullptr, -1);
     }
-    w.p1_raw = 0;
+    ps.p1_raw = 0;
     const int rows = B * p.E;
+    // the corrector's work riding on the pass (modes 1 / 2) on the community_small geometry: ONE kernel streams the block once and leaves
+    // P_0, H and the noise norm / the corrected state (k_hp_full; P_0 and H bit-identical to the two-kernel route); the launch_h that
+    // follows in the caller, asked for H of the block this pass took it from (mode 2: the corrected state in fuse->f1), finds it done
+    const bool hp_full = fuse && use_hp_full(rt, B, fuse->mode);        // (a GPU-only kernel: the emulation takes the two-kernel route)
 #ifndef CCSD_EMU
-    // community_small geometry, at least one complex per CU, the corrector's work riding on the pass (modes 1 / 2): ONE kernel streams
-    // the block once and leaves P_0, H and the noise norm / the corrected state (k_hp_full; P_0 and H bit-identical to the two-kernel
-    // route); the launch_h that follows in the caller finds H done
-    // (mode 1 -- the norms pass, whose only extra is the noise norm -- is slower fused: 370 us against 129 + 213, the eight waves of the one
-    // workgroup a CU holds run in lockstep; CCSD_HP_FULL_NORMS turns it on for A/B)
-    if (fuse && (fuse->mode == 2 || (fuse->mode == 1 && pl->opt_hp_full_norms)) && hp_full_ok(pl, B)) {
+    if (hp_full) {
         const HodgeLayerD& h = p.hl[0];
         const float* WT = (const float*)pl->wp + h.wcatT;
-        const size_t lds = (size_t)(2 * 192 * H_LD + 2 * 16 * H_LD) * 4;
         prof_mark(const_cast<ccsd_plan*>(pl), KID_GEMM_H, stream);
         if (fuse->mode == 1)
-            hipLaunchKernelGGL((k_hp_full<190, 1140, 1>), dim3(B), dim3(512), lds, (hipStream_t)stream, rank2, WT, w.H, w.P0, h.wc, p.f_hmask, *fuse);
+            hipLaunchKernelGGL((k_hp_full<CCSD_FULL_E, CCSD_FULL_K, 1>), dim3(B), dim3(512), HP_FULL_LDS, (hipStream_t)stream, rank2, WT, w.H, w.P0, h.wc, p.f_hmask, *fuse);
         else
-            hipLaunchKernelGGL((k_hp_full<190, 1140, 2>), dim3(B), dim3(512), lds, (hipStream_t)stream, rank2, WT, w.H, w.P0, h.wc, p.f_hmask, *fuse);
+            hipLaunchKernelGGL((k_hp_full<CCSD_FULL_E, CCSD_FULL_K, 2>), dim3(B), dim3(512), HP_FULL_LDS, (hipStream_t)stream, rank2, WT, w.H, w.P0, h.wc, p.f_hmask, *fuse);
         prof_mark(const_cast<ccsd_plan*>(pl), KID_GEMM_H, stream);
         LAUNCH_CHECK();
-        w.h_done = p.f_cnum == 2;            // (more powers: k_gemm_pow needs launch_h's loop -- not this geometry's shipped network)
+        ps.h_src = fuse->mode == 2 ? fuse->f1 : rank2;
         return CCSD_OK;
     }
 #endif
+    (void)hp_full;
     {
         const HodgeLayerD& h = p.hl[0];
         dim3 g((h.wc + T_BN - 1) / T_BN, (rows + T_BM - 1) / T_BM, 1);
@@ -679,26 +732,10 @@ static int launch_p(const ccsd_plan* pl, int B, const float* adj, const float* r
         P0Fuse pf{};
         if (fuse) pf = *fuse;
 #ifndef CCSD_EMU
-        const int nt = (h.wc + 15) / 16, Kp = (p.K + 31) & ~31;
-        if (nt <= 4 && !pl->opt_old_gemm_p) {     // narrow projections: no 64-column padding
-            const dim3 g0((rows + T_BM - 1) / T_BM);
-            const float* WT = (const float*)pl->wp + h.wcatT;
-#define P0_GO(NT_, KC_, M_) hipLaunchKernelGGL((k_gemm_p0<NT_, KC_, M_>), g0, dim3(256), 0, (hipStream_t)stream, rank2, WT, w.P0, rows, p.K, Kp, h.wc, pf)
-#define P0_MODES(NT_, KC_) do { if (pf.mode == 1) P0_GO(NT_, KC_, 1); else if (pf.mode == 2) P0_GO(NT_, KC_, 2); \
-                                else if (pf.mode == 3) P0_GO(NT_, KC_, 3); else if (pf.mode == 4) P0_GO(NT_, KC_, 4); else P0_GO(NT_, KC_, 0); } while (0)
-            switch (nt) {
-                case 1:
-                    if (p.K == 1140 && p.geo_off != 1) P0_MODES(1, 1140);
-                    else if (p.K == 8436 && p.geo_off != 1) P0_MODES(1, 8436);
-                    else P0_MODES(1, 0);
-                    break;
-                case 2: P0_MODES(2, 0); break;
-                case 3: P0_MODES(3, 0); break;
-                default: P0_MODES(4, 0); break;
-            }
-#undef P0_MODES
-#undef P0_GO
-        } else
+        if (rt.p0 >= 0)      // narrow projections (a GPU-only kernel: the emulation launches the wide one)
+            hipLaunchKernelGGL(P0_TABLE[rt.p0].fn[pf.mode], dim3((rows + T_BM - 1) / T_BM), dim3(256), 0, (hipStream_t)stream, rank2,
+                               (const float*)pl->wp + h.wcatT, w.P0, rows, p.K, (p.K + 31) & ~31, h.wc, pf);
+        else
 #endif
         {
             const float* src = rank2;
@@ -731,7 +768,7 @@ static int launch_p(const ccsd_plan* pl, int B, const float* adj, const float* r
         const int kchunk = ((nslab + S - 1) / S) * T_BK;
         S = (p.K + kchunk - 1) / kchunk;
         g.z = S;
-        float* P1 = pl->h_general ? w.hgP[0] : w.P1;
+        float* P1 = rt.h_general ? w.hgP[0] : w.P1;
         CCSD_LAUNCH(k_gemm_p, g, dim3(CCSD_NTHREADS), 0, stream, rank2, (const float*)pl->w, S > 1 ? w.psplit : P1, rows, p.E, p.K, h.wc,
                     h.wcat, 1, h0.mval, h0.cin, (const float*)w.acoef, (const unsigned long long*)w.offbits,
                     (const unsigned char*)pl->edges, (const unsigned long long*)pl->cells, kchunk);
@@ -741,7 +778,7 @@ static int launch_p(const ccsd_plan* pl, int B, const float* adj, const float* r
             CCSD_LAUNCH(k_sum_splits, dim3(grid_for(n, 256)), dim3(CCSD_NTHREADS), 0, stream, (const float*)w.psplit, P1, n, S);
             LAUNCH_CHECK();
         }
-        if (pl->h_general) {
+        if (rt.h_general) {
             // R_1 = fl fr mlp_value_0(a_c o rank2), materialised for the layers behind it (launch_xa goes on from here)
             const int cw = p.E > 128 ? 32 : 64;
             CCSD_LAUNCH(k_hodge_value, dim3((p.K + cw - 1) / cw, B), dim3(CCSD_NTHREADS), (size_t)p.E * cw * 4, stream, rank2, (const float*)nullptr, 0,
@@ -753,46 +790,32 @@ static int launch_p(const ccsd_plan* pl, int B, const float* adj, const float* r
     return CCSD_OK;
 }
 static int launch_lg(const ccsd_plan* pl, int B, XaArgs& xa, NoiseArgs& na, Workspace& w, void* stream);
-static int launch_xa(const ccsd_plan* pl, int B, XaArgs& xa, NoiseArgs& na, Workspace& w, void* stream, bool set_b = false) {
-    if (pl->lg) return launch_lg(pl, B, xa, na, w, stream);
+static int launch_xa(const ccsd_plan* pl, int B, XaArgs& xa, NoiseArgs& na, const Pass& ps, Workspace& w, void* stream, bool set_b = false) {
+    const Route& rt = pl->rt;
+    if (rt.lg) return launch_lg(pl, B, xa, na, w, stream);
     xa.P0 = set_b ? w.P0b : w.P0; xa.P1 = set_b ? w.P1b : w.P1; xa.U1 = set_b ? w.U1b : w.U1; xa.chan_ws = w.chan;
-    xa.p1_raw = w.p1_raw; xa.dbg = pl->dbg ? pl->dbg + 32 : nullptr;
-    xa.stagger_mask = pl->opt_xa_stagger_mask; xa.stagger_sleep = pl->opt_xa_stagger_sleep; xa.prio_mode = pl->opt_xa_prio;
-    // Threads per graph.  256 (four waves) is right when the batch fills the chip -- 1024 graphs = four co-resident workgroups per CU --
-    // and k_xa is bound by the latency of one graph's critical path either way; when the batch leaves a CU with one or two workgroups
-    // (B <= 256 / <= 512) the same graph runs on sixteen / eight waves: every per-pair, per-tile and per-element loop of the kernel strides
-    // by the workgroup's thread count (zinc250k B = 256: 419 -> 293 us per launch; community_small_CC B = 512: 418 -> 349 us; ENZYMES_small_CC
-    // B = 64: 236 -> 180 us).  Only the instances compiled for 4 waves per SIMD without a fixed thread count take more than 256 (XA_4WAVES in
-    // ccsd_k_xa.h); CCSD_XA_THREADS (read at plan creation) overrides the choice (diagnostic: 64 .. 1024).
-    int xa_threads = pl->opt_xa_threads;
-    const int v0 = xa_variant(pl->h);
-    // most threads the variant's instance may be launched with (its __launch_bounds__, XA_4WAVES in ccsd_k_xa.h; the qm9 instances have
-    // their 256 compiled in -- an override moves those plans to the run-time-geometry twin below)
-    const bool fixed256 = v0 == XA_PLAIN9 || v0 == XA_BAKED9;
-    const int max_threads = (pl->h.chan_global && v0 != XA_BAKED20 && v0 != XA_BAKED38) ? 256 : 1024;
-    if (xa_threads == 0) xa_threads = (fixed256 || max_threads == 256) ? 256 : B <= 256 ? 1024 : B <= 512 ? 512 : 256;
-    if (xa_threads > max_threads) xa_threads = max_threads;
+    xa.p1_raw = ps.p1_raw; xa.dbg = pl->dbg ? pl->dbg + 32 : nullptr;
+    xa.stagger_mask = pl->knobs.xa_stagger_mask; xa.stagger_sleep = pl->knobs.xa_stagger_sleep; xa.prio_mode = pl->knobs.xa_prio;
+    int xa_threads;
+    const XaEntry* inst = xa_launch(rt, B, &xa_threads);
     prof_mark(const_cast<ccsd_plan*>(pl), KID_XA, stream);
     xa.wp = pl->wp; xa.hpairs = pl->hpairs;
     const dim3 xblk(CCSD_NTHREADS == 1 ? 1 : xa_threads);
     const size_t xlds = (size_t)pl->h.xa_lds_floats * 4;
-#define XA_GO(G_, V_, XA_, BLK_, LDS_, STR_) CCSD_LAUNCH((k_xa<G_, V_>), dim3(B), BLK_, LDS_, STR_, (const PlanD*)pl->d, (const float*)pl->w, \
-                                                         (const unsigned char*)pl->edges, XA_, na)
-    int variant = xa_variant(pl->h);
-    if ((variant == XA_PLAIN9 || variant == XA_BAKED9) && xa_threads != 256) variant = XA_PLAIN;      // (they have their 256 threads compiled in)
-    if (pl->h_general) {
+#define XA_LAUNCH(XA_) CCSD_LAUNCH(inst->fn, dim3(B), xblk, xlds, stream, (const PlanD*)pl->d, (const float*)pl->w, (const unsigned char*)pl->edges, XA_, na)
+    if (rt.h_general) {
         // general hodge stack: layer l >= 2 projects R_l = fl fr mlp_value_(l-1)(cat_c H^(l-1)_c R_(l-1)).  H^(l-1) is the dense output of
         // layer l - 2 inside k_xa: a launch that stops behind it dumps it, k_hodge_value forms R_l, k_gemm_p projects it -- then the next
         // layer, and at last the full launch with every P_l delivered.  (launch_p left P_0, P_1 and R_1.)
         const PlanD& p = pl->h;
-        if (variant != XA_GEN) return set_err(CCSD_ERR_RUNTIME, "general hodge stack needs k_xa<., XA_GEN>");
+        if (rt.xa_variant != XA_GEN) return set_err(CCSD_ERR_RUNTIME, "general hodge stack needs k_xa<., XA_GEN>");
         xa.pdirect = 1;
         for (int l = 1; l < p.h_L; ++l) xa.Pd[l - 1] = w.hgP[l - 1];
         const int rows = B * p.E;
         for (int l = 2; l < p.h_L; ++l) {
             XaArgs pre = xa;
             pre.hdump_layer = l - 1; pre.hdump = w.hgH; pre.hdump_stride = (int)w.hg_hstride;
-            if (pl->h.chan_global) XA_GO(true, XA_GEN, pre, xblk, xlds, stream); else XA_GO(false, XA_GEN, pre, xblk, xlds, stream);
+            XA_LAUNCH(pre);
             LAUNCH_CHECK();
             const HodgeLayerD& hp = ccsd_hl(p, l - 1);
             const HodgeLayerD& h = ccsd_hl(p, l);
@@ -808,32 +831,15 @@ static int launch_xa(const ccsd_plan* pl, int B, XaArgs& xa, NoiseArgs& na, Work
             LAUNCH_CHECK();
         }
     }
-    if (pl->h.chan_global) {
-        if (variant == XA_HB) XA_GO(true, XA_HB, xa, xblk, xlds, stream);
-        else if (variant == XA_GMH) XA_GO(true, XA_GMH, xa, xblk, xlds, stream);
-        else if (variant == XA_GEN) XA_GO(true, XA_GEN, xa, xblk, xlds, stream);
-        else if (variant == XA_PLAIN20) XA_GO(true, XA_PLAIN20, xa, xblk, xlds, stream);
-        else if (variant == XA_BAKED20) XA_GO(true, XA_BAKED20, xa, xblk, xlds, stream);
-        else if (variant == XA_PLAIN38) XA_GO(true, XA_PLAIN38, xa, xblk, xlds, stream);
-        else if (variant == XA_BAKED38) XA_GO(true, XA_BAKED38, xa, xblk, xlds, stream);
-        else XA_GO(true, XA_PLAIN, xa, xblk, xlds, stream);
-    } else {
-        if (variant == XA_HB) XA_GO(false, XA_HB, xa, xblk, xlds, stream);
-        else if (variant == XA_GMH) XA_GO(false, XA_GMH, xa, xblk, xlds, stream);
-        else if (variant == XA_GEN) XA_GO(false, XA_GEN, xa, xblk, xlds, stream);
-        else if (variant == XA_PLAIN9) XA_GO(false, XA_PLAIN9, xa, xblk, xlds, stream);
-        else if (variant == XA_BAKED9) XA_GO(false, XA_BAKED9, xa, xblk, xlds, stream);
-        else if (variant == XA_BAKEDENZ) XA_GO(false, XA_BAKEDENZ, xa, xblk, xlds, stream);
-        else XA_GO(false, XA_PLAIN, xa, xblk, xlds, stream);
-    }
-#undef XA_GO
+    XA_LAUNCH(xa);
+#undef XA_LAUNCH
     prof_mark(const_cast<ccsd_plan*>(pl), KID_XA, stream);
     LAUNCH_CHECK();
     return CCSD_OK;
 }
 // Tiled graph-network route (ccsd_k_lg.h): ScoreNetworkX on (xX, adjX) and ScoreNetworkA on (xA, adjA) as a sequence of launches over
 // the workspace (LgWs fields of Workspace), then the epilogues of k_xa's contract (mode, coefficients, mean pointers, norm2[b][4]).
-// Graph-only plans never fuse the corrector apply into this pass (fused_apply_ok), so a CorrFuse here is an error.
+// Graph-only plans never fuse the corrector apply into this pass (resolve_route), so a CorrFuse here is an error.
 static int launch_lg(const ccsd_plan* pl, int B, XaArgs& xa, NoiseArgs& na, Workspace& w, void* stream) {
     const PlanD& p = pl->h;
     if (xa.cf.on) return set_err(CCSD_ERR_RUNTIME, "tiled graph-network route: no fused corrector apply");
@@ -905,9 +911,9 @@ static int launch_hf(const ccsd_plan* pl, int B, const float* rank2, RankEpi& ep
 #define HF_GEN1(EC_, KC_) CCSD_LAUNCH((k_hf_score<false, 8, 1, EC_, KC_>), g, dim3(CCSD_NTHREADS), 0, stream, HF_ARGS)
 #define HF_GO(NP_) \
     do { \
-        if (p.f_affine && NP_ == 1) GEO_EK(p, HF_AFF1); \
+        if (p.f_affine && NP_ == 1) GEO_EK(pl->rt.geo, HF_AFF1); \
         else if (p.f_affine) CCSD_LAUNCH((k_hf_score<true, 8, NP_>), g, dim3(CCSD_NTHREADS), 0, stream, HF_ARGS); \
-        else if (fw <= 8 && NP_ == 1) GEO_EK(p, HF_GEN1); \
+        else if (fw <= 8 && NP_ == 1) GEO_EK(pl->rt.geo, HF_GEN1); \
         else if (fw <= 8) CCSD_LAUNCH((k_hf_score<false, 8, NP_>), g, dim3(CCSD_NTHREADS), 0, stream, HF_ARGS); \
         else if (fw <= CCSD_FW) CCSD_LAUNCH((k_hf_score<false, CCSD_FW, NP_>), g, dim3(CCSD_NTHREADS), 0, stream, HF_ARGS); \
         else CCSD_LAUNCH((k_hf_score<false, CCSD_FWMAX, NP_>), g, dim3(CCSD_NTHREADS), 0, stream, HF_ARGS); \
@@ -935,7 +941,7 @@ static int launch_ew1(const ccsd_plan* pl, int B, const float* rank2, RankEpi& e
     a.E = p.E; a.K = p.K; a.mt = MaskTab{w.mfr, w.mfl, w.Kp, w.Ep};
     prof_mark(const_cast<ccsd_plan*>(pl), KID_EW1, stream);
 #define EW1_GO(EC_, KC_) CCSD_LAUNCH((k_ew1<EC_, KC_>), dim3(w.nchunk, B), dim3(CCSD_NTHREADS), 0, stream, a, na)
-    GEO_EK(p, EW1_GO);
+    GEO_EK(pl->rt.geo, EW1_GO);
 #undef EW1_GO
     prof_mark(const_cast<ccsd_plan*>(pl), KID_EW1, stream);
     LAUNCH_CHECK();
@@ -945,37 +951,23 @@ static int launch_ew1(const ccsd_plan* pl, int B, const float* rank2, RankEpi& e
 // merge_draw >= 0: merged launch -- after this (predictor) pass the kernel runs the NEXT corrector's norms pass on the new block
 // (draw index merge_draw; raw score -> w.net_r, partials -> w.part, projections -> the second buffer set)
 static int launch_r2(const ccsd_plan* pl, int B, const float* rank2, const float* adj, const float* flags, int want_p,
-                     RankEpi& ep, NoiseArgs& na, Workspace& w, void* stream, const CorrFuse* cf = nullptr, int merge_draw = -1) {
+                     RankEpi& ep, NoiseArgs& na, Pass& ps, Workspace& w, void* stream, const CorrFuse* cf = nullptr, int merge_draw = -1) {
+    const Route& rt = pl->rt;
     R2Args ra{};
     if (cf) ra.cf = *cf;
     // launches of the sampler loop that carry the fused corrector apply work on states this library produced: masked (R2Args::masked)
-    ra.masked = (cf && cf->on && pl->opt_r2_masked) ? 1 : 0;
+    ra.masked = (cf && cf->on) ? 1 : 0;
     if (merge_draw >= 0) {
         ra.merge = 1; ra.draw_r2 = (unsigned)merge_draw;
         ra.P0b = w.P0b; ra.P1b = w.P1b; ra.U1b = w.U1b; ra.net2 = w.net_r; ra.part2 = w.part;
     }
     ra.rank2 = rank2; ra.adj = adj; ra.flags = flags; ra.offbits = w.offbits; ra.P0 = w.P0; ra.P1 = w.P1; ra.U1 = w.U1; ra.want_p = want_p;
-    ra.ldk = pl->r2_ldk; ra.ldh = pl->r2_ldh; ra.dbg = pl->dbg; ra.wp = pl->wp;
-    ra.stagger_mask = pl->opt_r2_stagger_mask; ra.stagger_sleep = pl->opt_r2_stagger_sleep;
-    if (want_p && pl->h.h_L > 1) w.p1_raw = pl->h.hl[0].mval.n == 1;
+    ra.ldk = rt.r2_ldk; ra.ldh = rt.r2_ldh; ra.dbg = pl->dbg; ra.wp = pl->wp;
+    ra.stagger_mask = pl->knobs.r2_stagger_mask; ra.stagger_sleep = pl->knobs.r2_stagger_sleep;
+    if (want_p && pl->h.h_L > 1) ps.p1_raw = r2_p1_raw(pl->h);
     prof_mark(const_cast<ccsd_plan*>(pl), KID_R2, stream);
-    const dim3 blk(CCSD_NTHREADS == 1 ? 1 : 512);
-#define R2_GO(MT_, RS_, A_, G_) \
-    CCSD_LAUNCH((k_r2<MT_, RS_, A_, G_>), dim3(B), blk, pl->r2_lds, stream, (const PlanD*)pl->d, (const float*)pl->w, \
-                (const unsigned char*)pl->edges, (const unsigned long long*)pl->cells, ra, ep, na)
-    const int qm9 = r2_qm9(pl);
-    if (qm9 == 2) {
-        CCSD_LAUNCH((k_r2<3, 1, true, false, 2>), dim3(B), blk, pl->r2_lds, stream, (const PlanD*)pl->d, (const float*)pl->w,
-                    (const unsigned char*)pl->edges, (const unsigned long long*)pl->cells, ra, ep, na);
-    } else if (qm9 == 1) {
-        CCSD_LAUNCH((k_r2<3, 1, true, false, 1>), dim3(B), blk, pl->r2_lds, stream, (const PlanD*)pl->d, (const float*)pl->w,
-                    (const unsigned char*)pl->edges, (const unsigned long long*)pl->cells, ra, ep, na);
-    } else if (qm9 == 3) {
-        CCSD_LAUNCH((k_r2<3, 0, false, false, 1>), dim3(B), blk, pl->r2_lds, stream, (const PlanD*)pl->d, (const float*)pl->w,
-                    (const unsigned char*)pl->edges, (const unsigned long long*)pl->cells, ra, ep, na);
-    } else
-    R2_DISPATCH(pl, R2_GO);
-#undef R2_GO
+    CCSD_LAUNCH(rt.r2->fn, dim3(B), dim3(CCSD_NTHREADS == 1 ? 1 : 512), rt.r2_lds, stream, (const PlanD*)pl->d, (const float*)pl->w,
+                (const unsigned char*)pl->edges, (const unsigned long long*)pl->cells, ra, ep, na);
     prof_mark(const_cast<ccsd_plan*>(pl), KID_R2, stream);
     LAUNCH_CHECK();
     return CCSD_OK;
@@ -993,37 +985,6 @@ static NoiseArgs make_noise(const ccsd_noise_t* n, uint64_t seed, int64_t off, u
     na.flat_r = flat_r;
     return na;
 }
-// The Langevin corrector's rank2 draws are keyed by flat groups of four consecutive elements (NoiseArgs::flat_r): they are
-// generated where rank2 streams through registers in 16-byte pieces (k_r2's block load, k_langevin_apply, k_noise_norm).
-// Priors, predictor draws and the three draws of an S4 step keep the 4-row groups of the MFMA epilogues.
-static inline int corrector_flat(const ccsd_plan* pl) { return pl->cfg.predictor != CCSD_PRED_S4 ? 1 : 0; }
-
-// does ccsd_sampler_run fuse the Langevin corrector's apply pass into the predictor launches of this plan?
-// merged k_r2 launches (predictor of step i + rank-2 side of the norms pass of step i + 1): the row-strip instantiation of the
-// kernel (E = 33..36, affine ScoreNetworkF, linear mlp_value), pair-wise block load (K even, E K a multiple of 4)
-static inline bool merge_ok(const ccsd_plan* pl) {
-    if (!pl->fused_r2 || pl->opt_no_fused_apply || pl->opt_no_merge) return false;
-    int mt, rs; bool aff, gen1;
-    r2_shape(pl, &mt, &rs, &aff, &gen1);
-    return mt == 3 && rs == 1 && aff && !gen1 && (pl->h.K & 1) == 0 && ((pl->h.E * pl->h.K) & 3) == 0;
-}
-// tiled rank-2 path (k_gemm_h / k_gemm_p0 / k_hf_score: community_small_CC) with ONE hodge layer: the corrector's rank2 work rides on
-// the layer-0 projection pass (P0Fuse) -- flat-keyed corrector draws, K a multiple of 4 (a Philox group = one 16-byte piece of a row)
-static inline bool tiled_fuse_ok(const ccsd_plan* pl) {
-    return pl->cfg.is_cc && !pl->fused_r2 && !pl->ew1 && pl->h.h_L == 1 && (pl->h.K & 3) == 0 && pl->cfg.predictor != CCSD_PRED_S4 &&
-           pl->cfg.corrector == CCSD_CORR_LANGEVIN && !pl->opt_no_tiled_fuse;
-}
-// element-wise ScoreNetworkF plans (k_ew1's: affine, cnum = 1) with ONE hodge layer: the whole rank-2 side of a half-step rides on the
-// layer-0 projection pass (P0Fuse modes 3 / 4) -- one read of rank2 per norms pass, one read + one write per predictor pass
-static inline bool ew1_fuse_ok(const ccsd_plan* pl) {
-    return pl->ew1 && pl->h.h_L == 1 && (pl->h.K & 3) == 0 && pl->cfg.corrector == CCSD_CORR_LANGEVIN && !pl->opt_no_tiled_fuse;
-}
-// (k_r2 plans; k_ew1 plans whose hodge projections do not depend on the adjacency: one hodge layer; tiled plans with one hodge layer)
-static inline bool fused_apply_ok(const ccsd_plan* pl) {
-    return (pl->fused_r2 || (pl->ew1 && pl->h.h_L <= 1) || tiled_fuse_ok(pl)) && !pl->opt_no_fused_apply;
-}
-// every rank2 draw of a k_ew1 plan is keyed by flat groups (the kernel streams 16-byte pieces); otherwise only the corrector's
-static inline int predictor_flat(const ccsd_plan* pl) { return pl->ew1 ? 1 : 0; }
 
 // ---------------- API ----------------
 extern "C" int ccsd_score(ccsd_plan_t* pl, int32_t target, int32_t B, const ccsd_state_t* in, const float* flags,
@@ -1035,21 +996,22 @@ extern "C" int ccsd_score(ccsd_plan_t* pl, int32_t target, int32_t B, const ccsd
     Workspace w = carve_ws(pl, B, workspace);
     if ((st = launch_flagbits(pl, B, flags, w, stream))) return st;
     NoiseArgs na{};
+    Pass ps;
     if (target == CCSD_TARGET_X || target == CCSD_TARGET_ADJ) {
         XaArgs xa{};
         xa.xX = xa.xA = in->x; xa.adjX = xa.adjA = in->adj; xa.flags = flags;
         xa.do_x = target == CCSD_TARGET_X; xa.do_a = !xa.do_x; xa.mode = MODE_SCORE;
         xa.ss_x = xa.ss_a = sscale; xa.out_x = xa.out_a = out;
-        if (xa.do_a && (st = launch_p(pl, B, in->adj, in->rank2, w, stream))) return st;
-        return launch_xa(pl, B, xa, na, w, stream);
+        if (xa.do_a && (st = launch_p(pl, B, in->adj, in->rank2, ps, w, stream))) return st;
+        return launch_xa(pl, B, xa, na, ps, w, stream);
     }
     if (target == CCSD_TARGET_RANK2) {
         if (!pl->h.is_cc) return set_err(CCSD_ERR_INVALID, "rank2 score requested from a graph-only plan");
         RankEpi ep{};
         ep.mode = MODE_SCORE; ep.sscale = sscale; ep.out = out;
-        if (pl->fused_r2) return launch_r2(pl, B, in->rank2, in->adj, flags, 0, ep, na, w, stream);
-        if (pl->ew1) return launch_ew1(pl, B, in->rank2, ep, na, w, stream);
-        if ((st = launch_h(pl, B, in->rank2, w, stream))) return st;
+        if (pl->rt.r2_family == R2_FUSED) return launch_r2(pl, B, in->rank2, in->adj, flags, 0, ep, na, ps, w, stream);
+        if (pl->rt.r2_family == R2_EW1) return launch_ew1(pl, B, in->rank2, ep, na, w, stream);
+        if ((st = launch_h(pl, B, in->rank2, ps, w, stream))) return st;
         return launch_hf(pl, B, in->rank2, ep, na, w, stream);
     }
     return set_err(CCSD_ERR_UNSUPPORTED, "Object not yet supported. Select from [x, adj, rank2].");
@@ -1077,7 +1039,7 @@ static int draws_to_state(ccsd_plan* pl, int32_t B, const float* flags, const cc
         pl->init_off_cap = (size_t)B;
     }
     unsigned long long* offbits = pl->init_off;
-    if (!pl->lg) CCSD_LAUNCH(k_flagbits, dim3(grid_for(B, 256)), dim3(CCSD_NTHREADS), 0, stream, flags, offbits, B, p.N);   // (graph-only on the tiled route: no rank-2 draws read it)
+    if (!pl->rt.lg) CCSD_LAUNCH(k_flagbits, dim3(grid_for(B, 256)), dim3(CCSD_NTHREADS), 0, stream, flags, offbits, B, p.N);   // (graph-only on the tiled route: no rank-2 draws read it)
     NoiseArgs na = make_noise(raw, seed, sample_offset, base, flat_r);
     const long long total = (long long)B * (p.N * p.F + p.N * p.N) +
                             (p.is_cc ? (flat_r ? (long long)B * (((long long)p.E * p.K + 3) / 4) : (long long)B * ((p.E + 3) / 4) * p.K) : 0);
@@ -1100,25 +1062,32 @@ extern "C" int ccsd_noise_draws(ccsd_plan_t* pl, int32_t B, const float* flags, 
     if (step < 0 || step >= pl->cfg.diff_steps || phase < 0 || phase >= per_step) return set_err(CCSD_ERR_INVALID, "step / phase out of range");
     const bool corr = pl->cfg.predictor != CCSD_PRED_S4 && phase < pl->cfg.n_corr_steps && pl->cfg.corrector == CCSD_CORR_LANGEVIN;
     return draws_to_state(pl, B, flags, nullptr, seed, sample_offset, draw_base(pl, step, phase), out, stream,
-                          corr ? corrector_flat(pl) : predictor_flat(pl));
+                          corr ? pl->rt.corrector_flat : pl->rt.predictor_flat);
 }
 
 extern "C" int ccsd_plan_query(const ccsd_plan_t* pl, int32_t what, int64_t* value) {
     if (!pl || !value) return set_err(CCSD_ERR_INVALID, "NULL argument");
+    const Route& r = pl->rt;
+    const int hint = pl->cfg.batch_hint;        // the batch the batch-dependent answers are given for
     switch (what) {
-        case CCSD_QUERY_FUSED_R2: *value = pl->fused_r2; break;
-        case CCSD_QUERY_XA_VARIANT: *value = xa_variant(pl->h); break;
-        case CCSD_QUERY_R2_LDS_BYTES: *value = (int64_t)pl->r2_lds; break;
+        case CCSD_QUERY_FUSED_R2: *value = r.r2_family == R2_FUSED; break;
+        case CCSD_QUERY_XA_VARIANT: *value = r.xa_variant; break;
+        case CCSD_QUERY_R2_LDS_BYTES: *value = (int64_t)r.r2_lds; break;
         case CCSD_QUERY_XA_LDS_BYTES: *value = (int64_t)pl->h.xa_lds_floats * 4; break;
-        case CCSD_QUERY_FUSED_LOOP: {   // ccsd_sampler_run fuses the Langevin apply into the predictor launches
-            const bool s4 = pl->cfg.predictor == CCSD_PRED_S4;
-            *value = (!s4 && pl->cfg.corrector == CCSD_CORR_LANGEVIN && pl->cfg.n_corr_steps == 1 && fused_apply_ok(pl)) ? 1 : 0;
-            break;
-        }
-        case CCSD_QUERY_MERGED_R2: *value = (pl->cfg.predictor != CCSD_PRED_S4 && pl->cfg.corrector == CCSD_CORR_LANGEVIN && pl->cfg.n_corr_steps == 1 &&
-                                             fused_apply_ok(pl) && merge_ok(pl)) ? 1 : 0; break;
-        case CCSD_QUERY_EW1: *value = pl->ew1; break;
-        case CCSD_QUERY_LARGE_GRAPH: *value = pl->lg; break;
+        case CCSD_QUERY_FUSED_LOOP: *value = r.loop == LOOP_LANGEVIN_FUSED; break;
+        case CCSD_QUERY_MERGED_R2: *value = r.merged; break;
+        case CCSD_QUERY_EW1: *value = r.r2_family == R2_EW1; break;
+        case CCSD_QUERY_LARGE_GRAPH: *value = r.lg; break;
+        case CCSD_QUERY_R2_FAMILY: *value = r.r2_family; break;
+        case CCSD_QUERY_R2_INSTANCE: *value = r.r2 ? ((((int64_t)r.r2->mt * 10 + r.r2->rs) * 10 + r.r2->affine) * 10 + r.r2->gen1) * 10 + r.r2->qm9 : -1; break;
+        case CCSD_QUERY_LOOP_FORM: *value = r.loop; break;
+        case CCSD_QUERY_H_FULL: *value = use_h_full(r, hint); break;
+        case CCSD_QUERY_HP_FULL: *value = (use_hp_full(r, hint, 2) ? 1 : 0) | (use_hp_full(r, hint, 1) ? 2 : 0); break;
+        case CCSD_QUERY_P0_NARROW: *value = r.p0 >= 0 ? (int64_t)P0_TABLE[r.p0].nt * 100000 + P0_TABLE[r.p0].kc : 0; break;
+        case CCSD_QUERY_TILED_FUSE: *value = r.tiled_fuse; break;
+        case CCSD_QUERY_EW1_FUSE: *value = r.ew1_fuse; break;
+        case CCSD_QUERY_H_GENERAL: *value = r.h_general; break;
+        case CCSD_QUERY_GEO_EK: *value = r.geo; break;
         default: return set_err(CCSD_ERR_INVALID, "unknown query");
     }
     return CCSD_OK;
@@ -1133,20 +1102,23 @@ static int corrector_norms(ccsd_plan* pl, int B, int step, int it, const ccsd_st
                            Workspace& w, void* stream, bool keep_net = true, bool r2_done = false) {
     const PlanD& p = pl->h;
     int st;
-    NoiseArgs na = make_noise(noise, seed, off, draw_base(pl, step, it), corrector_flat(pl));
+    NoiseArgs na = make_noise(noise, seed, off, draw_base(pl, step, it), pl->rt.corrector_flat);
     // A-net sees (x_0, adj_cur, rank2_0): hodge projections from the base rank2, edge coefficients from adj_cur.
     // When the rank2 iterate is still the base state the fused kernel serves both the A-net's projections
     // and ScoreNetworkF in one pass over rank2.
-    const bool fused = pl->fused_r2 && p.is_cc && cur->rank2 == base->rank2;
+    const Route& rt = pl->rt;
+    Pass ps;
+    const bool fused = rt.r2_family == R2_FUSED && cur->rank2 == base->rank2;
     // tiled path, one hodge layer: the noise norm of the corrector's (flat-keyed, in-kernel) rank2 draw rides on the projection pass
-    const bool zfuse = !fused && tiled_fuse_ok(pl) && na.flat_r && !na.zr;
+    const bool zfuse = !fused && rt.tiled_fuse && na.flat_r && !na.zr;
     // element-wise ScoreNetworkF plans: raw score + both norms per row ride on it too (no k_ew1 launch in this pass)
-    const bool e1fuse = !fused && ew1_fuse_ok(pl) && na.flat_r && !na.zr;
+    const bool e1fuse = !fused && rt.ew1_fuse && na.flat_r && !na.zr;
     int ntiles = w.ntiles;
     if (fused) {
         RankEpi ep{};
         ep.mode = MODE_NORMS; ep.out = w.net_r; ep.part = w.part;
-        if (!r2_done && (st = launch_r2(pl, B, cur->rank2, cur->adj, flags, 1, ep, na, w, stream))) return st;
+        if (r2_done) ps.p1_raw = r2_p1_raw(p);          // (as the merged launch left the second buffer set)
+        else if ((st = launch_r2(pl, B, cur->rank2, cur->adj, flags, 1, ep, na, ps, w, stream))) return st;
         ntiles = 1;
     } else {
         P0Fuse pf{};
@@ -1159,17 +1131,18 @@ static int corrector_norms(ccsd_plan* pl, int B, int step, int it, const ccsd_st
             pf.mt = MaskTab{w.mfr, w.mfl, w.Kp, w.Ep}; pf.E = p.E; pf.alpha = p.f_alpha; pf.gamma = p.f_gamma;
             pf.net_out = keep_net ? w.net_r : nullptr;
         }
-        if ((st = launch_p(pl, B, cur->adj, base->rank2, w, stream, pf.mode ? &pf : nullptr))) return st;
+        if ((st = launch_p(pl, B, cur->adj, base->rank2, ps, w, stream, pf.mode ? &pf : nullptr))) return st;
     }
     XaArgs xa{};
     xa.xX = cur->x; xa.adjX = base->adj;      // score_x(x_cur, adj_0)      solver.py:761
     xa.xA = base->x; xa.adjA = cur->adj;      // score_adj(x_0, adj_cur)    solver.py:775
     xa.flags = flags; xa.do_x = xa.do_a = 1; xa.mode = MODE_NORMS;
     xa.out_x = w.net_x; xa.out_a = w.net_adj; xa.norm2 = w.norm2;
-    if ((st = launch_xa(pl, B, xa, na, w, stream, fused && r2_done))) return st;
-    if (p.is_cc && !fused && pl->ew1 && e1fuse && cur->rank2 == base->rank2) {
+    if ((st = launch_xa(pl, B, xa, na, ps, w, stream, fused && r2_done))) return st;
+    const bool ew1 = rt.r2_family == R2_EW1;
+    if (p.is_cc && !fused && ew1 && e1fuse && cur->rank2 == base->rank2) {
         ntiles = p.E;                            // (per-row partials written by the projection pass above)
-    } else if (p.is_cc && !fused && pl->ew1) {
+    } else if (p.is_cc && !fused && ew1) {
         // element-wise ScoreNetworkF: one streaming pass gives both norm partials per (sample, chunk); the raw score is kept only
         // for a separate ccsd_corrector_apply (the fused loop recomputes it)
         RankEpi ep{};
@@ -1177,7 +1150,7 @@ static int corrector_norms(ccsd_plan* pl, int B, int step, int it, const ccsd_st
         if ((st = launch_ew1(pl, B, cur->rank2, ep, na, w, stream, keep_net ? w.net_r : nullptr))) return st;
         ntiles = w.nchunk;
     } else if (p.is_cc && !fused) {
-        if ((st = launch_h(pl, B, cur->rank2, w, stream))) return st;
+        if ((st = launch_h(pl, B, cur->rank2, ps, w, stream))) return st;
         RankEpi ep{};
         ep.mode = MODE_NORMS; ep.out = w.net_r; ep.part = w.part;
         if ((st = launch_hf(pl, B, cur->rank2, ep, na, w, stream))) return st;
@@ -1186,10 +1159,10 @@ static int corrector_norms(ccsd_plan* pl, int B, int step, int it, const ccsd_st
     if (p.is_cc && !fused) {
         // tiled path: the noise norm of a flat-keyed Philox draw comes from its own (traffic-free) kernel; the per-tile partials of
         // k_hf_score and its chunk partials are reduced per sample first (one workgroup per sample), then over the batch
-        const bool zk = na.flat_r && !na.zr && !pl->ew1;
+        const bool zk = na.flat_r && !na.zr && !ew1;
         if (zk && !zfuse) {
 #define NN_GO(EC_, KC_) CCSD_LAUNCH((k_noise_norm<EC_, KC_>), dim3(w.nchunk, B), dim3(CCSD_NTHREADS), 0, stream, na, (MaskTab{w.mfr, w.mfl, w.Kp, w.Ep}), p.E, p.K, w.zpart)
-            GEO_EK(p, NN_GO);
+            GEO_EK(pl->rt.geo, NN_GO);
 #undef NN_GO
             LAUNCH_CHECK();
         }
@@ -1201,7 +1174,7 @@ static int corrector_norms(ccsd_plan* pl, int B, int step, int it, const ccsd_st
             part = w.part2; ntiles = 1;
         }
     }
-    CCSD_LAUNCH(k_normsum, dim3(1), dim3(CCSD_NTHREADS == 1 ? 1 : (B > 512 ? 1024 : B > 256 ? 512 : 256)), 0, stream, (const float*)w.norm2, part, B, ntiles,
+    CCSD_LAUNCH(k_normsum, dim3(1), dim3(CCSD_NTHREADS == 1 ? 1 : normsum_threads(B)), 0, stream, (const float*)w.norm2, part, B, ntiles,
                 p.is_cc, sums);
     LAUNCH_CHECK();
     return CCSD_OK;
@@ -1210,7 +1183,7 @@ static int corrector_apply(ccsd_plan* pl, int B, int step, int it, const ccsd_st
                            const ccsd_noise_t* noise, uint64_t seed, int64_t off, const float* sums, ccsd_state_t* out,
                            Workspace& w, void* stream) {
     const PlanD& p = pl->h;
-    NoiseArgs na = make_noise(noise, seed, off, draw_base(pl, step, it), corrector_flat(pl));
+    NoiseArgs na = make_noise(noise, seed, off, draw_base(pl, step, it), pl->rt.corrector_flat);
     LangArgs a{};
     a.x = cur->x; a.adj = cur->adj; a.r = cur->rank2;
     a.nx = w.net_x; a.nadj = w.net_adj; a.nr = w.net_r;
@@ -1225,7 +1198,7 @@ static int corrector_apply(ccsd_plan* pl, int B, int step, int it, const ccsd_st
     const long long total = (long long)B * (p.N * p.F + p.N * p.N) + (p.is_cc ? (long long)B * (((long long)p.E * p.K + 3) / 4) : 0);
     prof_mark(pl, KID_LANGEVIN, stream);
 #define LA_GO(EC_, KC_) CCSD_LAUNCH((k_langevin_apply<EC_, KC_>), dim3(grid_for(total, 256)), dim3(CCSD_NTHREADS), 0, stream, a, na, (MaskTab{w.mfr, w.mfl, w.Kp, w.Ep}))
-    GEO_EK(p, LA_GO);
+    GEO_EK(pl->rt.geo, LA_GO);
 #undef LA_GO
     prof_mark(pl, KID_LANGEVIN, stream);
     LAUNCH_CHECK();
@@ -1236,10 +1209,11 @@ static int predictor(ccsd_plan* pl, int B, int step, const ccsd_state_t* in, con
                      const float* fuse_sums = nullptr, bool merge_next = false) {
     const PlanD& p = pl->h;
     int st;
-    NoiseArgs na = make_noise(noise, seed, off, draw_base(pl, step, pl->cfg.n_corr_steps), predictor_flat(pl));
+    NoiseArgs na = make_noise(noise, seed, off, draw_base(pl, step, pl->cfg.n_corr_steps), pl->rt.predictor_flat);
     const ccsd_step_coef_t* c = &pl->coef[(size_t)step * 3];
-    const bool fused = pl->fused_r2 && p.is_cc;
-    const bool ew1 = pl->ew1 && p.is_cc && !fused;
+    const Route& rt = pl->rt;
+    Pass ps;
+    const bool fused = rt.r2_family == R2_FUSED, ew1 = rt.r2_family == R2_EW1;
     const float* r2_in = in->rank2;           // what the rank-2 kernels of the tiled path read (the corrected state when the apply is fused)
     CorrFuse cf{};
     if (fuse_sums) {   // the Langevin corrector's apply pass runs in the prologues of this half-step's kernels
@@ -1256,8 +1230,8 @@ static int predictor(ccsd_plan* pl, int B, int step, const ccsd_state_t* in, con
         // merged launch: the rank-2 side of the NEXT step's norms pass follows in the same launch (its corrector draw: rank2 slot of
         // draw_base(step + 1, 0))
         const int md = merge_next ? (int)draw_base(pl, step + 1, 0) + 2 : -1;
-        if ((st = launch_r2(pl, B, in->rank2, in->adj, flags, 1, ep, na, w, stream, &cf, md))) return st;
-    } else if (ew1 && cf.on && ew1_fuse_ok(pl) && !na.zr) {
+        if ((st = launch_r2(pl, B, in->rank2, in->adj, flags, 1, ep, na, ps, w, stream, &cf, md))) return st;
+    } else if (ew1 && cf.on && rt.ew1_fuse && !na.zr) {
         // element-wise ScoreNetworkF, one hodge layer: corrector apply + projection + predictor update in ONE pass over rank2
         P0Fuse pf{};
         pf.mode = 4; pf.seed = na.seed; pf.b_off = na.b_off; pf.draw = cf.draw_r; pf.draw_pred = na.draw_r;
@@ -1265,7 +1239,7 @@ static int predictor(ccsd_plan* pl, int B, int step, const ccsd_state_t* in, con
         pf.alpha = p.f_alpha; pf.gamma = p.f_gamma; pf.pa = c[2].pa; pf.pb = c[2].pb; pf.pc = c[2].pc;
         pf.out = out->rank2; pf.mean = mean ? mean->rank2 : nullptr;
         pf.f1 = w.net_r;                         // (host emulation only: its projection runs as a pass of its own over the corrected state)
-        if ((st = launch_p(pl, B, in->adj, in->rank2, w, stream, &pf))) return st;
+        if ((st = launch_p(pl, B, in->adj, in->rank2, ps, w, stream, &pf))) return st;
     } else if (ew1) {
         // element-wise ScoreNetworkF first: with the fused apply it produces the corrected rank2 (in the raw-score scratch, which
         // the fused loop does not fill) that the hodge projections of the A-network must see
@@ -1273,16 +1247,16 @@ static int predictor(ccsd_plan* pl, int B, int step, const ccsd_state_t* in, con
         ep.mode = MODE_PRED; ep.pa = c[2].pa; ep.pb = c[2].pb; ep.pc = c[2].pc;
         ep.out = out->rank2; ep.mean = mean ? mean->rank2 : nullptr;
         if ((st = launch_ew1(pl, B, in->rank2, ep, na, w, stream, nullptr, &cf, w.net_r))) return st;
-        if ((st = launch_p(pl, B, in->adj, cf.on ? (const float*)w.net_r : in->rank2, w, stream))) return st;
-    } else if (cf.on && tiled_fuse_ok(pl)) {
+        if ((st = launch_p(pl, B, in->adj, cf.on ? (const float*)w.net_r : in->rank2, ps, w, stream))) return st;
+    } else if (cf.on && rt.tiled_fuse) {
         // tiled path: the corrector apply rides on the projection pass -- corrected rank2 written in place over the raw scores it
         // consumes (w.net_r), P_0 taken of it; k_gemm_h / k_hf_score below read the corrected state from there
         P0Fuse pf{};
         pf.mode = 2; pf.net = w.net_r; pf.f1 = w.net_r; pf.seed = na.seed; pf.b_off = na.b_off; pf.draw = cf.draw_r;
         pf.mt = MaskTab{w.mfr, w.mfl, w.Kp, w.Ep}; pf.E = p.E; pf.cf = cf;
-        if ((st = launch_p(pl, B, in->adj, in->rank2, w, stream, &pf))) return st;
+        if ((st = launch_p(pl, B, in->adj, in->rank2, ps, w, stream, &pf))) return st;
         r2_in = w.net_r;
-    } else if ((st = launch_p(pl, B, in->adj, in->rank2, w, stream))) return st;
+    } else if ((st = launch_p(pl, B, in->adj, in->rank2, ps, w, stream))) return st;
     XaArgs xa{};
     xa.xX = xa.xA = in->x; xa.adjX = xa.adjA = in->adj; xa.flags = flags;
     xa.do_x = xa.do_a = 1; xa.mode = MODE_PRED;
@@ -1291,9 +1265,9 @@ static int predictor(ccsd_plan* pl, int B, int step, const ccsd_state_t* in, con
     xa.out_x = out->x; xa.out_a = out->adj;
     xa.mean_x = mean ? mean->x : nullptr; xa.mean_a = mean ? mean->adj : nullptr;
     xa.cf = cf;
-    if ((st = launch_xa(pl, B, xa, na, w, stream))) return st;
+    if ((st = launch_xa(pl, B, xa, na, ps, w, stream))) return st;
     if (p.is_cc && !fused && !ew1) {
-        if ((st = launch_h(pl, B, r2_in, w, stream))) return st;
+        if ((st = launch_h(pl, B, r2_in, ps, w, stream))) return st;
         RankEpi ep{};
         ep.mode = MODE_PRED; ep.pa = c[2].pa; ep.pb = c[2].pb; ep.pc = c[2].pc;
         ep.out = out->rank2; ep.mean = mean ? mean->rank2 : nullptr;
@@ -1393,9 +1367,8 @@ extern "C" int ccsd_sampler_run(ccsd_plan_t* pl, int32_t B, const float* flags, 
     if (st || (st = check_state(pl, state, "state")) || (st = check_state(pl, scratch, "scratch")) ||
         (st = check_state(pl, result, "result"))) return st;
     if (first_step < 0 || last_step > pl->cfg.diff_steps || first_step >= last_step) return set_err(CCSD_ERR_INVALID, "bad step range");
-    const bool s4 = pl->cfg.predictor == CCSD_PRED_S4;
-    const bool lang = pl->cfg.corrector == CCSD_CORR_LANGEVIN && !s4;
-    if (lang && pl->cfg.n_corr_steps != 1)
+    const Route& rt = pl->rt;
+    if (rt.loop == LOOP_STEPWISE)
         return set_err(CCSD_ERR_UNSUPPORTED, "ccsd_sampler_run handles n_steps == 1; drive other values step by step");
     const PlanD& p = pl->h;
     Workspace w = carve_ws(pl, B, workspace);
@@ -1405,25 +1378,24 @@ extern "C" int ccsd_sampler_run(ccsd_plan_t* pl, int32_t B, const float* flags, 
     for (int step = first_step; step < last_step; ++step) {
         const bool lastone = step == last_step - 1;
         const bool want_mean = pl->cfg.denoise && (lastone || traj);
-        if (s4) {   // scores + first draw + norm sums at the state, then the element-wise S4 update: a -> b, swap
+        if (rt.loop == LOOP_S4) {   // scores + first draw + norm sums at the state, then the element-wise S4 update: a -> b, swap
             if ((st = corrector_norms(pl, B, step, 0, &a, &a, flags, nullptr, seed, sample_offset, w.sums, w, stream))) return st;
             if ((st = s4_apply(pl, B, step, &a, flags, nullptr, nullptr, nullptr, seed, sample_offset, w.sums, &b,
                                want_mean ? result : nullptr, w, stream))) return st;
             ccsd_state_t t = a; a = b; b = t;
-        } else if (lang && fused_apply_ok(pl)) {
+        } else if (rt.loop == LOOP_LANGEVIN_FUSED) {
             // a -> [norms pass] ; [apply fused into the predictor kernels] -> b ; swap roles.  Merged k_r2 launches: the predictor's
             // k_r2 also runs the rank-2 side of the next step's norms pass on the block it has just produced (r2_done below)
-            const bool merged = merge_ok(pl);
-            const bool r2_done = merged && step > first_step;
-            const bool merge_next = merged && !lastone;
-            if ((st = corrector_norms(pl, B, step, 0, &a, &a, flags, nullptr, seed, sample_offset, w.sums, w, stream, /*keep_net=*/pl->fused_r2 != 0, r2_done))) return st;
+            const bool r2_done = rt.merged && step > first_step;
+            const bool merge_next = rt.merged && !lastone;
+            if ((st = corrector_norms(pl, B, step, 0, &a, &a, flags, nullptr, seed, sample_offset, w.sums, w, stream, /*keep_net=*/rt.r2_family == R2_FUSED, r2_done))) return st;
             // u_1 = fr . Wcat_1 depends on the flags alone: the run's first (general) k_r2 launch has just written it; the masked launches
             // of the loop leave both copies alone (R2Args::masked), so the second buffer set gets its copy once
-            if (merged && !r2_done && pl->opt_r2_masked && p.h_L > 1 && p.hl[0].mval.n == 1)
+            if (rt.merged && !r2_done && r2_p1_raw(p))
                 RT_CHECK(rt_d2d_async(w.U1b, w.U1, (size_t)B * p.h_pw * 4, stream));
             if ((st = predictor(pl, B, step, &a, flags, nullptr, seed, sample_offset, &b, want_mean ? result : nullptr, w, stream, w.sums, merge_next))) return st;
             ccsd_state_t t = a; a = b; b = t;
-        } else if (lang) {   // a -> (corrector) -> b -> (predictor) -> a
+        } else if (rt.loop == LOOP_LANGEVIN) {   // a -> (corrector) -> b -> (predictor) -> a
             if ((st = corrector_norms(pl, B, step, 0, &a, &a, flags, nullptr, seed, sample_offset, w.sums, w, stream))) return st;
             if ((st = corrector_apply(pl, B, step, 0, &a, flags, nullptr, seed, sample_offset, w.sums, &b, w, stream))) return st;
             if ((st = predictor(pl, B, step, &b, flags, nullptr, seed, sample_offset, &a, want_mean ? result : nullptr, w, stream))) return st;

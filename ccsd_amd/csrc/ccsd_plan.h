@@ -167,14 +167,19 @@ struct PlanBuilder {
     int pcur = 0;     // packed (chain) weight buffer
     // reserve padded copies of an MLP's linears for mlp_chain_tile
     void chainify(MlpD& m, unsigned allowed);
-    void transposed(MlpD& m) {          // (non-chained MLPs that run through block_linear; CCSD_NO_MLP_WT: diagnostic)
-        if (m.chain || getenv("CCSD_NO_MLP_WT")) return;
+    void transposed(MlpD& m) {          // (non-chained MLPs that run through block_linear; no_mlp_wt: diagnostic)
+        if (m.chain || no_mlp_wt) return;
         for (int i = 0; i < m.n; ++i) { m.pw[i] = pcur; pcur += (i == 0 ? m.in : m.hid) * (((i == m.n - 1 ? m.out : m.hid) + 15) & ~15); }
         m.pb[0] = CCSD_MLP_WT;
     }
     std::string err;
     int status = CCSD_OK;
-    int lg_force = 0;   // in: CCSD_LARGE_GRAPH=1 (read once by ccsd_plan_create) -- the tiled route for any eligible plan
+    // in: the plan-shaping switches, read from the environment once by ccsd_plan_create (read_knobs, ccsd_api.h)
+    int lg_force = 0;   // CCSD_LARGE_GRAPH=1: the tiled route for any eligible plan
+    int no_mlp_wt = 0;  // CCSD_NO_MLP_WT
+    int xa_pass = -1;   // CCSD_XA_PASS: first k_xa LDS budget candidate tried (-1: by batch_hint)
+    int xa_gch = 0;     // CCSD_XA_GCH: the channel stack in the HBM workspace first
+    int verbose = 0;    // CCSD_VERBOSE
     int lg = 0;         // out: the plan takes the tiled graph-network route (ccsd_k_lg.h) instead of k_xa
     int take(int64_t n) {
         int o = cur;
@@ -198,7 +203,6 @@ struct PlanBuilder {
 
 inline void PlanBuilder::chainify(MlpD& m, unsigned allowed) {
     m.chain = 0;
-    if (getenv("CCSD_NO_CHAIN")) return;
     const int ni = pad16(m.in) / 16, nh = m.n > 1 ? pad16(m.hid) / 16 : 1, no = pad16(m.out) / 16;
     for (int sidx = 1; sidx < CCSD_NSHAPES && !m.chain; ++sidx) {
         const int* sh = CCSD_CHAIN_SHAPES[sidx];
@@ -538,16 +542,15 @@ static inline size_t ccsd_build_plan(const ccsd_config_t* c, PlanD* p, PlanBuild
     for (int l = 0; l < p->h_L; ++l) if (ccsd_hl(*p, l).matt.n > hw_n) hw_n = ccsd_hl(*p, l).matt.n;
     auto ld_of = [](int rows) { int r = (rows + 15) / 16 * 16; if (r % 32 == 0) r += 8; return r; };   // 2-way conflicts at worst
     int best_total = -1;
-    const char* skip = getenv("CCSD_XA_PASS");
     // Large graphs (zinc250k: 46 channels x 38 x 38 = 266 KB): second round of candidates with the channel stack in the
     // HBM workspace (L2-resident, one slab per graph) and only the per-layer working set in LDS.  CCSD_XA_GCH=1 forces it.
     // Start at the budget that keeps ceil(batch / #CUs) workgroups co-resident per CU (batch_hint; unknown = 4 per CU, the
     // qm9_CC B = 1024 case), then grow.  Within a budget the channel stack in LDS is tried before the HBM variant: with the
     // residency the batch needs, more workgroups per CU buy nothing and the HBM stack costs.
-    const int gch_first = getenv("CCSD_XA_GCH") ? 1 : 0;
+    const int gch_first = pb.xa_gch;
     int need = c->batch_hint > 0 ? (c->batch_hint + 255) / 256 : 4;
     need = need < 1 ? 1 : need > 4 ? 4 : need;
-    for (int pass = skip ? atoi(skip) : 4 - need; pass < NCAND && best_total < 0; ++pass)
+    for (int pass = pb.xa_pass >= 0 ? pb.xa_pass : 4 - need; pass < NCAND && best_total < 0; ++pass)
     for (int gch = gch_first; gch < 2 && best_total < 0; ++gch) {
         if (stage_on[pass] && (wst_full == 0 || gch)) continue;
         p->chan_global = gch;
@@ -650,13 +653,13 @@ static inline size_t ccsd_build_plan(const ccsd_config_t* c, PlanD* p, PlanBuild
     // tiles of 16, and room for its own [x_fdim + max(F, 4)][ldn] + 16 floats inside the budget the layout already fits.
     p->x_late = 0; p->o_lx = 0;
     if (best_total > 0 && !p->x_gmh && !p->hb_L && !p->chan_global && p->x_fin.chain && p->a_fin.chain && p->a_L >= 2 && N <= 16 && E <= 48 &&
-        p->al[0].mlp.chain && p->al[1].mlp.chain && getenv("CCSD_NO_XLATE") == nullptr) {
+        p->al[0].mlp.chain && p->al[1].mlp.chain) {
         const int lx = (p->x_fdim + (F > 4 ? F : 4)) * p->ldn + 16;
         int cap = 160 * 1024 / 4;
         for (int q = NCAND - 1; q >= 0; --q) if (best_total * 4 <= budgets_b[q]) cap = budgets_b[q] / 4;
         if (best_total + lx <= cap) { p->x_late = 1; p->o_lx = best_total; best_total += lx; p->xa_lds_floats = best_total; if (p->x_gmh) p->x_lds_floats = best_total; }
     }
-    if (getenv("CCSD_VERBOSE"))
+    if (pb.verbose)
         fprintf(stderr, "[ccsd] k_xa LDS %d B (cg=%d pch=%d/%d pchp=%d/%d stage=%d floats, channel stack in %s)\n", best_total * 4, p->cg, p->pch, p->ldp, p->pchp, p->ldpp, p->wst_floats, p->chan_global ? "HBM" : "LDS");
     if (best_total < 0 || (size_t)best_total * 4 > 160 * 1024) {
         if (!lg_reason) pb.lg = 1;         // no k_xa layout: the tiled route serves the plan

@@ -165,8 +165,20 @@ enum {
     CCSD_QUERY_MERGED_R2 = 5,     /* 1: ... and k_r2 runs the predictor half-step of step i and the rank-2 side of the norms pass of step i + 1
                                      in one launch (one block load per PC step) */
     CCSD_QUERY_EW1 = 6,           /* 1: element-wise rank-2 kernel k_ew1 (affine ScoreNetworkF without a Hodge Laplacian term, cnum = 1) */
-    CCSD_QUERY_LARGE_GRAPH = 7    /* 1: the tiled graph-network kernels k_lg_* serve the graph networks instead of k_xa (graph-only plans above
+    CCSD_QUERY_LARGE_GRAPH = 7,   /* 1: the tiled graph-network kernels k_lg_* serve the graph networks instead of k_xa (graph-only plans above
                                      64 nodes or without a k_xa LDS layout, up to N = 512; CCSD_LARGE_GRAPH=1 at plan creation forces it) */
+    /* the rest of the plan's route; answers that depend on the batch are given for config.batch_hint */
+    CCSD_QUERY_R2_FAMILY = 8,     /* rank-2 side: 0 none (graph-only), 1 fused k_r2, 2 element-wise k_ew1, 3 tiled (k_gemm_h + k_hf_score) */
+    CCSD_QUERY_R2_INSTANCE = 9,   /* k_r2<MT, RS, AFFINE, GEN1, QM9> as the decimal digits MT RS AFFINE GEN1 QM9 (31102 = k_r2<3, 1, true, false, 2>); -1: no k_r2 */
+    CCSD_QUERY_LOOP_FORM = 10,    /* ccsd_sampler_run: 0 predictor only, 1 Langevin with an apply launch of its own, 2 Langevin with the apply fused into
+                                     the predictor launches, 3 S4, 4 none (Langevin with n_steps != 1: step-wise calls only) */
+    CCSD_QUERY_H_FULL = 11,       /* 1: H = F F^T comes from k_gemm_h_full (one workgroup per complex) */
+    CCSD_QUERY_HP_FULL = 12,      /* k_hp_full (P_0, H and the corrector's rank2 work in one pass): bit 0 in the predictor pass, bit 1 in the norms pass */
+    CCSD_QUERY_P0_NARROW = 13,    /* layer-0 hodge projection: 0 wide (k_gemm_p) or none; else k_gemm_p0<NT, KC, .> as NT * 100000 + KC */
+    CCSD_QUERY_TILED_FUSE = 14,   /* 1: tiled rank-2 side, the Langevin corrector's rank2 work rides on the layer-0 projection pass */
+    CCSD_QUERY_EW1_FUSE = 15,     /* 1: k_ew1 plans, the whole rank-2 side of a half-step rides on the layer-0 projection pass */
+    CCSD_QUERY_H_GENERAL = 16,    /* 1: general hodge stack (R_l materialised layer by layer) */
+    CCSD_QUERY_GEO_EK = 17        /* general-path kernels: 0 run-time (E, K); 1 community_small, 2 zinc250k, 3 ENZYMES_small compiled in */
 };
 int ccsd_plan_query(const ccsd_plan_t* plan, int32_t what, int64_t* value);
 
