@@ -14,7 +14,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 HIP_LIB_PATH = os.path.join(HERE, "libccsd_hip.so")
 
 ABI_VERSION = 5
-OK, ERR_INVALID, ERR_UNSUPPORTED, ERR_WEIGHTS, ERR_RUNTIME, ERR_WORKSPACE = range(6)
+OK, ERR_INVALID, ERR_UNSUPPORTED, ERR_WEIGHTS, ERR_RUNTIME, ERR_WORKSPACE, ERR_CALLBACK = range(7)
 SDE_VP, SDE_VE, SDE_SUBVP = 0, 1, 2
 PRED_EULER, PRED_REVERSE, PRED_S4 = 0, 1, 2
 CORR_NONE, CORR_LANGEVIN = 0, 1
@@ -24,7 +24,7 @@ EXPORTS = [
     "ccsd_plan_create", "ccsd_plan_destroy", "ccsd_weight_count", "ccsd_rank2_dims", "ccsd_workspace_bytes",
     "ccsd_last_error", "ccsd_score", "ccsd_init_state", "ccsd_corrector_norms", "ccsd_corrector_apply",
     "ccsd_predictor", "ccsd_s4_apply", "ccsd_sampler_run", "ccsd_quantize", "ccsd_rank2_cells", "ccsd_profile_kernel", "ccsd_profile_stride", "ccsd_profile_read", "ccsd_profile_launches", "ccsd_debug_stamps",
-    "ccsd_noise_draws", "ccsd_plan_query",
+    "ccsd_noise_draws", "ccsd_plan_query", "ccsd_sampler_run_ex",
 ]
 QUERIES = {"fused_r2": 0, "xa_variant": 1, "r2_lds_bytes": 2, "xa_lds_bytes": 3, "fused_loop": 4, "merged_r2": 5, "ew1": 6, "large_graph": 7,
            "r2_family": 8, "r2_instance": 9, "loop_form": 10, "h_full": 11, "hp_full": 12, "p0_narrow": 13, "tiled_fuse": 14, "ew1_fuse": 15,
@@ -58,6 +58,14 @@ class State(C.Structure):
 
 class Noise(C.Structure):
     _fields_ = [("zx", C.c_void_p), ("zadj", C.c_void_p), ("zrank2", C.c_void_p)]
+
+
+# ccsd_reduce_fn: int (*)(float* sums_dev, int32_t n, void* stream, void* user)
+REDUCE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p)
+
+
+class RunOptions(C.Structure):
+    _fields_ = [("reduce", REDUCE_FN), ("user", C.c_void_p)]
 
 
 class CcsdError(RuntimeError):
@@ -113,6 +121,8 @@ class Library:
         L.ccsd_s4_apply.restype = C.c_int
         L.ccsd_sampler_run.argtypes = [vp, i32, vp, u64, i64, i32, i32, P(State), P(State), P(State), vp, vp, sz, vp]
         L.ccsd_sampler_run.restype = C.c_int
+        L.ccsd_sampler_run_ex.argtypes = L.ccsd_sampler_run.argtypes + [P(RunOptions)]
+        L.ccsd_sampler_run_ex.restype = C.c_int
         L.ccsd_quantize.argtypes = [vp, i64, f32, vp, vp]
         L.ccsd_quantize.restype = C.c_int
         L.ccsd_rank2_cells.argtypes = [vp, i32, i32, i64, f32, vp, vp, vp]

@@ -80,8 +80,9 @@ static Knobs read_knobs() {
 
 // Which kernels serve a plan: fixed by (config, the weights' architecture, knobs), resolved once by resolve_route().
 enum { R2_NONE = 0, R2_FUSED = 1, R2_EW1 = 2, R2_TILED = 3 };       // rank-2 family: graph-only / k_r2 / k_ew1 / k_gemm_h + k_hf_score
-// form of ccsd_sampler_run's loop (LOOP_STEPWISE: Langevin with n_corr_steps != 1, which the call refuses)
-enum { LOOP_PRED_ONLY = 0, LOOP_LANGEVIN = 1, LOOP_LANGEVIN_FUSED = 2, LOOP_S4 = 3, LOOP_STEPWISE = 4 };
+// form of ccsd_sampler_run's loop (LOOP_LANGEVIN_MULTI: Langevin with n_corr_steps != 1 -- the inner iterations run one after the
+// other through a third state buffer out of the workspace, every apply a launch of its own)
+enum { LOOP_PRED_ONLY = 0, LOOP_LANGEVIN = 1, LOOP_LANGEVIN_FUSED = 2, LOOP_S4 = 3, LOOP_LANGEVIN_MULTI = 4 };
 struct Route {
     // graph-network side
     int lg = 0;                     // tiled route (ccsd_k_lg.h) instead of k_xa: graph-only plans k_xa cannot place (N > 64, no LDS layout), or
@@ -271,7 +272,7 @@ static int resolve_route(ccsd_plan* pl) {
     // ---- ccsd_sampler_run.  The Langevin apply fuses into the predictor launches of k_r2 plans, of k_ew1 plans whose hodge
     // projections do not depend on the adjacency (at most one hodge layer) and of tiled plans with one hodge layer
     const bool fused_apply = (fused || (ew1 && p.h_L <= 1) || r.tiled_fuse) && !k.no_fused_apply;
-    r.loop = s4 ? LOOP_S4 : !langevin ? LOOP_PRED_ONLY : c.n_corr_steps != 1 ? LOOP_STEPWISE : fused_apply ? LOOP_LANGEVIN_FUSED : LOOP_LANGEVIN;
+    r.loop = s4 ? LOOP_S4 : !langevin ? LOOP_PRED_ONLY : c.n_corr_steps != 1 ? LOOP_LANGEVIN_MULTI : fused_apply ? LOOP_LANGEVIN_FUSED : LOOP_LANGEVIN;
     // merged k_r2 launches (predictor of step i + rank-2 side of the norms pass of step i + 1): the row-strip instantiation of the
     // kernel (E = 33..36, affine ScoreNetworkF, linear mlp_value), pair-wise block load (K even, E K a multiple of 4)
     // (k_hp_full's mode 2 is the fused apply: only the fused loop's predictor pass carries it)
@@ -540,6 +541,7 @@ struct Workspace {
     // [B][N][x_fdim], its X W [B][N][nhid], its masked net [B][N][F]; k_lg_fin's per-tile norm partials [B][lg_tiles][2]
     float *lg_S, *lg_att, *lg_dis, *lg_Y, *lg_QKV, *lg_x[2], *lg_xcat, *lg_xY, *lg_xnet, *lg_part;
     int lg_tiles;
+    ccsd_state_t third;             // LOOP_LANGEVIN_MULTI with more than one inner iteration: the second corrector iterate of ccsd_sampler_run
     size_t bytes;
 };
 // What one pass (a norms pass, a predictor pass, one ccsd_score) hands from launcher to launcher.
@@ -611,6 +613,11 @@ static Workspace carve_ws(const ccsd_plan* pl, int B, void* base) {
         w.lg_xY = (float*)take((size_t)B * N * p.x_nhid * 4);
         w.lg_xnet = (float*)take((size_t)B * N * p.F * 4);
         w.lg_part = (float*)take((size_t)B * w.lg_tiles * 2 * 4);
+    }
+    if (pl->rt.loop == LOOP_LANGEVIN_MULTI && pl->cfg.n_corr_steps > 1) {      // (last: no plan with n_steps == 1 moves)
+        w.third.x = (float*)take((size_t)B * p.N * p.F * 4);
+        w.third.adj = (float*)take((size_t)B * p.N * p.N * 4);
+        w.third.rank2 = p.is_cc ? (float*)take((size_t)B * E * K * 4) : nullptr;
     }
     w.bytes = o;
     return w;
@@ -1360,26 +1367,30 @@ extern "C" int ccsd_s4_apply(ccsd_plan_t* pl, int32_t B, int32_t step, const ccs
     return s4_apply(pl, B, step, cur, flags, noise1, noise2, noise3, seed, sample_offset, norm_sums, out, mean, w, stream);
 }
 
-extern "C" int ccsd_sampler_run(ccsd_plan_t* pl, int32_t B, const float* flags, uint64_t seed, int64_t sample_offset,
-                                int32_t first_step, int32_t last_step, ccsd_state_t* state, ccsd_state_t* scratch,
-                                ccsd_state_t* result, float* traj, void* workspace, size_t ws_bytes, void* stream) {
+// The loop behind ccsd_sampler_run (no hook) and ccsd_sampler_run_ex.  `reduce` is called once per norms pass, after its k_normsum
+// has been enqueued and before any reader of w.sums is: the launches are the same with and without it.
+static int sampler_run(ccsd_plan_t* pl, int32_t B, const float* flags, uint64_t seed, int64_t sample_offset,
+                       int32_t first_step, int32_t last_step, ccsd_state_t* state, ccsd_state_t* scratch,
+                       ccsd_state_t* result, float* traj, void* workspace, size_t ws_bytes, void* stream,
+                       ccsd_reduce_fn reduce, void* user) {
     int st = check_common(pl, B, flags, workspace, ws_bytes);
     if (st || (st = check_state(pl, state, "state")) || (st = check_state(pl, scratch, "scratch")) ||
         (st = check_state(pl, result, "result"))) return st;
     if (first_step < 0 || last_step > pl->cfg.diff_steps || first_step >= last_step) return set_err(CCSD_ERR_INVALID, "bad step range");
     const Route& rt = pl->rt;
-    if (rt.loop == LOOP_STEPWISE)
-        return set_err(CCSD_ERR_UNSUPPORTED, "ccsd_sampler_run handles n_steps == 1; drive other values step by step");
     const PlanD& p = pl->h;
     Workspace w = carve_ws(pl, B, workspace);
     if ((st = launch_flagbits(pl, B, flags, w, stream))) return st;
     const size_t nx = (size_t)p.N * p.F, na = (size_t)p.N * p.N, nr = p.is_cc ? (size_t)p.E * p.K : 0;
     ccsd_state_t a = *state, b = *scratch;   // a = live buffer
+    // exact multi-GPU mode: the caller all-reduces the six sums in place, ordered on `stream`
+#define REDUCE_SUMS() do { if (reduce && reduce(w.sums, 6, stream, user)) return set_err(CCSD_ERR_CALLBACK, "the reduce hook of ccsd_sampler_run_ex failed"); } while (0)
     for (int step = first_step; step < last_step; ++step) {
         const bool lastone = step == last_step - 1;
         const bool want_mean = pl->cfg.denoise && (lastone || traj);
         if (rt.loop == LOOP_S4) {   // scores + first draw + norm sums at the state, then the element-wise S4 update: a -> b, swap
             if ((st = corrector_norms(pl, B, step, 0, &a, &a, flags, nullptr, seed, sample_offset, w.sums, w, stream))) return st;
+            REDUCE_SUMS();
             if ((st = s4_apply(pl, B, step, &a, flags, nullptr, nullptr, nullptr, seed, sample_offset, w.sums, &b,
                                want_mean ? result : nullptr, w, stream))) return st;
             ccsd_state_t t = a; a = b; b = t;
@@ -1389,6 +1400,7 @@ extern "C" int ccsd_sampler_run(ccsd_plan_t* pl, int32_t B, const float* flags, 
             const bool r2_done = rt.merged && step > first_step;
             const bool merge_next = rt.merged && !lastone;
             if ((st = corrector_norms(pl, B, step, 0, &a, &a, flags, nullptr, seed, sample_offset, w.sums, w, stream, /*keep_net=*/rt.r2_family == R2_FUSED, r2_done))) return st;
+            REDUCE_SUMS();
             // u_1 = fr . Wcat_1 depends on the flags alone: the run's first (general) k_r2 launch has just written it; the masked launches
             // of the loop leave both copies alone (R2Args::masked), so the second buffer set gets its copy once
             if (rt.merged && !r2_done && r2_p1_raw(p))
@@ -1397,8 +1409,21 @@ extern "C" int ccsd_sampler_run(ccsd_plan_t* pl, int32_t B, const float* flags, 
             ccsd_state_t t = a; a = b; b = t;
         } else if (rt.loop == LOOP_LANGEVIN) {   // a -> (corrector) -> b -> (predictor) -> a
             if ((st = corrector_norms(pl, B, step, 0, &a, &a, flags, nullptr, seed, sample_offset, w.sums, w, stream))) return st;
+            REDUCE_SUMS();
             if ((st = corrector_apply(pl, B, step, 0, &a, flags, nullptr, seed, sample_offset, w.sums, &b, w, stream))) return st;
             if ((st = predictor(pl, B, step, &b, flags, nullptr, seed, sample_offset, &a, want_mean ? result : nullptr, w, stream))) return st;
+        } else if (rt.loop == LOOP_LANGEVIN_MULTI && pl->cfg.n_corr_steps > 0) {
+            // a = base -> (corrector 0) -> b -> (corrector 1) -> third -> (corrector 2) -> b ... -> (predictor) -> a.  Every inner
+            // iteration scores against the base state with its own target's tensor taken from the current iterate (corrector_norms)
+            const ccsd_state_t* cur = &a;
+            for (int it = 0; it < pl->cfg.n_corr_steps; ++it) {
+                ccsd_state_t* out = (it & 1) ? &w.third : &b;
+                if ((st = corrector_norms(pl, B, step, it, &a, cur, flags, nullptr, seed, sample_offset, w.sums, w, stream))) return st;
+                REDUCE_SUMS();
+                if ((st = corrector_apply(pl, B, step, it, cur, flags, nullptr, seed, sample_offset, w.sums, out, w, stream))) return st;
+                cur = out;
+            }
+            if ((st = predictor(pl, B, step, cur, flags, nullptr, seed, sample_offset, &a, want_mean ? result : nullptr, w, stream))) return st;
         } else {      // a -> (predictor) -> b, then swap roles
             if ((st = predictor(pl, B, step, &a, flags, nullptr, seed, sample_offset, &b, want_mean ? result : nullptr, w, stream))) return st;
             ccsd_state_t t = a; a = b; b = t;
@@ -1421,7 +1446,21 @@ extern "C" int ccsd_sampler_run(ccsd_plan_t* pl, int32_t B, const float* flags, 
         RT_CHECK(rt_d2d_async(result->adj, a.adj, (size_t)B * na * 4, stream));
         if (nr) RT_CHECK(rt_d2d_async(result->rank2, a.rank2, (size_t)B * nr * 4, stream));
     }
+#undef REDUCE_SUMS
     return CCSD_OK;
+}
+extern "C" int ccsd_sampler_run(ccsd_plan_t* pl, int32_t B, const float* flags, uint64_t seed, int64_t sample_offset,
+                                int32_t first_step, int32_t last_step, ccsd_state_t* state, ccsd_state_t* scratch,
+                                ccsd_state_t* result, float* traj, void* workspace, size_t ws_bytes, void* stream) {
+    return sampler_run(pl, B, flags, seed, sample_offset, first_step, last_step, state, scratch, result, traj, workspace, ws_bytes,
+                       stream, nullptr, nullptr);
+}
+extern "C" int ccsd_sampler_run_ex(ccsd_plan_t* pl, int32_t B, const float* flags, uint64_t seed, int64_t sample_offset,
+                                   int32_t first_step, int32_t last_step, ccsd_state_t* state, ccsd_state_t* scratch,
+                                   ccsd_state_t* result, float* traj, void* workspace, size_t ws_bytes, void* stream,
+                                   const ccsd_run_options_t* options) {
+    return sampler_run(pl, B, flags, seed, sample_offset, first_step, last_step, state, scratch, result, traj, workspace, ws_bytes,
+                       stream, options ? options->reduce : nullptr, options ? options->user : nullptr);
 }
 
 extern "C" int ccsd_quantize(const float* in, int64_t n, float thr, int64_t* out, void* stream) {

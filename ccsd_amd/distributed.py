@@ -19,7 +19,9 @@ rank -- the same contract as the reference's DataParallel call, so Sampler_*.sam
 
 Modes:
   exact=True   the six norm sums are all-reduced, Philox is keyed by the global sample index: the sharded run
-               reproduces the single-process run of the whole batch (tests/test_multiprocess_gloo.py);
+               reproduces the single-process run of the whole batch (tests/test_multiprocess_gloo.py).  The all-reduce is the
+               reduce hook of the library loop (ccsd_sampler_run_ex): the same single C call, merged and fused launches as
+               the independent mode, plus one collective per norms pass ordered on the stream (no host synchronisation);
   exact=False  per-shard Langevin norms, no per-step communication (what the reference's own `divide_batch`
                does to the statistics); bench.py measures this mode.
 """

@@ -185,28 +185,79 @@ class PCEngine:
                                               self._noise(noise2, B), self._noise(noise3, B), seed, sample_offset,
                                               _ptr(sums), C.byref(so), sm, ws, n, self._stream()))
 
+    def _reduce_options(self, reduce):
+        """ccsd_run_options_t around a Python `reduce(sums)` callable -> (options or None, keep-alive objects, error cell).  The
+        hook hands `reduce` a float32 view of the six norm sums inside the engine's own workspace tensor (a slice of self._ws: no
+        copy, the all-reduce lands where the kernels read).  An exception raised by `reduce` is kept in the cell and turned into a
+        non-zero return: the C loop stops, and the caller re-raises it once the C call is back."""
+        if reduce is None:
+            return None, None, None
+        ws, err = self._ws, []
+
+        def hook(sums_dev, n, stream, user):
+            try:
+                off = sums_dev - ws.data_ptr()
+                if off < 0 or off + 4 * n > ws.numel():
+                    raise _lib.CcsdError("reduce hook: the norm sums lie outside the engine's workspace")
+                reduce(ws[off:off + 4 * n].view(torch.float32))
+                return 0
+            except BaseException as e:      # (nothing may propagate into the C frame)
+                err.append(e)
+                return 1
+
+        cb = _lib.REDUCE_FN(hook)
+        opts = _lib.RunOptions(cb, None)
+        return opts, (cb, opts, hook), err
+
     def run(self, flags, state, scratch, result, seed: int = 0, sample_offset: int = 0, first_step: int = 0,
-            last_step: Optional[int] = None, traj: Optional[torch.Tensor] = None):
+            last_step: Optional[int] = None, traj: Optional[torch.Tensor] = None, reduce=None):
+        """The library loop (ccsd_sampler_run; ccsd_sampler_run_ex when `reduce` is given).  PRECONDITION: `state` is MASKED by
+        `flags` -- x rows, adj rows / columns and rank2 rows / columns of switched-off nodes hold zeros, as in everything init_state
+        or an earlier run wrote; the loop's rank-2 kernels skip re-masking rank2 (include/ccsd_hip.h).
+        reduce: callable taking the six Langevin norm sums as a float32 device tensor of 6 elements, called once per norms pass
+        (every Langevin inner iteration, every S4 step); it reduces them IN PLACE, ordered on the current stream
+        (torch.distributed.all_reduce does).  An exception it raises stops the loop and is re-raised here; the state buffers
+        are then undefined."""
         B = flags.shape[0]
         s, sc, r = self._state(*state, B), self._state(*scratch, B, "scratch"), self._state(*result, B, "result")
         ws, n = self._workspace(B)
         last = self.diff_steps if last_step is None else last_step
-        self.lib.check(self.lib.ccsd_sampler_run(self.handle, B, _ptr(flags), seed, sample_offset, first_step, last,
-                                                 C.byref(s), C.byref(sc), C.byref(r), _ptr(traj), ws, n, self._stream()))
+        opts, keep, err = self._reduce_options(reduce)
+        if opts is None:
+            rc = self.lib.ccsd_sampler_run(self.handle, B, _ptr(flags), seed, sample_offset, first_step, last,
+                                           C.byref(s), C.byref(sc), C.byref(r), _ptr(traj), ws, n, self._stream())
+        else:
+            rc = self.lib.ccsd_sampler_run_ex(self.handle, B, _ptr(flags), seed, sample_offset, first_step, last,
+                                              C.byref(s), C.byref(sc), C.byref(r), _ptr(traj), ws, n, self._stream(), C.byref(opts))
+            del keep                        # (the callback object lived through the call)
+            if err:
+                raise err[0]
+        self.lib.check(rc)
 
     def init_and_run(self, flags, state, scratch, result, seed: int = 0, sample_offset: int = 0, first_step: int = 0,
-                     last_step: Optional[int] = None, traj: Optional[torch.Tensor] = None):
+                     last_step: Optional[int] = None, traj: Optional[torch.Tensor] = None, reduce=None):
         """init_state (in-kernel Philox prior) followed by run, with every argument of both calls prepared BEFORE the first one is
         issued: the two C calls go out back to back, so the GPU is not left idle between the prior draw and the loop's first
-        launches while Python checks shapes and builds structs (a 20-step call is ~5 ms: ~25 us of that gap is 0.5 %)."""
+        launches while Python checks shapes and builds structs (a 20-step call is ~5 ms: ~25 us of that gap is 0.5 %).
+        init_state writes a masked prior, which is the masked-state PRECONDITION of run (see there); `reduce`: as in run."""
         B = flags.shape[0]
         s, sc, r = self._state(*state, B), self._state(*scratch, B, "scratch"), self._state(*result, B, "result")
         ws, n = self._workspace(B)
         last = self.diff_steps if last_step is None else last_step
         fp, tp, stream, lib, h = _ptr(flags), _ptr(traj), self._stream(), self.lib, self.handle
+        opts, keep, err = self._reduce_options(reduce)
         rc0 = lib.ccsd_init_state(h, B, fp, None, seed, sample_offset, C.byref(s), stream)
-        rc1 = lib.ccsd_sampler_run(h, B, fp, seed, sample_offset, first_step, last, C.byref(s), C.byref(sc), C.byref(r), tp, ws, n, stream) if rc0 == 0 else 0
+        if rc0 != 0:
+            rc1 = 0
+        elif opts is None:
+            rc1 = lib.ccsd_sampler_run(h, B, fp, seed, sample_offset, first_step, last, C.byref(s), C.byref(sc), C.byref(r), tp, ws, n, stream)
+        else:
+            rc1 = lib.ccsd_sampler_run_ex(h, B, fp, seed, sample_offset, first_step, last, C.byref(s), C.byref(sc), C.byref(r), tp, ws, n, stream,
+                                          C.byref(opts))
+            del keep
         lib.check(rc0)
+        if err:
+            raise err[0]
         lib.check(rc1)
 
     def profile_kernel(self, name: Optional[str]):

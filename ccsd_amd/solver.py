@@ -5,7 +5,8 @@ Same signature, closure signature and return tuple as ccsd/src/solver.py:856-117
   CC:    pc_sampler(model_x, model_adj, model_rank2, init_flags) -> (x, adj, rank2, nfe, diff_traj)
 
 Extra keyword-only knobs (not in the reference):
-  rng        "philox" (default): counter-based noise generated inside the kernels, one C call for the loop;
+  rng        "philox" (default): counter-based noise generated inside the kernels, one C call for the loop (the library loop,
+                      ccsd_sampler_run / ccsd_sampler_run_ex: every n_steps, every corrector, with or without a process group);
              "torch": priors from the CPU generator and in-loop noise from randn_like on the state's
                       device, in the reference's draw order (what the reference itself does, solver.py:1111-1113,
                       graph_utils.py:171);
@@ -14,7 +15,13 @@ Extra keyword-only knobs (not in the reference):
   keep_traj  record diff_traj (the reference always does; default False here because only the plotting
              code consumes it -- SURVEY.md section 7).  With keep_traj=False an empty list is returned.
   group      torch.distributed process group: all-reduce the six Langevin norm sums across ranks so that
-             a sharded batch reproduces the single-process step size exactly.
+             a sharded batch reproduces the single-process step size exactly.  With rng="philox" and
+             torch.distributed initialised the all-reduce is the reduce hook of the library loop (one C call, no host
+             synchronisation: the collective is ordered on the current stream); a group object without an initialised
+             torch.distributed has nothing to reduce over and takes the Python-driven step-wise loop, as host-supplied noise
+             (rng="torch", "torch_cpu") always does.  `pc_sampler.last_loop` says which loop the last call took: "library" or
+             "stepwise" (None before the first call and for a zero-step call); `pc_sampler.force_stepwise = True` sends every
+             later call through the step-wise driver (measurement and tests: both loops compute the same values bit for bit).
   seed, sample_offset, call_stride
              Philox stream: the draws of sample b of a call are keyed by (seed, global sample index), with
              global index = sample_offset + calls_so_far * call_stride + b.  The closure counts its calls, so the
@@ -147,9 +154,18 @@ def get_pc_sampler(sde_x: SDE, sde_adj: SDE, shape_x: Sequence[int], shape_adj: 
                 if keep_traj:
                     per = sum(s[1] * s[2] for s in shapes[:nt])
                     traj = torch.empty(diff_steps, per, device=dev)
-                # the single C call covers n_steps == 1; more inner Langevin steps (solver.py:1131-1137) and the exact
-                # multi-GPU mode are driven step by step (same kernels, Philox noise generated in them)
-                stepwise = group is not None or (corrector == "Langevin" and n_steps != 1 and not s4)
+                # the library loop serves every philox plan: n_steps != 1 inside the C call, the exact multi-GPU mode through its
+                # reduce hook.  Step-wise only: a group with no initialised torch.distributed behind it (nothing to reduce over;
+                # the suites hold the two loops against each other this way) and pc_sampler.force_stepwise
+                reduce = None
+                stepwise = bool(pc_sampler.force_stepwise)
+                if group is not None:
+                    import torch.distributed as dist
+
+                    if dist.is_available() and dist.is_initialized():
+                        reduce = lambda sums: dist.all_reduce(sums, group=group)   # six floats over RCCL / gloo: exact batch-global step size
+                    else:
+                        stepwise = True
                 if last == 0 or stepwise:
                     eng.init_state(flags, state, None, the_seed, offset)
                 if last == 0:
@@ -157,9 +173,11 @@ def get_pc_sampler(sde_x: SDE, sde_adj: SDE, shape_x: Sequence[int], shape_adj: 
                         if dst is not None:
                             dst.copy_(src)
                 elif not stepwise:
-                    eng.init_and_run(flags, state, scratch, result, the_seed, offset, 0, last, traj)   # (prior draw + loop, back to back)
+                    pc_sampler.last_loop = "library"
+                    eng.init_and_run(flags, state, scratch, result, the_seed, offset, 0, last, traj, reduce=reduce)   # (prior draw + loop, back to back)
                 else:
                     traj = None
+                    pc_sampler.last_loop = "stepwise"
                     _stepwise(eng, flags, state, scratch, result, None, the_seed, offset, last, diff_traj, keep_traj, group)
                 if traj is not None:
                     o = 0
@@ -179,6 +197,7 @@ def get_pc_sampler(sde_x: SDE, sde_adj: SDE, shape_x: Sequence[int], shape_adj: 
                     prior.append(sde_rank2.prior_sampling(shape_rank2).to(dev))
                 eng.init_state(flags, state, prior)
                 noise_fn = lambda k: draw(shapes[k], dev)
+                pc_sampler.last_loop = "stepwise"
                 _stepwise(eng, flags, state, scratch, result, noise_fn, the_seed, offset, last, diff_traj, keep_traj, group)
         if last == 0:
             out = state
@@ -190,7 +209,8 @@ def get_pc_sampler(sde_x: SDE, sde_adj: SDE, shape_x: Sequence[int], shape_adj: 
         return (*out[:nt], 0 if s4 else diff_steps * (n_steps + 1), diff_traj)
 
     def _stepwise(eng, flags, state, scratch, result, noise_fn, the_seed, off, last, diff_traj, keep, grp):
-        """Python-driven loop: used for host-supplied noise and for the exact multi-GPU mode."""
+        """Python-driven loop: host-supplied noise (rng="torch" / "torch_cpu"), and the yardstick the library loop is held against
+        (a group object without torch.distributed, pc_sampler.force_stepwise)."""
         import torch.distributed as dist
 
         dev = eng.device
@@ -244,6 +264,8 @@ def get_pc_sampler(sde_x: SDE, sde_adj: SDE, shape_x: Sequence[int], shape_adj: 
                     dst.copy_(src)
 
     pc_sampler.calls = 0
+    pc_sampler.last_loop = None
+    pc_sampler.force_stepwise = False
     pc_sampler.max_steps = max_steps
     pc_sampler.engine = lambda: next(iter(cache.values()), None)      # the PCEngine of the last model triple (measurement hooks)
     return pc_sampler

@@ -25,6 +25,9 @@
  *                              (solver.py:210-313, 367-463) + RSDE.sde/discretize (sde.py:180-340)
  * ccsd_s4_apply                the update half of one S4_solver step (solver.py:1296-1352, 1446-1529)
  * ccsd_sampler_run             the whole pc_sampler / s4_solver loop (solver.py:1109-1174, 1266-1352)
+ * ccsd_sampler_run_ex          the same loop with a reduce hook on the Langevin norm sums: the hook stands where DataParallel
+ *                              gathers the replicas' scores before torch.norm(...).mean() (solver.py:763-767;
+ *                              utils/loader.py:649-650)
  * ccsd_quantize                quantize_mol / quantize (graph_utils.py:181-213)
  * ccsd_rank2_cells             the rank-2 part of cc_from_incidence's input, as a cell bitmask (cc_utils.py:243-262)
  */
@@ -47,7 +50,8 @@ enum {
     CCSD_ERR_UNSUPPORTED = 2,   /* NotImplementedError: config outside the HIP path's envelope */
     CCSD_ERR_WEIGHTS = 3,       /* ValueError: weight blob size does not match the config */
     CCSD_ERR_RUNTIME = 4,       /* RuntimeError: HIP runtime failure (hipGetLastError text via ccsd_last_error) */
-    CCSD_ERR_WORKSPACE = 5      /* ValueError: workspace too small */
+    CCSD_ERR_WORKSPACE = 5,     /* ValueError: workspace too small */
+    CCSD_ERR_CALLBACK = 6       /* the reduce hook of ccsd_sampler_run_ex returned non-zero; the Python shim re-raises the hook's exception */
 };
 
 enum { CCSD_SDE_VP = 0, CCSD_SDE_VE = 1, CCSD_SDE_SUBVP = 2 };
@@ -171,7 +175,8 @@ enum {
     CCSD_QUERY_R2_FAMILY = 8,     /* rank-2 side: 0 none (graph-only), 1 fused k_r2, 2 element-wise k_ew1, 3 tiled (k_gemm_h + k_hf_score) */
     CCSD_QUERY_R2_INSTANCE = 9,   /* k_r2<MT, RS, AFFINE, GEN1, QM9> as the decimal digits MT RS AFFINE GEN1 QM9 (31102 = k_r2<3, 1, true, false, 2>); -1: no k_r2 */
     CCSD_QUERY_LOOP_FORM = 10,    /* ccsd_sampler_run: 0 predictor only, 1 Langevin with an apply launch of its own, 2 Langevin with the apply fused into
-                                     the predictor launches, 3 S4, 4 none (Langevin with n_steps != 1: step-wise calls only) */
+                                     the predictor launches, 3 S4, 4 Langevin with n_steps != 1 (the inner iterations one after the other, every apply a launch
+                                     of its own, through a third state buffer in the workspace) */
     CCSD_QUERY_H_FULL = 11,       /* 1: H = F F^T comes from k_gemm_h_full (one workgroup per complex) */
     CCSD_QUERY_HP_FULL = 12,      /* k_hp_full (P_0, H and the corrector's rank2 work in one pass): bit 0 in the predictor pass, bit 1 in the norms pass */
     CCSD_QUERY_P0_NARROW = 13,    /* layer-0 hodge projection: 0 wide (k_gemm_p) or none; else k_gemm_p0<NT, KC, .> as NT * 100000 + KC */
@@ -188,7 +193,8 @@ int ccsd_plan_query(const ccsd_plan_t* plan, int32_t what, int64_t* value);
  * workspace, and write
  * norm_sums_dev[6] = { sum_b ||net_x[b]||, sum_b ||net_adj[b]||, sum_b ||net_rank2[b]||,
  *                      sum_b ||z_x[b]||,  sum_b ||z_adj[b]||,  sum_b ||z_rank2[b]|| }.
- * In multi-GPU exact mode the caller all-reduces these six floats (RCCL) between the two phases. */
+ * In multi-GPU exact mode the caller all-reduces these six floats (RCCL) between the two phases (ccsd_sampler_run_ex does so
+ * inside the library loop, through its reduce hook). */
 int ccsd_corrector_norms(ccsd_plan_t* plan, int32_t B, int32_t step, int32_t corr_iter,
                          const ccsd_state_t* base, const ccsd_state_t* cur, const float* flags_dev, const ccsd_noise_t* noise,
                          uint64_t seed, int64_t sample_offset, float* norm_sums_dev,
@@ -224,10 +230,32 @@ int ccsd_s4_apply(ccsd_plan_t* plan, int32_t B, int32_t step, const ccsd_state_t
  * wrote.  The loop's rank-2 kernels rely on it (they skip re-masking rank2 in the hodge-projection loader); the step calls above
  * (ccsd_score, ccsd_corrector_norms, ccsd_predictor, ...) accept arbitrary states.  traj_dev (nullable): [diff_steps][N*F+N*N+E*K]
  * receives sample 0 of every step (diff_traj, solver.py:1150-1165).  first_step/last_step allow
- * running a sub-range [first_step, last_step) of the diff_steps steps. */
+ * running a sub-range [first_step, last_step) of the diff_steps steps.  Every sampler.n_steps runs here: with n_steps != 1 the
+ * Langevin inner iterations (solver.py:1131-1137) go through a third state buffer that ccsd_workspace_bytes includes. */
 int ccsd_sampler_run(ccsd_plan_t* plan, int32_t B, const float* flags_dev, uint64_t seed, int64_t sample_offset,
                      int32_t first_step, int32_t last_step, ccsd_state_t* state, ccsd_state_t* scratch,
                      ccsd_state_t* result, float* traj_dev, void* workspace, size_t workspace_bytes, void* stream);
+
+/* Exact multi-GPU mode inside the library loop.  With DataParallel the reference gathers the replicas' scores before
+ * torch.norm(...).mean() (solver.py:763-767; utils/loader.py:649-650), so the Langevin step size is batch-global; a sharded run
+ * reproduces it by summing the six norm sums (see ccsd_corrector_norms: sums, not means; the step size uses only the ratio
+ * zn / gn) over the shards.  The hook is called on the calling thread ONCE PER NORMS PASS -- every Langevin inner iteration of
+ * every step, every S4 step, never on corrector-free plans -- after the kernel that writes the sums has been enqueued on `stream`
+ * and before any kernel that reads them is.  sums_dev: dev, n = 6 floats in a buffer of at least 8.  The hook leaves the reduced
+ * values in place, ordered on `stream` (an RCCL all-reduce enqueued on it, or on a stream that waits for it and that it then
+ * waits for); it must not synchronise the device for correctness' sake.  A non-zero return stops the loop at once: nothing
+ * further is enqueued, the call returns CCSD_ERR_CALLBACK and state / scratch / result are undefined. */
+typedef int (*ccsd_reduce_fn)(float* sums_dev, int32_t n, void* stream, void* user);
+typedef struct {
+    ccsd_reduce_fn reduce;   /* NULL: no hook */
+    void* user;              /* handed to the hook */
+} ccsd_run_options_t;
+/* ccsd_sampler_run with options (NULL options or a NULL hook: exactly ccsd_sampler_run -- the same launches in number, order and
+ * arguments, with and without a hook). */
+int ccsd_sampler_run_ex(ccsd_plan_t* plan, int32_t B, const float* flags_dev, uint64_t seed, int64_t sample_offset,
+                        int32_t first_step, int32_t last_step, ccsd_state_t* state, ccsd_state_t* scratch,
+                        ccsd_state_t* result, float* traj_dev, void* workspace, size_t workspace_bytes, void* stream,
+                        const ccsd_run_options_t* options);
 
 /* quantize_mol: >=2.5->3, [1.5,2.5)->2, [0.5,1.5)->1, <0.5->0 (int64 out); thr<0 selects it, otherwise
  * quantize(t, thr): t<thr ? 0 : 1. */
