@@ -543,6 +543,7 @@ struct Workspace {
     int lg_tiles;
     ccsd_state_t third;             // LOOP_LANGEVIN_MULTI with more than one inner iteration: the second corrector iterate of ccsd_sampler_run
     size_t bytes;
+    MaskTab masks() const { return MaskTab{mfr, mfl, Kp, Ep}; }
 };
 // What one pass (a norms pass, a predictor pass, one ccsd_score) hands from launcher to launcher.
 struct Pass {
@@ -912,7 +913,7 @@ static int launch_hf(const ccsd_plan* pl, int B, const float* rank2, RankEpi& ep
     dim3 g(xcd_grid(B, ((p.K + T_BN - 1) / T_BN) * ((p.E + T_BM - 1) / T_BM)));
     prof_mark(const_cast<ccsd_plan*>(pl), KID_HF, stream);
 #define HF_ARGS (const PlanD*)pl->d, (const float*)pl->w, rank2, (const float*)w.H, (const unsigned long long*)w.offbits, \
-                (const unsigned char*)pl->edges, (const unsigned long long*)pl->cells, ep, na, B, (MaskTab{w.mfr, w.mfl, w.Kp, w.Ep})
+                (const unsigned char*)pl->edges, (const unsigned long long*)pl->cells, ep, na, B, w.masks()
     const int fw = fnet_width(p);
 #define HF_AFF1(EC_, KC_) CCSD_LAUNCH((k_hf_score<true, 8, 1, EC_, KC_>), g, dim3(CCSD_NTHREADS), 0, stream, HF_ARGS)
 #define HF_GEN1(EC_, KC_) CCSD_LAUNCH((k_hf_score<false, 8, 1, EC_, KC_>), g, dim3(CCSD_NTHREADS), 0, stream, HF_ARGS)
@@ -944,8 +945,11 @@ static int launch_ew1(const ccsd_plan* pl, int B, const float* rank2, RankEpi& e
     a.r = rank2; a.out = ep.out; a.mean = ep.mean; a.f1 = f1; a.net_out = net_out; a.part = ep.part;
     a.mode = ep.mode; a.apply = (cf && cf->on) ? 1 : 0;
     a.sscale = ep.sscale; a.pa = ep.pa; a.pb = ep.pb; a.pc = ep.pc; a.alpha = p.f_alpha; a.gamma = p.f_gamma;
-    if (a.apply) { a.sums = cf->sums; a.ss = cf->ss[2]; a.sde_alpha = cf->alpha[2]; a.snr = cf->snr; a.seps = cf->seps; a.draw_corr = cf->draw_r; }
-    a.E = p.E; a.K = p.K; a.mt = MaskTab{w.mfr, w.mfl, w.Kp, w.Ep};
+    if (a.apply) {
+        const LangCoef& lc = cf->lc;
+        a.sums = lc.sums; a.ss = lc.ss[2]; a.sde_alpha = lc.alpha[2]; a.snr = lc.snr; a.seps = lc.seps; a.draw_corr = cf->draw_r;
+    }
+    a.E = p.E; a.K = p.K; a.mt = w.masks();
     prof_mark(const_cast<ccsd_plan*>(pl), KID_EW1, stream);
 #define EW1_GO(EC_, KC_) CCSD_LAUNCH((k_ew1<EC_, KC_>), dim3(w.nchunk, B), dim3(CCSD_NTHREADS), 0, stream, a, na)
     GEO_EK(pl->rt.geo, EW1_GO);
@@ -991,6 +995,45 @@ static NoiseArgs make_noise(const ccsd_noise_t* n, uint64_t seed, int64_t off, u
     na.draw_x = base; na.draw_adj = base + 1; na.draw_r = base + 2;
     na.flat_r = flat_r;
     return na;
+}
+
+// the Langevin scalars of diffusion step `step` over the norm sums `sums` (k_normsum)
+static LangCoef lang_coef(const ccsd_plan* pl, int step, const float* sums) {
+    LangCoef lc{};
+    lc.sums = sums;
+    for (int t = 0; t < 3; ++t) {
+        const ccsd_step_coef_t& c = pl->coef[(size_t)step * 3 + t];
+        lc.ss[t] = c.sscale; lc.alpha[t] = c.alpha;
+    }
+    lc.snr = pl->h.snr; lc.seps = pl->h.seps;
+    return lc;
+}
+// k_langevin_apply's arguments (k_s4_apply's first part): cur + the raw scores of the norms pass -> out
+static LangArgs lang_args(const ccsd_plan* pl, int B, int step, const ccsd_state_t* cur, const float* flags, const float* sums,
+                          ccsd_state_t* out, const Workspace& w) {
+    const PlanD& p = pl->h;
+    LangArgs a{};
+    a.x = cur->x; a.adj = cur->adj; a.r = cur->rank2;
+    a.nx = w.net_x; a.nadj = w.net_adj; a.nr = w.net_r;
+    a.ox = out->x; a.oadj = out->adj; a.orr = out->rank2;
+    a.flags = flags; a.lc = lang_coef(pl, step, sums);
+    a.B = B; a.N = p.N; a.F = p.F; a.E = p.E; a.K = p.K; a.is_cc = p.is_cc;
+    return a;
+}
+// the fields every P0Fuse mode fills: the corrector's flat-keyed rank2 draw `draw` of the stream `na` and the mask tables
+static P0Fuse p0_fuse(const ccsd_plan* pl, int mode, const NoiseArgs& na, unsigned int draw, const Workspace& w) {
+    P0Fuse pf{};
+    pf.mode = mode; pf.seed = na.seed; pf.b_off = na.b_off; pf.draw = draw;
+    pf.mt = w.masks(); pf.E = pl->h.E;
+    return pf;
+}
+// the rank-2 predictor update of diffusion step `step` as an epilogue
+static RankEpi pred_epi(const ccsd_plan* pl, int step, ccsd_state_t* out, ccsd_state_t* mean) {
+    const ccsd_step_coef_t& c = pl->coef[(size_t)step * 3 + 2];
+    RankEpi ep{};
+    ep.mode = MODE_PRED; ep.pa = c.pa; ep.pb = c.pb; ep.pc = c.pc;
+    ep.out = out->rank2; ep.mean = mean ? mean->rank2 : nullptr;
+    return ep;
 }
 
 // ---------------- API ----------------
@@ -1129,13 +1172,10 @@ static int corrector_norms(ccsd_plan* pl, int B, int step, int it, const ccsd_st
         ntiles = 1;
     } else {
         P0Fuse pf{};
-        if (zfuse) {
-            pf.mode = 1; pf.zrow = w.zpart; pf.seed = na.seed; pf.b_off = na.b_off; pf.draw = na.draw_r;
-            pf.mt = MaskTab{w.mfr, w.mfl, w.Kp, w.Ep}; pf.E = p.E;
-        }
+        if (zfuse) { pf = p0_fuse(pl, 1, na, na.draw_r, w); pf.zrow = w.zpart; }
         if (e1fuse && cur->rank2 == base->rank2) {
-            pf.mode = 3; pf.zrow = w.part; pf.seed = na.seed; pf.b_off = na.b_off; pf.draw = na.draw_r;
-            pf.mt = MaskTab{w.mfr, w.mfl, w.Kp, w.Ep}; pf.E = p.E; pf.alpha = p.f_alpha; pf.gamma = p.f_gamma;
+            pf = p0_fuse(pl, 3, na, na.draw_r, w);
+            pf.zrow = w.part; pf.alpha = p.f_alpha; pf.gamma = p.f_gamma;
             pf.net_out = keep_net ? w.net_r : nullptr;
         }
         if ((st = launch_p(pl, B, cur->adj, base->rank2, ps, w, stream, pf.mode ? &pf : nullptr))) return st;
@@ -1168,7 +1208,7 @@ static int corrector_norms(ccsd_plan* pl, int B, int step, int it, const ccsd_st
         // k_hf_score and its chunk partials are reduced per sample first (one workgroup per sample), then over the batch
         const bool zk = na.flat_r && !na.zr && !ew1;
         if (zk && !zfuse) {
-#define NN_GO(EC_, KC_) CCSD_LAUNCH((k_noise_norm<EC_, KC_>), dim3(w.nchunk, B), dim3(CCSD_NTHREADS), 0, stream, na, (MaskTab{w.mfr, w.mfl, w.Kp, w.Ep}), p.E, p.K, w.zpart)
+#define NN_GO(EC_, KC_) CCSD_LAUNCH((k_noise_norm<EC_, KC_>), dim3(w.nchunk, B), dim3(CCSD_NTHREADS), 0, stream, na, w.masks(), p.E, p.K, w.zpart)
             GEO_EK(pl->rt.geo, NN_GO);
 #undef NN_GO
             LAUNCH_CHECK();
@@ -1191,20 +1231,10 @@ static int corrector_apply(ccsd_plan* pl, int B, int step, int it, const ccsd_st
                            Workspace& w, void* stream) {
     const PlanD& p = pl->h;
     NoiseArgs na = make_noise(noise, seed, off, draw_base(pl, step, it), pl->rt.corrector_flat);
-    LangArgs a{};
-    a.x = cur->x; a.adj = cur->adj; a.r = cur->rank2;
-    a.nx = w.net_x; a.nadj = w.net_adj; a.nr = w.net_r;
-    a.ox = out->x; a.oadj = out->adj; a.orr = out->rank2;
-    a.flags = flags; a.sums = sums;
-    for (int t = 0; t < 3; ++t) {
-        const ccsd_step_coef_t& c = pl->coef[(size_t)step * 3 + t];
-        a.ss[t] = c.sscale; a.alpha[t] = c.alpha;
-    }
-    a.snr = p.snr; a.seps = p.seps;
-    a.B = B; a.N = p.N; a.F = p.F; a.E = p.E; a.K = p.K; a.is_cc = p.is_cc;
+    LangArgs a = lang_args(pl, B, step, cur, flags, sums, out, w);
     const long long total = (long long)B * (p.N * p.F + p.N * p.N) + (p.is_cc ? (long long)B * (((long long)p.E * p.K + 3) / 4) : 0);
     prof_mark(pl, KID_LANGEVIN, stream);
-#define LA_GO(EC_, KC_) CCSD_LAUNCH((k_langevin_apply<EC_, KC_>), dim3(grid_for(total, 256)), dim3(CCSD_NTHREADS), 0, stream, a, na, (MaskTab{w.mfr, w.mfl, w.Kp, w.Ep}))
+#define LA_GO(EC_, KC_) CCSD_LAUNCH((k_langevin_apply<EC_, KC_>), dim3(grid_for(total, 256)), dim3(CCSD_NTHREADS), 0, stream, a, na, w.masks())
     GEO_EK(pl->rt.geo, LA_GO);
 #undef LA_GO
     prof_mark(pl, KID_LANGEVIN, stream);
@@ -1224,25 +1254,20 @@ static int predictor(ccsd_plan* pl, int B, int step, const ccsd_state_t* in, con
     const float* r2_in = in->rank2;           // what the rank-2 kernels of the tiled path read (the corrected state when the apply is fused)
     CorrFuse cf{};
     if (fuse_sums) {   // the Langevin corrector's apply pass runs in the prologues of this half-step's kernels
-        cf.on = 1; cf.net_x = w.net_x; cf.net_adj = w.net_adj; cf.net_r = w.net_r; cf.sums = fuse_sums;
-        for (int t = 0; t < 3; ++t) { cf.ss[t] = c[t].sscale; cf.alpha[t] = c[t].alpha; }
-        cf.snr = p.snr; cf.seps = p.seps;
+        cf.on = 1; cf.net_x = w.net_x; cf.net_adj = w.net_adj; cf.net_r = w.net_r; cf.lc = lang_coef(pl, step, fuse_sums);
         const unsigned int cb = draw_base(pl, step, 0);
         cf.draw_x = cb; cf.draw_adj = cb + 1; cf.draw_r = cb + 2;
     }
     if (fused) {
-        RankEpi ep{};
-        ep.mode = MODE_PRED; ep.pa = c[2].pa; ep.pb = c[2].pb; ep.pc = c[2].pc;
-        ep.out = out->rank2; ep.mean = mean ? mean->rank2 : nullptr;
+        RankEpi ep = pred_epi(pl, step, out, mean);
         // merged launch: the rank-2 side of the NEXT step's norms pass follows in the same launch (its corrector draw: rank2 slot of
         // draw_base(step + 1, 0))
         const int md = merge_next ? (int)draw_base(pl, step + 1, 0) + 2 : -1;
         if ((st = launch_r2(pl, B, in->rank2, in->adj, flags, 1, ep, na, ps, w, stream, &cf, md))) return st;
     } else if (ew1 && cf.on && rt.ew1_fuse && !na.zr) {
         // element-wise ScoreNetworkF, one hodge layer: corrector apply + projection + predictor update in ONE pass over rank2
-        P0Fuse pf{};
-        pf.mode = 4; pf.seed = na.seed; pf.b_off = na.b_off; pf.draw = cf.draw_r; pf.draw_pred = na.draw_r;
-        pf.mt = MaskTab{w.mfr, w.mfl, w.Kp, w.Ep}; pf.E = p.E; pf.cf = cf;
+        P0Fuse pf = p0_fuse(pl, 4, na, cf.draw_r, w);
+        pf.draw_pred = na.draw_r; pf.cf = cf;
         pf.alpha = p.f_alpha; pf.gamma = p.f_gamma; pf.pa = c[2].pa; pf.pb = c[2].pb; pf.pc = c[2].pc;
         pf.out = out->rank2; pf.mean = mean ? mean->rank2 : nullptr;
         pf.f1 = w.net_r;                         // (host emulation only: its projection runs as a pass of its own over the corrected state)
@@ -1250,17 +1275,14 @@ static int predictor(ccsd_plan* pl, int B, int step, const ccsd_state_t* in, con
     } else if (ew1) {
         // element-wise ScoreNetworkF first: with the fused apply it produces the corrected rank2 (in the raw-score scratch, which
         // the fused loop does not fill) that the hodge projections of the A-network must see
-        RankEpi ep{};
-        ep.mode = MODE_PRED; ep.pa = c[2].pa; ep.pb = c[2].pb; ep.pc = c[2].pc;
-        ep.out = out->rank2; ep.mean = mean ? mean->rank2 : nullptr;
+        RankEpi ep = pred_epi(pl, step, out, mean);
         if ((st = launch_ew1(pl, B, in->rank2, ep, na, w, stream, nullptr, &cf, w.net_r))) return st;
         if ((st = launch_p(pl, B, in->adj, cf.on ? (const float*)w.net_r : in->rank2, ps, w, stream))) return st;
     } else if (cf.on && rt.tiled_fuse) {
         // tiled path: the corrector apply rides on the projection pass -- corrected rank2 written in place over the raw scores it
         // consumes (w.net_r), P_0 taken of it; k_gemm_h / k_hf_score below read the corrected state from there
-        P0Fuse pf{};
-        pf.mode = 2; pf.net = w.net_r; pf.f1 = w.net_r; pf.seed = na.seed; pf.b_off = na.b_off; pf.draw = cf.draw_r;
-        pf.mt = MaskTab{w.mfr, w.mfl, w.Kp, w.Ep}; pf.E = p.E; pf.cf = cf;
+        P0Fuse pf = p0_fuse(pl, 2, na, cf.draw_r, w);
+        pf.net = w.net_r; pf.f1 = w.net_r; pf.cf = cf;
         if ((st = launch_p(pl, B, in->adj, in->rank2, ps, w, stream, &pf))) return st;
         r2_in = w.net_r;
     } else if ((st = launch_p(pl, B, in->adj, in->rank2, ps, w, stream))) return st;
@@ -1275,9 +1297,7 @@ static int predictor(ccsd_plan* pl, int B, int step, const ccsd_state_t* in, con
     if ((st = launch_xa(pl, B, xa, na, ps, w, stream))) return st;
     if (p.is_cc && !fused && !ew1) {
         if ((st = launch_h(pl, B, r2_in, ps, w, stream))) return st;
-        RankEpi ep{};
-        ep.mode = MODE_PRED; ep.pa = c[2].pa; ep.pb = c[2].pb; ep.pc = c[2].pc;
-        ep.out = out->rank2; ep.mean = mean ? mean->rank2 : nullptr;
+        RankEpi ep = pred_epi(pl, step, out, mean);
         if ((st = launch_hf(pl, B, r2_in, ep, na, w, stream))) return st;
     }
     return CCSD_OK;
@@ -1289,18 +1309,11 @@ static int s4_apply(ccsd_plan* pl, int B, int step, const ccsd_state_t* cur, con
                     ccsd_state_t* out, ccsd_state_t* mean, Workspace& w, void* stream) {
     const PlanD& p = pl->h;
     S4Args q{};
-    LangArgs& a = q.a;
-    a.x = cur->x; a.adj = cur->adj; a.r = cur->rank2;
-    a.nx = w.net_x; a.nadj = w.net_adj; a.nr = w.net_r;
-    a.ox = out->x; a.oadj = out->adj; a.orr = out->rank2;
-    a.flags = flags; a.sums = sums;
+    q.a = lang_args(pl, B, step, cur, flags, sums, out, w);
     for (int t = 0; t < 3; ++t) {
         const ccsd_step_coef_t& c = pl->coef[(size_t)step * 3 + t];
-        a.ss[t] = c.sscale; a.alpha[t] = c.alpha;
         q.m1[t] = c.m1; q.s1[t] = c.s1; q.d[t] = c.d; q.m2[t] = c.m2; q.s2[t] = c.s2;
     }
-    a.snr = p.snr; a.seps = p.seps;
-    a.B = B; a.N = p.N; a.F = p.F; a.E = p.E; a.K = p.K; a.is_cc = p.is_cc;
     q.mx = mean ? mean->x : nullptr; q.madj = mean ? mean->adj : nullptr; q.mr = mean ? mean->rank2 : nullptr;
     NoiseArgs na1 = make_noise(n1, seed, off, draw_base(pl, step, 0));
     NoiseArgs na2 = make_noise(n2, seed, off, draw_base(pl, step, 1));

@@ -292,9 +292,10 @@ __global__ __launch_bounds__(CCSD_LG_TB) void k_lg_fin(MlpD m, const float* __re
                 n2 = fmaf(net, net, n2);
                 z2 = fmaf(z, z, z2);
             } else {
-                const float mean = fmaf(xa.pa_a, adj[gi], xa.pb_a * net);
+                float mean;
+                const float nv = pred_update(xa.pa_a, xa.pb_a, xa.pc_a, adj[gi], net, z, &mean);
                 if (xa.mean_a) xa.mean_a[gi] = mean;
-                xa.out_a[gi] = fmaf(xa.pc_a, z, mean);
+                xa.out_a[gi] = nv;
             }
         }
     };
@@ -344,9 +345,10 @@ __global__ __launch_bounds__(CCSD_LG_TB) void k_lg_epi(const float* __restrict__
                     v[0] = fmaf(net, net, v[0]);
                     v[2] = fmaf(z, z, v[2]);
                 } else {
-                    const float mean = fmaf(xa.pa_x, x[gi], xa.pb_x * net);
+                    float mean;
+                    const float nv = pred_update(xa.pa_x, xa.pb_x, xa.pc_x, x[gi], net, z, &mean);
                     if (xa.mean_x) xa.mean_x[gi] = mean;
-                    xa.out_x[gi] = fmaf(xa.pc_x, z, mean);
+                    xa.out_x[gi] = nv;
                 }
             }
         }

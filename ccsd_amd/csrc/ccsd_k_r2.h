@@ -111,7 +111,7 @@ __global__ __launch_bounds__(512, 4) void k_r2(const PlanD* __restrict__ plan, c
         for (int t = tid; t < E * (Kp4 - K); t += nth) { const int e = t / (Kp4 - K), k = K + t % (Kp4 - K); sF[e * ldk + k] = 0.f; }
         if (adjpow) {
             float c1a = 0.f, c2a = 0.f;
-            if (ra.cf.on) corr_coef(ra.cf, 1, &c1a, &c2a);
+            if (ra.cf.on) langevin_coef(ra.cf.lc, 1, &c1a, &c2a);
             for (int i = tid; i < NN; i += nth) {
                 float v = ra.adj[(size_t)b * NN + i];
                 if (ra.cf.on) {   // the A-network of the predictor sees the corrected adjacency
@@ -119,7 +119,7 @@ __global__ __launch_bounds__(512, 4) void k_r2(const PlanD* __restrict__ plan, c
                     nc.zadj = nullptr; nc.draw_adj = ra.cf.draw_adj;
                     const int ii = i / N, jj = i % N;
                     const float z = raw_noise_adj(nc, b, ii, jj, N) * ra.flags[(size_t)b * N + ii] * ra.flags[(size_t)b * N + jj];
-                    v = fmaf(c2a, z, fmaf(c1a, ra.cf.net_adj[(size_t)b * NN + i], v));
+                    v = corr_apply(c1a, c2a, ra.cf.net_adj[(size_t)b * NN + i], v, z);
                 }
                 sAdj[i] = v; sAdj[NN + i] = v;
             }
@@ -131,15 +131,15 @@ __global__ __launch_bounds__(512, 4) void k_r2(const PlanD* __restrict__ plan, c
     // = one 16-byte load of this loop, so the corrector's work on rank2 happens here, where the block streams through registers:
     //  * norms launch (MODE_NORMS): the noise norm  sum (z fl fr)^2  of the draw (gen_noise_rank2 + torch.norm, cc_utils.py:613-615,
     //    solver.py:793-797) -- the epilogue then only squares the score;
-    //  * predictor launch of ccsd_sampler_run (cf.on): the fused corrector apply  F <- fma(c2, z fl fr, fma(c1, net, F))  with the raw
-    //    scores of the norms pass loaded alongside (same expression as k_langevin_apply), one pass, no LDS read-modify-write.
+    //  * predictor launch of ccsd_sampler_run (cf.on): the fused corrector apply  F <- corr_apply(net, F, z fl fr)  with the raw
+    //    scores of the norms pass loaded alongside, one pass, no LDS read-modify-write.
     // The loop is double buffered: the loads of batch i + 1 are in flight while batch i is processed (Philox + Box-Muller are ~100
     // vector instructions per group); the first batch is requested before the mask tables are built.  With K even (and E K a
     // multiple of 4) a group is two aligned pairs (e, k..k+1), (e', k'..k'+1): masks and LDS stores go pair-wise.
     float s_net = 0.f, s_z = 0.f;
     {
         float c1f = 0.f, c2f = 0.f;
-        if (ra.cf.on) corr_coef(ra.cf, 2, &c1f, &c2f);
+        if (ra.cf.on) langevin_coef(ra.cf.lc, 2, &c1f, &c2f);
         NoiseArgs nc = na;                                   // the corrector draw of this launch
         if (ra.cf.on) { nc.zr = nullptr; nc.draw_r = ra.cf.draw_r; }
         const bool znorm = ep.mode == MODE_NORMS && na.flat_r, zuse = znorm || ra.cf.on;
@@ -189,7 +189,7 @@ __global__ __launch_bounds__(512, 4) void k_r2(const PlanD* __restrict__ plan, c
                                 for (int j = 0; j < 4; ++j) {
                                     const float zz = z[j] * m[j];
                                     if (ZN && !CF) s_z = fmaf(zz, zz, s_z);
-                                    if (CF) vv[j] = fmaf(c2f, zz, fmaf(c1f, nn[j], vv[j]));
+                                    if (CF) vv[j] = corr_apply(c1f, c2f, nn[j], vv[j], zz);
                                 }
                                 if (CF && ZN) {
                                     // merged launch: the noise norm of the NEXT step's corrector draw (the norms pass that follows in this
@@ -239,7 +239,7 @@ __global__ __launch_bounds__(512, 4) void k_r2(const PlanD* __restrict__ plan, c
                     const float z = nc.zr ? nc.zr[(size_t)b * EK + t] : philox_normal1(nc.seed, nc.draw_r, nc.b_off + b, (unsigned)t);
                     const float zz = z * sFl[e] * (float)sFrb[k];
                     if (znorm) s_z = fmaf(zz, zz, s_z);
-                    if (ra.cf.on) v = fmaf(c2f, zz, fmaf(c1f, Ng[t], v));
+                    if (ra.cf.on) v = corr_apply(c1f, c2f, Ng[t], v, zz);
                 }
                 sF[e * ldk + k] = v;
             }
@@ -603,9 +603,9 @@ __global__ __launch_bounds__(512, 4) void k_r2(const PlanD* __restrict__ plan, c
                     s_net = fmaf(net, net, s_net);
                     if (eznorm) s_z = fmaf(zz, zz, s_z);
                 } else {
-                    const float mean = fmaf(ep.pa, f, ep.pb * net);
+                    float mean;
+                    const float nv = pred_update(ep.pa, ep.pb, ep.pc, f, net, zz, &mean);
                     if (ep.mean) ep.mean[gi] = mean;
-                    const float nv = fmaf(ep.pc, zz, mean);
                     ep.out[gi] = nv;
                     if (wb) sF[e * ldk + k] = nv;
                 }

@@ -489,8 +489,8 @@ __global__ void k_sum_splits(const float* __restrict__ parts, float* __restrict_
 // draw (NoiseArgs::flat_r), so the corrector's element-wise work rides on it:
 //   mode 1 (norms pass):      zrow[row] = sum_k (z fl fr)^2 of the row  -- the noise norm (gen_noise_rank2 + torch.norm,
 //                              cc_utils.py:613-615, solver.py:793-797); replaces k_noise_norm;
-//   mode 2 (predictor pass):  F1 = fma(c2, z fl fr, fma(c1, net, F)) -- the corrector apply, same expression as k_langevin_apply
-//                              (solver.py:797-801) -- is what goes into LDS (P_0 = F1 Wcat_0) AND out to `f1` for k_gemm_h / k_hf_score;
+//   mode 2 (predictor pass):  F1 = corr_apply(net, F, z fl fr) (solver.py:797-801) is what goes into LDS (P_0 = F1 Wcat_0) AND out
+//                              to `f1` for k_gemm_h / k_hf_score;
 //                              replaces k_langevin_apply's pass over rank2 and the projection's own read of the corrected state.
 // `f1` may alias `net` (every element is read, then written, by the same thread).
 // Plans whose ScoreNetworkF is affine with cnum = 1 (k_ew1's: net = fl fr (alpha F + gamma), no Hodge Laplacian term -- the N = 38
@@ -499,7 +499,7 @@ __global__ void k_sum_splits(const float* __restrict__ parts, float* __restrict_
 //                              ccsd_corrector_apply will want it); the projection is of the state as given;
 //   mode 4 (predictor pass):  F1 = corrector apply with the raw score recomputed in place (as k_ew1 does), P_0 = F1 Wcat_0,
 //                              new state = fma(pc, z' fl fr, fma(pa, F1, pb net(F1))) -> `out` (+ the mean -> `mean`), z' = the
-//                              predictor's flat-keyed draw.  Same expressions, in the same order, as k_ew1 / k_langevin_apply.
+//                              predictor's flat-keyed draw.
 // One read of rank2 per norms pass (k_ew1 + k_gemm_p0 read it twice) and one read + one write per predictor pass (k_ew1: one read, two
 // writes; k_gemm_p0: one more read): 18 GB instead of 36 GB per PC step at E = 703, K = 8436, B = 256.
 struct P0Fuse {
@@ -513,39 +513,71 @@ struct P0Fuse {
     unsigned int draw_pred;
     float* out; float* mean; float* net_out;
 };
-// element-wise form of the two modes (host emulation, whose projections run through the general k_gemm_p): one thread per flat group
+// The arithmetic of mode MODE on ONE flat Philox group (four consecutive elements of a row) held in registers -- the one body behind
+// k_gemm_p0, k_hp_full and k_p0_fuse_ew; the callers draw z (the corrector's) / zp (mode 4: the predictor's), look up the masks m and do
+// the loads and stores.  v: the state in, the corrected state out (modes 2 / 4: what the projection is taken of); n: the raw score beside
+// it (mode 2); c1 / c2: langevin_coef of the rank2 target (modes 2 / 4); zacc / nacc: the row's running sums of (z fl fr)^2 / net^2
+// (modes 1 / 3); o: the raw score (mode 3) or the new state (mode 4); mu: the mean (mode 4).
+template <int MODE>
+CCSD_DEV void p0_fuse_group(const P0Fuse& pf, float c1, float c2, const float* z, const float* zp, const float* m, float4& v, const float4& n,
+                            float& zacc, float& nacc, float* o, float* mu) {
+    if (MODE == 1) {
+#pragma unroll
+        for (int j = 0; j < 4; ++j) { const float zz = z[j] * m[j]; zacc = fmaf(zz, zz, zacc); }
+    } else if (MODE == 2) {
+        v.x = corr_apply(c1, c2, n.x, v.x, z[0] * m[0]); v.y = corr_apply(c1, c2, n.y, v.y, z[1] * m[1]);
+        v.z = corr_apply(c1, c2, n.z, v.z, z[2] * m[2]); v.w = corr_apply(c1, c2, n.w, v.w, z[3] * m[3]);
+    } else if (MODE == 3) {
+        const float f[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            o[j] = ew1_net(pf.alpha, pf.gamma, m[j], f[j]);
+            const float zz = z[j] * m[j];
+            nacc = fmaf(o[j], o[j], nacc);
+            zacc = fmaf(zz, zz, zacc);
+        }
+    } else {
+        float f[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            float net = ew1_net(pf.alpha, pf.gamma, m[j], f[j]);
+            f[j] = corr_apply(c1, c2, net, f[j], z[j] * m[j]);
+            net = ew1_net(pf.alpha, pf.gamma, m[j], f[j]);
+            o[j] = pred_update(pf.pa, pf.pb, pf.pc, f[j], net, zp[j] * m[j], &mu[j]);
+        }
+        v = make_float4(f[0], f[1], f[2], f[3]);
+    }
+}
+// the modes as a pass of their own, one thread per row (host emulation and wide projections, which run through the general k_gemm_p)
 __global__ void k_p0_fuse_ew(const float* __restrict__ rank2, P0Fuse pf, int rows, int K) {
     float c1 = 0.f, c2 = 0.f;
-    if (pf.mode == 2 || pf.mode == 4) corr_coef(pf.cf, 2, &c1, &c2);
+    if (pf.mode == 2 || pf.mode == 4) langevin_coef(pf.cf.lc, 2, &c1, &c2);
     const int E = pf.E;
     for (long long row = (long long)blockIdx.x * blockDim.x + threadIdx.x; row < rows; row += (long long)gridDim.x * blockDim.x) {
         const int b = (int)(row / E), e = (int)(row - (long long)b * E);
         float zs = 0.f, ns = 0.f;
         for (int k = 0; k < K; k += 4) {
-            float z[4], zp[4] = {0.f, 0.f, 0.f, 0.f}, m[4];
+            float z[4], zp[4] = {0.f, 0.f, 0.f, 0.f}, m[4], o[4], mu[4];
             const unsigned g = (unsigned)(((long long)e * K + k) >> 2);
             philox_normal4(pf.seed, pf.draw, pf.b_off + b, g, z);
             if (pf.mode == 4) philox_normal4(pf.seed, pf.draw_pred, pf.b_off + b, g, zp);
             group_masks(pf.mt, b, E, K, e, k, m);
-            for (int j = 0; j < 4; ++j) {
-                const float zz = z[j] * m[j];
-                const size_t gi = (size_t)row * K + k + j;
-                if (pf.mode == 1) zs = fmaf(zz, zz, zs);
-                else if (pf.mode == 2) pf.f1[gi] = fmaf(c2, zz, fmaf(c1, pf.net[gi], rank2[gi]));
-                else if (pf.mode == 3) {
-                    const float net = m[j] * fmaf(pf.alpha, rank2[gi], pf.gamma);
-                    ns = fmaf(net, net, ns); zs = fmaf(zz, zz, zs);
-                    if (pf.net_out) pf.net_out[gi] = net;
-                } else {
-                    float f = rank2[gi];
-                    float net = m[j] * fmaf(pf.alpha, f, pf.gamma);
-                    f = fmaf(c2, zz, fmaf(c1, net, f));
-                    pf.f1[gi] = f;
-                    net = m[j] * fmaf(pf.alpha, f, pf.gamma);
-                    const float mean = fmaf(pf.pa, f, pf.pb * net);
-                    if (pf.mean) pf.mean[gi] = mean;
-                    pf.out[gi] = fmaf(pf.pc, zp[j] * m[j], mean);
-                }
+            const size_t gi = (size_t)row * K + k;
+            auto ld4 = [&](const float* src) { return make_float4(src[gi], src[gi + 1], src[gi + 2], src[gi + 3]); };
+            auto st4 = [&](float* dst, const float4& q) { dst[gi] = q.x; dst[gi + 1] = q.y; dst[gi + 2] = q.z; dst[gi + 3] = q.w; };
+            float4 v = ld4(rank2), n = pf.mode == 2 ? ld4(pf.net) : v;
+            switch (pf.mode) {
+                case 1: p0_fuse_group<1>(pf, c1, c2, z, zp, m, v, n, zs, ns, o, mu); break;
+                case 2: p0_fuse_group<2>(pf, c1, c2, z, zp, m, v, n, zs, ns, o, mu); st4(pf.f1, v); break;
+                case 3:
+                    p0_fuse_group<3>(pf, c1, c2, z, zp, m, v, n, zs, ns, o, mu);
+                    if (pf.net_out) st4(pf.net_out, make_float4(o[0], o[1], o[2], o[3]));
+                    break;
+                default:
+                    p0_fuse_group<4>(pf, c1, c2, z, zp, m, v, n, zs, ns, o, mu);
+                    st4(pf.f1, v);                                             // (the projection that follows reads the corrected state here)
+                    if (pf.mean) st4(pf.mean, make_float4(mu[0], mu[1], mu[2], mu[3]));
+                    st4(pf.out, make_float4(o[0], o[1], o[2], o[3]));
             }
         }
         if (pf.mode == 1) pf.zrow[row] = zs;
@@ -582,7 +614,7 @@ __global__ __launch_bounds__(512, 2) void k_hp_full(const float* __restrict__ ra
     // thread -> (row r0 + 64 u, 4-float column group c4) of the 192 x 32 slab, u < 3; threads 0..127 also one group of the W slab
     const int r0 = tid >> 3, c4 = (tid & 7) * 4;
     float c1 = 0.f, c2 = 0.f, zacc[3] = {0.f, 0.f, 0.f};
-    if (MODE == 2) corr_coef(pf.cf, 2, &c1, &c2);
+    if (MODE == 2) langevin_coef(pf.cf.lc, 2, &c1, &c2);
     float4 rg[3], rn[3], rw;
     auto ldg = [&](int s) {
         const int k = s * H_BK + c4;
@@ -598,7 +630,7 @@ __global__ __launch_bounds__(512, 2) void k_hp_full(const float* __restrict__ ra
         }
         if (tid < 128) rw = *reinterpret_cast<const float4*>(WT + (size_t)r0 * Kp + k);   // (rows 0..15 of Wcat_0^T, zero-padded to Kp)
     };
-    // the corrector's work on the slab in registers (same expressions as k_gemm_p0's), then the slab goes to LDS
+    // the corrector's work on the slab in registers (p0_fuse_group), then the slab goes to LDS
     auto sts = [&](int s, int buf) {
         const int k = s * H_BK + c4;
 #pragma unroll
@@ -608,16 +640,9 @@ __global__ __launch_bounds__(512, 2) void k_hp_full(const float* __restrict__ ra
                 float z[4], m[4];
                 philox_normal4(pf.seed, pf.draw, pf.b_off + b, (unsigned)((row * K + k) >> 2), z);
                 group_masks(pf.mt, b, E, K, row, k, m);
-                if (MODE == 1) {
-#pragma unroll
-                    for (int j = 0; j < 4; ++j) { const float zz = z[j] * m[j]; zacc[u] = fmaf(zz, zz, zacc[u]); }
-                } else {
-                    float4& v = rg[u];
-                    const float4 n = rn[u];
-                    v.x = fmaf(c2, z[0] * m[0], fmaf(c1, n.x, v.x)); v.y = fmaf(c2, z[1] * m[1], fmaf(c1, n.y, v.y));
-                    v.z = fmaf(c2, z[2] * m[2], fmaf(c1, n.z, v.z)); v.w = fmaf(c2, z[3] * m[3], fmaf(c1, n.w, v.w));
-                    *reinterpret_cast<float4*>(pf.f1 + ((size_t)b * E + row) * K + k) = v;
-                }
+                float nacc = 0.f;                                     // (modes 3 / 4 are not this kernel's: nacc, o, mu stay unused)
+                p0_fuse_group<MODE>(pf, c1, c2, z, z, m, rg[u], rn[u], zacc[u], nacc, nullptr, nullptr);
+                if (MODE == 2) *reinterpret_cast<float4*>(pf.f1 + ((size_t)b * E + row) * K + k) = rg[u];
             }
             *reinterpret_cast<float4*>(Fs + buf * SLAB + row * H_LD + c4) = rg[u];
         }
@@ -765,7 +790,7 @@ __global__ __launch_bounds__(256) void k_gemm_p0(const float* __restrict__ rank2
     // fused corrector work (MODE != 0; K % 4 == 0): the thread's two rows of every slab are fixed -> (sample, edge) once
     float c1 = 0.f, c2 = 0.f, zacc[2] = {0.f, 0.f}, nacc[2] = {0.f, 0.f};
     int fb[2] = {0, 0}, fe[2] = {0, 0};
-    if (MODE == 2 || MODE == 4) corr_coef(pf.cf, 2, &c1, &c2);
+    if (MODE == 2 || MODE == 4) langevin_coef(pf.cf.lc, 2, &c1, &c2);
     if (MODE) {
 #pragma unroll
         for (int u = 0; u < 2; ++u) {
@@ -783,37 +808,12 @@ __global__ __launch_bounds__(256) void k_gemm_p0(const float* __restrict__ rank2
         float z[4], m[4];
         philox_normal4(pf.seed, pf.draw, pf.b_off + fb[u], (unsigned)((fe[u] * K + k) >> 2), z);
         group_masks(pf.mt, fb[u], pf.E, K, fe[u], k, m);
-        if (MODE == 1) {
-#pragma unroll
-            for (int j = 0; j < 4; ++j) { const float zz = z[j] * m[j]; zacc[u] = fmaf(zz, zz, zacc[u]); }
-        } else if (MODE == 2) {
-            v.x = fmaf(c2, z[0] * m[0], fmaf(c1, n.x, v.x)); v.y = fmaf(c2, z[1] * m[1], fmaf(c1, n.y, v.y));
-            v.z = fmaf(c2, z[2] * m[2], fmaf(c1, n.z, v.z)); v.w = fmaf(c2, z[3] * m[3], fmaf(c1, n.w, v.w));
-            *reinterpret_cast<float4*>(pf.f1 + (size_t)row * K + k) = v;
-        } else if (MODE == 3) {
-            const float f[4] = {v.x, v.y, v.z, v.w};
-            float net[4];
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                net[j] = m[j] * fmaf(pf.alpha, f[j], pf.gamma);                // fnet_element<AFFINE>, cnum = 1 (k_ew1)
-                const float zz = z[j] * m[j];
-                nacc[u] = fmaf(net[j], net[j], nacc[u]);
-                zacc[u] = fmaf(zz, zz, zacc[u]);
-            }
-            if (pf.net_out) *reinterpret_cast<float4*>(pf.net_out + (size_t)row * K + k) = make_float4(net[0], net[1], net[2], net[3]);
-        } else {
-            float zp[4];
-            philox_normal4(pf.seed, pf.draw_pred, pf.b_off + fb[u], (unsigned)((fe[u] * K + k) >> 2), zp);
-            float f[4] = {v.x, v.y, v.z, v.w}, o[4], mu[4];
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                float net = m[j] * fmaf(pf.alpha, f[j], pf.gamma);
-                f[j] = fmaf(c2, z[j] * m[j], fmaf(c1, net, f[j]));             // k_langevin_apply
-                net = m[j] * fmaf(pf.alpha, f[j], pf.gamma);
-                mu[j] = fmaf(pf.pa, f[j], pf.pb * net);                        // v_mean = pa*v + pb*net
-                o[j] = fmaf(pf.pc, zp[j] * m[j], mu[j]);
-            }
-            v = make_float4(f[0], f[1], f[2], f[3]);                            // the corrected state: what the projection is taken of
+        float zp[4], o[4], mu[4];
+        if (MODE == 4) philox_normal4(pf.seed, pf.draw_pred, pf.b_off + fb[u], (unsigned)((fe[u] * K + k) >> 2), zp);
+        p0_fuse_group<MODE>(pf, c1, c2, z, zp, m, v, n, zacc[u], nacc[u], o, mu);
+        if (MODE == 2) *reinterpret_cast<float4*>(pf.f1 + (size_t)row * K + k) = v;
+        if (MODE == 3 && pf.net_out) *reinterpret_cast<float4*>(pf.net_out + (size_t)row * K + k) = make_float4(o[0], o[1], o[2], o[3]);
+        if (MODE == 4) {       // (v: the corrected state, what the projection is taken of)
             *reinterpret_cast<float4*>(pf.out + (size_t)row * K + k) = make_float4(o[0], o[1], o[2], o[3]);
             if (pf.mean) *reinterpret_cast<float4*>(pf.mean + (size_t)row * K + k) = make_float4(mu[0], mu[1], mu[2], mu[3]);
         }
@@ -1212,9 +1212,10 @@ __global__ __launch_bounds__(256) void k_hf_score(const PlanD* __restrict__ plan
                             s_z = fmaf(zz, zz, s_z);
                         } else {
                             const float zz = z[s2] * m;                               // gen_noise_rank2, cc_utils.py:613-615
-                            const float mean = fmaf(ep.pa, f, ep.pb * net);           // v_mean = pa*v + pb*net
+                            float mean;
+                            const float nv = pred_update(ep.pa, ep.pb, ep.pc, f, net, zz, &mean);
                             if (MODE == 3) meanb[g] = mean;
-                            outb[g] = fmaf(ep.pc, zz, mean);
+                            outb[g] = nv;
                         }
                     }
                 }
@@ -1255,9 +1256,10 @@ __global__ __launch_bounds__(256) void k_hf_score(const PlanD* __restrict__ plan
                 s_net = fmaf(net, net, s_net);
                 s_z = fmaf(zz, zz, s_z);
             } else {
-                const float mean = fmaf(ep.pa, f, ep.pb * net);   // v_mean = pa*v + pb*net
+                float mean;
+                const float nv = pred_update(ep.pa, ep.pb, ep.pc, f, net, zz, &mean);
                 if (ep.mean) ep.mean[gi] = mean;
-                ep.out[gi] = fmaf(ep.pc, zz, mean);
+                ep.out[gi] = nv;
             }
         }
     });

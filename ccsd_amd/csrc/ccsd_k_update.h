@@ -104,28 +104,16 @@ __global__ void k_noise_norm(NoiseArgs na, MaskTab mt, int E_, int K_, float* __
 }
 
 // ---------------------------------------------------------------------------------------------
-// k_langevin_apply: step = (snr * zn / gn)^2 * 2 * alpha; v_mean = v + step*score;
-// v = v_mean + sqrt(2 step) * z * scale_eps          (solver.py:767-769, 781-783, 797-801)
-// score = sscale * net, so gn = |sscale| * sum|net| and step*score = step*sscale*net.
-// grid-stride over the three tensors of the whole batch.
+// k_langevin_apply: the Langevin corrector's apply (langevin_coef, corr_apply), grid-stride over the three tensors of the whole batch.
 // ---------------------------------------------------------------------------------------------
 struct LangArgs {
     const float* x; const float* adj; const float* r;          // state in
     const float* nx; const float* nadj; const float* nr;        // raw network outputs kept by the NORMS pass
     float* ox; float* oadj; float* orr;                          // state out
     const float* flags;
-    const float* sums;
-    float ss[3], alpha[3];
-    float snr, seps;
+    LangCoef lc;
     int B, N, F, E, K, is_cc;
 };
-CCSD_DEV void langevin_coef(const LangArgs& a, int t, float* c1, float* c2) {
-    const float gn = fabsf(a.ss[t]) * a.sums[t], zn = a.sums[3 + t];
-    const float q = a.snr * zn / gn;
-    const float step = q * q * 2.f * a.alpha[t];
-    *c1 = step * a.ss[t];
-    *c2 = sqrtf(step * 2.f) * a.seps;
-}
 template <int EC = 0, int KC = 0>       // E, K as compile-time constants (0: LangArgs'): GEO_EK in ccsd_api.h
 __global__ void k_langevin_apply(LangArgs a, NoiseArgs na, MaskTab mt) {
     if (EC) { a.E = EC; a.K = KC; }
@@ -137,9 +125,9 @@ __global__ void k_langevin_apply(LangArgs a, NoiseArgs na, MaskTab mt) {
     const long long total = nxe + nae + nre;
     const bool vec = (EK & 3) == 0;
     float c1x, c2x, c1a, c2a, c1r = 0.f, c2r = 0.f;
-    langevin_coef(a, 0, &c1x, &c2x);
-    langevin_coef(a, 1, &c1a, &c2a);
-    if (a.is_cc) langevin_coef(a, 2, &c1r, &c2r);
+    langevin_coef(a.lc, 0, &c1x, &c2x);
+    langevin_coef(a.lc, 1, &c1a, &c2a);
+    if (a.is_cc) langevin_coef(a.lc, 2, &c1r, &c2r);
     const FastDiv dK(a.K > 0 ? a.K : 1);
     for (long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x; t < total; t += (long long)gridDim.x * blockDim.x) {
         if (t < nre) {                                           // (the rank2 groups come first: the bulk of the work, aligned)
@@ -164,10 +152,8 @@ __global__ void k_langevin_apply(LangArgs a, NoiseArgs na, MaskTab mt) {
             float o[4], m[4];
             group_masks(mt, b, a.E, a.K, e, k, m);
 #pragma unroll
-            for (int s = 0; s < 4; ++s) {
-                const float zz = z[s] * m[s];
-                o[s] = fmaf(c2r, zz, fmaf(c1r, nv[s], v[s]));
-            }
+            for (int s = 0; s < 4; ++s)
+                o[s] = corr_apply(c1r, c2r, nv[s], v[s], z[s] * m[s]);
             if (vec) *reinterpret_cast<float4*>(a.orr + base) = make_float4(o[0], o[1], o[2], o[3]);
             else {
 #pragma unroll
@@ -178,12 +164,12 @@ __global__ void k_langevin_apply(LangArgs a, NoiseArgs na, MaskTab mt) {
             const long long u = t - nre;
             const int per = a.N * a.F, b = (int)(u / per), idx = (int)(u % per), i = idx / a.F;
             const float z = raw_noise_x(na, b, idx, per) * a.flags[(size_t)b * a.N + i];
-            a.ox[u] = fmaf(c2x, z, fmaf(c1x, a.nx[u], a.x[u]));
+            a.ox[u] = corr_apply(c1x, c2x, a.nx[u], a.x[u], z);
         } else {
             const long long u = t - nre - nxe;
             const int per = a.N * a.N, b = (int)(u / per), ij = (int)(u % per), i = ij / a.N, j = ij % a.N;
             const float z = raw_noise_adj(na, b, i, j, a.N) * a.flags[(size_t)b * a.N + i] * a.flags[(size_t)b * a.N + j];
-            a.oadj[u] = fmaf(c2a, z, fmaf(c1a, a.nadj[u], a.adj[u]));
+            a.oadj[u] = corr_apply(c1a, c2a, a.nadj[u], a.adj[u], z);
         }
     }
 }
@@ -195,9 +181,9 @@ __global__ void k_langevin_apply(LangArgs a, NoiseArgs na, MaskTab mt) {
 //   SCORE  out = sscale net
 //   NORMS  partial sums of net^2 and (z fl fr)^2 per (sample, chunk); the raw score is stored only on request (step-wise API:
 //          ccsd_corrector_apply reads it; ccsd_sampler_run recomputes it in the apply below instead of a 2 x E K x 4 B round trip)
-//   PRED   [fused Langevin corrector apply  F1 = fma(c2, z fl fr, fma(c1, net(F), F)), written to `f1`: the hodge projection
-//          GEMM of the A-network reads it]  then  mean = pa F1 + pb net(F1),  out = mean + pc z' fl fr   (solver.py:797-801, 429-457)
-// Same expressions as k_hf_score / k_langevin_apply.  grid (chunks of CCSD_NN_CH groups, B).
+//   PRED   [fused Langevin corrector apply  F1 = corr_apply(net(F), F, z fl fr), written to `f1`: the hodge projection GEMM of the
+//          A-network reads it]  then  mean = pa F1 + pb net(F1),  out = mean + pc z' fl fr   (solver.py:797-801, 429-457)
+// grid (chunks of CCSD_NN_CH groups, B).
 // ---------------------------------------------------------------------------------------------
 struct Ew1Args {
     const float* r; float* out; float* mean; float* f1; float* net_out; float* part;
@@ -216,13 +202,8 @@ __global__ void k_ew1(Ew1Args a, NoiseArgs na) {
     const FastDiv dK(a.K);
     const bool vec = (EK & 3) == 0;
     float c1 = 0.f, c2 = 0.f;
-    if (a.mode == MODE_PRED && a.apply) {
-        const float gn = fabsf(a.ss) * a.sums[2], zn = a.sums[5];          // (corr_coef / langevin_coef for the rank2 target)
-        const float q = a.snr * zn / gn;
-        const float step = q * q * 2.f * a.sde_alpha;
-        c1 = step * a.ss;
-        c2 = sqrtf(step * 2.f) * a.seps;
-    }
+    // (Ew1Args carries the rank2 target's scalars only: slot 2 of the LangCoef is the one that is read)
+    if (a.mode == MODE_PRED && a.apply) langevin_coef(LangCoef{a.sums, {0.f, 0.f, a.ss}, {0.f, 0.f, a.sde_alpha}, a.snr, a.seps}, 2, &c1, &c2);
     NoiseArgs nc = na;                                                      // corrector draw (NORMS: the launch's own draw)
     if (a.mode == MODE_PRED) { nc.zr = nullptr; nc.draw_r = a.draw_corr; }
     float s_net = 0.f, s_z = 0.f;
@@ -245,7 +226,7 @@ __global__ void k_ew1(Ew1Args a, NoiseArgs na) {
 #pragma unroll
         for (int s = 0; s < 4; ++s) {
             float f = v[s];
-            float net = m[s] * fmaf(a.alpha, f, a.gamma);                     // fnet_element<AFFINE>, cnum = 1
+            float net = ew1_net(a.alpha, a.gamma, m[s], f);
             if (a.mode == MODE_SCORE) {
                 o[s] = a.sscale * net;
             } else if (a.mode == MODE_NORMS) {
@@ -255,9 +236,9 @@ __global__ void k_ew1(Ew1Args a, NoiseArgs na) {
                 s_z = fmaf(zz, zz, s_z);
             } else {
                 if (a.apply) {
-                    f = fmaf(c2, zc[s] * m[s], fmaf(c1, net, f));             // k_langevin_apply
+                    f = corr_apply(c1, c2, net, f, zc[s] * m[s]);
                     w1[s] = f;
-                    net = m[s] * fmaf(a.alpha, f, a.gamma);
+                    net = ew1_net(a.alpha, a.gamma, m[s], f);
                 }
                 const float mean = fmaf(a.pa, f, a.pb * net);                 // v_mean = pa*v + pb*net (k_hf_score, MODE_PRED)
                 mu[s] = mean;
@@ -293,7 +274,7 @@ __global__ void k_ew1(Ew1Args a, NoiseArgs na) {
 
 // ---------------------------------------------------------------------------------------------
 // k_s4_apply: the update half of one S4_solver step (solver.py:1296-1352 graph, 1446-1529 CC), element-wise:
-//   v1 = v + step*score + sqrt(2 step)*z1*scale_eps        Langevin-style correction with the step's score
+//   v1 = corr_apply(net, v, z1)                            Langevin-style correction with the step's score
 //   v2 = m1*v1 + s1*z2                                     sde.transition(v1, t, dt/2)
 //   v3 = v2 + d*net                                        + Sdrift*dt, Sdrift = -g(t)^2 * score
 //   mean = m2*v3 ;  v = mean + s2*z3                       sde.transition(v3, t + dt/2, dt/2)
@@ -305,7 +286,7 @@ struct S4Args {
     float* mx; float* madj; float* mr;   // means (nullable)
 };
 CCSD_DEV float s4_chain(float v, float net, float z1, float z2, float z3, float c1, float c2, const S4Args& q, int t, float* mean) {
-    const float v1 = fmaf(c2, z1, fmaf(c1, net, v));
+    const float v1 = corr_apply(c1, c2, net, v, z1);
     const float v2 = fmaf(q.s1[t], z2, q.m1[t] * v1);
     const float v3 = fmaf(q.d[t], net, v2);
     const float mu = q.m2[t] * v3;
@@ -319,9 +300,9 @@ __global__ void k_s4_apply(S4Args q, NoiseArgs n1, NoiseArgs n2, NoiseArgs n3, c
     const long long nre = a.is_cc ? (long long)a.B * ((a.E + 3) / 4) * a.K : 0;
     const long long total = nxe + nae + nre;
     float c1x, c2x, c1a, c2a, c1r = 0.f, c2r = 0.f;
-    langevin_coef(a, 0, &c1x, &c2x);
-    langevin_coef(a, 1, &c1a, &c2a);
-    if (a.is_cc) langevin_coef(a, 2, &c1r, &c2r);
+    langevin_coef(a.lc, 0, &c1x, &c2x);
+    langevin_coef(a.lc, 1, &c1a, &c2a);
+    if (a.is_cc) langevin_coef(a.lc, 2, &c1r, &c2r);
     for (long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x; t < total; t += (long long)gridDim.x * blockDim.x) {
         float mu;
         if (t < nxe) {

@@ -56,22 +56,22 @@ struct XaArgs {
     float* hdump;
 };
 
-// fused Langevin corrector apply for x and adj held in LDS (same expressions as k_langevin_apply)
+// fused Langevin corrector apply for x and adj held in LDS
 CCSD_DEV void corr_apply_xa(const CorrFuse& cf, const NoiseArgs& na, int b, int N, int F, float* s_x, float* s_adj,
                             const float* s_flags) {
     float c1x, c2x, c1a, c2a;
-    corr_coef(cf, 0, &c1x, &c2x);
-    corr_coef(cf, 1, &c1a, &c2a);
+    langevin_coef(cf.lc, 0, &c1x, &c2x);
+    langevin_coef(cf.lc, 1, &c1a, &c2a);
     NoiseArgs nc = na;
     nc.zx = nullptr; nc.zadj = nullptr; nc.draw_x = cf.draw_x; nc.draw_adj = cf.draw_adj;
     for (int t = threadIdx.x; t < N * F; t += blockDim.x) {
         const float z = raw_noise_x(nc, b, t, N * F) * s_flags[t / F];
-        s_x[t] = fmaf(c2x, z, fmaf(c1x, cf.net_x[(size_t)b * N * F + t], s_x[t]));
+        s_x[t] = corr_apply(c1x, c2x, cf.net_x[(size_t)b * N * F + t], s_x[t], z);
     }
     for (int t = threadIdx.x; t < N * N; t += blockDim.x) {
         const int i = t / N, j = t % N;
         const float z = raw_noise_adj(nc, b, i, j, N) * s_flags[i] * s_flags[j];
-        s_adj[t] = fmaf(c2a, z, fmaf(c1a, cf.net_adj[(size_t)b * N * N + t], s_adj[t]));
+        s_adj[t] = corr_apply(c1a, c2a, cf.net_adj[(size_t)b * N * N + t], s_adj[t], z);
     }
 }
 
@@ -177,9 +177,10 @@ CCSD_DEV XLateOut xnet_late_stage(int stage, const PlanD& p, const float* __rest
                     r.n2 = fmaf(net, net, r.n2);
                     r.z2 = fmaf(z, z, r.z2);
                 } else {
-                    const float mean = fmaf(xa.pa_x, s_x[t], xa.pb_x * net);
+                    float mean;
+                    const float nv = pred_update(xa.pa_x, xa.pb_x, xa.pc_x, s_x[t], net, z, &mean);
                     if (xa.mean_x) xa.mean_x[gi] = mean;
-                    xa.out_x[gi] = fmaf(xa.pc_x, z, mean);
+                    xa.out_x[gi] = nv;
                 }
             }
         }
@@ -272,15 +273,15 @@ __global__ __launch_bounds__((VAR == XA_PLAIN9 || VAR == XA_BAKED9 || !XA_4WAVES
     const bool x_late = SEM == XA_PLAIN && !GCH && p.x_late && xa.do_x && xa.do_a && xa.xA == xa.xX && xa.adjA == xa.adjX;
     if (x_late) {
         // Everything the launch reads from HBM at its start is requested in ONE batch and meets ONE barrier: the inputs, the raw
-        // scores and norm sums of the fused corrector apply (same expressions as corr_apply_xa, the flags read from global memory
+        // scores and norm sums of the fused corrector apply (corr_apply_xa's work, the flags read from global memory
         // instead of waiting for their LDS copy), the edge table -- and the A-network's own staging (s_xcur, channel 0) is written
         // from the same registers.  (Was: load, barrier, apply, barrier, edge table, barrier, copy, barrier.)
         float c1x = 0.f, c2x = 0.f, c1a = 0.f, c2a = 0.f;
         NoiseArgs nc = na;
         const bool cfon = xa.cf.on != 0;
         if (cfon) {
-            corr_coef(xa.cf, 0, &c1x, &c2x);
-            corr_coef(xa.cf, 1, &c1a, &c2a);
+            langevin_coef(xa.cf.lc, 0, &c1x, &c2x);
+            langevin_coef(xa.cf.lc, 1, &c1a, &c2a);
             nc.zx = nullptr; nc.zadj = nullptr; nc.draw_x = xa.cf.draw_x; nc.draw_adj = xa.cf.draw_adj;
         }
         float* const xcur0 = sm + p.o_xcur;
@@ -293,7 +294,7 @@ __global__ __launch_bounds__((VAR == XA_PLAIN9 || VAR == XA_BAKED9 || !XA_4WAVES
             dF.divmod(t, i, f);
             if (cfon) {
                 const float z = raw_noise_x(nc, b, t, N * F) * fg[i];
-                v = fmaf(c2x, z, fmaf(c1x, xa.cf.net_x[(size_t)b * N * F + t], v));
+                v = corr_apply(c1x, c2x, xa.cf.net_x[(size_t)b * N * F + t], v, z);
             }
             s_x[t] = v;
             xcur0[f * ldn + i] = v;
@@ -303,7 +304,7 @@ __global__ __launch_bounds__((VAR == XA_PLAIN9 || VAR == XA_BAKED9 || !XA_4WAVES
             if (cfon) {
                 const int i = t / N, j = t % N;
                 const float z = raw_noise_adj(nc, b, i, j, N) * fg[i] * fg[j];
-                v = fmaf(c2a, z, fmaf(c1a, xa.cf.net_adj[(size_t)b * NN + t], v));
+                v = corr_apply(c1a, c2a, xa.cf.net_adj[(size_t)b * NN + t], v, z);
             }
             s_adj[t] = v;
             chan0[t] = v;
@@ -419,9 +420,10 @@ __global__ __launch_bounds__((VAR == XA_PLAIN9 || VAR == XA_BAKED9 || !XA_4WAVES
                     nx_net = fmaf(net, net, nx_net);
                     nx_z = fmaf(z, z, nx_z);
                 } else {
-                    const float mean = fmaf(xa.pa_x, s_x[t], xa.pb_x * net);
+                    float mean;
+                    const float nv = pred_update(xa.pa_x, xa.pb_x, xa.pc_x, s_x[t], net, z, &mean);
                     if (xa.mean_x) xa.mean_x[gi] = mean;
-                    xa.out_x[gi] = fmaf(xa.pc_x, z, mean);
+                    xa.out_x[gi] = nv;
                 }
             }
         }
@@ -1209,9 +1211,10 @@ __global__ __launch_bounds__((VAR == XA_PLAIN9 || VAR == XA_BAKED9 || !XA_4WAVES
                         na_net = fmaf(net, net, na_net);
                         na_z = fmaf(z, z, na_z);
                     } else {
-                        const float mean = fmaf(xa.pa_a, s_adj[ij], xa.pb_a * net);
+                        float mean;
+                        const float nv = pred_update(xa.pa_a, xa.pb_a, xa.pc_a, s_adj[ij], net, z, &mean);
                         if (xa.mean_a) xa.mean_a[gi] = mean;
-                        xa.out_a[gi] = fmaf(xa.pc_a, z, mean);
+                        xa.out_a[gi] = nv;
                     }
                 }
             }

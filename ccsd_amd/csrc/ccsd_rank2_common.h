@@ -1,5 +1,5 @@
 // ccsd_rank2_common.h -- helpers shared by the rank-2 kernels and the graph-network kernel: flag masks from the off-bit table,
-// epilogue modes, ScoreNetworkF per element, wave-level MFMA tile loops, the fused Langevin-apply coefficients.
+// epilogue modes, ScoreNetworkF per element, wave-level MFMA tile loops, the Langevin corrector of one element.
 // Part of the kernel source of libccsd_hip.so (see ccsd_kernels.h for the map).
 #pragma once
 #include "ccsd_dev.h"
@@ -217,21 +217,34 @@ CCSD_DEV float raw_noise_r1(const NoiseArgs& na, int b, int e, int k, int E, int
     return s == 0 ? n[0] : s == 1 ? n[1] : s == 2 ? n[2] : n[3];
 }
 
-// Langevin corrector apply fused into the predictor kernels (ccsd_sampler_run): v <- v + step*score + sqrt(2 step)*z*scale_eps
-// with step from the batch norm sums (solver.py:767-769, 781-783, 797-801); same arithmetic as k_langevin_apply.
+// ---------------------------------------------------------------------------------------------
+// The Langevin corrector and the predictor update of one element: the ONLY statement of this arithmetic (DESIGN.md section 4 lists the
+// sites that call it and the ones that still carry their own text).
+// ---------------------------------------------------------------------------------------------
+// the Langevin scalars of a launch (CorrFuse, LangArgs): norm sums of k_normsum, per-target sscale / alpha of the step
+struct LangCoef { const float* sums; float ss[3], alpha[3]; float snr, seps; };
+// Langevin step size of target t from the batch norm sums: step = (snr * zn / gn)^2 * 2 * alpha (solver.py:767-769).  score =
+// sscale * net, so gn = |sscale| * sum|net| and the apply below is v + c1 net + c2 z with c1 = step sscale, c2 = sqrt(2 step) scale_eps.
+CCSD_DEV void langevin_coef(const LangCoef& lc, int t, float* c1, float* c2) {
+    const float gn = fabsf(lc.ss[t]) * lc.sums[t], zn = lc.sums[3 + t];
+    const float q = lc.snr * zn / gn;
+    const float step = q * q * 2.f * lc.alpha[t];
+    *c1 = step * lc.ss[t];
+    *c2 = sqrtf(step * 2.f) * lc.seps;
+}
+// corrector apply: v_mean = v + step*score; v = v_mean + sqrt(2 step) * z * scale_eps, zz = the masked draw (solver.py:781-783, 797-801)
+CCSD_DEV float corr_apply(float c1, float c2, float net, float v, float zz) { return fmaf(c2, zz, fmaf(c1, net, v)); }
+// predictor update: v_mean = pa*v + pb*net; v = v_mean + pc * z, zz = the masked draw (solver.py:429-457)
+CCSD_DEV float pred_update(float pa, float pb, float pc, float v, float net, float zz, float* mean) {
+    *mean = fmaf(pa, v, pb * net);
+    return fmaf(pc, zz, *mean);
+}
+// ScoreNetworkF when it is affine with cnum = 1 (fnet_element<AFFINE> without a Hodge Laplacian term): net = fl fr (alpha F + gamma)
+CCSD_DEV float ew1_net(float alpha, float gamma, float m, float f) { return m * fmaf(alpha, f, gamma); }
+// Langevin corrector apply fused into the predictor kernels (ccsd_sampler_run): corr_apply with the step from the batch norm sums
 struct CorrFuse {
     int on;
     const float* net_x; const float* net_adj; const float* net_r;   // raw network outputs kept by the NORMS pass
-    const float* sums;
-    float ss[3], alpha[3];
-    float snr, seps;
+    LangCoef lc;
     unsigned int draw_x, draw_adj, draw_r;                            // corrector draw indices (predictor ones are in NoiseArgs)
 };
-CCSD_DEV void corr_coef(const CorrFuse& cf, int t, float* c1, float* c2) {
-    const float gn = fabsf(cf.ss[t]) * cf.sums[t], zn = cf.sums[3 + t];
-    const float q = cf.snr * zn / gn;
-    const float step = q * q * 2.f * cf.alpha[t];
-    *c1 = step * cf.ss[t];
-    *c2 = sqrtf(step * 2.f) * cf.seps;
-}
-
