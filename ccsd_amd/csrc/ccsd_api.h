@@ -44,9 +44,9 @@ static inline int fnet_width(const PlanD& p) {
 //   CCSD_HP_FULL_NORMS   hp_full_norms         k_hp_full in the norms pass too (slower: A/B only)              tests (gpu)
 //   CCSD_SPLIT_BF16=3    split_bf16            EXPERIMENT: split-precision k_gemm_h_full, NOT bit-identical    tests (gpu), bench.py, tools/dev
 //   CCSD_XA_THREADS      xa_threads            threads per graph of k_xa (64 .. 1024; 0 = by batch)            tests (gpu)
-//   CCSD_XA_PRIO         xa_prio               k_xa issue-priority scheme     } their other half is kernel     tools/dev
-//   CCSD_XA_STAGGER      xa_stagger_*          "mask,sleep" start stagger     } code: removing them is a       tools/dev
-//   CCSD_R2_STAGGER      r2_stagger_*          "mask,sleep" start stagger     } follow-up with the kernels     nobody
+//   CCSD_XA_PRIO         xa_prio               k_xa issue priority: 0 rotating (default), 1 none, 2 static.    nobody
+//                                              Lost on every workload (xiv); kept because k_xa<false, XA_HB> without the
+//                                              mode test needs 104 bytes of scratch instead of 100 (profiles/README.md r08)
 //   CCSD_LARGE_GRAPH=1   lg_force              tiled graph-network route for any eligible plan  (PlanBuilder)  tests (emu + gpu)
 //   CCSD_XA_PASS=<n>     xa_pass               first k_xa LDS budget candidate tried            (PlanBuilder)  tests (emu + gpu)
 //   CCSD_XA_GCH          xa_gch                channel stack in the HBM workspace first         (PlanBuilder)  tests (emu + gpu)
@@ -55,8 +55,7 @@ static inline int fnet_width(const PlanD& p) {
 //   CCSD_DUMP_PLAN[_NAME] dump_plan[_name]     write the plan's architecture bytes as a C header               tools/bake_plan.py
 struct Knobs {
     int no_fused_r2 = 0, hodge_general = 0, geo_off = 0, no_fused_apply = 0, no_h_full = 0, no_hp_full = 0, hp_full_norms = 0, split_bf16 = 0;
-    int xa_threads = 0, xa_prio = 0, xa_stagger_mask = 0, xa_stagger_sleep = 0, r2_stagger_mask = 0, r2_stagger_sleep = 0;
-    int lg_force = 0, xa_pass = -1, xa_gch = 0, no_mlp_wt = 0, verbose = 0;
+    int xa_threads = 0, xa_prio = 0, lg_force = 0, xa_pass = -1, xa_gch = 0, no_mlp_wt = 0, verbose = 0;
     const char *dump_plan = nullptr, *dump_plan_name = nullptr;
 };
 static Knobs read_knobs() {
@@ -69,8 +68,6 @@ static Knobs read_knobs() {
     if (const char* v = getenv("CCSD_SPLIT_BF16")) k.split_bf16 = atoi(v) == 3 ? 3 : 0;
     if (const char* v = getenv("CCSD_XA_THREADS")) { const int t = atoi(v); if (t >= 64 && t <= 1024 && t % 64 == 0) k.xa_threads = t; }
     if (const char* v = getenv("CCSD_XA_PRIO")) k.xa_prio = atoi(v);
-    if (const char* v = getenv("CCSD_XA_STAGGER")) sscanf(v, "%d,%d", &k.xa_stagger_mask, &k.xa_stagger_sleep);
-    if (const char* v = getenv("CCSD_R2_STAGGER")) sscanf(v, "%d,%d", &k.r2_stagger_mask, &k.r2_stagger_sleep);
     if (const char* v = getenv("CCSD_LARGE_GRAPH")) k.lg_force = atoi(v) == 1;
     if (const char* v = getenv("CCSD_XA_PASS")) k.xa_pass = atoi(v);
     k.xa_gch = on("CCSD_XA_GCH"); k.no_mlp_wt = on("CCSD_NO_MLP_WT"); k.verbose = on("CCSD_VERBOSE");
@@ -803,11 +800,11 @@ static int launch_xa(const ccsd_plan* pl, int B, XaArgs& xa, NoiseArgs& na, cons
     if (rt.lg) return launch_lg(pl, B, xa, na, w, stream);
     xa.P0 = set_b ? w.P0b : w.P0; xa.P1 = set_b ? w.P1b : w.P1; xa.U1 = set_b ? w.U1b : w.U1; xa.chan_ws = w.chan;
     xa.p1_raw = ps.p1_raw; xa.dbg = pl->dbg ? pl->dbg + 32 : nullptr;
-    xa.stagger_mask = pl->knobs.xa_stagger_mask; xa.stagger_sleep = pl->knobs.xa_stagger_sleep; xa.prio_mode = pl->knobs.xa_prio;
     int xa_threads;
     const XaEntry* inst = xa_launch(rt, B, &xa_threads);
     prof_mark(const_cast<ccsd_plan*>(pl), KID_XA, stream);
     xa.wp = pl->wp; xa.hpairs = pl->hpairs;
+    xa.prio_mode = pl->knobs.xa_prio;
     const dim3 xblk(CCSD_NTHREADS == 1 ? 1 : xa_threads);
     const size_t xlds = (size_t)pl->h.xa_lds_floats * 4;
 #define XA_LAUNCH(XA_) CCSD_LAUNCH(inst->fn, dim3(B), xblk, xlds, stream, (const PlanD*)pl->d, (const float*)pl->w, (const unsigned char*)pl->edges, XA_, na)
@@ -974,7 +971,6 @@ static int launch_r2(const ccsd_plan* pl, int B, const float* rank2, const float
     }
     ra.rank2 = rank2; ra.adj = adj; ra.flags = flags; ra.offbits = w.offbits; ra.P0 = w.P0; ra.P1 = w.P1; ra.U1 = w.U1; ra.want_p = want_p;
     ra.ldk = rt.r2_ldk; ra.ldh = rt.r2_ldh; ra.dbg = pl->dbg; ra.wp = pl->wp;
-    ra.stagger_mask = pl->knobs.r2_stagger_mask; ra.stagger_sleep = pl->knobs.r2_stagger_sleep;
     if (want_p && pl->h.h_L > 1) ps.p1_raw = r2_p1_raw(pl->h);
     prof_mark(const_cast<ccsd_plan*>(pl), KID_R2, stream);
     CCSD_LAUNCH(rt.r2->fn, dim3(B), dim3(CCSD_NTHREADS == 1 ? 1 : 512), rt.r2_lds, stream, (const PlanD*)pl->d, (const float*)pl->w,

@@ -18,7 +18,6 @@ struct R2Args {
     // is then a plain F Wcat_1 tile (no cell-mask conversion / product per element in its loader), and u_1 = fr . Wcat_1 -- a function of
     // the flags alone -- is not recomputed: U1 / U1b keep what the run's first (general) launch wrote.
     int masked;
-    int stagger_mask, stagger_sleep;   // workgroups with (blockIdx.x & mask) != 0 start `sleep` x 64 cycles late (see launch_r2)
     // Merged launch (ccsd_sampler_run, E = 36 geometry): the predictor half-step of PC step i, then -- on the new rank2 block, which
     // the epilogue also wrote back into LDS -- the norms pass of the corrector of step i + 1 (its ScoreNetworkF score to HBM, both
     // norm partials, the hodge projections of the new state into the second buffer set): one block load instead of two.
@@ -45,14 +44,14 @@ struct R2Args {
 // i.e. 4 rows x 16 columns x 4 k values per instruction -- the SAME operand addresses as the 16x16x4 tile code (B operand of
 // column l & 15, k slot group l >> 4), only the A row differs; the four k classes are summed with two lane swaps.
 // QM9 (1, 2): the qm9 geometry (E = 36, K = 466, N = 9, LDS strides 488 / 36) as compile-time constants: the index arithmetic on these
-// strides folds into immediates (as k_xa<false, XA_PLAIN9>); the host selects the instance only when the plan matches (r2_qm9()).
+// strides folds into immediates (as k_xa<false, XA_PLAIN9>); the host selects the instance only when the plan matches (resolve_route: Route::r2, its qm9 column).
 template <int MT, int RS, bool AFFINE, bool GEN1, int QM9 = 0>
 __global__ __launch_bounds__(512, 4) void k_r2(const PlanD* __restrict__ plan, const float* __restrict__ w,
                                             const unsigned char* __restrict__ edges,
                                             const unsigned long long* __restrict__ cells, R2Args ra, RankEpi ep,
                                             NoiseArgs na) {
     CCSD_DYN_SMEM(sm);
-    // QM9 with a baked plan (ccsd_baked_qm9.h; r2_qm9() == 2 when the plan's architecture bytes equal the baked ones): every plan
+    // QM9 with a baked plan (ccsd_baked_qm9.h; the qm9 column of Route::r2 is 2 when the plan's architecture bytes equal the baked ones): every plan
     // field but the weight-derived affine fold -- read through `pw` -- is a compile-time constant
     constexpr bool BAKED = QM9 == 2 && CCSD_BAKED_QM9_SIZE == sizeof(PlanD);
     const PlanD& pw = *plan;
@@ -591,7 +590,7 @@ __global__ __launch_bounds__(512, 4) void k_r2(const PlanD* __restrict__ plan, c
             if (e >= E) continue;
             const float f = sF[e * ldk + k];
             const float m = sFl[e] * fr;                         // flags_left * flags_right, cc_utils.py:590
-            const float hf1[CCSD_MAXCN - 1] = {hf[r], 0.f, 0.f};      // (cnum > 2 takes the tiled kernels: ccsd_plan::fused_r2)
+            const float hf1[CCSD_MAXCN - 1] = {hf[r], 0.f, 0.f};      // (cnum > 2 takes the tiled kernels: Route::r2_family)
             const float net = fnet_element<AFFINE>(pw, w, f, hf1, m);
             const size_t gi = ((size_t)b * E + e) * K + k;
             if (ep.mode == MODE_SCORE) {

@@ -52,6 +52,34 @@ static inline int xcd_grid(int B, int T) { return ((B + 7) / 8) * 8 * T; }
 // ---------------------------------------------------------------------------------------------
 #define H_BK 32   // k per slab (two 16-wide MFMA k blocks)
 #define H_LD 40   // LDS row stride in floats: 16-byte aligned rows, == 8 mod 32 -> conflict-free ds_read_b128 fragments
+#ifndef CCSD_EMU
+typedef float f32x4 __attribute__((ext_vector_type(4)));
+// The pieces the tiled rank-2 GEMM kernels share, stated once (DESIGN.md section 4 lists the sites that call them and the ones that
+// still carry their own text).
+// One 16-wide block of the contraction index of one 16 x 16 sub-tile: a, b = the lane's fragments of the two row slabs (one ds_read_b128
+// each), component j = step j of the block (MFMA k slot kq <-> k = 16 t + 4 kq + j).  k_gemm_h_full, k_hp_full, k_gemm_p0 and the two
+// single products of k_gemm_h, which promise each other bit-identical sub-tiles, all go through here; the interleaved 2 x 2 products of
+// k_gemm_h and k_hf_score are the same steps written out per accumulator pair.
+CCSD_DEV void frag_mma(f32x4& acc, const float4& a, const float4& b) {
+    const float av[4] = {a.x, a.y, a.z, a.w}, bv[4] = {b.x, b.y, b.z, b.w};
+#pragma unroll
+    for (int q = 0; q < 4; ++q) acc = __builtin_amdgcn_mfma_f32_16x16x4f32(av[q], bv[q], acc, 0, 0, 0);
+}
+// v = src[k .. k + 3] of a row of K floats: one 16-byte load where rows are whole groups (vec: K a multiple of 4), element by element
+// with zeros beyond K otherwise (the ragged tail).  (Through a reference: returned by value it changed the code of k_gemm_h and k_hf_score.)
+CCSD_DEV void row_load4(float4& v, const float* src, int k, int K, bool vec) {
+    if (vec && k + 3 < K) v = *reinterpret_cast<const float4*>(src + k);
+    else {
+        v.x = k < K ? src[k] : 0.f; v.y = k + 1 < K ? src[k + 1] : 0.f;
+        v.z = k + 2 < K ? src[k + 2] : 0.f; v.w = k + 3 < K ? src[k + 3] : 0.f;
+    }
+}
+// sum over the eight consecutive lanes that hold the eight column groups of a slab row: fixed butterfly, every lane gets the sum
+CCSD_DEV float row8_sum(float v) {
+    v += __shfl_xor(v, 1, 64); v += __shfl_xor(v, 2, 64); v += __shfl_xor(v, 4, 64);
+    return v;
+}
+#endif
 // EC, KC: E and K as compile-time constants (0: the run-time arguments) -- the instance for the community_small geometry
 template <int EC = 0, int KC = 0>
 __global__ __launch_bounds__(256) void k_gemm_h(const float* __restrict__ rank2, float* __restrict__ H, int E_, int K_,
@@ -85,7 +113,6 @@ __global__ __launch_bounds__(256) void k_gemm_h(const float* __restrict__ rank2,
     // before the MFMAs of the current one.
     __shared__ __align__(16) float As[T_BM * H_LD];
     __shared__ __align__(16) float Bs[T_BN * H_LD];
-    typedef float f32x4 __attribute__((ext_vector_type(4)));
     const int tid = threadIdx.x, wave = wave_index(), lane = tid & 63, l15 = lane & 15, kq = lane >> 4;
     const bool diag = tx == ty, vec = (K & 3) == 0;
     // Wave -> 16 x 16 sub-tiles.  Off-diagonal tiles: a 32 x 32 block (2 x 2 sub-tiles) per wave.  DIAGONAL tiles (half of a
@@ -103,11 +130,7 @@ __global__ __launch_bounds__(256) void k_gemm_h(const float* __restrict__ rank2,
         const int rc = row < E ? row : E - 1;
         const float* src = Fb + (size_t)rc * K;
         float4 v;
-        if (vec && k + 3 < K) v = *reinterpret_cast<const float4*>(src + k);
-        else {
-            v.x = k < K ? src[k] : 0.f; v.y = k + 1 < K ? src[k + 1] : 0.f;
-            v.z = k + 2 < K ? src[k + 2] : 0.f; v.w = k + 3 < K ? src[k + 3] : 0.f;
-        }
+        row_load4(v, src, k, K, vec);
         if (row >= E) v = make_float4(0.f, 0.f, 0.f, 0.f);
         return v;
     };
@@ -134,21 +157,14 @@ __global__ __launch_bounds__(256) void k_gemm_h(const float* __restrict__ rank2,
             const float4 a1 = *reinterpret_cast<const float4*>(As + ((row1 ? wm + 16 : wm) + l15) * H_LD + 16 * t + 4 * kq);
             const float4 b0 = *reinterpret_cast<const float4*>(Bp + (wn + l15) * H_LD + 16 * t + 4 * kq);
             const float4 b1 = *reinterpret_cast<const float4*>(Bp + (wn + 16 + l15) * H_LD + 16 * t + 4 * kq);
-            const float av0[4] = {a0.x, a0.y, a0.z, a0.w}, av1[4] = {a1.x, a1.y, a1.z, a1.w};
-            const float bv0[4] = {b0.x, b0.y, b0.z, b0.w}, bv1[4] = {b1.x, b1.y, b1.z, b1.w};
+            const float av0[4] = {a0.x, a0.y, a0.z, a0.w}, bv0[4] = {b0.x, b0.y, b0.z, b0.w}, bv1[4] = {b1.x, b1.y, b1.z, b1.w};
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
                 acc.a[0][0] = __builtin_amdgcn_mfma_f32_16x16x4f32(av0[j], bv0[j], acc.a[0][0], 0, 0, 0);
                 acc.a[0][1] = __builtin_amdgcn_mfma_f32_16x16x4f32(av0[j], bv1[j], acc.a[0][1], 0, 0, 0);
             }
-            if (r1c0) {
-#pragma unroll
-                for (int j = 0; j < 4; ++j) acc.a[1][0] = __builtin_amdgcn_mfma_f32_16x16x4f32(av1[j], bv0[j], acc.a[1][0], 0, 0, 0);
-            }
-            if (row1) {
-#pragma unroll
-                for (int j = 0; j < 4; ++j) acc.a[1][1] = __builtin_amdgcn_mfma_f32_16x16x4f32(av1[j], bv1[j], acc.a[1][1], 0, 0, 0);
-            }
+            if (r1c0) frag_mma(acc.a[1][0], a1, b0);
+            if (row1) frag_mma(acc.a[1][1], a1, b1);
         }
     }
     {
@@ -241,9 +257,8 @@ CCSD_DEV SplitFrag<SPLIT> split_frag(const float4& a, const float4& b) {
     for (int i = 0; i < 8; ++i) f.l[i] = (__bf16)r[i];
     return f;
 }
-typedef float f32x4_ __attribute__((ext_vector_type(4)));
 template <int SPLIT>
-CCSD_DEV f32x4_ split_mma(const SplitFrag<SPLIT>& a, const SplitFrag<SPLIT>& b, f32x4_ c) {      // (small terms first)
+CCSD_DEV f32x4 split_mma(const SplitFrag<SPLIT>& a, const SplitFrag<SPLIT>& b, f32x4 c) {      // (small terms first)
     if (SPLIT == 3) {
         c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a.m, b.m, c, 0, 0, 0);
         c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a.l, b.h, c, 0, 0, 0);
@@ -264,7 +279,6 @@ __global__ __launch_bounds__(256, 2) void k_gemm_h_full(const float* __restrict_
     __shared__ __align__(16) float Fs[2 * SLAB];
     const int b = blockIdx.x, tid = threadIdx.x, wave = wave_index(), lane = tid & 63, l15 = lane & 15, kq = lane >> 4;
     const float* Fb = rank2 + (size_t)b * E * K;
-    typedef float f32x4 __attribute__((ext_vector_type(4)));
     // thread -> (row r0 + 32 u, 4-float column group c4) of the 192 x 32 slab, u < 6
     const int r0 = tid >> 3, c4 = (tid & 7) * 4;
     float4 rg[6];
@@ -338,11 +352,7 @@ __global__ __launch_bounds__(256, 2) void k_gemm_h_full(const float* __restrict_
                 for (int i = 0; i < 6; ++i)
 #pragma unroll
                     for (int j = i; j < 6; ++j) {
-                        if (!(i == 0 && j == 1)) {                         // (given to the rectangle wave)
-                            const float av[4] = {f[i].x, f[i].y, f[i].z, f[i].w}, bv[4] = {f[j].x, f[j].y, f[j].z, f[j].w};
-#pragma unroll
-                            for (int q = 0; q < 4; ++q) acc[a] = __builtin_amdgcn_mfma_f32_16x16x4f32(av[q], bv[q], acc[a], 0, 0, 0);
-                        }
+                        if (!(i == 0 && j == 1)) frag_mma(acc[a], f[i], f[j]);      // (given to the rectangle wave)
                         ++a;
                     }
             } else {
@@ -355,17 +365,9 @@ __global__ __launch_bounds__(256, 2) void k_gemm_h_full(const float* __restrict_
 #pragma unroll
                 for (int i = 0; i < 3; ++i)
 #pragma unroll
-                    for (int j = 0; j < 6; ++j) {
-                        const float av[4] = {fa[i].x, fa[i].y, fa[i].z, fa[i].w}, bv[4] = {fb[j].x, fb[j].y, fb[j].z, fb[j].w};
-#pragma unroll
-                        for (int q = 0; q < 4; ++q) acc[a] = __builtin_amdgcn_mfma_f32_16x16x4f32(av[q], bv[q], acc[a], 0, 0, 0);
-                        ++a;
-                    }
+                    for (int j = 0; j < 6; ++j) { frag_mma(acc[a], fa[i], fb[j]); ++a; }
                 // the extra sub-tile: wave 2 -> (0, 1) = fa[0] x fa[1]; wave 3 -> (6, 7) = fb[0] x fb[1]
-                const float4 xa = wave == 2 ? fa[0] : fb[0], xb = wave == 2 ? fa[1] : fb[1];
-                const float av[4] = {xa.x, xa.y, xa.z, xa.w}, bv[4] = {xb.x, xb.y, xb.z, xb.w};
-#pragma unroll
-                for (int q = 0; q < 4; ++q) acc[18] = __builtin_amdgcn_mfma_f32_16x16x4f32(av[q], bv[q], acc[18], 0, 0, 0);
+                frag_mma(acc[18], wave == 2 ? fa[0] : fb[0], wave == 2 ? fa[1] : fb[1]);
             }
         }
         }
@@ -484,7 +486,7 @@ __global__ void k_sum_splits(const float* __restrict__ parts, float* __restrict_
 // transposed packed weights Wcat^T[col][Kp]) read back as ds_read_b128 permuted-k fragments; wave w owns rows
 // 16w..16w+15 and every 16-column tile, so no MFMA is spent on the 64-column padding of the general tile engine.
 // ---------------------------------------------------------------------------------------------
-// Fused Langevin-corrector work of the tiled path (h_L == 1, K a multiple of 4; ccsd_api.h: tiled_fuse_ok).  The projection kernel is
+// Fused Langevin-corrector work of the tiled path (h_L == 1, K a multiple of 4; ccsd_api.h: Route::tiled_fuse).  The projection kernel is
 // the one pass of a half-step that streams rank2 once, row by row, in 16-byte pieces = the flat Philox groups of the corrector's
 // draw (NoiseArgs::flat_r), so the corrector's element-wise work rides on it:
 //   mode 1 (norms pass):      zrow[row] = sum_k (z fl fr)^2 of the row  -- the noise norm (gen_noise_rank2 + torch.norm,
@@ -585,10 +587,9 @@ __global__ void k_p0_fuse_ew(const float* __restrict__ rank2, P0Fuse pf, int row
     }
 }
 #ifndef CCSD_EMU
-#ifndef CCSD_EMU
 // ---------------------------------------------------------------------------------------------
 // k_hp_full<EC, KC, MODE>: ONE pass over a complex's rank2 block per half-step on the tiled path (community_small geometry, one hodge
-// layer, wc <= 16: tiled_fuse_ok + the geometry): what k_gemm_p0<1, KC, MODE> and k_gemm_h_full<EC, KC> do in two --
+// layer, wc <= 16: Route::tiled_fuse + the geometry): what k_gemm_p0<1, KC, MODE> and k_gemm_h_full<EC, KC> do in two --
 //   * the Langevin corrector's element-wise work where the block streams through registers (P0Fuse, as in k_gemm_p0):
 //     MODE 1 the noise norm of the corrector's draw per row (-> pf.zrow), MODE 2 the corrector apply (corrected rank2 -> pf.f1,
 //     in place over the raw scores it consumes); everything below sees the corrected block;
@@ -610,7 +611,6 @@ __global__ __launch_bounds__(512, 2) void k_hp_full(const float* __restrict__ ra
     float* const Ws = sm + 2 * SLAB;              // [2][WSLAB]
     const int b = blockIdx.x, tid = threadIdx.x, wave = wave_index(), lane = tid & 63, l15 = lane & 15, kq = lane >> 4;
     const float* Fb = rank2 + (size_t)b * E * K;
-    typedef float f32x4 __attribute__((ext_vector_type(4)));
     // thread -> (row r0 + 64 u, 4-float column group c4) of the 192 x 32 slab, u < 3; threads 0..127 also one group of the W slab
     const int r0 = tid >> 3, c4 = (tid & 7) * 4;
     float c1 = 0.f, c2 = 0.f, zacc[3] = {0.f, 0.f, 0.f};
@@ -675,20 +675,10 @@ __global__ __launch_bounds__(512, 2) void k_hp_full(const float* __restrict__ ra
 #pragma unroll
                 for (int i = 0; i < 3; ++i)
 #pragma unroll
-                    for (int j = 0; j < 3; ++j) {
-                        const float av[4] = {fa[i].x, fa[i].y, fa[i].z, fa[i].w}, bv[4] = {fb[j].x, fb[j].y, fb[j].z, fb[j].w};
-#pragma unroll
-                        for (int q = 0; q < 4; ++q) acc[3 * i + j] = __builtin_amdgcn_mfma_f32_16x16x4f32(av[q], bv[q], acc[3 * i + j], 0, 0, 0);
-                    }
+                    for (int j = 0; j < 3; ++j) frag_mma(acc[3 * i + j], fa[i], fb[j]);
                 if (pA || pB) {
-                    const float wv[4] = {wq.x, wq.y, wq.z, wq.w};
 #pragma unroll
-                    for (int i = 0; i < 3; ++i) {
-                        const float4 x = pA ? fa[i] : fb[i];
-                        const float av[4] = {x.x, x.y, x.z, x.w};
-#pragma unroll
-                        for (int q = 0; q < 4; ++q) acc[9 + i] = __builtin_amdgcn_mfma_f32_16x16x4f32(av[q], wv[q], acc[9 + i], 0, 0, 0);
-                    }
+                    for (int i = 0; i < 3; ++i) frag_mma(acc[9 + i], pA ? fa[i] : fb[i], wq);
                 }
             } else {
                 float4 f[6];
@@ -700,13 +690,7 @@ __global__ __launch_bounds__(512, 2) void k_hp_full(const float* __restrict__ ra
 #pragma unroll
                     for (int i = 0; i < 3; ++i)
 #pragma unroll
-                        for (int j = i; j < 3; ++j) {
-                            const float4 &fi = f[3 * g + i], &fj = f[3 * g + j];
-                            const float av[4] = {fi.x, fi.y, fi.z, fi.w}, bv[4] = {fj.x, fj.y, fj.z, fj.w};
-#pragma unroll
-                            for (int q = 0; q < 4; ++q) acc[a] = __builtin_amdgcn_mfma_f32_16x16x4f32(av[q], bv[q], acc[a], 0, 0, 0);
-                            ++a;
-                        }
+                        for (int j = i; j < 3; ++j) { frag_mma(acc[a], f[3 * g + i], f[3 * g + j]); ++a; }
             }
         }
         if (s + 1 < NS) sts(s + 1, (s + 1) & 1);
@@ -716,8 +700,7 @@ __global__ __launch_bounds__(512, 2) void k_hp_full(const float* __restrict__ ra
         // a row's eight column groups sit in eight consecutive lanes: fixed butterfly, lane 0 of the group stores (as k_gemm_p0)
 #pragma unroll
         for (int u = 0; u < 3; ++u) {
-            float v = zacc[u];
-            v += __shfl_xor(v, 1, 64); v += __shfl_xor(v, 2, 64); v += __shfl_xor(v, 4, 64);
+            const float v = row8_sum(zacc[u]);
             const int row = r0 + 64 * u;
             if ((tid & 7) == 0 && row < E) pf.zrow[(size_t)b * E + row] = v;
         }
@@ -764,7 +747,6 @@ __global__ __launch_bounds__(512, 2) void k_hp_full(const float* __restrict__ ra
                 for (int j = i; j < 3; ++j) { store(d0 + 3 * g + i, d0 + 3 * g + j, acc[a]); ++a; }
     }
 }
-#endif
 
 template <int NT, int KC = 0, int MODE = 0>          // KC: K as a compile-time constant (0: the argument); Kp follows; MODE: P0Fuse::mode
 __global__ __launch_bounds__(256) void k_gemm_p0(const float* __restrict__ rank2, const float* __restrict__ WT, float* __restrict__ P,
@@ -772,19 +754,13 @@ __global__ __launch_bounds__(256) void k_gemm_p0(const float* __restrict__ rank2
     const int K = KC ? KC : K_, Kp = KC ? ((KC + 31) & ~31) : Kp_;
     __shared__ __align__(16) float As[T_BM * H_LD];
     __shared__ __align__(16) float Bs[16 * NT * H_LD];
-    typedef float f32x4 __attribute__((ext_vector_type(4)));
     const int tid = threadIdx.x, wave = wave_index(), lane = tid & 63, l15 = lane & 15, kq = lane >> 4;
     const int m0 = blockIdx.x * T_BM;
     const bool vec = (K & 3) == 0;
     const int r0 = tid >> 3, c4 = (tid & 7) * 4;           // (row, 4-float column group) of a 64 x 32 slab; rows r0, r0 + 32
     auto lda = [&](int row, int k) -> float4 {
-        const float* src = rank2 + (size_t)(row < rows ? row : rows - 1) * K;
         float4 v;
-        if (vec && k + 3 < K) v = *reinterpret_cast<const float4*>(src + k);
-        else {
-            v.x = k < K ? src[k] : 0.f; v.y = k + 1 < K ? src[k + 1] : 0.f;
-            v.z = k + 2 < K ? src[k + 2] : 0.f; v.w = k + 3 < K ? src[k + 3] : 0.f;
-        }
+        row_load4(v, rank2 + (size_t)(row < rows ? row : rows - 1) * K, k, K, vec);
         return v;
     };
     // fused corrector work (MODE != 0; K % 4 == 0): the thread's two rows of every slab are fixed -> (sample, edge) once
@@ -857,10 +833,7 @@ __global__ __launch_bounds__(256) void k_gemm_p0(const float* __restrict__ rank2
 #pragma unroll
             for (int c = 0; c < NT; ++c) {
                 const float4 bq = *reinterpret_cast<const float4*>(Bs + (16 * c + l15) * H_LD + 16 * t + 4 * kq);
-                acc[c] = __builtin_amdgcn_mfma_f32_16x16x4f32(a.x, bq.x, acc[c], 0, 0, 0);
-                acc[c] = __builtin_amdgcn_mfma_f32_16x16x4f32(a.y, bq.y, acc[c], 0, 0, 0);
-                acc[c] = __builtin_amdgcn_mfma_f32_16x16x4f32(a.z, bq.z, acc[c], 0, 0, 0);
-                acc[c] = __builtin_amdgcn_mfma_f32_16x16x4f32(a.w, bq.w, acc[c], 0, 0, 0);
+                frag_mma(acc[c], a, bq);
             }
         }
     };
@@ -876,9 +849,7 @@ __global__ __launch_bounds__(256) void k_gemm_p0(const float* __restrict__ rank2
         // the row's eight column groups sit in eight consecutive lanes: fixed butterfly, lane 0 of the group stores
 #pragma unroll
         for (int u = 0; u < 2; ++u) {
-            float v = zacc[u], w2 = nacc[u];
-            v += __shfl_xor(v, 1, 64); v += __shfl_xor(v, 2, 64); v += __shfl_xor(v, 4, 64);
-            if (MODE == 3) { w2 += __shfl_xor(w2, 1, 64); w2 += __shfl_xor(w2, 2, 64); w2 += __shfl_xor(w2, 4, 64); }
+            const float v = row8_sum(zacc[u]), w2 = MODE == 3 ? row8_sum(nacc[u]) : 0.f;
             const int row = m0 + r0 + 32 * u;
             if ((tid & 7) == 0 && row < rows) {
                 if (MODE == 1) pf.zrow[row] = v;
@@ -1070,7 +1041,6 @@ __global__ __launch_bounds__(256) void k_hf_score(const PlanD* __restrict__ plan
     __shared__ __align__(16) float As[T_BM * HLD];
     __shared__ __align__(16) float Bs[HBK * BLD];
     {
-        typedef float f32x4 __attribute__((ext_vector_type(4)));
         const int tid = threadIdx.x, wave = wave_index(), lane = tid & 63, l15 = lane & 15, kq = lane >> 4;
         const int wm = (wave >> 1) * 32, wn = (wave & 1) * 32;
         const bool vec = (K & 3) == 0;
@@ -1099,11 +1069,7 @@ __global__ __launch_bounds__(256) void k_hf_score(const PlanD* __restrict__ plan
                 const int k = k0 + bk + 16 * u, col = n0 + bc4;
                 const float* src = Fb + (unsigned)((k < E ? k : E - 1) * K);
                 float4 v;
-                if (vec && col + 3 < K) v = *reinterpret_cast<const float4*>(src + col);
-                else {
-                    v.x = col < K ? src[col] : 0.f; v.y = col + 1 < K ? src[col + 1] : 0.f;
-                    v.z = col + 2 < K ? src[col + 2] : 0.f; v.w = col + 3 < K ? src[col + 3] : 0.f;
-                }
+                row_load4(v, src, col, K, vec);
                 if (k >= E) v = make_float4(0.f, 0.f, 0.f, 0.f);
                 rb[u] = v;
             }
@@ -1168,7 +1134,6 @@ __global__ __launch_bounds__(256) void k_hf_score(const PlanD* __restrict__ plan
         // OUTSIDE the element loops -- no per-element mode branches, uniform base pointers + one 32-bit element offset per lane,
         // whole 4-row groups without row tests.  Same arithmetic, in the same order, as the general form below (fnet_element<true>):
         // the two agree bit for bit.  (PMC, community_small_CC: the general form issued 67 vector instructions per element.)
-        typedef float f32x4 __attribute__((ext_vector_type(4)));
         const int wave = wave_index(), lane = threadIdx.x & 63;
         const int wm = (wave >> 1) * 32, wn = (wave & 1) * 32, l15 = lane & 15, kq = lane >> 4;
         const float fa = p.f_alpha, fgam = p.f_gamma, fbe = p.f_betas[1];

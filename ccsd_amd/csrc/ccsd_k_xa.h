@@ -46,8 +46,7 @@ struct XaArgs {
     const unsigned char* hpairs;          // (e, e2), e <= e2: unordered pairs of the dense hodge layer
     long long* dbg;
     CorrFuse cf;
-    int prio_mode;                        // 0: priority = dispatch rank (default); 1: none; 2-4: diagnostic variants (CCSD_XA_PRIO)
-    int stagger_mask, stagger_sleep;      // diagnostic (CCSD_XA_STAGGER): workgroups with (blockIdx.x & mask) != 0 start sleep x 64 cycles late
+    int prio_mode;                        // 0: priority rotates with the phase (default); 1: none; 2: static, = dispatch rank (CCSD_XA_PRIO)
     // general hodge stack (h_L > 2 with a non-affine mlp_value; XA_GEN only, launch_xa drives it): the projections of the layers >= 1 come
     // materialised, Pd[l - 1] = R_l Wcat_l as [B * E][wc_l]; a launch with hdump_layer = s > 0 stops behind the dense hodge adjacency
     // H^s (the output of layer s - 1), writes it to hdump [B][hdump_stride] as [cout][E][E] and returns
@@ -216,7 +215,7 @@ __global__ __launch_bounds__((VAR == XA_PLAIN9 || VAR == XA_BAKED9 || !XA_4WAVES
     constexpr int SEM = xa_sem(VAR);
     constexpr bool HB = SEM == XA_HB || SEM == XA_GEN, GMH = SEM == XA_GMH || SEM == XA_GEN, CONVMLP = SEM == XA_GEN;
     // XA_PLAIN9: a third of k_xa's vector instructions are 32-bit integer index arithmetic on strides the plan supplies at run
-    // time (PMC, profiles/r03_c_phase_mix.txt); for the headline geometry they are compile-time constants (xa_variant() checks them)
+    // time (PMC, profiles/r03_c_phase_mix.txt); for the headline geometry they are compile-time constants (resolve_route checks them: Route::xa_variant)
     constexpr bool NFIX = VAR == XA_PLAIN9 || VAR == XA_BAKED9;          // everything fixed incl. F and the thread count
     constexpr int GN = xa_geo_n(VAR);                // node count compiled in (XA_PLAIN9 / XA_PLAIN20 / XA_PLAIN38), else 0
     const int N = GN ? GN : p.N, F = NFIX ? 4 : p.F, NN = N * N, E = GN ? GN * (GN - 1) / 2 : p.E, ldn = GN ? xa_geo_ld(GN) : p.ldn;
@@ -260,11 +259,6 @@ __global__ __launch_bounds__((VAR == XA_PLAIN9 || VAR == XA_BAKED9 || !XA_4WAVES
     };
     int prio_k = 1;
     prio_phase(0);
-#ifndef CCSD_EMU
-    if (xa.stagger_sleep && (blockIdx.x & xa.stagger_mask)) {
-        for (int i = 0; i < xa.stagger_sleep; i += 100) __builtin_amdgcn_s_sleep(100);
-    }
-#endif
     for (int i = tid; i < N; i += nth) s_flags[i] = xa.flags[(size_t)b * N + i];
     float nx_net = 0.f, nx_z = 0.f, na_net = 0.f, na_z = 0.f;
 
@@ -1172,7 +1166,7 @@ __global__ __launch_bounds__((VAR == XA_PLAIN9 || VAR == XA_BAKED9 || !XA_4WAVES
                 // symmetric input channels, masked diagonal: the E unordered pairs suffice (see the edge MLP above)
                 auto epf = [&](int e, int f, float v) { (void)f; const int i = edge_i(e), j = edge_j(e); f0[i * N + j] = v; f0[j * N + i] = v; };
                 // (the two widest shapes set the register demand of this whole region: the small-graph XA_PLAIN / XA_GMH variants leave them
-                // to k_xa<false, XA_GEN> -- xa_variant() routes such plans there -- and run without them)
+                // to k_xa<false, XA_GEN> -- resolve_route sends such plans there (Route::xa_variant) -- and run without them)
                 constexpr bool WIDE = GCH || SEM == XA_GEN || SEM == XA_HB;
                 if (m.chain == 3) mlp_chain<2, 4, 1>(m, wp, s_chan, NN, s_chan, m.in, E, pair_off, epf);
                 else if (m.chain == 4) mlp_chain<3, 5, 1>(m, wp, s_chan, NN, s_chan, m.in, E, pair_off, epf);

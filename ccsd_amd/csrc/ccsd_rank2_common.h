@@ -11,13 +11,13 @@ CCSD_DEV float cell_on(unsigned long long off, const unsigned long long* __restr
     return (cells[k] & off) ? 0.f : 1.f;
 }
 
-// The masks flags_left[e] * flags_right[k] of the four consecutive elements of flat group (e, k) .. of a sample's (E, K) block from
-// the byte tables of k_masktab (rows mfr + b Kp, mfl + b Ep): with K a multiple of 4 the group lies inside one row and k is a
-// multiple of 4 -- one 32-bit word of mfr and one byte of mfl; otherwise byte by byte across the row end.
 // row stride of the Hodge Laplacian buffers H, H^2, ... in the workspace (k_gemm_h / k_gemm_h_full / k_gemm_pow write, k_hf_score reads):
 // E rounded up to whole 16-byte groups, so that k_hf_score stages its rows of H with 16-byte loads (E = 190 -> 192; the pad columns
 // are never written and never used: the loader masks them)
 static inline __host__ __device__ int h_ld(int E) { return (E + 3) & ~3; }
+// The masks flags_left[e] * flags_right[k] of the four consecutive elements of flat group (e, k) .. of a sample's (E, K) block from
+// the byte tables of k_masktab (rows mfr + b Kp, mfl + b Ep): with K a multiple of 4 the group lies inside one row and k is a
+// multiple of 4 -- one 32-bit word of mfr and one byte of mfl; otherwise byte by byte across the row end.
 struct MaskTab { const unsigned char* mfr; const unsigned char* mfl; int Kp, Ep; };
 CCSD_DEV void group_masks(const MaskTab& mt, int b, int E, int K, int e, int k, float* m) {
     const unsigned char* fr = mt.mfr + (size_t)b * mt.Kp;
@@ -116,7 +116,7 @@ CCSD_DEV float fnet_element(const PlanD& p, const float* __restrict__ w, float f
 // ---------------------------------------------------------------------------------------------
 // k_r2: the whole rank-2 side of one joint score evaluation for ONE complex per workgroup, with the
 // complex's rank2 block resident in LDS (E x K fp32 = 67 KB for qm9_CC): one HBM read and one HBM
-// write of rank2 per half-step.  Used when E <= 64 and the block fits (ccsd_plan::fused_r2).
+// write of rank2 per half-step.  Used when E <= 64 and the block fits (Route::r2_family).
 //   phase 0  load F -> LDS (row stride ldk == 2 mod 32: conflict-free MFMA fragment reads), cell masks,
 //            adjacency powers' upper triangle (adj_to_hodgedual inputs)
 //   phase 1  MFMA tiles over the full K:  H = F F^T (upper-triangle tiles, mirrored),

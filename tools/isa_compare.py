@@ -8,7 +8,8 @@ unit whose assembly in DIR is newer than the tree's sources is not compiled agai
   identical     the function text, its .amdhsa_kernel descriptor and the resource comments behind it are byte-identical
   same opcodes  equal line count and opcode multiset, and unchanged descriptor / register / scratch / LDS / occupancy lines
   different     anything else (also: present in one tree only)
-followed by the resource lines of the NEW tree's symbol.  It compares text; it knows nothing about particular instructions.
+followed by the resource lines of the NEW tree's symbol and, where one of them moved, `[old -> new]` per moved figure.  It compares text;
+it knows nothing about particular instructions.
 Exit status 1 when any symbol is `different`.
 """
 import argparse
@@ -121,9 +122,10 @@ def main():
             totals[verdict.split(" (")[0]] += 1
             if re.search(a.pattern, name):
                 s = (n or o)["stats"]
+                moved = ", ".join(f"{k} {o['stats'].get(k)} -> {s.get(k)}" for k in STATS if o and n and o["stats"].get(k) != s.get(k))
                 print(f"{u:9s} {verdict:14s} lines {len((n or o)['body']):6d} vgpr {s.get('NumVgprs', -1):3d} agpr {s.get('NumAgprs', -1):3d} "
                       f"sgpr {s.get('TotalNumSgprs', -1):3d} scratch {s.get('ScratchSize', -1):4d} lds {s.get('LDSByteSize', -1):6d} "
-                      f"occ {s.get('Occupancy', -1)} bytes {s.get('codeLenInByte', -1):6d}  {name}")
+                      f"occ {s.get('Occupancy', -1)} bytes {s.get('codeLenInByte', -1):6d}  {name}" + (f"  [{moved}]" if moved else ""))
         same = old_rest == new_rest
         totals["identical" if same else "different"] += 1
         print(f"{u:9s} {'identical' if same else 'different':14s} <everything outside the functions: metadata, kernel arguments, variables>")
