@@ -47,7 +47,8 @@ static inline int fnet_width(const PlanD& p) {
 //   CCSD_XA_PRIO         xa_prio               k_xa issue priority: 0 rotating (default), 1 none, 2 static.    nobody
 //                                              Lost on every workload (xiv); kept because k_xa<false, XA_HB> without the
 //                                              mode test needs 104 bytes of scratch instead of 100 (profiles/README.md r08)
-//   CCSD_LARGE_GRAPH=1   lg_force              tiled graph-network route for any eligible plan  (PlanBuilder)  tests (emu + gpu)
+//   CCSD_LARGE_GRAPH=1|2 lg_force              tiled graph-network route for any eligible graph-only plan (1), (PlanBuilder)  tests (emu + gpu)
+//                                              for eligible combinatorial-complex plans too (2: ScoreNetworkA_CC, one hodge layer)
 //   CCSD_XA_PASS=<n>     xa_pass               first k_xa LDS budget candidate tried            (PlanBuilder)  tests (emu + gpu)
 //   CCSD_XA_GCH          xa_gch                channel stack in the HBM workspace first         (PlanBuilder)  tests (emu + gpu)
 //   CCSD_NO_MLP_WT       no_mlp_wt             no transposed copies of the non-chained MLPs     (PlanBuilder)  tests (gpu)
@@ -68,7 +69,7 @@ static Knobs read_knobs() {
     if (const char* v = getenv("CCSD_SPLIT_BF16")) k.split_bf16 = atoi(v) == 3 ? 3 : 0;
     if (const char* v = getenv("CCSD_XA_THREADS")) { const int t = atoi(v); if (t >= 64 && t <= 1024 && t % 64 == 0) k.xa_threads = t; }
     if (const char* v = getenv("CCSD_XA_PRIO")) k.xa_prio = atoi(v);
-    if (const char* v = getenv("CCSD_LARGE_GRAPH")) k.lg_force = atoi(v) == 1;
+    if (const char* v = getenv("CCSD_LARGE_GRAPH")) { const int f = atoi(v); k.lg_force = (f == 1 || f == 2) ? f : 0; }
     if (const char* v = getenv("CCSD_XA_PASS")) k.xa_pass = atoi(v);
     k.xa_gch = on("CCSD_XA_GCH"); k.no_mlp_wt = on("CCSD_NO_MLP_WT"); k.verbose = on("CCSD_VERBOSE");
     k.dump_plan = getenv("CCSD_DUMP_PLAN"); k.dump_plan_name = getenv("CCSD_DUMP_PLAN_NAME");
@@ -82,8 +83,8 @@ enum { R2_NONE = 0, R2_FUSED = 1, R2_EW1 = 2, R2_TILED = 3 };       // rank-2 fa
 enum { LOOP_PRED_ONLY = 0, LOOP_LANGEVIN = 1, LOOP_LANGEVIN_FUSED = 2, LOOP_S4 = 3, LOOP_LANGEVIN_MULTI = 4 };
 struct Route {
     // graph-network side
-    int lg = 0;                     // tiled route (ccsd_k_lg.h) instead of k_xa: graph-only plans k_xa cannot place (N > 64, no LDS layout), or
-                                    // any eligible plan under CCSD_LARGE_GRAPH=1; launch_xa hands such plans to launch_lg
+    int lg = 0;                     // tiled route (ccsd_k_lg.h) instead of k_xa: eligible plans (ccsd_lg_ineligible) k_xa cannot place (N > 64, no LDS
+                                    // layout), or any eligible plan under CCSD_LARGE_GRAPH (1: graph-only plans, 2: all); launch_xa hands such plans to launch_lg
     int xa_variant = 0;             // XA_* (what CCSD_QUERY_XA_VARIANT reports)
     const XaEntry* xa = nullptr;    // its instance, and the run-time-geometry twin that serves launches of a fixed-256 instance with
     const XaEntry* xa_twin = nullptr;   // another (diagnostic) thread count
@@ -256,9 +257,10 @@ static int resolve_route(ccsd_plan* pl) {
     }
     // tiled rank-2 path (k_gemm_h / k_gemm_p0 / k_hf_score: community_small_CC) with ONE hodge layer: the corrector's rank2 work rides on
     // the layer-0 projection pass (P0Fuse) -- flat-keyed corrector draws, K a multiple of 4 (a Philox group = one 16-byte piece of a row)
-    r.tiled_fuse = r.r2_family == R2_TILED && p.h_L == 1 && (K & 3) == 0 && !s4 && langevin;
+    // (plans on the tiled graph-network route take none of the three fusions below: launch_lg has no corrector prologue)
+    r.tiled_fuse = !r.lg && r.r2_family == R2_TILED && p.h_L == 1 && (K & 3) == 0 && !s4 && langevin;
     // k_ew1 plans with ONE hodge layer: one read of rank2 per norms pass, one read + one write per predictor pass (P0Fuse modes 3 / 4)
-    r.ew1_fuse = ew1 && p.h_L == 1 && (K & 3) == 0 && langevin;
+    r.ew1_fuse = !r.lg && ew1 && p.h_L == 1 && (K & 3) == 0 && langevin;
     // community_small geometry: one workgroup per complex, F streamed once (k_gemm_h_full; bit-identical), and ONE fused pass per
     // half-step (k_hp_full) instead of k_gemm_p0<., ., 1 / 2> + k_gemm_h_full.  In the norms pass (mode 1, whose only extra is the
     // noise norm) the fused pass is slower -- 370 us against 129 + 213, the eight waves of the one workgroup a CU holds run in
@@ -268,7 +270,7 @@ static int resolve_route(ccsd_plan* pl) {
 
     // ---- ccsd_sampler_run.  The Langevin apply fuses into the predictor launches of k_r2 plans, of k_ew1 plans whose hodge
     // projections do not depend on the adjacency (at most one hodge layer) and of tiled plans with one hodge layer
-    const bool fused_apply = (fused || (ew1 && p.h_L <= 1) || r.tiled_fuse) && !k.no_fused_apply;
+    const bool fused_apply = !r.lg && (fused || (ew1 && p.h_L <= 1) || r.tiled_fuse) && !k.no_fused_apply;
     r.loop = s4 ? LOOP_S4 : !langevin ? LOOP_PRED_ONLY : c.n_corr_steps != 1 ? LOOP_LANGEVIN_MULTI : fused_apply ? LOOP_LANGEVIN_FUSED : LOOP_LANGEVIN;
     // merged k_r2 launches (predictor of step i + rank-2 side of the norms pass of step i + 1): the row-strip instantiation of the
     // kernel (E = 33..36, affine ScoreNetworkF, linear mlp_value), pair-wise block load (K even, E K a multiple of 4)
@@ -645,7 +647,7 @@ static int check_state(const ccsd_plan* pl, const ccsd_state_t* s, const char* w
 }
 
 static int launch_flagbits(const ccsd_plan* pl, int B, const float* flags, Workspace& w, void* stream) {
-    if (pl->rt.lg) return CCSD_OK;       // (64-bit node masks feed only the rank-2 tables; the tiled route is graph-only and goes past 64 nodes)
+    if (pl->rt.lg && !pl->h.is_cc) return CCSD_OK;       // (64-bit node masks feed only the rank-2 tables; graph-only plans of the tiled route go past 64 nodes)
     CCSD_LAUNCH(k_flagbits, dim3(grid_for(B, 256)), dim3(CCSD_NTHREADS), 0, stream, flags, w.offbits, B, pl->h.N);
     LAUNCH_CHECK();
     if (pl->h.is_cc) {      // (consumers: k_ew1, k_langevin_apply, k_noise_norm; the fused rank-2 kernel builds its own masks in LDS)
@@ -797,8 +799,9 @@ static int launch_p(const ccsd_plan* pl, int B, const float* adj, const float* r
 static int launch_lg(const ccsd_plan* pl, int B, XaArgs& xa, NoiseArgs& na, Workspace& w, void* stream);
 static int launch_xa(const ccsd_plan* pl, int B, XaArgs& xa, NoiseArgs& na, const Pass& ps, Workspace& w, void* stream, bool set_b = false) {
     const Route& rt = pl->rt;
+    xa.P0 = set_b ? w.P0b : w.P0;
     if (rt.lg) return launch_lg(pl, B, xa, na, w, stream);
-    xa.P0 = set_b ? w.P0b : w.P0; xa.P1 = set_b ? w.P1b : w.P1; xa.U1 = set_b ? w.U1b : w.U1; xa.chan_ws = w.chan;
+    xa.P1 = set_b ? w.P1b : w.P1; xa.U1 = set_b ? w.U1b : w.U1; xa.chan_ws = w.chan;
     xa.p1_raw = ps.p1_raw; xa.dbg = pl->dbg ? pl->dbg + 32 : nullptr;
     int xa_threads;
     const XaEntry* inst = xa_launch(rt, B, &xa_threads);
@@ -844,7 +847,8 @@ static int launch_xa(const ccsd_plan* pl, int B, XaArgs& xa, NoiseArgs& na, cons
 }
 // Tiled graph-network route (ccsd_k_lg.h): ScoreNetworkX on (xX, adjX) and ScoreNetworkA on (xA, adjA) as a sequence of launches over
 // the workspace (LgWs fields of Workspace), then the epilogues of k_xa's contract (mode, coefficients, mean pointers, norm2[b][4]).
-// Graph-only plans never fuse the corrector apply into this pass (resolve_route), so a CorrFuse here is an error.
+// Combinatorial-complex plans (ScoreNetworkA_CC, one hodge layer): xa.P0 holds the layer-0 hodge projections launch_p / k_r2 left.
+// Plans on this route never fuse the corrector apply into this pass (resolve_route), so a CorrFuse here is an error.
 static int launch_lg(const ccsd_plan* pl, int B, XaArgs& xa, NoiseArgs& na, Workspace& w, void* stream) {
     const PlanD& p = pl->h;
     if (xa.cf.on) return set_err(CCSD_ERR_RUNTIME, "tiled graph-network route: no fused corrector apply");
@@ -874,6 +878,12 @@ static int launch_lg(const ccsd_plan* pl, int B, XaArgs& xa, NoiseArgs& na, Work
         const long long ss = (long long)p.a_fdim * NN;
         for (int c = 0; c < p.a_cinit; ++c)
             CCSD_LAUNCH(k_lg_pow, dim3(grid_for(NN, 256), B), blk, 0, stream, xa.adjA, w.lg_S, ss, N, c);
+        if (p.h_L == 1) {
+            // hodge branch of ScoreNetworkA_CC, one layer: per-edge arithmetic on the powers and P_0, scattered behind the graph channels
+            if (!xa.P0) return set_err(CCSD_ERR_RUNTIME, "tiled graph-network route: no hodge projections");
+            CCSD_LAUNCH(k_lg_hodge1, dim3(grid_for(p.E + N, 256), B), blk, 0, stream, p.hl[0], 1.0f / (float)sqrt((double)p.K), (const float*)pl->w,
+                        (const unsigned char*)pl->edges, xa.P0, w.lg_S, ss, p.a_nch_graph, N, p.E, xa.flags);
+        }
         for (int l = 0; l < p.a_L; ++l) {
             const AttnLayerD& L = p.al[l];
             const float* xin = l ? w.lg_x[(l - 1) & 1] : xa.xA;
@@ -1085,7 +1095,7 @@ static int draws_to_state(ccsd_plan* pl, int32_t B, const float* flags, const cc
         pl->init_off_cap = (size_t)B;
     }
     unsigned long long* offbits = pl->init_off;
-    if (!pl->rt.lg) CCSD_LAUNCH(k_flagbits, dim3(grid_for(B, 256)), dim3(CCSD_NTHREADS), 0, stream, flags, offbits, B, p.N);   // (graph-only on the tiled route: no rank-2 draws read it)
+    if (!pl->rt.lg || p.is_cc) CCSD_LAUNCH(k_flagbits, dim3(grid_for(B, 256)), dim3(CCSD_NTHREADS), 0, stream, flags, offbits, B, p.N);   // (graph-only plans of the tiled route: no rank-2 draws read it)
     NoiseArgs na = make_noise(raw, seed, sample_offset, base, flat_r);
     const long long total = (long long)B * (p.N * p.F + p.N * p.N) +
                             (p.is_cc ? (flat_r ? (long long)B * (((long long)p.E * p.K + 3) / 4) : (long long)B * ((p.E + 3) / 4) * p.K) : 0);

@@ -1,12 +1,15 @@
-// ccsd_k_lg.h -- the tiled graph-network path (k_lg_*): ScoreNetworkX + ScoreNetworkA for graph-only plans whose per-graph working
-// set does not fit one CU's LDS (N > 64, or k_xa's layout fails; CCSD_LARGE_GRAPH=1 forces it for any eligible plan).
+// ccsd_k_lg.h -- the tiled graph-network path (k_lg_*): ScoreNetworkX + ScoreNetworkA for plans whose per-graph working set does not
+// fit one CU's LDS (graph-only plans with N > 64, or k_xa's layout fails; CCSD_LARGE_GRAPH=1 forces it for any eligible graph-only
+// plan), and ScoreNetworkA_CC with ONE hodge layer for combinatorial complexes (N <= 64) without a k_xa layout (or under
+// CCSD_LARGE_GRAPH=2, which forces every eligible plan).
 // Part of the kernel source of libccsd_hip.so (see ccsd_kernels.h for the map).
 //
 // State lives in the HBM workspace (carve_ws, LgWs in ccsd_api.h) and every phase is a launch of its own that tiles each graph over
 // many workgroups.  The decomposition of one forward (launch_lg):
 //   ScoreNetworkX   k_lg_dis (D^-1/2 of adjX) ; per GCN layer: k_lg_xw (Y = D^-1/2 X W), k_lg_gcn (tanh(D^-1/2 A' Y + b) into the
 //                   concatenation) ; k_lg_nmlp (final MLP per node, mask_x)
-//   ScoreNetworkA   k_lg_pow (channel stack [A, A^2, ...]) ; per AttentionLayer: k_lg_dis, k_lg_xw (Q | K | V columns side by side),
+//   ScoreNetworkA   k_lg_pow (channel stack [A, A^2, ...]) ; ScoreNetworkA_CC: k_lg_hodge1 (the hodge channels, behind the graph
+//                   channels of the stack) ; per AttentionLayer: k_lg_dis, k_lg_xw (Q | K | V columns side by side),
 //                   k_lg_gcn, k_lg_nmlp (multi_channel, mask_x, tanh), k_lg_att (head-mean tanh(Q K^T / sqrt(fout)), symmetrised),
 //                   k_lg_edge (edge MLP on [att_c | adj_c] per entry, MFMA: mlp_chain_tile), k_lg_sym (out + out^T, mask_adjs) ;
 //                   k_lg_fin (final MLP per entry, MFMA: mlp_chain_tile, + the adjacency epilogue, per-tile norm partials)
@@ -37,6 +40,9 @@ struct LgGather {
 
 __global__ void k_lg_put(const float* __restrict__ src, int F, float* __restrict__ dst, int ldd, int rows);
 __global__ void k_lg_pow(const float* __restrict__ adj, float* __restrict__ S, long long sstride, int N, int c);
+__global__ void k_lg_hodge1(HodgeLayerD h, float rks, const float* __restrict__ w, const unsigned char* __restrict__ edges,
+                            const float* __restrict__ P0, float* __restrict__ S, long long sstride, int ch0, int N, int E,
+                            const float* __restrict__ flags);
 __global__ void k_lg_dis(const float* __restrict__ S, long long sstride, int ci0, int cin, int N, float* __restrict__ dis);
 __global__ void k_lg_xw(const float* __restrict__ X, long long xbs, int ldx, int fin, const float* __restrict__ W, int wcs, int ldy,
                         int cin, int N, const float* __restrict__ dis, float* __restrict__ Y);
@@ -364,6 +370,60 @@ __global__ __launch_bounds__(CCSD_LG_TB) void k_lg_epi(const float* __restrict__
         float* o = xa.norm2 + (size_t)b * 4;
         if (xa.do_x) { o[0] = v[0]; o[2] = v[2]; }
         if (xa.do_a) { o[1] = v[1]; o[3] = v[3]; }
+    }
+}
+// The hodge branch of ScoreNetworkA_CC with ONE HodgeAdjAttentionLayer (ScoreNetwork_A_CC.py:295-316; the oracle's score_network_a_cc),
+// k_xa's h_L == 1 branch with the same expressions.  adj_to_hodgedual makes the hodge adjacency of channel c diagonal with the upper
+// triangle of the adjacency power c on it (a_c[e] = S[c][i][j], e = (i, j), i < j), DenseHCNConv on a diagonal matrix is a row scaling
+// of the layer-0 projection P_0 = F Wcat_0 ([B][E][wc], left by the rank-2 side), and hodgedual_to_adj reads only the diagonal of the
+// layer's output: everything is arithmetic per edge.  Written at (i, j) and (j, i) of the stack: rows ch0 .. ch0 + cin the hodge
+// adjacency a_c itself, the next cout rows 2 tanh(fl^2 mlp_attention(head-mean logits)).  The work items behind the E edges are the N
+// diagonal entries of those rows: zero (nothing is scattered there, and the workspace is not cleared).
+// grid: (grid-stride over E + N, B)
+__global__ __launch_bounds__(CCSD_LG_TB) void k_lg_hodge1(HodgeLayerD h, float rks, const float* __restrict__ w, const unsigned char* __restrict__ edges,
+                                                         const float* __restrict__ P0, float* __restrict__ S, long long sstride, int ch0, int N,
+                                                         int E, const float* __restrict__ flags) {
+    __shared__ float s_hw[CCSD_MAXLIN * CCSD_HWBLK];                  // zero-padded mlp_attention weight blocks
+    __shared__ float s_q[CCSD_LG_TB][2 * CCSD_LG_HAD + 1];            // the calling thread's Q | K row of one channel
+    const int b = blockIdx.y, NN = N * N, qw = 2 * h.adim;
+    stage_mlp_blocks(h.matt, w, s_hw, (int)threadIdx.x, (int)blockDim.x);
+    __syncthreads();
+    float* Sb = S + (size_t)b * sstride;
+    float* Hb = Sb + (size_t)ch0 * NN;
+    const float* fl = flags + (size_t)b * N;
+    float* q = &s_q[threadIdx.x][0];
+    for (int t = blockIdx.x * blockDim.x + threadIdx.x; t < E + N; t += gridDim.x * blockDim.x) {
+        if (t >= E) {
+            const int i = t - E;
+            for (int c = 0; c < h.cin + h.cout; ++c) Hb[(size_t)c * NN + (size_t)i * N + i] = 0.f;
+            continue;
+        }
+        const int i = edges[2 * t], j = edges[2 * t + 1];
+        const size_t ij = (size_t)i * N + j, ji = (size_t)j * N + i;
+        const float* pr = P0 + ((size_t)b * E + t) * h.wc;
+        float in[CCSD_SMALLW], out[CCSD_SMALLW];
+#pragma unroll
+        for (int c = 0; c < CCSD_SMALLW; ++c) {
+            float sacc = 0.f;
+            if (c < h.cin) {
+                const float a = Sb[(size_t)c * NN + ij];
+                const float g = 1.0f / sqrtf(fmaxf(a, 1.f));
+                for (int d = 0; d < qw; ++d) q[d] = fmaf(g * a * g, pr[c * qw + d], w[h.bcat + c * qw + d]);
+                sacc = attn_logits(q, q + h.adim, h.nchunk, h.dsplit, rks) * (1.0f / (float)h.nchunk);
+                Hb[(size_t)c * NN + ij] = a;
+                Hb[(size_t)c * NN + ji] = a;
+            }
+            in[c] = sacc;
+        }
+        small_mlp_lds<CCSD_SMALLW>(s_hw, h.matt.n, in, out);     // mlp_attention -> mask -> tanh -> + transpose
+        const float fh = fl[i] * fl[j];
+#pragma unroll
+        for (int o = 0; o < CCSD_SMALLW; ++o)
+            if (o < h.cout) {
+                const float tv = tanh_f(out[o] * fh * fh);
+                Hb[(size_t)(h.cin + o) * NN + ij] = tv + tv;
+                Hb[(size_t)(h.cin + o) * NN + ji] = tv + tv;
+            }
     }
 }
 #undef LG_PT

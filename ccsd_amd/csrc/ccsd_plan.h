@@ -17,6 +17,7 @@
 #define CCSD_FWMAX 32     // ... in the tiled k_hf_score path
 #define CCSD_XA_MAXN 64   // k_xa: one graph per workgroup, its working set in one CU's LDS (node masks: one 64-bit word per graph)
 #define CCSD_LG_MAXN 512  // tiled graph-network route (ccsd_k_lg.h): ceiling on N (a graph's channel stack, fdim N^2 floats, is indexed in 32 bits)
+#define CCSD_LG_HAD 16    // ... and on the attention dimension of its one-layer hodge branch (k_lg_hodge1: a Q | K row per thread in LDS)
 
 struct MlpD {
     int n, in, hid, out;
@@ -175,7 +176,7 @@ struct PlanBuilder {
     std::string err;
     int status = CCSD_OK;
     // in: the plan-shaping switches, read from the environment once by ccsd_plan_create (read_knobs, ccsd_api.h)
-    int lg_force = 0;   // CCSD_LARGE_GRAPH=1: the tiled route for any eligible plan
+    int lg_force = 0;   // CCSD_LARGE_GRAPH: the tiled route for any eligible graph-only plan (1), for eligible combinatorial complexes too (2)
     int no_mlp_wt = 0;  // CCSD_NO_MLP_WT
     int xa_pass = -1;   // CCSD_XA_PASS: first k_xa LDS budget candidate tried (-1: by batch_hint)
     int xa_gch = 0;     // CCSD_XA_GCH: the channel stack in the HBM workspace first
@@ -277,9 +278,11 @@ static inline int round_ld(int rows) {  // node-row stride of the feature-major 
     return r;
 }
 
-// Why the tiled graph-network route (ccsd_k_lg.h) cannot serve a plan whose networks `p` holds (nullptr: it can).  It covers graph-only
-// plans with the plain ScoreNetworkX and a GCN-conv ScoreNetworkA whose edge MLPs are the 16-wide MFMA chains and whose final MLP is a
-// chained shape (fdim <= 64); ScoreNetworkX_GMH, conv = "MLP" and the combinatorial-complex networks stay with k_xa (N <= 64).
+// Why the tiled graph-network route (ccsd_k_lg.h) cannot serve a plan whose networks `p` holds (nullptr: it can).  It covers plans
+// with the plain ScoreNetworkX and a GCN-conv ScoreNetworkA whose edge MLPs are the 16-wide MFMA chains and whose final MLP is a
+// chained shape (fdim <= 64): graph-only ones, and combinatorial complexes (N <= 64) with ScoreNetworkA_CC and ONE
+// HodgeAdjAttentionLayer, whose hodge adjacency is diagonal (k_lg_hodge1).  ScoreNetworkX_GMH, conv = "MLP", ScoreNetworkA_Base_CC and
+// hodge stacks of two or more layers (the dense E x E layer) stay with k_xa.
 // dynamic LDS of the route's per-node MLP kernel k_lg_nmlp for one MLP: 16 rows of its input and of two activations (bytes)
 static inline size_t lg_nmlp_lds_of(const MlpD& m) {
     const int wmax = m.hid > m.out ? m.hid : m.out;
@@ -291,7 +294,10 @@ static inline size_t lg_nmlp_lds(const PlanD& p) {
     return v;
 }
 static inline const char* ccsd_lg_ineligible(const ccsd_config_t* c, const PlanD* p) {
-    if (c->is_cc || p->a_is_cc) return "combinatorial-complex plans";
+    if (p->a_is_cc == 2) return "ScoreNetworkA_Base_CC (no HodgeBaselineLayer on the route)";
+    if (p->h_L > 1) return "hodge stacks of two or more layers (the dense E x E hodge layer)";
+    if (c->is_cc && (p->a_is_cc != 1 || p->h_L != 1)) return "combinatorial-complex plans without ScoreNetworkA_CC";
+    if (p->h_L == 1 && p->hl[0].adim > CCSD_LG_HAD) return "hodge attention dimensions above 16";
     if (p->x_gmh) return "ScoreNetworkX_GMH";
     for (int l = 0; l < p->a_L; ++l) {
         const AttnLayerD& a = p->al[l];
@@ -497,7 +503,8 @@ static inline size_t ccsd_build_plan(const ccsd_config_t* c, PlanD* p, PlanBuild
         p->chan_rows = p->a_fdim;
         return nweights;            // (no k_xa layout: its LDS fields stay zero)
     }
-    if (pb.lg_force && !lg_reason) pb.lg = 1;
+    // (1 leaves combinatorial complexes on k_xa, as before the route served any of them: tests/golden/route_plans.json pins those plans)
+    if (pb.lg_force && !lg_reason && (!c->is_cc || pb.lg_force >= 2)) pb.lg = 1;
 
     // ---- k_xa LDS carve-up
     const int NN = N * N;
@@ -663,7 +670,7 @@ static inline size_t ccsd_build_plan(const ccsd_config_t* c, PlanD* p, PlanBuild
         fprintf(stderr, "[ccsd] k_xa LDS %d B (cg=%d pch=%d/%d pchp=%d/%d stage=%d floats, channel stack in %s)\n", best_total * 4, p->cg, p->pch, p->ldp, p->pchp, p->ldpp, p->wst_floats, p->chan_global ? "HBM" : "LDS");
     if (best_total < 0 || (size_t)best_total * 4 > 160 * 1024) {
         if (!lg_reason) pb.lg = 1;         // no k_xa layout: the tiled route serves the plan
-        else pb.fail(CCSD_ERR_UNSUPPORTED, "graph-network working set exceeds the 160 KB LDS of a CU");
+        else pb.fail(CCSD_ERR_UNSUPPORTED, std::string("graph-network working set exceeds the 160 KB LDS of a CU, and the tiled graph-network route does not serve ") + lg_reason);
     }
     return nweights;
 }

@@ -170,7 +170,9 @@ enum {
                                      in one launch (one block load per PC step) */
     CCSD_QUERY_EW1 = 6,           /* 1: element-wise rank-2 kernel k_ew1 (affine ScoreNetworkF without a Hodge Laplacian term, cnum = 1) */
     CCSD_QUERY_LARGE_GRAPH = 7,   /* 1: the tiled graph-network kernels k_lg_* serve the graph networks instead of k_xa (graph-only plans above
-                                     64 nodes or without a k_xa LDS layout, up to N = 512; CCSD_LARGE_GRAPH=1 at plan creation forces it) */
+                                     64 nodes or without a k_xa LDS layout, up to N = 512; combinatorial complexes with ScoreNetworkA_CC and one
+                                     hodge layer without a k_xa LDS layout, N <= 64; CCSD_LARGE_GRAPH=1 at plan creation forces it for
+                                     eligible graph-only plans, CCSD_LARGE_GRAPH=2 for eligible combinatorial complexes too) */
     /* the rest of the plan's route; answers that depend on the batch are given for config.batch_hint */
     CCSD_QUERY_R2_FAMILY = 8,     /* rank-2 side: 0 none (graph-only), 1 fused k_r2, 2 element-wise k_ew1, 3 tiled (k_gemm_h + k_hf_score) */
     CCSD_QUERY_R2_INSTANCE = 9,   /* k_r2<MT, RS, AFFINE, GEN1, QM9> as the decimal digits MT RS AFFINE GEN1 QM9 (31102 = k_r2<3, 1, true, false, 2>); -1: no k_r2 */

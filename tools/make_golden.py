@@ -80,16 +80,38 @@ SHIPPED = {
     # above 64 nodes: the tiled graph-network route (`python tools/make_golden.py large`)
     "gdss_enzymes": ("checkpoints/ENZYMES/gdss_enzymes.pth", False),
     "gdss_grid": ("checkpoints/grid/gdss_grid.pth", False),
+    # ScoreNetworkA_CC with one hodge layer at N = 49: the tiled graph-network route for combinatorial complexes
+    # (`python tools/make_golden.py grid_small_cc`; kept in a folder of its own, CC_LARGE_CKPT)
+    "ccsd_grid_small_CC": ("checkpoints/grid_small_CC/ccsd_grid_small_CC.pth", True),
 }
 SHIPPED_CKPT = os.path.join(GOLD, "ckpt")
+# (a folder below ckpt/: tests/test_large_graph.py pins the k_xa variant of every checkpoint that lies in ckpt/ itself)
+CC_LARGE_CKPT = os.path.join(SHIPPED_CKPT, "cc_large")
 MAX_FIXTURE = 1 << 20                # no committed file exceeds 1 MiB
 
 
-def export_checkpoint(name, table=CHECKPOINTS, dest=CKPT):
+def export_checkpoint(name, table=CHECKPOINTS, dest=CKPT, apply_ema=False):
+    """apply_ema (fixtures of checkpoints whose sample_*.yaml sets use_ema): the EMA shadow parameters are copied over the state
+    dicts' parameters (ema.copy_to(model.parameters()), sampler.py:469-471) in the returned checkpoint and in the files, so that
+    the fixture holds the weights the shipped configuration samples with; the json says so ("ema_applied") and lists the
+    parameters' names per part ("ema_params": a harness run with use_ema finds its ema_<part>/ entries among them)."""
     rel, is_cc = table[name]
     ck = refshim.load_reference_ckpt(rel)
     arrays = {}
     meta = {"name": name, "source": rel, "is_cc": is_cc, "config": plain(ck["model_config"])}
+    if apply_ema:
+        meta["ema_applied"], meta["ema_params"] = True, {}
+        for part in ["x", "adj"] + (["rank2"] if is_cc else []):
+            sd = ck[f"{part}_state_dict"]
+            m = ref_loader.load_model_from_ckpt(ck[f"params_{part}"], sd, "cpu")
+            names = [n for n, _ in m.named_parameters()]
+            shadow = ck.pop(f"ema_{part}")["shadow_params"]
+            assert len(names) == len(shadow)
+            pre = "module." if any(k.startswith("module.") for k in sd) else ""
+            for n, v in zip(names, shadow):
+                assert sd[pre + n].shape == v.shape
+                sd[pre + n] = v.detach().clone()
+            meta["ema_params"][part] = [n[7:] if n.startswith("module.") else n for n in names]
     for part in ["x", "adj"] + (["rank2"] if is_cc else []):
         meta[f"params_{part}"] = plain(ck[f"params_{part}"])
         sd = ck[f"{part}_state_dict"]
@@ -125,7 +147,7 @@ def export_checkpoint(name, table=CHECKPOINTS, dest=CKPT):
             fname = name + (".npz" if i == 0 else f".{i}.npz")
             np.savez_compressed(os.path.join(dest, fname), **{k: arrays[k] for k in ks})
             assert os.path.getsize(os.path.join(dest, fname)) <= MAX_FIXTURE, fname
-            meta["files"].append(fname)
+            meta["files"].append(os.path.relpath(os.path.join(dest, fname), SHIPPED_CKPT))   # (as tests/helpers.load_ckpt_np joins them)
     with open(os.path.join(dest, name + ".json"), "w") as f:
         json.dump(meta, f, indent=1, sort_keys=True)
     return ck
@@ -199,8 +221,9 @@ def save_golden(fname, out, summarize_large=False):
         assert os.path.getsize(path) <= MAX_FIXTURE, (fname, os.path.getsize(path))
 
 
-def g1_network_forwards(name, ck, is_cc, B, counts, seed=1234, summarize_large=False):
-    """G1/G2: per-network forward + score-fn scaling at three t."""
+def g1_network_forwards(name, ck, is_cc, B, counts, seed=1234, summarize_large=False, rank2_score=True):
+    """G1/G2: per-network forward + score-fn scaling at three t (rank2_score=False: none for rank2 -- a third summarised rank-2
+    array would take the file past MAX_FIXTURE at grid_small_CC's E)."""
     cfg = ck["model_config"]
     N, Fd = cfg["data"]["max_node_num"], cfg["data"]["max_feat_num"]
     d_min, d_max = (cfg["data"]["d_min"], cfg["data"]["d_max"]) if is_cc else (None, None)
@@ -221,7 +244,7 @@ def g1_network_forwards(name, ck, is_cc, B, counts, seed=1234, summarize_large=F
             for ti, tval in enumerate([1.0, 0.5, 1e-4]):
                 t = torch.ones(B) * tval
                 for part, m, s in zip(["x", "adj", "rank2"], models, sdes):
-                    if tag != "unit" or (part == "rank2" and ti != 1):
+                    if tag != "unit" or (part == "rank2" and (ti != 1 or not rank2_score)):
                         continue
                     fn = (ref_losses.get_score_fn_cc if is_cc else ref_losses.get_score_fn)(s, m, train=False, continuous=True)
                     out[f"{tag}/score_{part}_t{ti}"] = fn(*args, t).numpy()
@@ -914,8 +937,24 @@ def large_graph():
         print("large graph", name)
 
 
+def grid_small_cc():
+    """ccsd_grid_small_CC (N = 49, d = 3: E = 1176, K = 18424; ScoreNetworkA_CC with one hodge layer): the weights
+    sample_grid_small_CC.yaml samples with (use_ema: the EMA-applied ones) under tests/golden/ckpt/cc_large/, g1 forwards at B = 2 and
+    the first two steps of the shipped 1000-scale sampler (Reverse + Langevin, snr 0.1, scale_eps 0.7, the yaml's seed), rank-2
+    arrays as summaries."""
+    name = "ccsd_grid_small_CC"
+    smp = dict(predictor="Reverse", corrector="Langevin", snr=0.1, scale_eps=0.7, n_steps=1)
+    ck = export_checkpoint(name, SHIPPED, CC_LARGE_CKPT, apply_ema=True)
+    g1_network_forwards(name, ck, True, 2, [49, 30], summarize_large=True, rank2_score=False)
+    g5_pc_runs(name, ck, True, 2, [49, 30], smp, {"n1000_first2": (None, 2)}, seed=12, summarize_large=True)
+    print("grid_small_cc", name)
+
+
 def main():
     only = set(sys.argv[1:])
+    if only == {"grid_small_cc"}:
+        grid_small_cc()
+        return
     if only == {"shipped"}:
         shipped()
         return
