@@ -48,7 +48,7 @@ static inline int fnet_width(const PlanD& p) {
 //                                              Lost on every workload (xiv); kept because k_xa<false, XA_HB> without the
 //                                              mode test needs 104 bytes of scratch instead of 100 (profiles/README.md r08)
 //   CCSD_LARGE_GRAPH=1|2 lg_force              tiled graph-network route for any eligible graph-only plan (1), (PlanBuilder)  tests (emu + gpu)
-//                                              for eligible combinatorial-complex plans too (2: ScoreNetworkA_CC, one hodge layer)
+//                                              for eligible combinatorial-complex plans too (2: ScoreNetworkA_CC with one hodge layer, ScoreNetworkA_Base_CC)
 //   CCSD_XA_PASS=<n>     xa_pass               first k_xa LDS budget candidate tried            (PlanBuilder)  tests (emu + gpu)
 //   CCSD_XA_GCH          xa_gch                channel stack in the HBM workspace first         (PlanBuilder)  tests (emu + gpu)
 //   CCSD_NO_MLP_WT       no_mlp_wt             no transposed copies of the non-chained MLPs     (PlanBuilder)  tests (gpu)
@@ -117,6 +117,7 @@ struct Route {
 struct ccsd_plan {
     ccsd_config_t cfg;
     PlanD h;                    // host copy
+    HodgeBaseD hbx[CCSD_LG_MAXHB];   // every HodgeBaselineLayer of ScoreNetworkA_Base_CC (h.hb holds the first two): arguments of the k_lg_hb_* launches
     PlanD* d = nullptr;         // device copy
     float* w = nullptr;         // device weights
     float* wp = nullptr;        // device: zero-padded copies of the chain MLPs' linears (mlp_chain_tile)
@@ -384,6 +385,7 @@ extern "C" int ccsd_plan_create(const ccsd_config_t* cfg, const float* weights, 
     pl->nweights = ccsd_build_plan(cfg, &pl->h, pb);
     if (pb.status != CCSD_OK) { delete pl; return set_err(pb.status, pb.err); }
     pl->rt.lg = pb.lg;
+    memcpy(pl->hbx, pb.hbx, sizeof(pl->hbx));
     pl->h.geo_off = k.geo_off;
     pl->npacked = (size_t)pb.pcur;
     if (pl->nweights != n_weights) {
@@ -449,9 +451,9 @@ extern "C" int ccsd_plan_create(const ccsd_config_t* cfg, const float* weights, 
             ccsd_pack_mlp(pl->h.gl[l].mlp, weights, packed.data()); ccsd_pack_mlp(pl->h.gl[l].mc, weights, packed.data());
             ccsd_pack_qkv(pl->h.gl[l], weights, packed.data()); ccsd_pack_mc(pl->h.gl[l], weights, packed.data());
         }
-        if (pl->h.hb_L) ccsd_pack_mlp(pl->h.hb[0].mh, weights, packed.data());
-        for (int l = 0; l < pl->h.hb_L; ++l) {   // transposed copies of the BaselineBlocks' weights
-            const HodgeBaseD& h = pl->h.hb[l];
+        for (int l = 0; l < pl->h.hb_L; ++l) {   // mlp_hodge of the dense layers; transposed copies of the BaselineBlocks' weights
+            const HodgeBaseD& h = pl->hbx[l];
+            ccsd_pack_mlp(h.mh, weights, packed.data());
             for (int c = 0; c < h.cin; ++c) {
                 const float* blk = weights + h.blk_base + (size_t)c * h.blk_stride;    // W1[hid][E] b1[hid] W2[E][hid] b2[E]
                 const float* w2 = blk + h.hid * E + h.hid;
@@ -494,6 +496,11 @@ extern "C" int ccsd_plan_create(const ccsd_config_t* cfg, const float* weights, 
         }
         if (r.r2 && r.r2_lds > 64 * 1024) PC(rt_set_max_dyn_smem((const void*)r.r2->fn, r.r2_lds));
         if (r.lg && lg_nmlp_lds(pl->h) > 64 * 1024) PC(rt_set_max_dyn_smem((const void*)k_lg_nmlp, lg_nmlp_lds(pl->h)));
+        if (r.lg && pl->h.hb_L > 1) {
+            size_t v = 0;
+            for (int l = 0; l + 1 < pl->h.hb_L; ++l) if (lg_hb_dense_lds(pl->hbx[l]) > v) v = lg_hb_dense_lds(pl->hbx[l]);
+            if (v > 64 * 1024) PC(rt_set_max_dyn_smem((const void*)k_lg_hb_dense, v));
+        }
 #ifndef CCSD_EMU
         if (r.hp_full_modes) {      // k_hp_full: 66.6 KB of dynamic LDS
             PC(rt_set_max_dyn_smem((const void*)k_hp_full<CCSD_FULL_E, CCSD_FULL_K, 1>, HP_FULL_LDS));
@@ -540,6 +547,11 @@ struct Workspace {
     // [B][N][x_fdim], its X W [B][N][nhid], its masked net [B][N][F]; k_lg_fin's per-tile norm partials [B][lg_tiles][2]
     float *lg_S, *lg_att, *lg_dis, *lg_Y, *lg_QKV, *lg_x[2], *lg_xcat, *lg_xY, *lg_xnet, *lg_part;
     int lg_tiles;
+    // ... ScoreNetworkA_Base_CC: hidden rows of a layer's BaselineBlocks [B][cin][E][hid]; the dense output [B][cout][E][E] of a layer
+    // but the last (ONE buffer: the next layer's hidden rows are all that reads it, and they are complete before the next dense
+    // output is written); per-sample strides in floats
+    float *lg_hbg, *lg_hbH;
+    size_t lg_hbg_stride, lg_hbH_stride;
     ccsd_state_t third;             // LOOP_LANGEVIN_MULTI with more than one inner iteration: the second corrector iterate of ccsd_sampler_run
     size_t bytes;
     MaskTab masks() const { return MaskTab{mfr, mfl, Kp, Ep}; }
@@ -613,6 +625,17 @@ static Workspace carve_ws(const ccsd_plan* pl, int B, void* base) {
         w.lg_xY = (float*)take((size_t)B * N * p.x_nhid * 4);
         w.lg_xnet = (float*)take((size_t)B * N * p.F * 4);
         w.lg_part = (float*)take((size_t)B * w.lg_tiles * 2 * 4);
+        if (p.hb_L) {
+            size_t g = 0, hd = 0;
+            for (int l = 0; l < p.hb_L; ++l) {
+                const HodgeBaseD& h = pl->hbx[l];
+                if ((size_t)h.cin * E * h.hid > g) g = (size_t)h.cin * E * h.hid;
+                if (l + 1 < p.hb_L && (size_t)h.cout * E * E > hd) hd = (size_t)h.cout * E * E;
+            }
+            w.lg_hbg_stride = g; w.lg_hbH_stride = hd;
+            w.lg_hbg = (float*)take((size_t)B * g * 4);
+            w.lg_hbH = (float*)take((size_t)B * hd * 4);
+        }
     }
     if (pl->rt.loop == LOOP_LANGEVIN_MULTI && pl->cfg.n_corr_steps > 1) {      // (last: no plan with n_steps == 1 moves)
         w.third.x = (float*)take((size_t)B * p.N * p.F * 4);
@@ -847,7 +870,8 @@ static int launch_xa(const ccsd_plan* pl, int B, XaArgs& xa, NoiseArgs& na, cons
 }
 // Tiled graph-network route (ccsd_k_lg.h): ScoreNetworkX on (xX, adjX) and ScoreNetworkA on (xA, adjA) as a sequence of launches over
 // the workspace (LgWs fields of Workspace), then the epilogues of k_xa's contract (mode, coefficients, mean pointers, norm2[b][4]).
-// Combinatorial-complex plans (ScoreNetworkA_CC, one hodge layer): xa.P0 holds the layer-0 hodge projections launch_p / k_r2 left.
+// Combinatorial-complex plans: ScoreNetworkA_CC with one hodge layer (xa.P0 holds the layer-0 hodge projections launch_p / k_r2 left), or
+// ScoreNetworkA_Base_CC (its hodge branch reads only the adjacency powers).
 // Plans on this route never fuse the corrector apply into this pass (resolve_route), so a CorrFuse here is an error.
 static int launch_lg(const ccsd_plan* pl, int B, XaArgs& xa, NoiseArgs& na, Workspace& w, void* stream) {
     const PlanD& p = pl->h;
@@ -883,6 +907,30 @@ static int launch_lg(const ccsd_plan* pl, int B, XaArgs& xa, NoiseArgs& na, Work
             if (!xa.P0) return set_err(CCSD_ERR_RUNTIME, "tiled graph-network route: no hodge projections");
             CCSD_LAUNCH(k_lg_hodge1, dim3(grid_for(p.E + N, 256), B), blk, 0, stream, p.hl[0], 1.0f / (float)sqrt((double)p.K), (const float*)pl->w,
                         (const unsigned char*)pl->edges, xa.P0, w.lg_S, ss, p.a_nch_graph, N, p.E, xa.flags);
+        }
+        if (p.hb_L) {
+            // hodge branch of ScoreNetworkA_Base_CC (k_lg_hb_*): input channels and layer 0's hidden rows; per layer but the last its dense
+            // E x E output (the diagonal goes to the stack) and the next layer's hidden rows from it; the last layer on its diagonal only
+            const int E = p.E, et = (E + 15) / 16;
+            const unsigned char* edges = (const unsigned char*)pl->edges;
+            const float* wts = (const float*)pl->w;
+            const float* wpk = (const float*)pl->wp;
+            int ch = p.a_nch_graph + p.a_cinit;
+            CCSD_LAUNCH(k_lg_hb_in, dim3(grid_for(E + N, 256), B), blk, 0, stream, pl->hbx[0], p.a_nch_hodge, wts, edges, w.lg_S, ss, p.a_nch_graph, N, E,
+                        w.lg_hbg, (long long)w.lg_hbg_stride);
+            for (int l = 0; l + 1 < p.hb_L; ++l) {
+                const HodgeBaseD& h = pl->hbx[l];
+                const HodgeBaseD& hn = pl->hbx[l + 1];
+                float* Hl = w.lg_hbH;
+                CCSD_LAUNCH(k_lg_hb_dense, dim3(et * (et + 1) / 2, B), blk, lg_hb_dense_lds(h), stream, h, wts, wpk, edges, (const float*)w.lg_hbg,
+                            (long long)w.lg_hbg_stride, Hl, (long long)w.lg_hbH_stride, w.lg_S, ss, ch, N, E, xa.flags);
+                CCSD_LAUNCH(k_lg_hb_hid, dim3((et + 3) / 4, hn.cin, B), blk, 0, stream, hn, wts, wpk, (const float*)Hl, (long long)w.lg_hbH_stride, E,
+                            w.lg_hbg, (long long)w.lg_hbg_stride);
+                ch += h.cout;
+            }
+            CCSD_LAUNCH(k_lg_hb_diag, dim3(grid_for(E, 256), B), blk, 0, stream, pl->hbx[p.hb_L - 1], wts, edges, (const float*)w.lg_hbg,
+                        (long long)w.lg_hbg_stride, w.lg_S, ss, ch, N, E, xa.flags);
+            LAUNCH_CHECK();
         }
         for (int l = 0; l < p.a_L; ++l) {
             const AttnLayerD& L = p.al[l];

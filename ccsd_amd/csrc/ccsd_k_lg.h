@@ -1,7 +1,7 @@
 // ccsd_k_lg.h -- the tiled graph-network path (k_lg_*): ScoreNetworkX + ScoreNetworkA for plans whose per-graph working set does not
 // fit one CU's LDS (graph-only plans with N > 64, or k_xa's layout fails; CCSD_LARGE_GRAPH=1 forces it for any eligible graph-only
-// plan), and ScoreNetworkA_CC with ONE hodge layer for combinatorial complexes (N <= 64) without a k_xa layout (or under
-// CCSD_LARGE_GRAPH=2, which forces every eligible plan).
+// plan), and for combinatorial complexes (N <= 64) without a k_xa layout (or under CCSD_LARGE_GRAPH=2, which forces every eligible
+// plan): ScoreNetworkA_CC with ONE hodge layer, and ScoreNetworkA_Base_CC with 1 to 8 HodgeBaselineLayers (more than two: always here).
 // Part of the kernel source of libccsd_hip.so (see ccsd_kernels.h for the map).
 //
 // State lives in the HBM workspace (carve_ws, LgWs in ccsd_api.h) and every phase is a launch of its own that tiles each graph over
@@ -9,7 +9,8 @@
 //   ScoreNetworkX   k_lg_dis (D^-1/2 of adjX) ; per GCN layer: k_lg_xw (Y = D^-1/2 X W), k_lg_gcn (tanh(D^-1/2 A' Y + b) into the
 //                   concatenation) ; k_lg_nmlp (final MLP per node, mask_x)
 //   ScoreNetworkA   k_lg_pow (channel stack [A, A^2, ...]) ; ScoreNetworkA_CC: k_lg_hodge1 (the hodge channels, behind the graph
-//                   channels of the stack) ; per AttentionLayer: k_lg_dis, k_lg_xw (Q | K | V columns side by side),
+//                   channels of the stack) ; ScoreNetworkA_Base_CC: k_lg_hb_in, per layer but the last k_lg_hb_dense + k_lg_hb_hid,
+//                   k_lg_hb_diag (the same channels from the HodgeBaselineLayers) ; per AttentionLayer: k_lg_dis, k_lg_xw (Q | K | V columns side by side),
 //                   k_lg_gcn, k_lg_nmlp (multi_channel, mask_x, tanh), k_lg_att (head-mean tanh(Q K^T / sqrt(fout)), symmetrised),
 //                   k_lg_edge (edge MLP on [att_c | adj_c] per entry, MFMA: mlp_chain_tile), k_lg_sym (out + out^T, mask_adjs) ;
 //                   k_lg_fin (final MLP per entry, MFMA: mlp_chain_tile, + the adjacency epilogue, per-tile norm partials)
@@ -43,6 +44,15 @@ __global__ void k_lg_pow(const float* __restrict__ adj, float* __restrict__ S, l
 __global__ void k_lg_hodge1(HodgeLayerD h, float rks, const float* __restrict__ w, const unsigned char* __restrict__ edges,
                             const float* __restrict__ P0, float* __restrict__ S, long long sstride, int ch0, int N, int E,
                             const float* __restrict__ flags);
+__global__ void k_lg_hb_in(HodgeBaseD h, int nch, const float* __restrict__ w, const unsigned char* __restrict__ edges, float* __restrict__ S,
+                           long long sstride, int ch0, int N, int E, float* __restrict__ G, long long gstride);
+__global__ void k_lg_hb_dense(HodgeBaseD h, const float* __restrict__ w, const float* __restrict__ wp, const unsigned char* __restrict__ edges,
+                              const float* __restrict__ G, long long gstride, float* __restrict__ Hout, long long hstride, float* __restrict__ S,
+                              long long sstride, int ch0, int N, int E, const float* __restrict__ flags);
+__global__ void k_lg_hb_hid(HodgeBaseD h, const float* __restrict__ w, const float* __restrict__ wp, const float* __restrict__ Hin, long long hstride,
+                            int E, float* __restrict__ G, long long gstride);
+__global__ void k_lg_hb_diag(HodgeBaseD h, const float* __restrict__ w, const unsigned char* __restrict__ edges, const float* __restrict__ G,
+                             long long gstride, float* __restrict__ S, long long sstride, int ch0, int N, int E, const float* __restrict__ flags);
 __global__ void k_lg_dis(const float* __restrict__ S, long long sstride, int ci0, int cin, int N, float* __restrict__ dis);
 __global__ void k_lg_xw(const float* __restrict__ X, long long xbs, int ldx, int fin, const float* __restrict__ W, int wcs, int ldy,
                         int cin, int N, const float* __restrict__ dis, float* __restrict__ Y);
@@ -60,6 +70,11 @@ __global__ void k_lg_fin(MlpD m, const float* __restrict__ wp, const float* __re
                          const float* __restrict__ flags, const float* __restrict__ adj, XaArgs xa, NoiseArgs na, float* __restrict__ part);
 __global__ void k_lg_epi(const float* __restrict__ xnet, const float* __restrict__ x, const float* __restrict__ flags, XaArgs xa,
                          NoiseArgs na, const float* __restrict__ part, int ntiles, int N, int F);
+
+// k_lg_hb_dense's LDS (floats / bytes): the hidden rows and the W2 rows of the tile's 16 + 16 edges per channel (odd row stride: the 16
+// lanes along an edge index read 16 banks), their b2, and mlp_hodge's input [cin][256 pairs]
+static inline __host__ __device__ int lg_hb_row_ld(int hid) { return hid | 1; }
+static inline size_t lg_hb_dense_lds(const HodgeBaseD& h) { return ((size_t)4 * h.cin * 16 * lg_hb_row_ld(h.hid) + 32 * h.cin + 256 * h.cin) * 4; }
 
 #if defined(CCSD_LG_UNIT) || defined(CCSD_EMU)
 // per-thread work items of a CCSD_LG_TB-sized tile: one per thread on the GPU, the whole tile in the emulation's one thread
@@ -423,6 +438,219 @@ __global__ __launch_bounds__(CCSD_LG_TB) void k_lg_hodge1(HodgeLayerD h, float r
                 const float tv = tanh_f(out[o] * fh * fh);
                 Hb[(size_t)(h.cin + o) * NN + ij] = tv + tv;
                 Hb[(size_t)(h.cin + o) * NN + ji] = tv + tv;
+            }
+    }
+}
+
+
+// ---- The hodge branch of ScoreNetworkA_Base_CC (ScoreNetwork_A_Base_CC.py:295-316; the oracle's score_network_a_base_cc): L
+// HodgeBaselineLayers (hodge_layers.py:259-284, 381-416) on the E x E hodge adjacency channels, k_xa's HB block with the same
+// expressions, the dense layers tiled through the workspace.  Per input channel c of a layer a BaselineBlock (weights
+// W1[hid][E] b1[hid] W2[E][hid] b2[E]): g_c[e] = elu(W1 H_c[e] + b1) (hidden rows), T_c[e][e'] = tanh(W2[e'] . g_c[e] + b2[e']); mlp_hodge
+// mixes the symmetrised channels (T_c + T_c^T) / 2 per (e, e'), then mask_hodge_adjs, tanh, + transpose.  The layers' rank-2 outputs
+// never reach the score and are not evaluated; adj_to_hodgedual makes the first layer's input diagonal (a_c[e] on it: entry (i, j) of
+// adjacency power c), and hodgedual_to_adj reads only the diagonal of every layer's output, so the last layer is evaluated there
+// alone.  Stack rows ch0 ..: the a_c, then every layer's diagonal, at (i, j) and (j, i) of each edge, zero on the node diagonal.
+// No atomics, fixed summation orders: launches repeat bit for bit.
+
+// the input channels into the stack (rows ch0 .. ch0 + cin; zeros on the node diagonal of all nch hodge rows: nothing else writes
+// there, and the workspace is not cleared) and the first layer's hidden rows G[b][c][e][h] = elu(W1_c[h][e] a_c[e] + b1_c[h])
+// grid: (grid-stride over E + N, B)
+__global__ __launch_bounds__(CCSD_LG_TB) void k_lg_hb_in(HodgeBaseD h, int nch, const float* __restrict__ w, const unsigned char* __restrict__ edges,
+                                                        float* __restrict__ S, long long sstride, int ch0, int N, int E, float* __restrict__ G,
+                                                        long long gstride) {
+    const int b = blockIdx.y, NN = N * N, hid = h.hid;
+    float* Sb = S + (size_t)b * sstride;
+    float* Hb = Sb + (size_t)ch0 * NN;
+    float* Gb = G + (size_t)b * gstride;
+    for (int t = blockIdx.x * blockDim.x + threadIdx.x; t < E + N; t += gridDim.x * blockDim.x) {
+        if (t >= E) {
+            const int i = t - E;
+            for (int c = 0; c < nch; ++c) Hb[(size_t)c * NN + (size_t)i * N + i] = 0.f;
+            continue;
+        }
+        const int i = edges[2 * t], j = edges[2 * t + 1];
+        const size_t ij = (size_t)i * N + j, ji = (size_t)j * N + i;
+        for (int c = 0; c < h.cin; ++c) {
+            const float* blk = w + h.blk_base + (size_t)c * h.blk_stride;
+            const float a = Sb[(size_t)c * NN + ij];
+            Hb[(size_t)c * NN + ij] = a;
+            Hb[(size_t)c * NN + ji] = a;
+            float* g = Gb + ((size_t)c * E + t) * hid;
+            for (int hh = 0; hh < hid; ++hh) g[hh] = elu1(fmaf(blk[(size_t)hh * E + t], a, blk[(size_t)hid * E + hh]));
+        }
+    }
+}
+
+// The dense output of a layer but the last from its hidden rows: Hout[b][o][e][e'] = 2 tanh(fl(i) fl(j) fl(i') fl(j') mlp_hodge(S)_o),
+// S_c = (T_c[e][e'] + T_c[e'][e]) / 2.  One 16 x 16 tile (e, e') of the upper triangle per workgroup, mirrored on store (a tile on the
+// diagonal computes both halves itself: the two orders of a pair go through the same operations, the result is symmetric bit for
+// bit).  The 256 pairs' block outputs go to LDS, one pair per thread; mlp_hodge then runs per 16-pair tile on MFMA (mlp_chain_tile,
+// the 16-wide chain shape: the planner chains it for every dense layer), four tiles per wave.  The diagonal also goes to stack rows
+// ch0 .. ch0 + cout.  Ragged last tile: rows beyond E are staged from row E - 1 and never stored.
+// dynamic LDS: lg_hb_dense_lds(h).  grid: (nt (nt + 1) / 2, B), nt = ceil(E / 16)
+__global__ __launch_bounds__(CCSD_LG_TB) void k_lg_hb_dense(HodgeBaseD h, const float* __restrict__ w, const float* __restrict__ wp,
+                                                           const unsigned char* __restrict__ edges, const float* __restrict__ G, long long gstride,
+                                                           float* __restrict__ Hout, long long hstride, float* __restrict__ S, long long sstride,
+                                                           int ch0, int N, int E, const float* __restrict__ flags) {
+    CCSD_DYN_SMEM(sm);
+    const int b = blockIdx.y, tid = threadIdx.x, nth = blockDim.x, NN = N * N;
+    const int nt = (E + 15) / 16;
+    int t = blockIdx.x, ty = 0;                  // upper-triangle tile t -> (row tile ty, column tile ty + t), row-major
+    while (t >= nt - ty) { t -= nt - ty; ++ty; }
+    const int e0 = 16 * ty, f0 = 16 * (ty + t);
+    const bool diag = t == 0;
+    const int hid = h.hid, hp = lg_hb_row_ld(hid), cin = h.cin;
+    float* s_g = sm;                             // [side][cin][16][hp]: hidden rows of the tile's row edges (side 0) / column edges (1)
+    float* s_w = s_g + 2 * cin * 16 * hp;        // ... their rows of W2
+    float* s_b = s_w + 2 * cin * 16 * hp;        // [side][cin][16]: their b2
+    float* s_S = s_b + 2 * cin * 16;             // [cin][256]: mlp_hodge's input, pair u = 16 r + q
+    const float* Gb = G + (size_t)b * gstride;
+    for (int u = tid; u < 2 * cin * 16 * hid; u += nth) {
+        const int hh = u % hid, v = u / hid, r = v & 15, sc = v >> 4, c = sc % cin, side = sc / cin;
+        const int e = (side ? f0 : e0) + r, ec = e < E ? e : E - 1;
+        const float* blk = w + h.blk_base + (size_t)c * h.blk_stride;
+        s_g[(sc * 16 + r) * hp + hh] = Gb[((size_t)c * E + ec) * hid + hh];
+        s_w[(sc * 16 + r) * hp + hh] = blk[(size_t)hid * E + hid + (size_t)ec * hid + hh];
+    }
+    for (int u = tid; u < 2 * cin * 16; u += nth) {
+        const int r = u & 15, sc = u >> 4, c = sc % cin, side = sc / cin;
+        const int e = (side ? f0 : e0) + r, ec = e < E ? e : E - 1;
+        s_b[u] = w[h.blk_base + (size_t)c * h.blk_stride + 2 * (size_t)hid * E + hid + ec];
+    }
+    __syncthreads();
+    for (int u = tid; u < 256; u += nth) {
+        const int r = u >> 4, q = u & 15;
+        for (int c = 0; c < cin; ++c) {
+            const float* gr = s_g + (c * 16 + r) * hp;
+            const float* wr = s_w + (c * 16 + r) * hp;
+            const float* gq = s_g + ((cin + c) * 16 + q) * hp;
+            const float* wq = s_w + ((cin + c) * 16 + q) * hp;
+            float a1 = 0.f, a2 = 0.f;
+            for (int hh = 0; hh < hid; ++hh) {
+                a1 = fmaf(gr[hh], wq[hh], a1);       // W2[e'] . g[e]
+                a2 = fmaf(gq[hh], wr[hh], a2);       // W2[e] . g[e']
+            }
+            const float t1 = tanh_f(a1 + s_b[(cin + c) * 16 + q]), t2 = tanh_f(a2 + s_b[c * 16 + r]);
+            s_S[c * 256 + u] = (diag && r == q) ? t1 : (t1 + t2) * 0.5f;
+        }
+    }
+    __syncthreads();
+    float* Hb = Hout + (size_t)b * hstride;
+    float* Sb = S + (size_t)b * sstride + (size_t)ch0 * NN;
+    const float* fl = flags + (size_t)b * N;
+    auto ident = [](int r) { return r; };
+    auto epi = [&](int u, int o, float v) {
+        const int e = e0 + (u >> 4), f = f0 + (u & 15);
+        if (e >= E || f >= E) return;
+        const int i = edges[2 * e], j = edges[2 * e + 1], i2 = edges[2 * f], j2 = edges[2 * f + 1];
+        const float fh = fl[i] * fl[j] * fl[i2] * fl[j2];
+        const float tv = tanh_f(v * fh), val = tv + tv;
+        float* Ho = Hb + (size_t)o * E * E;
+        Ho[(size_t)e * E + f] = val;
+        if (!diag) Ho[(size_t)f * E + e] = val;
+        else if (e == f) {
+            Sb[(size_t)o * NN + (size_t)i * N + j] = val;
+            Sb[(size_t)o * NN + (size_t)j * N + i] = val;
+        }
+    };
+#ifdef CCSD_EMU
+    for (int wv = 0; wv < CCSD_LG_TB / 64; ++wv)
+#else
+    const int wv = wave_index();
+#endif
+        for (int q4 = 0; q4 < 4; ++q4) mlp_chain_tile<1, 1, 1>(h.mh, wp, s_S, 256, s_S, h.mh.in, 16 * (4 * wv + q4), 256, ident, epi);
+}
+
+// The hidden rows of a layer with dense input: G[b][c][e][h] = elu(sum_e' W1_c[h][e'] Hin[b][c][e][e'] + b1_c[h]) -- an (E x E) . (E x hid)
+// product per channel, hid <= 16 (CCSD_LG_HBW).  One 16-row x 16-column v_mfma_f32_16x16x4_f32 tile per wave over the whole E, in the
+// permuted-k fragment order of the tiled GEMM kernels (frag_mma, row_load4: k slot kq of step j of block t <-> e' = 16 t + 4 kq + j), B
+// operand from the packed W1^T [E][hid] (HodgeBaseD::w1t).  Each row of Hin is read once: the pass is HBM-bound.  The ragged last row
+// tile reads row E - 1 and stores nothing; the ragged k tail and the columns beyond hid are zeros by guard, not by padding.
+// grid: (ceil(ceil(E / 16) / 4), cin, B)
+__global__ __launch_bounds__(CCSD_LG_TB) void k_lg_hb_hid(HodgeBaseD h, const float* __restrict__ w, const float* __restrict__ wp,
+                                                         const float* __restrict__ Hin, long long hstride, int E, float* __restrict__ G,
+                                                         long long gstride) {
+    const int c = blockIdx.y, b = blockIdx.z, hid = h.hid;
+    const float* Hc = Hin + (size_t)b * hstride + (size_t)c * E * E;
+    const float* b1 = w + h.blk_base + (size_t)c * h.blk_stride + (size_t)hid * E;
+    const float* W1t = wp + h.w1t + (size_t)c * E * hid;
+    float* Gc = G + (size_t)b * gstride + (size_t)c * E * hid;
+#ifdef CCSD_EMU
+    for (int wv = 0; wv < CCSD_LG_TB / 64; ++wv) {
+        const int m0 = 16 * (4 * blockIdx.x + wv);
+        for (int e = m0; e < m0 + 16 && e < E; ++e)
+            for (int hh = 0; hh < hid; ++hh) {
+                float acc = 0.f;
+                for (int k = 0; k < E; ++k) acc = fmaf(Hc[(size_t)e * E + k], W1t[(size_t)k * hid + hh], acc);
+                Gc[(size_t)e * hid + hh] = elu1(acc + b1[hh]);
+            }
+    }
+#else
+    const int m0 = 16 * (4 * blockIdx.x + wave_index());
+    if (m0 >= E) return;
+    const int lane = threadIdx.x & 63, l15 = lane & 15, kq = lane >> 4;
+    const float* row = Hc + (size_t)(m0 + l15 < E ? m0 + l15 : E - 1) * E;
+    const bool vec = (E & 3) == 0, col = l15 < hid;
+    const float* wcol = W1t + (col ? l15 : 0);
+    f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+    for (int k0 = 0; k0 < E; k0 += 16) {
+        const int k = k0 + 4 * kq;
+        float4 a, bq;
+        row_load4(a, row, k, E, vec);
+        bq.x = (col && k < E) ? wcol[(size_t)(k < E ? k : E - 1) * hid] : 0.f;
+        bq.y = (col && k + 1 < E) ? wcol[(size_t)(k + 1 < E ? k + 1 : E - 1) * hid] : 0.f;
+        bq.z = (col && k + 2 < E) ? wcol[(size_t)(k + 2 < E ? k + 2 : E - 1) * hid] : 0.f;
+        bq.w = (col && k + 3 < E) ? wcol[(size_t)(k + 3 < E ? k + 3 : E - 1) * hid] : 0.f;
+        frag_mma(acc, a, bq);
+    }
+    if (col) {
+        const float bb = b1[l15];
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            const int e = m0 + 4 * kq + r;
+            if (e < E) Gc[(size_t)e * hid + l15] = elu1(acc[r] + bb);
+        }
+    }
+#endif
+}
+
+// The last layer, on its diagonal: d_c[e] = tanh(W2_c[e] . g_c[e] + b2_c[e]), mlp_hodge per edge (the per-thread MLP from zero-padded
+// 16 x 16 blocks in LDS), mask, 2 tanh into stack rows ch0 .. ch0 + cout at (i, j) and (j, i).  grid: (grid-stride over E, B)
+__global__ __launch_bounds__(CCSD_LG_TB) void k_lg_hb_diag(HodgeBaseD h, const float* __restrict__ w, const unsigned char* __restrict__ edges,
+                                                          const float* __restrict__ G, long long gstride, float* __restrict__ S, long long sstride,
+                                                          int ch0, int N, int E, const float* __restrict__ flags) {
+    __shared__ float s_mh[CCSD_MAXLIN * (CCSD_FW * CCSD_FW + CCSD_FW)];
+    const int b = blockIdx.y, NN = N * N, hid = h.hid;
+    stage_mlp_blocks_w<CCSD_FW>(h.mh, w, s_mh);
+    __syncthreads();
+    const float* Gb = G + (size_t)b * gstride;
+    float* Sb = S + (size_t)b * sstride + (size_t)ch0 * NN;
+    const float* fl = flags + (size_t)b * N;
+    for (int e = blockIdx.x * blockDim.x + threadIdx.x; e < E; e += gridDim.x * blockDim.x) {
+        float in[CCSD_FW], out[CCSD_FW];
+#pragma unroll
+        for (int c = 0; c < CCSD_FW; ++c) {
+            float v = 0.f;
+            if (c < h.cin) {
+                const float* blk = w + h.blk_base + (size_t)c * h.blk_stride;
+                const float* w2 = blk + (size_t)hid * E + hid + (size_t)e * hid;
+                const float* g = Gb + ((size_t)c * E + e) * hid;
+                float acc = 0.f;
+                for (int hh = 0; hh < hid; ++hh) acc = fmaf(g[hh], w2[hh], acc);
+                v = tanh_f(acc + blk[2 * (size_t)hid * E + hid + e]);
+            }
+            in[c] = v;
+        }
+        small_mlp_ldsw<CCSD_FW>(s_mh, h.mh.n, in, out);
+        const int i = edges[2 * e], j = edges[2 * e + 1];
+        const float fh = fl[i] * fl[j];
+#pragma unroll
+        for (int o = 0; o < CCSD_FW; ++o)
+            if (o < h.cout) {
+                const float tv = tanh_f(out[o] * fh * fh);
+                Sb[(size_t)o * NN + (size_t)i * N + j] = tv + tv;
+                Sb[(size_t)o * NN + (size_t)j * N + i] = tv + tv;
             }
     }
 }

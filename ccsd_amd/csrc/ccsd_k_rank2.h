@@ -53,27 +53,7 @@ static inline int xcd_grid(int B, int T) { return ((B + 7) / 8) * 8 * T; }
 #define H_BK 32   // k per slab (two 16-wide MFMA k blocks)
 #define H_LD 40   // LDS row stride in floats: 16-byte aligned rows, == 8 mod 32 -> conflict-free ds_read_b128 fragments
 #ifndef CCSD_EMU
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-// The pieces the tiled rank-2 GEMM kernels share, stated once (DESIGN.md section 4 lists the sites that call them and the ones that
-// still carry their own text).
-// One 16-wide block of the contraction index of one 16 x 16 sub-tile: a, b = the lane's fragments of the two row slabs (one ds_read_b128
-// each), component j = step j of the block (MFMA k slot kq <-> k = 16 t + 4 kq + j).  k_gemm_h_full, k_hp_full, k_gemm_p0 and the two
-// single products of k_gemm_h, which promise each other bit-identical sub-tiles, all go through here; the interleaved 2 x 2 products of
-// k_gemm_h and k_hf_score are the same steps written out per accumulator pair.
-CCSD_DEV void frag_mma(f32x4& acc, const float4& a, const float4& b) {
-    const float av[4] = {a.x, a.y, a.z, a.w}, bv[4] = {b.x, b.y, b.z, b.w};
-#pragma unroll
-    for (int q = 0; q < 4; ++q) acc = __builtin_amdgcn_mfma_f32_16x16x4f32(av[q], bv[q], acc, 0, 0, 0);
-}
-// v = src[k .. k + 3] of a row of K floats: one 16-byte load where rows are whole groups (vec: K a multiple of 4), element by element
-// with zeros beyond K otherwise (the ragged tail).  (Through a reference: returned by value it changed the code of k_gemm_h and k_hf_score.)
-CCSD_DEV void row_load4(float4& v, const float* src, int k, int K, bool vec) {
-    if (vec && k + 3 < K) v = *reinterpret_cast<const float4*>(src + k);
-    else {
-        v.x = k < K ? src[k] : 0.f; v.y = k + 1 < K ? src[k + 1] : 0.f;
-        v.z = k + 2 < K ? src[k + 2] : 0.f; v.w = k + 3 < K ? src[k + 3] : 0.f;
-    }
-}
+// (frag_mma / row_load4, the fragment pieces the tiled GEMM kernels share: ccsd_rank2_common.h -- k_lg_hb_hid calls them too)
 // sum over the eight consecutive lanes that hold the eight column groups of a slab row: fixed butterfly, every lane gets the sum
 CCSD_DEV float row8_sum(float v) {
     v += __shfl_xor(v, 1, 64); v += __shfl_xor(v, 2, 64); v += __shfl_xor(v, 4, 64);

@@ -18,6 +18,8 @@
 #define CCSD_XA_MAXN 64   // k_xa: one graph per workgroup, its working set in one CU's LDS (node masks: one 64-bit word per graph)
 #define CCSD_LG_MAXN 512  // tiled graph-network route (ccsd_k_lg.h): ceiling on N (a graph's channel stack, fdim N^2 floats, is indexed in 32 bits)
 #define CCSD_LG_HAD 16    // ... and on the attention dimension of its one-layer hodge branch (k_lg_hodge1: a Q | K row per thread in LDS)
+#define CCSD_LG_MAXHB 8   // ... on the HodgeBaselineLayers of ScoreNetworkA_Base_CC (k_lg_hb_*; PlanD::hb holds the first CCSD_MAXHL, PlanBuilder::hbx all)
+#define CCSD_LG_HBW 16    // ... and on their BaselineBlocks' hidden widths: one MFMA column tile (k_lg_hb_hid)
 
 struct MlpD {
     int n, in, hid, out;
@@ -108,8 +110,8 @@ struct PlanD {
     // ---- variants off the headline path, kept behind the fields every launch reads (scalar-cache footprint)
     int chan_rows;               // rows of the channel stack: max(a_fdim, g_nch)
     int f_blk;                   // ScoreNetworkF's general path from zero-padded 8x8 blocks behind the weight blob (-1: none)
-    int hb_L;                     // ScoreNetworkA_Base_CC: HodgeBaselineLayers (0 otherwise)
-    HodgeBaseD hb[CCSD_MAXHL];
+    int hb_L;                     // ScoreNetworkA_Base_CC: HodgeBaselineLayers (0 otherwise; above CCSD_MAXHL only on the tiled route,
+    HodgeBaseD hb[CCSD_MAXHL];    // whose kernels take their layer's descriptor as an argument: ccsd_plan::hbx)
     int o_hbw;                    // k_xa LDS: mlp_hodge weight blocks of both layers (2 * CCSD_MAXLIN * (16*16+16) floats)
     int o_hbg, o_hbd, hb_rows;    // k_xa LDS: hidden rows of layer 0 [cin][E][hid]; diagonals of layer 1's blocks [cin][E]; rows per chunk
     // HodgeAdjAttentionLayers 2.. (num_layers_h > 2; k_xa<., XA_GEN>), and the layout of the projections k_r2 hands over for
@@ -182,6 +184,7 @@ struct PlanBuilder {
     int xa_gch = 0;     // CCSD_XA_GCH: the channel stack in the HBM workspace first
     int verbose = 0;    // CCSD_VERBOSE
     int lg = 0;         // out: the plan takes the tiled graph-network route (ccsd_k_lg.h) instead of k_xa
+    HodgeBaseD hbx[CCSD_LG_MAXHB] = {};   // out: every HodgeBaselineLayer of ScoreNetworkA_Base_CC (the route's k_lg_hb_* launches)
     int take(int64_t n) {
         int o = cur;
         cur += (int)n;
@@ -281,8 +284,9 @@ static inline int round_ld(int rows) {  // node-row stride of the feature-major 
 // Why the tiled graph-network route (ccsd_k_lg.h) cannot serve a plan whose networks `p` holds (nullptr: it can).  It covers plans
 // with the plain ScoreNetworkX and a GCN-conv ScoreNetworkA whose edge MLPs are the 16-wide MFMA chains and whose final MLP is a
 // chained shape (fdim <= 64): graph-only ones, and combinatorial complexes (N <= 64) with ScoreNetworkA_CC and ONE
-// HodgeAdjAttentionLayer, whose hodge adjacency is diagonal (k_lg_hodge1).  ScoreNetworkX_GMH, conv = "MLP", ScoreNetworkA_Base_CC and
-// hodge stacks of two or more layers (the dense E x E layer) stay with k_xa.
+// HodgeAdjAttentionLayer, whose hodge adjacency is diagonal (k_lg_hodge1), or with ScoreNetworkA_Base_CC, 1 to CCSD_LG_MAXHB
+// HodgeBaselineLayers and BaselineBlocks at most CCSD_LG_HBW wide (k_lg_hb_*: the dense E x E layers tiled through the workspace).
+// ScoreNetworkX_GMH, conv = "MLP", wider BaselineBlocks and ScoreNetworkA_CC stacks of two or more layers stay with k_xa.
 // dynamic LDS of the route's per-node MLP kernel k_lg_nmlp for one MLP: 16 rows of its input and of two activations (bytes)
 static inline size_t lg_nmlp_lds_of(const MlpD& m) {
     const int wmax = m.hid > m.out ? m.hid : m.out;
@@ -294,9 +298,10 @@ static inline size_t lg_nmlp_lds(const PlanD& p) {
     return v;
 }
 static inline const char* ccsd_lg_ineligible(const ccsd_config_t* c, const PlanD* p) {
-    if (p->a_is_cc == 2) return "ScoreNetworkA_Base_CC (no HodgeBaselineLayer on the route)";
+    if (p->a_is_cc == 2 && (c->h_nhid > CCSD_LG_HBW || (c->h_num_layers > 1 && c->h_adim > CCSD_LG_HBW)))
+        return "ScoreNetworkA_Base_CC with BaselineBlocks wider than 16";
     if (p->h_L > 1) return "hodge stacks of two or more layers (the dense E x E hodge layer)";
-    if (c->is_cc && (p->a_is_cc != 1 || p->h_L != 1)) return "combinatorial-complex plans without ScoreNetworkA_CC";
+    if (c->is_cc && p->a_is_cc != 2 && (p->a_is_cc != 1 || p->h_L != 1)) return "combinatorial-complex plans without ScoreNetworkA_CC";
     if (p->h_L == 1 && p->hl[0].adim > CCSD_LG_HAD) return "hodge attention dimensions above 16";
     if (p->x_gmh) return "ScoreNetworkX_GMH";
     for (int l = 0; l < p->a_L; ++l) {
@@ -397,12 +402,12 @@ static inline size_t ccsd_build_plan(const ccsd_config_t* c, PlanD* p, PlanBuild
     p->h_L = 0; p->a_nch_hodge = 0; p->hb_L = 0;
     if (c->a_is_cc_net == 2) {
         if (!c->is_cc) { pb.fail(CCSD_ERR_INVALID, "ScoreNetworkA_Base_CC is only for combinatorial complexes"); return 0; }
-        if (c->h_num_layers < 1 || c->h_num_layers > 2) {
-            pb.fail(CCSD_ERR_UNSUPPORTED, "HIP path supports 1 or 2 HodgeBaselineLayers"); return 0; }
+        if (c->h_num_layers < 1 || c->h_num_layers > CCSD_LG_MAXHB) {
+            pb.fail(CCSD_ERR_UNSUPPORTED, "HIP path supports 1 to 8 HodgeBaselineLayers"); return 0; }
         p->hb_L = c->h_num_layers;
         int hch = c->a_c_init;
         for (int l = 0; l < p->hb_L; ++l) {
-            HodgeBaseD& h = p->hb[l];
+            HodgeBaseD& h = pb.hbx[l];
             const bool first = (l == 0), last = (l == p->hb_L - 1) && !first;
             h.cin = first ? c->a_c_init : c->h_c_hid;
             h.cout = last ? c->h_c_final : c->h_c_hid;
@@ -414,9 +419,12 @@ static inline size_t ccsd_build_plan(const ccsd_config_t* c, PlanD* p, PlanBuild
             h.w1t = pb.pcur; pb.pcur += h.cin * h.hid * E;
             const int hid = 2 * (h.cin > h.cout ? h.cin : h.cout);
             h.mh = pb.mlp(c->h_num_linears, h.cin, hid, h.cout);
-            if (first) pb.chainify(h.mh, CCSD_CHAIN_EDGE);       // the dense first layer evaluates it per (e, e') pair on MFMA
+            // a dense layer evaluates it per (e, e') pair on MFMA: the first one (k_xa, k_lg_hb_dense) and, on the tiled route, every other
+            // layer but the last (only stacks of more than two have such a layer: no plan k_xa serves moves)
+            if (first || l < p->hb_L - 1) pb.chainify(h.mh, CCSD_CHAIN_EDGE);
             if (h.cin > CCSD_FW || (c->h_num_linears > 1 && hid > CCSD_FW) || h.cout > CCSD_FW) {
                 pb.fail(CCSD_ERR_UNSUPPORTED, "HodgeBaselineLayer mlp_hodge wider than 16"); return 0; }
+            if (l < CCSD_MAXHL) p->hb[l] = h;
             hch += h.cout;
         }
         p->a_nch_hodge = hch;
@@ -503,6 +511,18 @@ static inline size_t ccsd_build_plan(const ccsd_config_t* c, PlanD* p, PlanBuild
         p->chan_rows = p->a_fdim;
         return nweights;            // (no k_xa layout: its LDS fields stay zero)
     }
+    // ScoreNetworkA_Base_CC with more than two HodgeBaselineLayers: k_xa's hodge branch is written for one or two, only the route serves
+    if (p->hb_L > CCSD_MAXHL) {
+        if (lg_reason) { pb.fail(CCSD_ERR_UNSUPPORTED, std::string("more than 2 HodgeBaselineLayers need the tiled graph-network route, which does not serve ") + lg_reason); return 0; }
+        pb.lg = 1;
+        p->ldn = round_ld(N);
+        p->chan_rows = p->a_fdim;
+        return nweights;
+    }
+    // ... and a dense HodgeBaselineLayer beyond E = 255 -- the envelope k_xa's dense hodge layers are built and tested in (ccsd_plan_create
+    // holds ScoreNetworkA_CC stacks to it; every shipped Base_CC geometry lies inside: E = 36 .. 190) -- takes the route where it is
+    // eligible: one workgroup per complex would walk the E^2 pairs alone (grid_small_Base_CC: E = 1176, a 148 KB k_xa layout)
+    if (p->hb_L > 1 && E > 255 && !lg_reason) pb.lg = 1;
     // (1 leaves combinatorial complexes on k_xa, as before the route served any of them: tests/golden/route_plans.json pins those plans)
     if (pb.lg_force && !lg_reason && (!c->is_cc || pb.lg_force >= 2)) pb.lg = 1;
 

@@ -1,10 +1,11 @@
 """Throughput of ccsd_grid_small_CC (N = 49, E = 1176, K = 18424) on the tiled graph-network route: ccsd_sampler_run on the MI355X at
-the batch and sampler of sample_grid_small_CC.yaml (8 complexes, Reverse + Langevin, snr 0.1, scale_eps 0.7).  Prints one JSON line:
-complexes/s, ms/step, the time per launch of the graph-network side (launch_lg: the k_lg_* kernels of one pass, k_lg_hodge1 among
+the batch and sampler of sample_grid_small_CC.yaml (8 complexes, Reverse + Langevin, snr 0.1, scale_eps 0.7); --arch base_cc: its
+ablation twin, the ScoreNetworkA_Base_CC of grid_small_Base_CC.yaml beside the same X and F networks (k_lg_hb_*).  Prints one JSON line:
+complexes/s, ms/step, the time per launch of the graph-network side (launch_lg: the k_lg_* kernels of one pass, the hodge branch among
 them) and of the rank-2 kernels (HIP events around every launch, in a run of their own), and the CPU restatement's (oracle) time
 for one PC step at the same batch.  bench.py measures the flagship workload; this tool covers a geometry it does not.
 
-    python tools/bench_cc_large_graph.py [--steps 20] [--warmup 3] [--batch 8] [--no-cpu]
+    python tools/bench_cc_large_graph.py [--arch cc|base_cc] [--steps 20] [--warmup 3] [--batch 8] [--no-cpu]
 """
 import argparse
 import json
@@ -22,7 +23,8 @@ from ccsd_amd.plan import rank2_dim  # noqa: E402
 from oracle import ccsd_oracle as O  # noqa: E402
 from tests.helpers import load_ckpt_np, make_flags  # noqa: E402
 
-CKPT = "cc_large/ccsd_grid_small_CC"                 # tests/golden/ckpt/: the EMA-applied weights the yaml samples with
+# tests/golden/ckpt/: the EMA-applied weights sample_grid_small_CC.yaml samples with; the constructed A-network of the Base_CC twin
+CKPTS = {"cc": "cc_large/ccsd_grid_small_CC", "base_cc": "base_cc_route/ccsd_grid_small_Base_CC"}
 SAMPLER = dict(predictor="Reverse", corrector="Langevin", snr=0.1, scale_eps=0.7)
 COUNTS = [49, 42, 36, 30, 25, 49, 35, 28]            # node counts of the grid_small training split
 NAMES = ("x", "adj", "rank2")
@@ -33,12 +35,13 @@ KERNELS = {"graph_network_pass": "k_xa", "k_gemm_p": "k_gemm_p", "k_gemm_h": "k_
 
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--arch", choices=sorted(CKPTS), default="cc")
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--batch", type=int, default=8)
     ap.add_argument("--no-cpu", action="store_true")
     a = ap.parse_args()
-    meta, parts = load_ckpt_np(CKPT)
+    meta, parts = load_ckpt_np(CKPTS[a.arch])
     cfg = meta["config"]
     d = cfg["data"]
     N, F, d_min, d_max = d["max_node_num"], d["max_feat_num"], d["d_min"], d["d_max"]
@@ -60,7 +63,7 @@ def main():
     eng.init_and_run(dflags, state, scratch, result, 1, 0, 0, a.steps)
     torch.cuda.synchronize()
     sec = time.perf_counter() - t0
-    out = {"workload": "ccsd_grid_small_CC", "N": N, "E": E, "K": K, "batch": B, "sampler": "Reverse+Langevin", "steps": a.steps,
+    out = {"workload": meta["name"], "N": N, "E": E, "K": K, "batch": B, "sampler": "Reverse+Langevin", "steps": a.steps,
            "complexes_per_s_at_1000_steps": B / (sec / a.steps * 1000.0), "ms_per_step": 1e3 * sec / a.steps,
            "loop_form": eng.query("loop_form")}
     # per-launch split (events around every launch break back-to-back dispatch: not part of the timed run above)

@@ -950,8 +950,86 @@ def grid_small_cc():
     print("grid_small_cc", name)
 
 
+# ScoreNetworkA_Base_CC on the tiled graph-network route (`python tools/make_golden.py base_cc_route`): no such checkpoints ship, the
+# A-networks come from the reference's constructor under a fixed seed (biases perturbed, as in the kat_* fixtures).  Kept in a folder
+# of its own below ckpt/, like CC_LARGE_CKPT.
+BASE_CC_CKPT = os.path.join(SHIPPED_CKPT, "base_cc_route")
+# the A-network of config/grid_small_Base_CC.yaml (its `num_layers_mlp: !` keeps the file itself from loading)
+GRID_BASE_ADJ = dict(model_type="ScoreNetworkA_Base_CC", is_cc=True, max_feat_num=5, max_node_num=49, nhid=24, num_layers=6, num_linears=2,
+                     c_init=2, c_hid=4, c_final=4, adim=24, num_heads=4, conv="GCN", use_bn=False, d_min=3, d_max=3, nhid_h=2,
+                     num_layers_h=2, num_linears_h=1, c_hid_h=2, c_final_h=2, hidden_h=2)
+
+
+def _constructed(params, seed):
+    """A network from the reference's constructor under torch.manual_seed(seed), biases drawn N(0, 0.2) (the reference zeroes them)."""
+    ref_cc.default_mask.cache_clear()            # (see build_models)
+    torch.manual_seed(seed)
+    m = ref_loader.load_model(params)
+    for k, p_ in m.named_parameters():
+        if k.endswith("bias"):
+            p_.data.normal_(0, 0.2)
+    return m.eval()
+
+
+def _write_constructed(name, cfg, params, state_dicts, note):
+    """A checkpoint-shaped fixture under BASE_CC_CKPT (json + one npz below MAX_FIXTURE), and the dict build_models takes."""
+    os.makedirs(BASE_CC_CKPT, exist_ok=True)
+    arrays = {f"{p}/{k}": v.detach().cpu().numpy().astype(np.float32) for p, sd in state_dicts.items() for k, v in sd.items()}
+    path = os.path.join(BASE_CC_CKPT, name + ".npz")
+    np.savez_compressed(path, **arrays)
+    assert os.path.getsize(path) <= MAX_FIXTURE, (name, os.path.getsize(path))
+    meta = {"name": name, "source": note, "is_cc": True, "config": plain(cfg), "files": [os.path.relpath(path, SHIPPED_CKPT)]}
+    meta.update({f"params_{p}": plain(v) for p, v in params.items()})
+    with open(os.path.join(BASE_CC_CKPT, name + ".json"), "w") as f:
+        json.dump(meta, f, indent=1, sort_keys=True)
+    ck = {"model_config": refshim.EasyDict(cfg)}
+    for p in params:
+        ck[f"params_{p}"], ck[f"{p}_state_dict"] = params[p], state_dicts[p]
+    return ck
+
+
+def base_cc_route():
+    """(a) The A-network of grid_small_Base_CC.yaml (N = 49, two HodgeBaselineLayers) beside the X and F networks of the
+    cc_large/ccsd_grid_small_CC fixture: g1 forwards at B = 2 (counts 49 and 30).  (b) The networks of ego_small_Base_CC.yaml (three
+    HodgeBaselineLayers) at N = 7, d 3..5 (E = 21, K = 91): g1 forwards and two steps of the yaml's sampler (Euler, no corrector) at 4
+    scales; at N = 12, d 3..4 (E = 66: four row tiles + 2): g1 forwards."""
+    import yaml
+
+    with open(os.path.join(CC_LARGE_CKPT, "ccsd_grid_small_CC.json")) as f:
+        gm = json.load(f)
+    z = {}
+    for fname in gm["files"]:
+        a = np.load(os.path.join(SHIPPED_CKPT, fname))
+        z.update({k: a[k] for k in a.files})
+    sds = {p: {k.split("/", 1)[1]: torch.from_numpy(v) for k, v in z.items() if k.startswith(p + "/")} for p in ("x", "rank2")}
+    sds["adj"] = _constructed(GRID_BASE_ADJ, 4901).state_dict()
+    cfg = dict(gm["config"], model=dict(gm["config"]["model"], adj="ScoreNetworkA_Base_CC", c_hid=4, hidden_h=2))
+    name = "ccsd_grid_small_Base_CC"
+    ck = _write_constructed(name, cfg, {"x": gm["params_x"], "adj": GRID_BASE_ADJ, "rank2": gm["params_rank2"]}, sds,
+                            "A-network: reference constructor, torch.manual_seed(4901); X and F networks: cc_large/ccsd_grid_small_CC")
+    g1_network_forwards(name, ck, True, 2, [49, 30], summarize_large=True, rank2_score=False)
+
+    with open(os.path.join(refshim.REFERENCE_ROOT, "config", "ego_small_Base_CC.yaml")) as f:
+        ego = yaml.safe_load(f)
+    smp = dict(ego["sampler"], sde_override={p: {"num_scales": 4} for p in ("x", "adj", "rank2")})
+    for N, d_max, counts, seed in ((7, 5, [7, 5, 0, 1, 2], 701), (12, 4, [12, 7, 0, 1, 2], 1201)):
+        cfg = dict(ego, data=dict(ego["data"], max_node_num=N, d_max=d_max))
+        px, pa, pf = ref_loader.load_model_params(refshim.EasyDict(cfg), is_cc=True)
+        params = {"x": dict(px), "adj": dict(pa), "rank2": dict(pf)}
+        sds = {p: _constructed(params[p], seed + i).state_dict() for i, p in enumerate(("x", "adj", "rank2"))}
+        name = f"ccsd_ego_small_Base_CC_n{N}"
+        ck = _write_constructed(name, cfg, params, sds, f"reference constructors, torch.manual_seed({seed} + part index)")
+        g1_network_forwards(name, ck, True, len(counts), counts, summarize_large=True)
+        if N == 7:
+            g5_pc_runs(name, ck, True, 2, [7, 5], smp, {"n4_first2": (None, 2)}, seed=12)
+    print("base_cc_route done")
+
+
 def main():
     only = set(sys.argv[1:])
+    if only == {"base_cc_route"}:
+        base_cc_route()
+        return
     if only == {"grid_small_cc"}:
         grid_small_cc()
         return
