@@ -48,7 +48,7 @@ static inline int fnet_width(const PlanD& p) {
 //                                              Lost on every workload (xiv); kept because k_xa<false, XA_HB> without the
 //                                              mode test needs 104 bytes of scratch instead of 100 (profiles/README.md r08)
 //   CCSD_LARGE_GRAPH=1|2 lg_force              tiled graph-network route for any eligible graph-only plan (1), (PlanBuilder)  tests (emu + gpu)
-//                                              for eligible combinatorial-complex plans too (2: ScoreNetworkA_CC with one hodge layer, ScoreNetworkA_Base_CC)
+//                                              for eligible combinatorial-complex plans too (2: ScoreNetworkA_CC, ScoreNetworkA_Base_CC)
 //   CCSD_XA_PASS=<n>     xa_pass               first k_xa LDS budget candidate tried            (PlanBuilder)  tests (emu + gpu)
 //   CCSD_XA_GCH          xa_gch                channel stack in the HBM workspace first         (PlanBuilder)  tests (emu + gpu)
 //   CCSD_NO_MLP_WT       no_mlp_wt             no transposed copies of the non-chained MLPs     (PlanBuilder)  tests (gpu)
@@ -96,7 +96,8 @@ struct Route {
     size_t r2_lds = 0;
     // general hodge stack: more than two HodgeAdjAttentionLayers whose later projections cannot be folded into rank2's (a non-affine
     // mlp_value, or no fused rank-2 kernel for the geometry): R_l is materialised layer by layer (k_hodge_value) from the dense hodge
-    // adjacencies k_xa<., XA_GEN> dumps (launch_xa); CCSD_HODGE_GENERAL forces it for any plan with more than two layers
+    // adjacencies k_xa<., XA_GEN> dumps (launch_xa); CCSD_HODGE_GENERAL forces it for any plan with more than two layers, and plans on
+    // the tiled route always take it (launch_lg: the dense adjacencies are in its workspace buffer already)
     int h_general = 0;
     int geo = 0;                    // index of the plan's (E, K) in CCSD_GEO_LIST (0: run-time values)
     int p0 = -1;                    // index of the narrow layer-0 projection's k_gemm_p0 in CCSD_P0_LIST (-1: wide, k_gemm_p)
@@ -118,6 +119,7 @@ struct ccsd_plan {
     ccsd_config_t cfg;
     PlanD h;                    // host copy
     HodgeBaseD hbx[CCSD_LG_MAXHB];   // every HodgeBaselineLayer of ScoreNetworkA_Base_CC (h.hb holds the first two): arguments of the k_lg_hb_* launches
+    MlpD hdm[CCSD_MAXHL + CCSD_MAXHLX];   // route plans with two or more HodgeAdjAttentionLayers: the chained mlp_attention of k_lg_hd_dense (PlanBuilder::hdm)
     PlanD* d = nullptr;         // device copy
     float* w = nullptr;         // device weights
     float* wp = nullptr;        // device: zero-padded copies of the chain MLPs' linears (mlp_chain_tile)
@@ -241,7 +243,7 @@ static int resolve_route(ccsd_plan* pl) {
         for (int l = 0; l + 1 < p.h_L; ++l) affine_values = affine_values && ccsd_hl(p, l).mval.n == 1;
         // (the folded route -- k_r2 hands over one consolidated projection, k_xa chains the M_j -- is built and tested for up to four layers;
         // r2_lds keeps reporting what the fused kernel would have taken)
-        if (!affine_values || !fused || p.h_L > 4 || k.hodge_general) { r.h_general = 1; fused = false; r.r2 = nullptr; }
+        if (!affine_values || !fused || p.h_L > 4 || k.hodge_general || r.lg) { r.h_general = 1; fused = false; r.r2 = nullptr; }
     }
     // element-wise rank-2 side (k_ew1): affine ScoreNetworkF without a Hodge Laplacian term (cnum = 1), tiled path, PC samplers
     const bool ew1 = c.is_cc && !fused && aff && p.f_cnum == 1 && !s4;
@@ -386,6 +388,7 @@ extern "C" int ccsd_plan_create(const ccsd_config_t* cfg, const float* weights, 
     if (pb.status != CCSD_OK) { delete pl; return set_err(pb.status, pb.err); }
     pl->rt.lg = pb.lg;
     memcpy(pl->hbx, pb.hbx, sizeof(pl->hbx));
+    memcpy(pl->hdm, pb.hdm, sizeof(pl->hdm));
     pl->h.geo_off = k.geo_off;
     pl->npacked = (size_t)pb.pcur;
     if (pl->nweights != n_weights) {
@@ -465,6 +468,7 @@ extern "C" int ccsd_plan_create(const ccsd_config_t* cfg, const float* weights, 
             }
         }
         ccsd_pack_mlp(pl->h.a_fin, weights, packed.data());
+        if (pl->rt.lg) for (int l = 0; l + 1 < pl->h.h_L; ++l) ccsd_pack_mlp(pl->hdm[l], weights, packed.data());
         for (int l = 0; l < pl->h.h_L; ++l) {   // Wcat^T of the hodge projections for k_r2
             const HodgeLayerD& h = ccsd_hl(pl->h, l);
             const int Kp = (K + 31) & ~31;
@@ -474,7 +478,7 @@ extern "C" int ccsd_plan_create(const ccsd_config_t* cfg, const float* weights, 
         PC(rt_malloc((void**)&pl->wp, packed.size() * sizeof(float)));
         PC(rt_h2d(pl->wp, packed.data(), packed.size() * sizeof(float)));
     }
-    if (pl->h.h_L > 1) {
+    if (pl->h.h_L > 1 && !pl->rt.lg) {     // (k_xa's pair table; the tiled route walks tiles)
         if (E > 255) { ccsd_plan_destroy(pl); return set_err(CCSD_ERR_UNSUPPORTED, "dense hodge layer needs E <= 255"); }
         std::vector<unsigned char> hp;
         for (int e = 0; e < E; ++e)
@@ -501,6 +505,9 @@ extern "C" int ccsd_plan_create(const ccsd_config_t* cfg, const float* weights, 
             for (int l = 0; l + 1 < pl->h.hb_L; ++l) if (lg_hb_dense_lds(pl->hbx[l]) > v) v = lg_hb_dense_lds(pl->hbx[l]);
             if (v > 64 * 1024) PC(rt_set_max_dyn_smem((const void*)k_lg_hb_dense, v));
         }
+        // (k_lg_hd_dense stays below 64 KB: at most 8 channels of 2 x 16 rows of 33 floats + 256 pairs)
+        if (r.lg && r.h_general && (size_t)E * (E > 128 ? 32 : 64) * 4 > 64 * 1024)
+            PC(rt_set_max_dyn_smem((const void*)k_hodge_value, (size_t)E * (E > 128 ? 32 : 64) * 4));
 #ifndef CCSD_EMU
         if (r.hp_full_modes) {      // k_hp_full: 66.6 KB of dynamic LDS
             PC(rt_set_max_dyn_smem((const void*)k_hp_full<CCSD_FULL_E, CCSD_FULL_K, 1>, HP_FULL_LDS));
@@ -552,6 +559,11 @@ struct Workspace {
     // output is written); per-sample strides in floats
     float *lg_hbg, *lg_hbH;
     size_t lg_hbg_stride, lg_hbH_stride;
+    // ... ScoreNetworkA_CC stacks of two or more layers: the Q | K rows of a layer [B][cin][E][2 adim]; D^-1/2 of a dense input
+    // [B][cin][E]; the per-edge factors of a raw P_1 [B][2][E]; the dense output [B][cout][E][E] of a layer but the last (ONE buffer, see
+    // ccsd_k_lg.h; the general stack's hgH where that is carved); per-sample strides in floats
+    float *lg_hdq, *lg_hdd, *lg_hdpc, *lg_hdH;
+    size_t lg_hdq_stride, lg_hdH_stride;
     ccsd_state_t third;             // LOOP_LANGEVIN_MULTI with more than one inner iteration: the second corrector iterate of ccsd_sampler_run
     size_t bytes;
     MaskTab masks() const { return MaskTab{mfr, mfl, Kp, Ep}; }
@@ -635,6 +647,21 @@ static Workspace carve_ws(const ccsd_plan* pl, int B, void* base) {
             w.lg_hbg_stride = g; w.lg_hbH_stride = hd;
             w.lg_hbg = (float*)take((size_t)B * g * 4);
             w.lg_hbH = (float*)take((size_t)B * hd * 4);
+        }
+        if (p.h_L > 1) {
+            size_t q = 0, d = 0, hd = 0;
+            for (int l = 0; l < p.h_L; ++l) {
+                const HodgeLayerD& h = ccsd_hl(p, l);
+                if ((size_t)h.cin * E * 2 * h.adim > q) q = (size_t)h.cin * E * 2 * h.adim;
+                if (l > 0 && (size_t)h.cin * E > d) d = (size_t)h.cin * E;
+                if (l + 1 < p.h_L && (size_t)h.cout * E * E > hd) hd = (size_t)h.cout * E * E;
+            }
+            w.lg_hdq_stride = q;
+            w.lg_hdq = (float*)take((size_t)B * q * 4);
+            w.lg_hdd = (float*)take((size_t)B * d * 4);
+            w.lg_hdpc = (float*)take((size_t)B * 2 * E * 4);
+            if (pl->rt.h_general) { w.lg_hdH = w.hgH; w.lg_hdH_stride = w.hg_hstride; }
+            else { w.lg_hdH_stride = hd; w.lg_hdH = (float*)take((size_t)B * hd * 4); }
         }
     }
     if (pl->rt.loop == LOOP_LANGEVIN_MULTI && pl->cfg.n_corr_steps > 1) {      // (last: no plan with n_steps == 1 moves)
@@ -823,9 +850,10 @@ static int launch_lg(const ccsd_plan* pl, int B, XaArgs& xa, NoiseArgs& na, Work
 static int launch_xa(const ccsd_plan* pl, int B, XaArgs& xa, NoiseArgs& na, const Pass& ps, Workspace& w, void* stream, bool set_b = false) {
     const Route& rt = pl->rt;
     xa.P0 = set_b ? w.P0b : w.P0;
+    xa.P1 = set_b ? w.P1b : w.P1; xa.U1 = set_b ? w.U1b : w.U1; xa.p1_raw = ps.p1_raw;
     if (rt.lg) return launch_lg(pl, B, xa, na, w, stream);
-    xa.P1 = set_b ? w.P1b : w.P1; xa.U1 = set_b ? w.U1b : w.U1; xa.chan_ws = w.chan;
-    xa.p1_raw = ps.p1_raw; xa.dbg = pl->dbg ? pl->dbg + 32 : nullptr;
+    xa.chan_ws = w.chan;
+    xa.dbg = pl->dbg ? pl->dbg + 32 : nullptr;
     int xa_threads;
     const XaEntry* inst = xa_launch(rt, B, &xa_threads);
     prof_mark(const_cast<ccsd_plan*>(pl), KID_XA, stream);
@@ -870,7 +898,8 @@ static int launch_xa(const ccsd_plan* pl, int B, XaArgs& xa, NoiseArgs& na, cons
 }
 // Tiled graph-network route (ccsd_k_lg.h): ScoreNetworkX on (xX, adjX) and ScoreNetworkA on (xA, adjA) as a sequence of launches over
 // the workspace (LgWs fields of Workspace), then the epilogues of k_xa's contract (mode, coefficients, mean pointers, norm2[b][4]).
-// Combinatorial-complex plans: ScoreNetworkA_CC with one hodge layer (xa.P0 holds the layer-0 hodge projections launch_p / k_r2 left), or
+// Combinatorial-complex plans: ScoreNetworkA_CC (xa.P0 holds the layer-0 hodge projections launch_p / k_r2 left; two layers: xa.P1 the
+// second layer's, finished or as k_r2's raw factors with xa.U1; three or more: the general hodge stack, whose layer loop runs here), or
 // ScoreNetworkA_Base_CC (its hodge branch reads only the adjacency powers).
 // Plans on this route never fuse the corrector apply into this pass (resolve_route), so a CorrFuse here is an error.
 static int launch_lg(const ccsd_plan* pl, int B, XaArgs& xa, NoiseArgs& na, Workspace& w, void* stream) {
@@ -907,6 +936,58 @@ static int launch_lg(const ccsd_plan* pl, int B, XaArgs& xa, NoiseArgs& na, Work
             if (!xa.P0) return set_err(CCSD_ERR_RUNTIME, "tiled graph-network route: no hodge projections");
             CCSD_LAUNCH(k_lg_hodge1, dim3(grid_for(p.E + N, 256), B), blk, 0, stream, p.hl[0], 1.0f / (float)sqrt((double)p.K), (const float*)pl->w,
                         (const unsigned char*)pl->edges, xa.P0, w.lg_S, ss, p.a_nch_graph, N, p.E, xa.flags);
+        }
+        if (p.h_L > 1) {
+            // hodge branch of ScoreNetworkA_CC, two or more layers (k_lg_hd_*): layer 0's Q | K rows per edge; per layer l but the last its
+            // dense E x E output H^(l+1) (the diagonal goes to the stack), D^-1/2 of it and the next layer's Q | K rows from it and P_(l+1);
+            // the last layer on its diagonal only.  General stack (three or more layers; launch_p left P_0, P_1 and R_1): while H^j is in
+            // the buffer, R_(j+1) = fl fr mlp_value_j(cat_c H^j_c R_j) (k_hodge_value) and P_(j+1) = R_(j+1) Wcat_(j+1) (k_gemm_p) for the layer behind
+            const Route& rtp = pl->rt;
+            if (!xa.P0 || (!rtp.h_general && !xa.P1)) return set_err(CCSD_ERR_RUNTIME, "tiled graph-network route: no hodge projections");
+            if (p.h_L > 2 && !rtp.h_general) return set_err(CCSD_ERR_RUNTIME, "tiled graph-network route: more than two hodge layers need the general hodge stack");
+            const int E = p.E, et = (E + 15) / 16, rows = B * E;
+            const unsigned char* edges = (const unsigned char*)pl->edges;
+            const float* wts = (const float*)pl->w;
+            const float rks = 1.0f / (float)sqrt((double)p.K);
+            const long long qs = (long long)w.lg_hdq_stride, hs = (long long)w.lg_hdH_stride;
+            int ch = p.a_nch_graph + p.a_cinit;
+            CCSD_LAUNCH(k_lg_hd_qk0, dim3(grid_for(E + N, 256), B), blk, 0, stream, p.hl[0], p.a_nch_hodge, wts, edges, xa.P0, w.lg_S, ss, p.a_nch_graph, N, E,
+                        w.lg_hdq, qs);
+            for (int j = 1; j < p.h_L; ++j) {
+                const HodgeLayerD& hp = ccsd_hl(p, j - 1);
+                const HodgeLayerD& h = ccsd_hl(p, j);
+                CCSD_LAUNCH(k_lg_hd_dense, dim3(et * (et + 1) / 2, B), blk, lg_hd_dense_lds(hp), stream, hp, pl->hdm[j - 1], rks, (const float*)pl->wp, edges,
+                            (const float*)w.lg_hdq, qs, w.lg_hdH, hs, w.lg_S, ss, ch, N, E, xa.flags);
+                ch += hp.cout;
+                LAUNCH_CHECK();
+                if (rtp.h_general && j + 1 < p.h_L) {
+                    const HodgeLayerD& hn = ccsd_hl(p, j + 1);
+                    float* Rn = w.hgR[j & 1];
+                    const int cw = E > 128 ? 32 : 64;
+                    CCSD_LAUNCH(k_hodge_value, dim3((p.K + cw - 1) / cw, B), dim3(CCSD_NTHREADS), (size_t)E * cw * 4, stream, (const float*)w.hgR[(j - 1) & 1],
+                                (const float*)w.lg_hdH, (int)hs, (const float*)nullptr, wts, h.mval, h.cin, Rn, E, p.K, cw,
+                                (const unsigned long long*)w.offbits, edges, (const unsigned long long*)pl->cells);
+                    LAUNCH_CHECK();
+                    CCSD_LAUNCH(k_gemm_p, dim3((hn.wc + T_BN - 1) / T_BN, (rows + T_BM - 1) / T_BM, 1), dim3(CCSD_NTHREADS), 0, stream, (const float*)Rn,
+                                wts, w.hgP[j], rows, E, p.K, hn.wc, hn.wcat, 0, hn.mval, hn.cin, (const float*)nullptr,
+                                (const unsigned long long*)w.offbits, edges, (const unsigned long long*)pl->cells, p.K);
+                    LAUNCH_CHECK();
+                }
+                const bool raw = j == 1 && !rtp.h_general && xa.p1_raw;
+                LgHdRaw rw{};
+                if (raw) {
+                    if (!xa.U1) return set_err(CCSD_ERR_RUNTIME, "tiled graph-network route: raw hodge projections without their u_1");
+                    rw = LgHdRaw{wts, (const float*)w.lg_S, xa.flags, edges, w.lg_hdpc, ss, N, p.hl[0].cin, p.hl[0].mval.w[0], p.hl[0].mval.b[0]};
+                }
+                const float* Pj = rtp.h_general ? (const float*)w.hgP[j - 1] : xa.P1;
+                CCSD_LAUNCH(k_lg_hd_dis, dim3(grid_for((long long)h.cin * E, 256), B), blk, 0, stream, (const float*)w.lg_hdH, hs, h.cin, E, w.lg_hdd, rw);
+                CCSD_LAUNCH(k_lg_hd_conv, dim3((et + 3) / 4, h.cin, B), blk, 0, stream, h, wts, (const float*)w.lg_hdH, hs, (const float*)w.lg_hdd, Pj, h.wc,
+                            raw ? (const float*)w.lg_hdpc : (const float*)nullptr, raw ? xa.U1 : (const float*)nullptr, E, w.lg_hdq, qs);
+                LAUNCH_CHECK();
+            }
+            CCSD_LAUNCH(k_lg_hd_diag, dim3(grid_for(E, 256), B), blk, 0, stream, ccsd_hl(p, p.h_L - 1), rks, wts, edges, (const float*)w.lg_hdq, qs, w.lg_S, ss,
+                        ch, N, E, xa.flags);
+            LAUNCH_CHECK();
         }
         if (p.hb_L) {
             // hodge branch of ScoreNetworkA_Base_CC (k_lg_hb_*): input channels and layer 0's hidden rows; per layer but the last its dense

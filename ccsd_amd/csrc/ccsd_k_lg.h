@@ -1,15 +1,17 @@
 // ccsd_k_lg.h -- the tiled graph-network path (k_lg_*): ScoreNetworkX + ScoreNetworkA for plans whose per-graph working set does not
 // fit one CU's LDS (graph-only plans with N > 64, or k_xa's layout fails; CCSD_LARGE_GRAPH=1 forces it for any eligible graph-only
 // plan), and for combinatorial complexes (N <= 64) without a k_xa layout (or under CCSD_LARGE_GRAPH=2, which forces every eligible
-// plan): ScoreNetworkA_CC with ONE hodge layer, and ScoreNetworkA_Base_CC with 1 to 8 HodgeBaselineLayers (more than two: always here).
+// plan): ScoreNetworkA_CC with 1 to 8 HodgeAdjAttentionLayers (two or more: E <= CCSD_LG_HD_MAXE, and always here beyond E = 255), and
+// ScoreNetworkA_Base_CC with 1 to 8 HodgeBaselineLayers (more than two: always here).
 // Part of the kernel source of libccsd_hip.so (see ccsd_kernels.h for the map).
 //
 // State lives in the HBM workspace (carve_ws, LgWs in ccsd_api.h) and every phase is a launch of its own that tiles each graph over
 // many workgroups.  The decomposition of one forward (launch_lg):
 //   ScoreNetworkX   k_lg_dis (D^-1/2 of adjX) ; per GCN layer: k_lg_xw (Y = D^-1/2 X W), k_lg_gcn (tanh(D^-1/2 A' Y + b) into the
 //                   concatenation) ; k_lg_nmlp (final MLP per node, mask_x)
-//   ScoreNetworkA   k_lg_pow (channel stack [A, A^2, ...]) ; ScoreNetworkA_CC: k_lg_hodge1 (the hodge channels, behind the graph
-//                   channels of the stack) ; ScoreNetworkA_Base_CC: k_lg_hb_in, per layer but the last k_lg_hb_dense + k_lg_hb_hid,
+//   ScoreNetworkA   k_lg_pow (channel stack [A, A^2, ...]) ; ScoreNetworkA_CC, one hodge layer: k_lg_hodge1 (the hodge channels, behind the
+//                   graph channels of the stack) ; two or more: k_lg_hd_qk0, per layer but the last k_lg_hd_dense + k_lg_hd_dis +
+//                   k_lg_hd_conv, k_lg_hd_diag (the dense E x E layers tiled through the workspace) ; ScoreNetworkA_Base_CC: k_lg_hb_in, per layer but the last k_lg_hb_dense + k_lg_hb_hid,
 //                   k_lg_hb_diag (the same channels from the HodgeBaselineLayers) ; per AttentionLayer: k_lg_dis, k_lg_xw (Q | K | V columns side by side),
 //                   k_lg_gcn, k_lg_nmlp (multi_channel, mask_x, tanh), k_lg_att (head-mean tanh(Q K^T / sqrt(fout)), symmetrised),
 //                   k_lg_edge (edge MLP on [att_c | adj_c] per entry, MFMA: mlp_chain_tile), k_lg_sym (out + out^T, mask_adjs) ;
@@ -44,6 +46,26 @@ __global__ void k_lg_pow(const float* __restrict__ adj, float* __restrict__ S, l
 __global__ void k_lg_hodge1(HodgeLayerD h, float rks, const float* __restrict__ w, const unsigned char* __restrict__ edges,
                             const float* __restrict__ P0, float* __restrict__ S, long long sstride, int ch0, int N, int E,
                             const float* __restrict__ flags);
+// per-edge factors of P_1 = fl (s Q_1 + b u_1) when k_r2 delivered the raw Q_1, u_1 (XaArgs::p1_raw; k_xa's hodge_early): k_lg_hd_dis writes
+// pc[b][0][e] = fl s[e], pc[b][1][e] = fl b, s = sum_c w_c a_c[e] over the first layer's linear mlp_value (pc == nullptr: nothing to do)
+struct LgHdRaw {
+    const float *w, *S, *flags;
+    const unsigned char* edges;
+    float* pc;
+    long long sstride;
+    int N, cin0, mw, mb;
+};
+__global__ void k_lg_hd_qk0(HodgeLayerD h, int nch, const float* __restrict__ w, const unsigned char* __restrict__ edges, const float* __restrict__ P0,
+                            float* __restrict__ S, long long sstride, int ch0, int N, int E, float* __restrict__ QK, long long qstride);
+__global__ void k_lg_hd_dense(HodgeLayerD h, MlpD matt, float rks, const float* __restrict__ wp, const unsigned char* __restrict__ edges,
+                              const float* __restrict__ QK, long long qstride, float* __restrict__ Hout, long long hstride, float* __restrict__ S,
+                              long long sstride, int ch0, int N, int E, const float* __restrict__ flags);
+__global__ void k_lg_hd_dis(const float* __restrict__ Hin, long long hstride, int cin, int E, float* __restrict__ dis, LgHdRaw raw);
+__global__ void k_lg_hd_conv(HodgeLayerD h, const float* __restrict__ w, const float* __restrict__ Hin, long long hstride, const float* __restrict__ dis,
+                             const float* __restrict__ P, int ldp, const float* __restrict__ pc, const float* __restrict__ U, int E,
+                             float* __restrict__ QK, long long qstride);
+__global__ void k_lg_hd_diag(HodgeLayerD h, float rks, const float* __restrict__ w, const unsigned char* __restrict__ edges, const float* __restrict__ QK,
+                             long long qstride, float* __restrict__ S, long long sstride, int ch0, int N, int E, const float* __restrict__ flags);
 __global__ void k_lg_hb_in(HodgeBaseD h, int nch, const float* __restrict__ w, const unsigned char* __restrict__ edges, float* __restrict__ S,
                            long long sstride, int ch0, int N, int E, float* __restrict__ G, long long gstride);
 __global__ void k_lg_hb_dense(HodgeBaseD h, const float* __restrict__ w, const float* __restrict__ wp, const unsigned char* __restrict__ edges,
@@ -75,6 +97,8 @@ __global__ void k_lg_epi(const float* __restrict__ xnet, const float* __restrict
 // lanes along an edge index read 16 banks), their b2, and mlp_hodge's input [cin][256 pairs]
 static inline __host__ __device__ int lg_hb_row_ld(int hid) { return hid | 1; }
 static inline size_t lg_hb_dense_lds(const HodgeBaseD& h) { return ((size_t)4 * h.cin * 16 * lg_hb_row_ld(h.hid) + 32 * h.cin + 256 * h.cin) * 4; }
+// k_lg_hd_dense's: the Q | K rows of the tile's 16 + 16 edges per channel (the same odd row stride) and mlp_attention's input [cin][256 pairs]
+static inline size_t lg_hd_dense_lds(const HodgeLayerD& h) { return ((size_t)2 * h.cin * 16 * lg_hb_row_ld(2 * h.adim) + 256 * h.cin) * 4; }
 
 #if defined(CCSD_LG_UNIT) || defined(CCSD_EMU)
 // per-thread work items of a CCSD_LG_TB-sized tile: one per thread on the GPU, the whole tile in the emulation's one thread
@@ -387,20 +411,52 @@ __global__ __launch_bounds__(CCSD_LG_TB) void k_lg_epi(const float* __restrict__
         if (xa.do_a) { o[1] = v[1]; o[3] = v[3]; }
     }
 }
-// The hodge branch of ScoreNetworkA_CC with ONE HodgeAdjAttentionLayer (ScoreNetwork_A_CC.py:295-316; the oracle's score_network_a_cc),
-// k_xa's h_L == 1 branch with the same expressions.  adj_to_hodgedual makes the hodge adjacency of channel c diagonal with the upper
-// triangle of the adjacency power c on it (a_c[e] = S[c][i][j], e = (i, j), i < j), DenseHCNConv on a diagonal matrix is a row scaling
-// of the layer-0 projection P_0 = F Wcat_0 ([B][E][wc], left by the rank-2 side), and hodgedual_to_adj reads only the diagonal of the
-// layer's output: everything is arithmetic per edge.  Written at (i, j) and (j, i) of the stack: rows ch0 .. ch0 + cin the hodge
-// adjacency a_c itself, the next cout rows 2 tanh(fl^2 mlp_attention(head-mean logits)).  The work items behind the E edges are the N
-// diagonal entries of those rows: zero (nothing is scattered there, and the workspace is not cleared).
+// ---- The hodge branch of ScoreNetworkA_CC (ScoreNetwork_A_CC.py:295-316; the oracle's score_network_a_cc), k_xa's with the same
+// expressions.  adj_to_hodgedual makes the hodge adjacency of channel c diagonal with the upper triangle of the adjacency power c on it
+// (a_c[e] = S[c][i][j], e = (i, j), i < j), DenseHCNConv on a diagonal matrix is a row scaling of the layer-0 projection P_0 = F Wcat_0
+// ([B][E][wc], left by the rank-2 side), and hodgedual_to_adj reads only the diagonal of every layer's output.  The two pieces every
+// stack is made of, stated once:
+
+// the first layer's Q | K row of channel c of one edge: g a g P_0[e][block c] + b, g = rsqrt(max(1, a)) (no self-loop: dense_hcn)
+CCSD_DEV void lg_hd_qk0_row(const HodgeLayerD& h, const float* __restrict__ w, const float* __restrict__ pr, int c, float a, float* q) {
+    const int qw = 2 * h.adim;
+    const float g = 1.0f / sqrtf(fmaxf(a, 1.f));
+    for (int d = 0; d < qw; ++d) q[d] = fmaf(g * a * g, pr[c * qw + d], w[h.bcat + c * qw + d]);
+}
+// a layer's output on the diagonal, from the Q | K rows qrow(c) of one edge: head-mean logits -> mlp_attention (zero-padded blocks in
+// LDS) -> mask -> tanh -> + transpose, into rows Ho[0 .. cout) of the stack at (i, j) and (j, i)
+template <class QROW>
+CCSD_DEV void lg_hd_diag_edge(const HodgeLayerD& h, float rks, const float* s_hw, QROW qrow, float fh, float* Ho, int NN, size_t ij, size_t ji) {
+    float in[CCSD_SMALLW], out[CCSD_SMALLW];
+#pragma unroll
+    for (int c = 0; c < CCSD_SMALLW; ++c) {
+        float sacc = 0.f;
+        if (c < h.cin) {
+            const float* q = qrow(c);
+            sacc = attn_logits(q, q + h.adim, h.nchunk, h.dsplit, rks) * (1.0f / (float)h.nchunk);
+        }
+        in[c] = sacc;
+    }
+    small_mlp_lds<CCSD_SMALLW>(s_hw, h.matt.n, in, out);     // mlp_attention -> mask -> tanh -> + transpose
+#pragma unroll
+    for (int o = 0; o < CCSD_SMALLW; ++o)
+        if (o < h.cout) {
+            const float tv = tanh_f(out[o] * fh * fh);
+            Ho[(size_t)o * NN + ij] = tv + tv;
+            Ho[(size_t)o * NN + ji] = tv + tv;
+        }
+}
+
+// ONE HodgeAdjAttentionLayer: everything is arithmetic per edge.  Written at (i, j) and (j, i) of the stack: rows ch0 .. ch0 + cin the
+// hodge adjacency a_c itself, the next cout rows 2 tanh(fl^2 mlp_attention(head-mean logits)).  The work items behind the E edges are
+// the N diagonal entries of those rows: zero (nothing is scattered there, and the workspace is not cleared).
 // grid: (grid-stride over E + N, B)
 __global__ __launch_bounds__(CCSD_LG_TB) void k_lg_hodge1(HodgeLayerD h, float rks, const float* __restrict__ w, const unsigned char* __restrict__ edges,
                                                          const float* __restrict__ P0, float* __restrict__ S, long long sstride, int ch0, int N,
                                                          int E, const float* __restrict__ flags) {
     __shared__ float s_hw[CCSD_MAXLIN * CCSD_HWBLK];                  // zero-padded mlp_attention weight blocks
     __shared__ float s_q[CCSD_LG_TB][2 * CCSD_LG_HAD + 1];            // the calling thread's Q | K row of one channel
-    const int b = blockIdx.y, NN = N * N, qw = 2 * h.adim;
+    const int b = blockIdx.y, NN = N * N;
     stage_mlp_blocks(h.matt, w, s_hw, (int)threadIdx.x, (int)blockDim.x);
     __syncthreads();
     float* Sb = S + (size_t)b * sstride;
@@ -416,29 +472,245 @@ __global__ __launch_bounds__(CCSD_LG_TB) void k_lg_hodge1(HodgeLayerD h, float r
         const int i = edges[2 * t], j = edges[2 * t + 1];
         const size_t ij = (size_t)i * N + j, ji = (size_t)j * N + i;
         const float* pr = P0 + ((size_t)b * E + t) * h.wc;
-        float in[CCSD_SMALLW], out[CCSD_SMALLW];
-#pragma unroll
-        for (int c = 0; c < CCSD_SMALLW; ++c) {
-            float sacc = 0.f;
-            if (c < h.cin) {
-                const float a = Sb[(size_t)c * NN + ij];
-                const float g = 1.0f / sqrtf(fmaxf(a, 1.f));
-                for (int d = 0; d < qw; ++d) q[d] = fmaf(g * a * g, pr[c * qw + d], w[h.bcat + c * qw + d]);
-                sacc = attn_logits(q, q + h.adim, h.nchunk, h.dsplit, rks) * (1.0f / (float)h.nchunk);
-                Hb[(size_t)c * NN + ij] = a;
-                Hb[(size_t)c * NN + ji] = a;
-            }
-            in[c] = sacc;
+        auto qrow = [&](int c) {
+            const float a = Sb[(size_t)c * NN + ij];
+            lg_hd_qk0_row(h, w, pr, c, a, q);
+            Hb[(size_t)c * NN + ij] = a;
+            Hb[(size_t)c * NN + ji] = a;
+            return (const float*)q;
+        };
+        lg_hd_diag_edge(h, rks, s_hw, qrow, fl[i] * fl[j], Hb + (size_t)h.cin * NN, NN, ij, ji);
+    }
+}
+
+// ---- TWO OR MORE HodgeAdjAttentionLayers (hodge_attention.py:290-325; the oracle's hodge_adj_attention_layer), E <= CCSD_LG_HD_MAXE.
+// Layer l sees the dense hodge adjacency channels H^l [cin][E][E] (H^0: the diagonal a_c) and the projection P_l = R_l Wcat_l of its
+// rank-2 features ([B][E][wc_l], delivered by the rank-2 side: launch_lg):
+//   dis_c[e] = rsqrt(max(1, sum_e' H_c[e][e']))                                        (k_lg_hd_dis; the diagonal counts as it is)
+//   Q | K_c[e] = dis_c[e] sum_e' H_c[e][e'] dis_c[e'] P_l[e'][block c] + b            (k_lg_hd_conv; l = 0: k_lg_hd_qk0, per edge)
+//   A_c[e][e'] = mean over heads of tanh(Q_h[e] . K_h[e'] / sqrt(K)), (A + A^T) / 2
+//   H^(l+1) = 2 tanh(fh[e] fh[e'] mlp_attention(cat_c A_c)),  fh[e] = fl(i) fl(j)      (k_lg_hd_dense; A is symmetric: h + h^T = 2 h)
+// The diagonal of every layer's output goes behind the graph channels of the stack, at (i, j) and (j, i); only the last layer's
+// diagonal is ever read, so the last layer is evaluated there alone (k_lg_hd_diag).  The dense output lives in ONE workspace buffer
+// [B][c_hid_h][E][E]: k_lg_hd_dis / k_lg_hd_conv (and k_hodge_value of the general stack) are all that read it, and the next layer's
+// dense pass, which overwrites it, reads only the Q | K rows they left.  No atomics, fixed summation orders: launches repeat bit for bit.
+
+// the input channels into the stack (rows ch0 .. ch0 + cin; zeros on the node diagonal of all nch hodge rows) and layer 0's Q | K rows
+// QK[b][c][e][2 adim].  grid: (grid-stride over E + N, B)
+__global__ __launch_bounds__(CCSD_LG_TB) void k_lg_hd_qk0(HodgeLayerD h, int nch, const float* __restrict__ w, const unsigned char* __restrict__ edges,
+                                                         const float* __restrict__ P0, float* __restrict__ S, long long sstride, int ch0, int N,
+                                                         int E, float* __restrict__ QK, long long qstride) {
+    const int b = blockIdx.y, NN = N * N, qw = 2 * h.adim;
+    float* Sb = S + (size_t)b * sstride;
+    float* Hb = Sb + (size_t)ch0 * NN;
+    float* Qb = QK + (size_t)b * qstride;
+    for (int t = blockIdx.x * blockDim.x + threadIdx.x; t < E + N; t += gridDim.x * blockDim.x) {
+        if (t >= E) {
+            const int i = t - E;
+            for (int c = 0; c < nch; ++c) Hb[(size_t)c * NN + (size_t)i * N + i] = 0.f;
+            continue;
         }
-        small_mlp_lds<CCSD_SMALLW>(s_hw, h.matt.n, in, out);     // mlp_attention -> mask -> tanh -> + transpose
-        const float fh = fl[i] * fl[j];
-#pragma unroll
-        for (int o = 0; o < CCSD_SMALLW; ++o)
-            if (o < h.cout) {
-                const float tv = tanh_f(out[o] * fh * fh);
-                Hb[(size_t)(h.cin + o) * NN + ij] = tv + tv;
-                Hb[(size_t)(h.cin + o) * NN + ji] = tv + tv;
+        const int i = edges[2 * t], j = edges[2 * t + 1];
+        const size_t ij = (size_t)i * N + j, ji = (size_t)j * N + i;
+        const float* pr = P0 + ((size_t)b * E + t) * h.wc;
+        for (int c = 0; c < h.cin; ++c) {
+            const float a = Sb[(size_t)c * NN + ij];
+            lg_hd_qk0_row(h, w, pr, c, a, Qb + ((size_t)c * E + t) * qw);
+            Hb[(size_t)c * NN + ij] = a;
+            Hb[(size_t)c * NN + ji] = a;
+        }
+    }
+}
+
+// upper-triangle tile t of an nt x nt grid of tiles, row-major -> row tile ty, column tile ty + dt
+CCSD_DEV void lg_tri_tile(int t, int nt, int& ty, int& dt) {
+    ty = 0;
+    while (t >= nt - ty) { t -= nt - ty; ++ty; }
+    dt = t;
+}
+// entry (e, f) of output channel o of a dense hodge layer, v = the channel mix before the mask: 2 tanh(fl(i) fl(j) fl(i') fl(j') v) into
+// Hb [cout][E][E], mirrored (a tile on the diagonal computes both halves itself); the diagonal also into row o of Sb at (i, j) and (j, i)
+CCSD_DEV void lg_dense_store(float v, int o, int e, int f, bool diag, int E, int N, const unsigned char* __restrict__ edges,
+                             const float* __restrict__ fl, float* __restrict__ Hb, float* __restrict__ Sb) {
+    if (e >= E || f >= E) return;
+    const int i = edges[2 * e], j = edges[2 * e + 1], i2 = edges[2 * f], j2 = edges[2 * f + 1];
+    const float fh = fl[i] * fl[j] * fl[i2] * fl[j2];
+    const float tv = tanh_f(v * fh), val = tv + tv;
+    float* Ho = Hb + (size_t)o * E * E;
+    Ho[(size_t)e * E + f] = val;
+    if (!diag) Ho[(size_t)f * E + e] = val;
+    else if (e == f) {
+        const int NN = N * N;
+        Sb[(size_t)o * NN + (size_t)i * N + j] = val;
+        Sb[(size_t)o * NN + (size_t)j * N + i] = val;
+    }
+}
+
+// The dense output of a layer but the last from its Q | K rows.  One 16 x 16 tile (e, e') of the upper triangle per workgroup, mirrored
+// on store (a tile on the diagonal computes both halves itself: the two orders of a pair add the same two logit sums, the result is
+// symmetric bit for bit).  The rows of the tile's 16 + 16 edges of every channel are staged in LDS; the 256 pairs' symmetrised
+// attentions (both orders of the head products, k_xa's expression) go to LDS, one pair per thread; mlp_attention then runs per 16-pair
+// tile on MFMA (mlp_chain_tile, the 16-wide chain shape: matt = the layer's mlp_attention with its packed copies, PlanBuilder::hdm), four
+// tiles per wave.  Ragged last tile: rows beyond E are staged from row E - 1 and never stored.
+// dynamic LDS: lg_hd_dense_lds(h).  grid: (nt (nt + 1) / 2, B), nt = ceil(E / 16)
+__global__ __launch_bounds__(CCSD_LG_TB) void k_lg_hd_dense(HodgeLayerD h, MlpD matt, float rks, const float* __restrict__ wp,
+                                                           const unsigned char* __restrict__ edges, const float* __restrict__ QK, long long qstride,
+                                                           float* __restrict__ Hout, long long hstride, float* __restrict__ S, long long sstride,
+                                                           int ch0, int N, int E, const float* __restrict__ flags) {
+    CCSD_DYN_SMEM(sm);
+    const int b = blockIdx.y, tid = threadIdx.x, nth = blockDim.x, NN = N * N;
+    int ty, dt;
+    lg_tri_tile(blockIdx.x, (E + 15) / 16, ty, dt);
+    const int e0 = 16 * ty, f0 = 16 * (ty + dt);
+    const bool diag = dt == 0;
+    const int cin = h.cin, qw = 2 * h.adim, ldq = lg_hb_row_ld(qw);
+    float* s_q = sm;                             // [side][cin][16][ldq]: Q | K rows of the tile's row edges (side 0) / column edges (1)
+    float* s_S = s_q + 2 * cin * 16 * ldq;       // [cin][256]: mlp_attention's input, pair u = 16 r + q
+    const float* Qb = QK + (size_t)b * qstride;
+    for (int u = tid; u < 2 * cin * 16 * qw; u += nth) {
+        const int d = u % qw, v = u / qw, r = v & 15, sc = v >> 4, c = sc % cin, side = sc / cin;
+        const int e = (side ? f0 : e0) + r, ec = e < E ? e : E - 1;
+        s_q[(sc * 16 + r) * ldq + d] = Qb[((size_t)c * E + ec) * qw + d];
+    }
+    __syncthreads();
+    const float rnc = 1.0f / (float)h.nchunk;
+    for (int u = tid; u < 256; u += nth) {
+        const int r = u >> 4, q = u & 15;
+        for (int c = 0; c < cin; ++c) {
+            const float* q1 = s_q + (c * 16 + r) * ldq;
+            const float* q2 = s_q + ((cin + c) * 16 + q) * ldq;
+            const float s1 = attn_logits(q1, q2 + h.adim, h.nchunk, h.dsplit, rks);
+            const float s2 = attn_logits(q2, q1 + h.adim, h.nchunk, h.dsplit, rks);
+            s_S[c * 256 + u] = (s1 * rnc + s2 * rnc) * 0.5f;
+        }
+    }
+    __syncthreads();
+    float* Hb = Hout + (size_t)b * hstride;
+    float* Sb = S + (size_t)b * sstride + (size_t)ch0 * NN;
+    const float* fl = flags + (size_t)b * N;
+    auto ident = [](int r) { return r; };
+    auto epi = [&](int u, int o, float v) { lg_dense_store(v, o, e0 + (u >> 4), f0 + (u & 15), diag, E, N, edges, fl, Hb, Sb); };
+#ifdef CCSD_EMU
+    for (int wv = 0; wv < CCSD_LG_TB / 64; ++wv)
+#else
+    const int wv = wave_index();
+#endif
+        for (int q4 = 0; q4 < 4; ++q4) mlp_chain_tile<1, 1, 1>(matt, wp, s_S, 256, s_S, matt.in, 16 * (4 * wv + q4), 256, ident, epi);
+}
+
+// dis[b][c][e] = rsqrt(max(1, sum_e' Hin[b][c][e][e'])) of a dense input (the matrix is symmetric bit for bit: the sum walks the column,
+// consecutive threads read consecutive words), and, for the raw P_1 of the fused rank-2 family, its per-edge factors (LgHdRaw)
+// grid: (grid-stride over cin E, B)
+__global__ __launch_bounds__(CCSD_LG_TB) void k_lg_hd_dis(const float* __restrict__ Hin, long long hstride, int cin, int E, float* __restrict__ dis,
+                                                         LgHdRaw raw) {
+    const int b = blockIdx.y;
+    for (int t = blockIdx.x * blockDim.x + threadIdx.x; t < cin * E; t += gridDim.x * blockDim.x) {
+        const int c = t / E, e = t - c * E;
+        const float* col = Hin + (size_t)b * hstride + (size_t)c * E * E + e;
+        float s = 0.f;
+        for (int e2 = 0; e2 < E; ++e2) s += col[(size_t)e2 * E];
+        dis[((size_t)b * cin + c) * E + e] = 1.0f / sqrtf(fmaxf(s, 1.f));
+    }
+    if (!raw.pc) return;
+    const int NN = raw.N * raw.N;
+    const float mvb0 = raw.w[raw.mb];
+    for (int e = blockIdx.x * blockDim.x + threadIdx.x; e < E; e += gridDim.x * blockDim.x) {
+        const int i = raw.edges[2 * e], j = raw.edges[2 * e + 1];
+        float sc = 0.f;
+        for (int c = 0; c < raw.cin0; ++c) sc = fmaf(raw.w[raw.mw + c], raw.S[(size_t)b * raw.sstride + (size_t)c * NN + (size_t)i * raw.N + j], sc);
+        const float fl = raw.flags[(size_t)b * raw.N + i] * raw.flags[(size_t)b * raw.N + j];
+        raw.pc[((size_t)b * 2) * E + e] = fl * sc;
+        raw.pc[((size_t)b * 2 + 1) * E + e] = fl * mvb0;
+    }
+}
+
+// Q | K rows of a layer with dense input: QK[b][c][e][d] = dis_c[e] sum_e' Hin[b][c][e][e'] dis_c[e'] P[b][e'][c 2 adim + d] + b_c[d] -- an
+// (E x E) . (E x 2 adim) product per channel, 2 adim <= 32 (CCSD_LG_HAD).  One 16-row tile per wave over the whole E and both 16-column
+// tiles, v_mfma_f32_16x16x4_f32 in the permuted-k fragment order of the tiled GEMM kernels (frag_mma, row_load4: k_lg_hb_hid's form);
+// dis[e'] is folded into the B operand, dis[e] and the bias are applied in the epilogue.  P: row stride ldp; pc != nullptr: P holds
+// the raw factors Q_1 and U [B][ldp] the row u_1, P_1[e'] = pc[0][e'] Q_1[e'] + pc[1][e'] u_1 (k_xa's p1_compose).  Each row of Hin is
+// read once: the pass is HBM-bound.  The ragged last row tile reads row E - 1 and stores nothing; the ragged k tail and the columns
+// beyond 2 adim are zeros by guard, not by padding.
+// grid: (ceil(ceil(E / 16) / 4), cin, B)
+__global__ __launch_bounds__(CCSD_LG_TB) void k_lg_hd_conv(HodgeLayerD h, const float* __restrict__ w, const float* __restrict__ Hin, long long hstride,
+                                                          const float* __restrict__ dis, const float* __restrict__ P, int ldp,
+                                                          const float* __restrict__ pc, const float* __restrict__ U, int E,
+                                                          float* __restrict__ QK, long long qstride) {
+    const int c = blockIdx.y, b = blockIdx.z, qw = 2 * h.adim;
+    const float* Hc = Hin + (size_t)b * hstride + (size_t)c * E * E;
+    const float* dg = dis + ((size_t)b * h.cin + c) * E;
+    const float* Pb = P + (size_t)b * E * ldp + c * qw;
+    const float* pcb = pc ? pc + (size_t)b * 2 * E : nullptr;
+    const float* Ub = pc ? U + (size_t)b * ldp + c * qw : nullptr;
+    const float* bias = w + h.bcat + c * qw;
+    float* Qc = QK + (size_t)b * qstride + (size_t)c * E * qw;
+    // B operand: row k (< E), column d (< qw) of dis . P_l
+    auto bval = [&](int k, int d) {
+        const float pv = Pb[(size_t)k * ldp + d];
+        return dg[k] * (pcb ? fmaf(pcb[k], pv, pcb[E + k] * Ub[d]) : pv);
+    };
+#ifdef CCSD_EMU
+    for (int wv = 0; wv < CCSD_LG_TB / 64; ++wv) {
+        const int m0 = 16 * (4 * blockIdx.x + wv);
+        for (int e = m0; e < m0 + 16 && e < E; ++e)
+            for (int d = 0; d < qw; ++d) {
+                float acc = 0.f;
+                for (int k = 0; k < E; ++k) acc = fmaf(Hc[(size_t)e * E + k], bval(k, d), acc);
+                Qc[(size_t)e * qw + d] = fmaf(dg[e], acc, bias[d]);
             }
+    }
+#else
+    const int m0 = 16 * (4 * blockIdx.x + wave_index());
+    if (m0 >= E) return;
+    const int lane = threadIdx.x & 63, l15 = lane & 15, kq = lane >> 4;
+    const float* row = Hc + (size_t)(m0 + l15 < E ? m0 + l15 : E - 1) * E;
+    const bool vec = (E & 3) == 0, two = qw > 16;
+    const int d0 = l15 < qw ? l15 : qw - 1, d1 = 16 + l15 < qw ? 16 + l15 : qw - 1;
+    const bool col0 = l15 < qw, col1 = 16 + l15 < qw;
+    f32x4 acc0 = {0.f, 0.f, 0.f, 0.f}, acc1 = {0.f, 0.f, 0.f, 0.f};
+    for (int k0 = 0; k0 < E; k0 += 16) {
+        const int k = k0 + 4 * kq;
+        float4 a, bq;
+        row_load4(a, row, k, E, vec);
+        const int ka = k < E ? k : E - 1, kb = k + 1 < E ? k + 1 : E - 1, kc = k + 2 < E ? k + 2 : E - 1, kd = k + 3 < E ? k + 3 : E - 1;
+        bq.x = (col0 && k < E) ? bval(ka, d0) : 0.f;
+        bq.y = (col0 && k + 1 < E) ? bval(kb, d0) : 0.f;
+        bq.z = (col0 && k + 2 < E) ? bval(kc, d0) : 0.f;
+        bq.w = (col0 && k + 3 < E) ? bval(kd, d0) : 0.f;
+        frag_mma(acc0, a, bq);
+        if (two) {
+            bq.x = (col1 && k < E) ? bval(ka, d1) : 0.f;
+            bq.y = (col1 && k + 1 < E) ? bval(kb, d1) : 0.f;
+            bq.z = (col1 && k + 2 < E) ? bval(kc, d1) : 0.f;
+            bq.w = (col1 && k + 3 < E) ? bval(kd, d1) : 0.f;
+            frag_mma(acc1, a, bq);
+        }
+    }
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+        const int e = m0 + 4 * kq + r;
+        if (e >= E) continue;
+        if (col0) Qc[(size_t)e * qw + l15] = fmaf(dg[e], acc0[r], bias[l15]);
+        if (two && col1) Qc[(size_t)e * qw + 16 + l15] = fmaf(dg[e], acc1[r], bias[16 + l15]);
+    }
+#endif
+}
+
+// The last layer, on its diagonal, from its Q | K rows: lg_hd_diag_edge into stack rows ch0 .. ch0 + cout.  grid: (grid-stride over E, B)
+__global__ __launch_bounds__(CCSD_LG_TB) void k_lg_hd_diag(HodgeLayerD h, float rks, const float* __restrict__ w, const unsigned char* __restrict__ edges,
+                                                          const float* __restrict__ QK, long long qstride, float* __restrict__ S, long long sstride,
+                                                          int ch0, int N, int E, const float* __restrict__ flags) {
+    __shared__ float s_hw[CCSD_MAXLIN * CCSD_HWBLK];
+    const int b = blockIdx.y, NN = N * N, qw = 2 * h.adim;
+    stage_mlp_blocks(h.matt, w, s_hw, (int)threadIdx.x, (int)blockDim.x);
+    __syncthreads();
+    const float* Qb = QK + (size_t)b * qstride;
+    float* Sb = S + (size_t)b * sstride + (size_t)ch0 * NN;
+    const float* fl = flags + (size_t)b * N;
+    for (int e = blockIdx.x * blockDim.x + threadIdx.x; e < E; e += gridDim.x * blockDim.x) {
+        const int i = edges[2 * e], j = edges[2 * e + 1];
+        auto qrow = [&](int c) { return Qb + ((size_t)c * E + e) * qw; };
+        lg_hd_diag_edge(h, rks, s_hw, qrow, fl[i] * fl[j], Sb, NN, (size_t)i * N + j, (size_t)j * N + i);
     }
 }
 
@@ -495,9 +767,8 @@ __global__ __launch_bounds__(CCSD_LG_TB) void k_lg_hb_dense(HodgeBaseD h, const 
                                                            int ch0, int N, int E, const float* __restrict__ flags) {
     CCSD_DYN_SMEM(sm);
     const int b = blockIdx.y, tid = threadIdx.x, nth = blockDim.x, NN = N * N;
-    const int nt = (E + 15) / 16;
-    int t = blockIdx.x, ty = 0;                  // upper-triangle tile t -> (row tile ty, column tile ty + t), row-major
-    while (t >= nt - ty) { t -= nt - ty; ++ty; }
+    int ty, t;                                   // upper-triangle tile -> (row tile ty, column tile ty + t)
+    lg_tri_tile(blockIdx.x, (E + 15) / 16, ty, t);
     const int e0 = 16 * ty, f0 = 16 * (ty + t);
     const bool diag = t == 0;
     const int hid = h.hid, hp = lg_hb_row_ld(hid), cin = h.cin;
@@ -540,20 +811,7 @@ __global__ __launch_bounds__(CCSD_LG_TB) void k_lg_hb_dense(HodgeBaseD h, const 
     float* Sb = S + (size_t)b * sstride + (size_t)ch0 * NN;
     const float* fl = flags + (size_t)b * N;
     auto ident = [](int r) { return r; };
-    auto epi = [&](int u, int o, float v) {
-        const int e = e0 + (u >> 4), f = f0 + (u & 15);
-        if (e >= E || f >= E) return;
-        const int i = edges[2 * e], j = edges[2 * e + 1], i2 = edges[2 * f], j2 = edges[2 * f + 1];
-        const float fh = fl[i] * fl[j] * fl[i2] * fl[j2];
-        const float tv = tanh_f(v * fh), val = tv + tv;
-        float* Ho = Hb + (size_t)o * E * E;
-        Ho[(size_t)e * E + f] = val;
-        if (!diag) Ho[(size_t)f * E + e] = val;
-        else if (e == f) {
-            Sb[(size_t)o * NN + (size_t)i * N + j] = val;
-            Sb[(size_t)o * NN + (size_t)j * N + i] = val;
-        }
-    };
+    auto epi = [&](int u, int o, float v) { lg_dense_store(v, o, e0 + (u >> 4), f0 + (u & 15), diag, E, N, edges, fl, Hb, Sb); };
 #ifdef CCSD_EMU
     for (int wv = 0; wv < CCSD_LG_TB / 64; ++wv)
 #else

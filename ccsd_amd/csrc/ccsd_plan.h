@@ -17,7 +17,8 @@
 #define CCSD_FWMAX 32     // ... in the tiled k_hf_score path
 #define CCSD_XA_MAXN 64   // k_xa: one graph per workgroup, its working set in one CU's LDS (node masks: one 64-bit word per graph)
 #define CCSD_LG_MAXN 512  // tiled graph-network route (ccsd_k_lg.h): ceiling on N (a graph's channel stack, fdim N^2 floats, is indexed in 32 bits)
-#define CCSD_LG_HAD 16    // ... and on the attention dimension of its one-layer hodge branch (k_lg_hodge1: a Q | K row per thread in LDS)
+#define CCSD_LG_HAD 16    // ... and on the attention dimensions of its ScoreNetworkA_CC hodge branch (k_lg_hodge1: a Q | K row per thread in LDS; k_lg_hd_conv: two MFMA column tiles)
+#define CCSD_LG_HD_MAXE 703   // ... on E of ScoreNetworkA_CC stacks of two or more layers (k_lg_hd_*: zinc250k's geometry, N = 38; the dense buffer is c_hid_h E^2 floats per complex)
 #define CCSD_LG_MAXHB 8   // ... on the HodgeBaselineLayers of ScoreNetworkA_Base_CC (k_lg_hb_*; PlanD::hb holds the first CCSD_MAXHL, PlanBuilder::hbx all)
 #define CCSD_LG_HBW 16    // ... and on their BaselineBlocks' hidden widths: one MFMA column tile (k_lg_hb_hid)
 
@@ -185,6 +186,9 @@ struct PlanBuilder {
     int verbose = 0;    // CCSD_VERBOSE
     int lg = 0;         // out: the plan takes the tiled graph-network route (ccsd_k_lg.h) instead of k_xa
     HodgeBaseD hbx[CCSD_LG_MAXHB] = {};   // out: every HodgeBaselineLayer of ScoreNetworkA_Base_CC (the route's k_lg_hb_* launches)
+    // out (route plans with two or more HodgeAdjAttentionLayers): mlp_attention of every layer but the last with packed copies for
+    // mlp_chain_tile (k_lg_hd_dense).  Kept out of PlanD, and reserved behind everything else in the packed buffer: no plan k_xa serves moves
+    MlpD hdm[CCSD_MAXHL + CCSD_MAXHLX] = {};
     int take(int64_t n) {
         int o = cur;
         cur += (int)n;
@@ -283,10 +287,11 @@ static inline int round_ld(int rows) {  // node-row stride of the feature-major 
 
 // Why the tiled graph-network route (ccsd_k_lg.h) cannot serve a plan whose networks `p` holds (nullptr: it can).  It covers plans
 // with the plain ScoreNetworkX and a GCN-conv ScoreNetworkA whose edge MLPs are the 16-wide MFMA chains and whose final MLP is a
-// chained shape (fdim <= 64): graph-only ones, and combinatorial complexes (N <= 64) with ScoreNetworkA_CC and ONE
-// HodgeAdjAttentionLayer, whose hodge adjacency is diagonal (k_lg_hodge1), or with ScoreNetworkA_Base_CC, 1 to CCSD_LG_MAXHB
-// HodgeBaselineLayers and BaselineBlocks at most CCSD_LG_HBW wide (k_lg_hb_*: the dense E x E layers tiled through the workspace).
-// ScoreNetworkX_GMH, conv = "MLP", wider BaselineBlocks and ScoreNetworkA_CC stacks of two or more layers stay with k_xa.
+// chained shape (fdim <= 64): graph-only ones, and combinatorial complexes (N <= 64) with ScoreNetworkA_CC -- ONE
+// HodgeAdjAttentionLayer, whose hodge adjacency is diagonal (k_lg_hodge1), or 2 to 8 of them up to E = CCSD_LG_HD_MAXE (k_lg_hd_*),
+// attention dimensions at most CCSD_LG_HAD -- or with ScoreNetworkA_Base_CC, 1 to CCSD_LG_MAXHB HodgeBaselineLayers and BaselineBlocks
+// at most CCSD_LG_HBW wide (k_lg_hb_*); the dense E x E layers of both are tiled through the workspace.
+// ScoreNetworkX_GMH, conv = "MLP", wider BaselineBlocks and ScoreNetworkA_CC stacks of two or more layers beyond E = 703 stay with k_xa.
 // dynamic LDS of the route's per-node MLP kernel k_lg_nmlp for one MLP: 16 rows of its input and of two activations (bytes)
 static inline size_t lg_nmlp_lds_of(const MlpD& m) {
     const int wmax = m.hid > m.out ? m.hid : m.out;
@@ -300,9 +305,9 @@ static inline size_t lg_nmlp_lds(const PlanD& p) {
 static inline const char* ccsd_lg_ineligible(const ccsd_config_t* c, const PlanD* p) {
     if (p->a_is_cc == 2 && (c->h_nhid > CCSD_LG_HBW || (c->h_num_layers > 1 && c->h_adim > CCSD_LG_HBW)))
         return "ScoreNetworkA_Base_CC with BaselineBlocks wider than 16";
-    if (p->h_L > 1) return "hodge stacks of two or more layers (the dense E x E hodge layer)";
-    if (c->is_cc && p->a_is_cc != 2 && (p->a_is_cc != 1 || p->h_L != 1)) return "combinatorial-complex plans without ScoreNetworkA_CC";
-    if (p->h_L == 1 && p->hl[0].adim > CCSD_LG_HAD) return "hodge attention dimensions above 16";
+    if (p->h_L > 1 && p->E > CCSD_LG_HD_MAXE) return "hodge stacks of two or more layers beyond E = 703 (the dense E x E hodge layer)";
+    if (c->is_cc && p->a_is_cc != 2 && (p->a_is_cc != 1 || p->h_L < 1)) return "combinatorial-complex plans without ScoreNetworkA_CC";
+    for (int l = 0; l < p->h_L; ++l) if (ccsd_hl(*p, l).adim > CCSD_LG_HAD) return "hodge attention dimensions above 16";
     if (p->x_gmh) return "ScoreNetworkX_GMH";
     for (int l = 0; l < p->a_L; ++l) {
         const AttnLayerD& a = p->al[l];
@@ -523,6 +528,8 @@ static inline size_t ccsd_build_plan(const ccsd_config_t* c, PlanD* p, PlanBuild
     // holds ScoreNetworkA_CC stacks to it; every shipped Base_CC geometry lies inside: E = 36 .. 190) -- takes the route where it is
     // eligible: one workgroup per complex would walk the E^2 pairs alone (grid_small_Base_CC: E = 1176, a 148 KB k_xa layout)
     if (p->hb_L > 1 && E > 255 && !lg_reason) pb.lg = 1;
+    // ... and so does a ScoreNetworkA_CC stack of two or more layers there: k_xa's pair table of the dense layer holds edge indices in bytes
+    if (p->h_L > 1 && E > 255 && !lg_reason) pb.lg = 1;
     // (1 leaves combinatorial complexes on k_xa, as before the route served any of them: tests/golden/route_plans.json pins those plans)
     if (pb.lg_force && !lg_reason && (!c->is_cc || pb.lg_force >= 2)) pb.lg = 1;
 
@@ -692,6 +699,8 @@ static inline size_t ccsd_build_plan(const ccsd_config_t* c, PlanD* p, PlanBuild
         if (!lg_reason) pb.lg = 1;         // no k_xa layout: the tiled route serves the plan
         else pb.fail(CCSD_ERR_UNSUPPORTED, std::string("graph-network working set exceeds the 160 KB LDS of a CU, and the tiled graph-network route does not serve ") + lg_reason);
     }
+    if (pb.lg && p->h_L > 1)
+        for (int l = 0; l + 1 < p->h_L; ++l) { pb.hdm[l] = ccsd_hl(*p, l).matt; pb.chainify(pb.hdm[l], CCSD_CHAIN_EDGE); }
     return nweights;
 }
 
