@@ -99,6 +99,9 @@ struct Route {
     // adjacencies k_xa<., XA_GEN> dumps (launch_xa); CCSD_HODGE_GENERAL forces it for any plan with more than two layers, and plans on
     // the tiled route always take it (launch_lg: the dense adjacencies are in its workspace buffer already)
     int h_general = 0;
+    // hodge MLPs wider than 8 (PlanBuilder::h_wide; always on the tiled route and the tiled rank-2 family): mlp_attention on the last layer's
+    // diagonal as the 16-wide MFMA chain (k_lg_hodge1_w / k_lg_hd_diag_w), mlp_value from 16 x 16 blocks (k_gemm_p_w / k_hodge_value_w)
+    int h_wide = 0;
     int geo = 0;                    // index of the plan's (E, K) in CCSD_GEO_LIST (0: run-time values)
     int p0 = -1;                    // index of the narrow layer-0 projection's k_gemm_p0 in CCSD_P0_LIST (-1: wide, k_gemm_p)
     int h_full = 0;                 // launch_h's H = F F^T may come from k_gemm_h_full (use_h_full)
@@ -120,6 +123,7 @@ struct ccsd_plan {
     PlanD h;                    // host copy
     HodgeBaseD hbx[CCSD_LG_MAXHB];   // every HodgeBaselineLayer of ScoreNetworkA_Base_CC (h.hb holds the first two): arguments of the k_lg_hb_* launches
     MlpD hdm[CCSD_MAXHL + CCSD_MAXHLX];   // route plans with two or more HodgeAdjAttentionLayers: the chained mlp_attention of k_lg_hd_dense (PlanBuilder::hdm)
+    MlpD afin_lg;               // route plans whose final MLP has 57 to 64 channels: its chained form (PlanBuilder::afin_lg; chain == 0: h.a_fin is chained)
     PlanD* d = nullptr;         // device copy
     float* w = nullptr;         // device weights
     float* wp = nullptr;        // device: zero-padded copies of the chain MLPs' linears (mlp_chain_tile)
@@ -223,7 +227,7 @@ static int resolve_route(ccsd_plan* pl) {
         return nullptr;
     };
     bool fused = false;
-    if (c.is_cc && E <= 64 && !k.no_fused_r2) {
+    if (c.is_cc && E <= 64 && !k.no_fused_r2 && !r.h_wide) {        // (k_r2 evaluates mlp_value 8 wide)
         const int Kp4 = (K + 31) & ~31, Ep4 = (E + 3) & ~3;   // K zero-padded to whole 8-step MFMA batches
         int ldk = Kp4; while ((ldk & 31) != 8 && (ldk & 31) != 24) ldk += 4;   // conflict-free ds_read_b128 fragment reads (16 rows x 4 k-quads)
         const int ldh = Ep4;                                                 // 16-byte aligned rows: phase 2 re-reads H's fragments per column tile as ds_read_b128
@@ -246,7 +250,7 @@ static int resolve_route(ccsd_plan* pl) {
         if (!affine_values || !fused || p.h_L > 4 || k.hodge_general || r.lg) { r.h_general = 1; fused = false; r.r2 = nullptr; }
     }
     // element-wise rank-2 side (k_ew1): affine ScoreNetworkF without a Hodge Laplacian term (cnum = 1), tiled path, PC samplers
-    const bool ew1 = c.is_cc && !fused && aff && p.f_cnum == 1 && !s4;
+    const bool ew1 = c.is_cc && !fused && aff && p.f_cnum == 1 && !s4 && !r.h_wide;
     r.r2_family = !c.is_cc ? R2_NONE : fused ? R2_FUSED : ew1 ? R2_EW1 : R2_TILED;
     if (p.geo_off != 1) for (const GeoEntry& g : GEO_TABLE) if (E == g.E && K == g.K) r.geo = g.idx;
     if (p.h_L >= 1) {       // narrow layer-0 projection (at most four 16-column tiles): no 64-column padding, K compiled in where listed
@@ -386,9 +390,10 @@ extern "C" int ccsd_plan_create(const ccsd_config_t* cfg, const float* weights, 
     pb.lg_force = k.lg_force; pb.xa_pass = k.xa_pass; pb.xa_gch = k.xa_gch; pb.no_mlp_wt = k.no_mlp_wt; pb.verbose = k.verbose;
     pl->nweights = ccsd_build_plan(cfg, &pl->h, pb);
     if (pb.status != CCSD_OK) { delete pl; return set_err(pb.status, pb.err); }
-    pl->rt.lg = pb.lg;
+    pl->rt.lg = pb.lg; pl->rt.h_wide = pb.h_wide;
     memcpy(pl->hbx, pb.hbx, sizeof(pl->hbx));
     memcpy(pl->hdm, pb.hdm, sizeof(pl->hdm));
+    pl->afin_lg = pb.afin_lg;
     pl->h.geo_off = k.geo_off;
     pl->npacked = (size_t)pb.pcur;
     if (pl->nweights != n_weights) {
@@ -468,7 +473,10 @@ extern "C" int ccsd_plan_create(const ccsd_config_t* cfg, const float* weights, 
             }
         }
         ccsd_pack_mlp(pl->h.a_fin, weights, packed.data());
-        if (pl->rt.lg) for (int l = 0; l + 1 < pl->h.h_L; ++l) ccsd_pack_mlp(pl->hdm[l], weights, packed.data());
+        if (pl->rt.lg) {
+            for (int l = 0; l < pl->h.h_L; ++l) ccsd_pack_mlp(pl->hdm[l], weights, packed.data());     // (the last layer's: wide plans only)
+            if (pl->afin_lg.chain) ccsd_pack_mlp(pl->afin_lg, weights, packed.data());
+        }
         for (int l = 0; l < pl->h.h_L; ++l) {   // Wcat^T of the hodge projections for k_r2
             const HodgeLayerD& h = ccsd_hl(pl->h, l);
             const int Kp = (K + 31) & ~31;
@@ -507,7 +515,7 @@ extern "C" int ccsd_plan_create(const ccsd_config_t* cfg, const float* weights, 
         }
         // (k_lg_hd_dense stays below 64 KB: at most 8 channels of 2 x 16 rows of 33 floats + 256 pairs)
         if (r.lg && r.h_general && (size_t)E * (E > 128 ? 32 : 64) * 4 > 64 * 1024)
-            PC(rt_set_max_dyn_smem((const void*)k_hodge_value, (size_t)E * (E > 128 ? 32 : 64) * 4));
+            PC(rt_set_max_dyn_smem(r.h_wide ? (const void*)k_hodge_value_w : (const void*)k_hodge_value, (size_t)E * (E > 128 ? 32 : 64) * 4));
 #ifndef CCSD_EMU
         if (r.hp_full_modes) {      // k_hp_full: 66.6 KB of dynamic LDS
             PC(rt_set_max_dyn_smem((const void*)k_hp_full<CCSD_FULL_E, CCSD_FULL_K, 1>, HP_FULL_LDS));
@@ -826,7 +834,7 @@ static int launch_p(const ccsd_plan* pl, int B, const float* adj, const float* r
         S = (p.K + kchunk - 1) / kchunk;
         g.z = S;
         float* P1 = rt.h_general ? w.hgP[0] : w.P1;
-        CCSD_LAUNCH(k_gemm_p, g, dim3(CCSD_NTHREADS), 0, stream, rank2, (const float*)pl->w, S > 1 ? w.psplit : P1, rows, p.E, p.K, h.wc,
+        CCSD_LAUNCH(rt.h_wide ? k_gemm_p_w : k_gemm_p, g, dim3(CCSD_NTHREADS), 0, stream, rank2, (const float*)pl->w, S > 1 ? w.psplit : P1, rows, p.E, p.K, h.wc,
                     h.wcat, 1, h0.mval, h0.cin, (const float*)w.acoef, (const unsigned long long*)w.offbits,
                     (const unsigned char*)pl->edges, (const unsigned long long*)pl->cells, kchunk);
         LAUNCH_CHECK();
@@ -838,7 +846,7 @@ static int launch_p(const ccsd_plan* pl, int B, const float* adj, const float* r
         if (rt.h_general) {
             // R_1 = fl fr mlp_value_0(a_c o rank2), materialised for the layers behind it (launch_xa goes on from here)
             const int cw = p.E > 128 ? 32 : 64;
-            CCSD_LAUNCH(k_hodge_value, dim3((p.K + cw - 1) / cw, B), dim3(CCSD_NTHREADS), (size_t)p.E * cw * 4, stream, rank2, (const float*)nullptr, 0,
+            CCSD_LAUNCH(rt.h_wide ? k_hodge_value_w : k_hodge_value, dim3((p.K + cw - 1) / cw, B), dim3(CCSD_NTHREADS), (size_t)p.E * cw * 4, stream, rank2, (const float*)nullptr, 0,
                         (const float*)w.acoef, (const float*)pl->w, h0.mval, h0.cin, w.hgR[0], p.E, p.K, cw,
                         (const unsigned long long*)w.offbits, (const unsigned char*)pl->edges, (const unsigned long long*)pl->cells);
             LAUNCH_CHECK();
@@ -934,8 +942,13 @@ static int launch_lg(const ccsd_plan* pl, int B, XaArgs& xa, NoiseArgs& na, Work
         if (p.h_L == 1) {
             // hodge branch of ScoreNetworkA_CC, one layer: per-edge arithmetic on the powers and P_0, scattered behind the graph channels
             if (!xa.P0) return set_err(CCSD_ERR_RUNTIME, "tiled graph-network route: no hodge projections");
-            CCSD_LAUNCH(k_lg_hodge1, dim3(grid_for(p.E + N, 256), B), blk, 0, stream, p.hl[0], 1.0f / (float)sqrt((double)p.K), (const float*)pl->w,
-                        (const unsigned char*)pl->edges, xa.P0, w.lg_S, ss, p.a_nch_graph, N, p.E, xa.flags);
+            if (pl->rt.h_wide) {
+                CCSD_LAUNCH(k_lg_hodge1_w, dim3(grid_for(p.E, 256), B), blk, 0, stream, p.hl[0], pl->hdm[0], 1.0f / (float)sqrt((double)p.K), (const float*)pl->w,
+                            (const float*)pl->wp, (const unsigned char*)pl->edges, xa.P0, w.lg_S, ss, p.a_nch_graph, N, p.E, xa.flags);
+            } else {
+                CCSD_LAUNCH(k_lg_hodge1, dim3(grid_for(p.E + N, 256), B), blk, 0, stream, p.hl[0], 1.0f / (float)sqrt((double)p.K), (const float*)pl->w,
+                            (const unsigned char*)pl->edges, xa.P0, w.lg_S, ss, p.a_nch_graph, N, p.E, xa.flags);
+            }
         }
         if (p.h_L > 1) {
             // hodge branch of ScoreNetworkA_CC, two or more layers (k_lg_hd_*): layer 0's Q | K rows per edge; per layer l but the last its
@@ -964,7 +977,7 @@ static int launch_lg(const ccsd_plan* pl, int B, XaArgs& xa, NoiseArgs& na, Work
                     const HodgeLayerD& hn = ccsd_hl(p, j + 1);
                     float* Rn = w.hgR[j & 1];
                     const int cw = E > 128 ? 32 : 64;
-                    CCSD_LAUNCH(k_hodge_value, dim3((p.K + cw - 1) / cw, B), dim3(CCSD_NTHREADS), (size_t)E * cw * 4, stream, (const float*)w.hgR[(j - 1) & 1],
+                    CCSD_LAUNCH(rtp.h_wide ? k_hodge_value_w : k_hodge_value, dim3((p.K + cw - 1) / cw, B), dim3(CCSD_NTHREADS), (size_t)E * cw * 4, stream, (const float*)w.hgR[(j - 1) & 1],
                                 (const float*)w.lg_hdH, (int)hs, (const float*)nullptr, wts, h.mval, h.cin, Rn, E, p.K, cw,
                                 (const unsigned long long*)w.offbits, edges, (const unsigned long long*)pl->cells);
                     LAUNCH_CHECK();
@@ -985,8 +998,13 @@ static int launch_lg(const ccsd_plan* pl, int B, XaArgs& xa, NoiseArgs& na, Work
                             raw ? (const float*)w.lg_hdpc : (const float*)nullptr, raw ? xa.U1 : (const float*)nullptr, E, w.lg_hdq, qs);
                 LAUNCH_CHECK();
             }
-            CCSD_LAUNCH(k_lg_hd_diag, dim3(grid_for(E, 256), B), blk, 0, stream, ccsd_hl(p, p.h_L - 1), rks, wts, edges, (const float*)w.lg_hdq, qs, w.lg_S, ss,
-                        ch, N, E, xa.flags);
+            if (rtp.h_wide) {
+                CCSD_LAUNCH(k_lg_hd_diag_w, dim3(grid_for(E, 256), B), blk, 0, stream, ccsd_hl(p, p.h_L - 1), pl->hdm[p.h_L - 1], rks, (const float*)pl->wp, edges,
+                            (const float*)w.lg_hdq, qs, w.lg_S, ss, ch, N, E, xa.flags);
+            } else {
+                CCSD_LAUNCH(k_lg_hd_diag, dim3(grid_for(E, 256), B), blk, 0, stream, ccsd_hl(p, p.h_L - 1), rks, wts, edges, (const float*)w.lg_hdq, qs, w.lg_S, ss,
+                            ch, N, E, xa.flags);
+            }
             LAUNCH_CHECK();
         }
         if (p.hb_L) {
@@ -1034,8 +1052,13 @@ static int launch_lg(const ccsd_plan* pl, int B, XaArgs& xa, NoiseArgs& na, Work
             CCSD_LAUNCH(k_lg_sym, dim3(grid_for((long long)L.cout * NN, 256), B), blk, 0, stream, w.lg_S, ss, L.co0, L.cout, N, xa.flags);
             LAUNCH_CHECK();
         }
-        CCSD_LAUNCH(k_lg_fin, dim3(w.lg_tiles, B), blk, 0, stream, p.a_fin, (const float*)pl->wp, (const float*)w.lg_S, ss, N, xa.flags, xa.adjA,
-                    xa, na, w.lg_part);
+        if (pl->afin_lg.chain) {
+            CCSD_LAUNCH(k_lg_fin_w, dim3(w.lg_tiles, B), blk, 0, stream, pl->afin_lg, (const float*)pl->wp, (const float*)w.lg_S, ss, N, xa.flags, xa.adjA,
+                        xa, na, w.lg_part);
+        } else {
+            CCSD_LAUNCH(k_lg_fin, dim3(w.lg_tiles, B), blk, 0, stream, p.a_fin, (const float*)pl->wp, (const float*)w.lg_S, ss, N, xa.flags, xa.adjA,
+                        xa, na, w.lg_part);
+        }
         LAUNCH_CHECK();
     }
     CCSD_LAUNCH(k_lg_epi, dim3(B), blk, 0, stream, (const float*)w.lg_xnet, xa.xX, xa.flags, xa, na, (const float*)w.lg_part, w.lg_tiles, N, F);
@@ -1273,6 +1296,7 @@ extern "C" int ccsd_plan_query(const ccsd_plan_t* pl, int32_t what, int64_t* val
         case CCSD_QUERY_EW1_FUSE: *value = r.ew1_fuse; break;
         case CCSD_QUERY_H_GENERAL: *value = r.h_general; break;
         case CCSD_QUERY_GEO_EK: *value = r.geo; break;
+        case CCSD_QUERY_H_WIDE: *value = r.h_wide; break;
         default: return set_err(CCSD_ERR_INVALID, "unknown query");
     }
     return CCSD_OK;

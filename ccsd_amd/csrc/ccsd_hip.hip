@@ -1,4 +1,4 @@
-// ccsd_hip.hip -- product translation unit 1 of 6: the C ABI (libccsd_hip.so) and the small kernels.  k_r2 / k_xa are
+// ccsd_hip.hip -- product translation unit 1 of 8: the C ABI (libccsd_hip.so) and the small kernels.  k_r2 / k_xa are
 // instantiated in ccsd_r2*.hip / ccsd_xa.hip and only declared here.
 // Build (see __graft_entry__.build): hipcc --offload-arch=gfx950 -O3 -fPIC -c <unit>.hip for the units in parallel,
 // then hipcc --offload-arch=gfx950 -shared *.o -o libccsd_hip.so

@@ -2,7 +2,8 @@
 // fit one CU's LDS (graph-only plans with N > 64, or k_xa's layout fails; CCSD_LARGE_GRAPH=1 forces it for any eligible graph-only
 // plan), and for combinatorial complexes (N <= 64) without a k_xa layout (or under CCSD_LARGE_GRAPH=2, which forces every eligible
 // plan): ScoreNetworkA_CC with 1 to 8 HodgeAdjAttentionLayers (two or more: E <= CCSD_LG_HD_MAXE, and always here beyond E = 255), and
-// ScoreNetworkA_Base_CC with 1 to 8 HodgeBaselineLayers (more than two: always here).
+// ScoreNetworkA_Base_CC with 1 to 8 HodgeBaselineLayers (more than two: always here).  ScoreNetworkA_CC plans whose hodge MLPs have a Linear
+// wider than 8 (up to 16) are always here.
 // Part of the kernel source of libccsd_hip.so (see ccsd_kernels.h for the map).
 //
 // State lives in the HBM workspace (carve_ws, LgWs in ccsd_api.h) and every phase is a launch of its own that tiles each graph over
@@ -11,7 +12,8 @@
 //                   concatenation) ; k_lg_nmlp (final MLP per node, mask_x)
 //   ScoreNetworkA   k_lg_pow (channel stack [A, A^2, ...]) ; ScoreNetworkA_CC, one hodge layer: k_lg_hodge1 (the hodge channels, behind the
 //                   graph channels of the stack) ; two or more: k_lg_hd_qk0, per layer but the last k_lg_hd_dense + k_lg_hd_dis +
-//                   k_lg_hd_conv, k_lg_hd_diag (the dense E x E layers tiled through the workspace) ; ScoreNetworkA_Base_CC: k_lg_hb_in, per layer but the last k_lg_hb_dense + k_lg_hb_hid,
+//                   k_lg_hd_conv, k_lg_hd_diag (the dense E x E layers tiled through the workspace; hodge MLPs wider than 8: k_lg_hodge1_w /
+//                   k_lg_hd_diag_w, mlp_attention on the diagonal through the MFMA chain too) ; ScoreNetworkA_Base_CC: k_lg_hb_in, per layer but the last k_lg_hb_dense + k_lg_hb_hid,
 //                   k_lg_hb_diag (the same channels from the HodgeBaselineLayers) ; per AttentionLayer: k_lg_dis, k_lg_xw (Q | K | V columns side by side),
 //                   k_lg_gcn, k_lg_nmlp (multi_channel, mask_x, tanh), k_lg_att (head-mean tanh(Q K^T / sqrt(fout)), symmetrised),
 //                   k_lg_edge (edge MLP on [att_c | adj_c] per entry, MFMA: mlp_chain_tile), k_lg_sym (out + out^T, mask_adjs) ;
@@ -21,7 +23,7 @@
 // (DenseGCNConv, add_loop: the diagonal is SET to 1).  The oracle (oracle/ccsd_oracle.py: dense_gcn, attention, attention_layer,
 // score_network_a, score_network_x) is the specification.
 //
-// Build: the definitions are compiled in ccsd_lg.hip (CCSD_LG_UNIT) and in the host emulation; ccsd_hip.hip sees the declarations.
+// Build: the definitions are compiled in ccsd_lg.hip (CCSD_LG_UNIT; k_lg_fin_w in ccsd_lgw.hip) and in the host emulation; ccsd_hip.hip sees the declarations.
 // Every per-graph base is a 64-bit offset; offsets inside one graph stay below fdim * N^2 < 2^31 for N <= CCSD_LG_MAXN.
 #pragma once
 #include "ccsd_dev.h"
@@ -66,6 +68,13 @@ __global__ void k_lg_hd_conv(HodgeLayerD h, const float* __restrict__ w, const f
                              float* __restrict__ QK, long long qstride);
 __global__ void k_lg_hd_diag(HodgeLayerD h, float rks, const float* __restrict__ w, const unsigned char* __restrict__ edges, const float* __restrict__ QK,
                              long long qstride, float* __restrict__ S, long long sstride, int ch0, int N, int E, const float* __restrict__ flags);
+// ... of plans with hodge MLPs wider than 8 (Route::h_wide): mlp_attention on the diagonal through the MFMA chain, matt = PlanBuilder::hdm's copy
+__global__ void k_lg_hodge1_w(HodgeLayerD h, MlpD matt, float rks, const float* __restrict__ w, const float* __restrict__ wp,
+                              const unsigned char* __restrict__ edges, const float* __restrict__ P0, float* __restrict__ S, long long sstride, int ch0,
+                              int N, int E, const float* __restrict__ flags);
+__global__ void k_lg_hd_diag_w(HodgeLayerD h, MlpD matt, float rks, const float* __restrict__ wp, const unsigned char* __restrict__ edges,
+                               const float* __restrict__ QK, long long qstride, float* __restrict__ S, long long sstride, int ch0, int N, int E,
+                               const float* __restrict__ flags);
 __global__ void k_lg_hb_in(HodgeBaseD h, int nch, const float* __restrict__ w, const unsigned char* __restrict__ edges, float* __restrict__ S,
                            long long sstride, int ch0, int N, int E, float* __restrict__ G, long long gstride);
 __global__ void k_lg_hb_dense(HodgeBaseD h, const float* __restrict__ w, const float* __restrict__ wp, const unsigned char* __restrict__ edges,
@@ -90,6 +99,8 @@ __global__ void k_lg_edge(MlpD m, const float* __restrict__ wp, const float* __r
 __global__ void k_lg_sym(float* __restrict__ S, long long sstride, int co0, int cout, int N, const float* __restrict__ flags);
 __global__ void k_lg_fin(MlpD m, const float* __restrict__ wp, const float* __restrict__ S, long long sstride, int N,
                          const float* __restrict__ flags, const float* __restrict__ adj, XaArgs xa, NoiseArgs na, float* __restrict__ part);
+__global__ void k_lg_fin_w(MlpD m, const float* __restrict__ wp, const float* __restrict__ S, long long sstride, int N,
+                           const float* __restrict__ flags, const float* __restrict__ adj, XaArgs xa, NoiseArgs na, float* __restrict__ part);
 __global__ void k_lg_epi(const float* __restrict__ xnet, const float* __restrict__ x, const float* __restrict__ flags, XaArgs xa,
                          NoiseArgs na, const float* __restrict__ part, int ntiles, int N, int F);
 
@@ -313,61 +324,20 @@ __global__ __launch_bounds__(CCSD_LG_TB) void k_lg_sym(float* __restrict__ S, lo
 // the no-diagonal and flag masks and k_xa's adjacency epilogue (same contract and expressions, ccsd_k_xa.h): SCORE ss * net; NORMS
 // raw net + per-workgroup partials (net^2, z^2) to part[b][tile][2]; PRED mean = pa adj + pb net, out = mean + pc z.
 // grid: (ceil(N^2 / 64), B)
-__global__ __launch_bounds__(CCSD_LG_TB) void k_lg_fin(MlpD m, const float* __restrict__ wp, const float* __restrict__ S, long long sstride, int N,
-                                                      const float* __restrict__ flags, const float* __restrict__ adj, XaArgs xa, NoiseArgs na,
-                                                      float* __restrict__ part) {
-    __shared__ float red[16 * 2];
-    const int b = blockIdx.y, NN = N * N;
-    const float* X = S + (size_t)b * sstride;
-    const float* fl = flags + (size_t)b * N;
-    float n2 = 0.f, z2 = 0.f;
-    auto ident = [](int r) { return r; };
-    auto epi = [&](int ij, int f, float v) {
-        (void)f;
-        const int i = ij / N, j = ij - i * N;
-        const float fm = fl[i] * fl[j];
-        const float net = (i == j) ? 0.f : v * fm;               // * no-diag mask, then mask_adjs
-        const size_t gi = (size_t)b * NN + ij;
-        if (xa.mode == MODE_SCORE) {
-            xa.out_a[gi] = xa.ss_a * net;
-        } else {
-            const float z = raw_noise_adj(na, b, i, j, N) * fm;    // gen_noise(sym=True), graph_utils.py:173-175
-            if (xa.mode == MODE_NORMS) {
-                xa.out_a[gi] = net;
-                n2 = fmaf(net, net, n2);
-                z2 = fmaf(z, z, z2);
-            } else {
-                float mean;
-                const float nv = pred_update(xa.pa_a, xa.pb_a, xa.pc_a, adj[gi], net, z, &mean);
-                if (xa.mean_a) xa.mean_a[gi] = mean;
-                xa.out_a[gi] = nv;
-            }
-        }
-    };
-#ifdef CCSD_EMU
-    for (int wv = 0; wv < CCSD_LG_FIN_ROWS / 16; ++wv)
-#else
-    const int wv = wave_index();
+// k_lg_fin: the shapes of CCSD_CHAIN_AFIN (m = PlanD::a_fin); k_lg_fin_w (ccsd_lgw.hip): the one shape of CCSD_CHAIN_AFIN_LG (57 to 64
+// channels, m = PlanBuilder::afin_lg)
+#define LG_FIN_KERNEL k_lg_fin
+#define LG_FIN_CHAIN                                                                                \
+    if (m.chain == 3) mlp_chain_tile<2, 4, 1>(m, wp, X, NN, X, m.in, p0, NN, ident, epi);           \
+    else if (m.chain == 4) mlp_chain_tile<3, 5, 1>(m, wp, X, NN, X, m.in, p0, NN, ident, epi);      \
+    else if (m.chain == 5) mlp_chain_tile<3, 6, 1>(m, wp, X, NN, X, m.in, p0, NN, ident, epi);      \
+    else mlp_chain_tile<4, 7, 1>(m, wp, X, NN, X, m.in, p0, NN, ident, epi);
+#include "ccsd_lg_fin.inc"
+#undef LG_FIN_KERNEL
+#undef LG_FIN_CHAIN
+#ifdef CCSD_EMU          // (the product compiles k_lg_fin_w in a unit of its own, ccsd_lgw.hip)
+#include "ccsd_lg_fin_w.inc"
 #endif
-    {
-        const int p0 = blockIdx.x * CCSD_LG_FIN_ROWS + 16 * wv;
-        if (p0 < NN) {
-            if (m.chain == 3) mlp_chain_tile<2, 4, 1>(m, wp, X, NN, X, m.in, p0, NN, ident, epi);
-            else if (m.chain == 4) mlp_chain_tile<3, 5, 1>(m, wp, X, NN, X, m.in, p0, NN, ident, epi);
-            else if (m.chain == 5) mlp_chain_tile<3, 6, 1>(m, wp, X, NN, X, m.in, p0, NN, ident, epi);
-            else mlp_chain_tile<4, 7, 1>(m, wp, X, NN, X, m.in, p0, NN, ident, epi);
-        }
-    }
-    if (xa.mode == MODE_NORMS) {
-        float t2[2] = {n2, z2};
-        block_sums<2>(t2, red);
-        if (threadIdx.x == 0) {
-            float* o = part + ((size_t)b * gridDim.x + blockIdx.x) * 2;
-            o[0] = t2[0];
-            o[1] = t2[1];
-        }
-    }
-}
 
 // the node-feature epilogue (k_xa's: SCORE / NORMS / PRED on the masked net) and, in NORMS mode, norm2[b][4] in k_normsum's layout:
 // |net_x|^2, |net_adj|^2 (k_lg_fin's tile partials, fixed order), |z_x|^2, |z_adj|^2.  One workgroup per sample.
@@ -712,6 +682,86 @@ __global__ __launch_bounds__(CCSD_LG_TB) void k_lg_hd_diag(HodgeLayerD h, float 
         auto qrow = [&](int c) { return Qb + ((size_t)c * E + e) * qw; };
         lg_hd_diag_edge(h, rks, s_hw, qrow, fl[i] * fl[j], Sb, NN, (size_t)i * N + j, (size_t)j * N + i);
     }
+}
+
+// ---- Hodge MLPs wider than 8 (num_linears_h >= 2 with a hidden width of 9 .. 16; Route::h_wide).  lg_hd_diag_edge's per-thread MLP is 8
+// wide -- at 16 its two register arrays would not fit beside the Q | K walk --, so mlp_attention on the diagonal runs as the dense pass
+// runs it: the 16-wide MFMA chain (mlp_chain_tile<1, 1, 1>) on the packed copies of PlanBuilder::hdm, 16 edges per tile.  One pass of a
+// workgroup takes CCSD_LG_TB consecutive edges from e0: every thread leaves the head-mean logits of its edge's channels in LDS
+// (s_S [cin][CCSD_LG_TB], mlp_attention's input, feature-major), then each wave runs four tiles; the epilogue is lg_hd_diag_edge's (mask, 2 tanh,
+// both orders of the node pair).  qrow(c, e): the Q | K row of channel c of edge e.  The same expressions as the narrow form but for the
+// summation order inside the MLP (the chain's).
+template <class QROW>
+CCSD_DEV void lg_hd_diag_tiles(const HodgeLayerD& h, const MlpD& matt, float rks, const float* __restrict__ wp, float* s_S, int e0, int E, QROW qrow,
+                               const unsigned char* __restrict__ edges, const float* __restrict__ fl, float* Ho, int N) {
+    const int NN = N * N;
+    const float rnc = 1.0f / (float)h.nchunk;
+    for (int u = (int)threadIdx.x; u < CCSD_LG_TB; u += (int)blockDim.x) {
+        const int e = e0 + u;
+        if (e >= E) continue;                       // (a tile's rows beyond E are clamped to its last valid row by mlp_chain_tile)
+        for (int c = 0; c < h.cin; ++c) {
+            const float* q = qrow(c, e);
+            s_S[c * CCSD_LG_TB + u] = attn_logits(q, q + h.adim, h.nchunk, h.dsplit, rks) * rnc;
+        }
+    }
+    __syncthreads();
+    const int rows = E - e0 < CCSD_LG_TB ? E - e0 : CCSD_LG_TB;
+    auto ident = [](int r) { return r; };
+    auto epi = [&](int u, int o, float v) {
+        const int i = edges[2 * (e0 + u)], j = edges[2 * (e0 + u) + 1];
+        const float fh = fl[i] * fl[j];
+        const float tv = tanh_f(v * fh * fh);
+        Ho[(size_t)o * NN + (size_t)i * N + j] = tv + tv;
+        Ho[(size_t)o * NN + (size_t)j * N + i] = tv + tv;
+    };
+#ifdef CCSD_EMU
+    for (int wv = 0; wv < CCSD_LG_TB / 64; ++wv)
+#else
+    const int wv = wave_index();
+#endif
+        for (int q4 = 0; q4 < 4; ++q4) {
+            const int p0 = 16 * (4 * wv + q4);
+            if (p0 < rows) mlp_chain_tile<1, 1, 1>(matt, wp, s_S, CCSD_LG_TB, s_S, matt.in, p0, rows, ident, epi);
+        }
+    __syncthreads();                                // (the next pass rewrites s_S)
+}
+
+// k_lg_hodge1 for such a plan (matt = hdm[0]).  grid: (grid-stride over E in passes of CCSD_LG_TB, B)
+__global__ __launch_bounds__(CCSD_LG_TB) void k_lg_hodge1_w(HodgeLayerD h, MlpD matt, float rks, const float* __restrict__ w, const float* __restrict__ wp,
+                                                           const unsigned char* __restrict__ edges, const float* __restrict__ P0, float* __restrict__ S,
+                                                           long long sstride, int ch0, int N, int E, const float* __restrict__ flags) {
+    __shared__ float s_S[CCSD_SMALLW * CCSD_LG_TB];
+    __shared__ float s_q[CCSD_LG_TB][2 * CCSD_LG_HAD + 1];
+    const int b = blockIdx.y, NN = N * N;
+    float* Sb = S + (size_t)b * sstride;
+    float* Hb = Sb + (size_t)ch0 * NN;
+    const float* fl = flags + (size_t)b * N;
+    float* q = &s_q[threadIdx.x][0];
+    for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < N; i += gridDim.x * blockDim.x)
+        for (int c = 0; c < h.cin + h.cout; ++c) Hb[(size_t)c * NN + (size_t)i * N + i] = 0.f;
+    auto qrow = [&](int c, int e) {
+        const int i = edges[2 * e], j = edges[2 * e + 1];
+        const size_t ij = (size_t)i * N + j, ji = (size_t)j * N + i;
+        const float a = Sb[(size_t)c * NN + ij];
+        lg_hd_qk0_row(h, w, P0 + ((size_t)b * E + e) * h.wc, c, a, q);
+        Hb[(size_t)c * NN + ij] = a;
+        Hb[(size_t)c * NN + ji] = a;
+        return (const float*)q;
+    };
+    for (int e0 = blockIdx.x * CCSD_LG_TB; e0 < E; e0 += gridDim.x * CCSD_LG_TB)
+        lg_hd_diag_tiles(h, matt, rks, wp, s_S, e0, E, qrow, edges, fl, Hb + (size_t)h.cin * NN, N);
+}
+// k_lg_hd_diag for such a plan (matt = hdm[h_L - 1]).  grid: (grid-stride over E in passes of CCSD_LG_TB, B)
+__global__ __launch_bounds__(CCSD_LG_TB) void k_lg_hd_diag_w(HodgeLayerD h, MlpD matt, float rks, const float* __restrict__ wp,
+                                                            const unsigned char* __restrict__ edges, const float* __restrict__ QK, long long qstride,
+                                                            float* __restrict__ S, long long sstride, int ch0, int N, int E,
+                                                            const float* __restrict__ flags) {
+    __shared__ float s_S[CCSD_SMALLW * CCSD_LG_TB];
+    const int b = blockIdx.y, qw = 2 * h.adim;
+    const float* Qb = QK + (size_t)b * qstride;
+    auto qrow = [&](int c, int e) { return Qb + ((size_t)c * E + e) * qw; };
+    for (int e0 = blockIdx.x * CCSD_LG_TB; e0 < E; e0 += gridDim.x * CCSD_LG_TB)
+        lg_hd_diag_tiles(h, matt, rks, wp, s_S, e0, E, qrow, edges, flags + (size_t)b * N, S + (size_t)b * sstride + (size_t)(ch0 * N) * N, N);
 }
 
 

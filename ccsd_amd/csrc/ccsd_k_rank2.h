@@ -396,15 +396,30 @@ __global__ __launch_bounds__(256, 2) void k_gemm_h_full(const float* __restrict_
 //          with the layer-0 hodge adjacency diagonal, cc_utils.py:1536) -- produced on the fly, never stored.
 // grid (ceil(wc/64), ceil(B*E/64), 1)
 // ---------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void k_gemm_p(const float* __restrict__ rank2, const float* __restrict__ W,
-                                                float* __restrict__ P, int rows, int E, int K, int wc, int wcat_off,
-                                                int layer, MlpD mval, int cin, const float* __restrict__ acoef,
-                                                const unsigned long long* __restrict__ offbits,
-                                                const unsigned char* __restrict__ edges,
-                                                const unsigned long long* __restrict__ cells, int kchunk) {
+// mlp_value per rank-2 element from zero-padded blocks in LDS (broadcast reads): MW = CCSD_SMALLW, the 8 x 8 blocks of CCSD_HWBLK floats, or
+// MW = CCSD_HWIDE, 16 x 16 + 16 floats per Linear, for plans whose hodge MLPs are wider than 8 (Route::h_wide: k_gemm_p_w, k_hodge_value_w)
+template <int MW>
+struct MvalBlocks {
+    static constexpr int FLOATS = CCSD_MAXLIN * (MW == CCSD_SMALLW ? CCSD_HWBLK : MW * MW + MW);
+    static CCSD_DEV void stage(const MlpD& m, const float* __restrict__ w, float* blk) {
+        if constexpr (MW == CCSD_SMALLW) stage_mlp_blocks(m, w, blk, (int)threadIdx.x, (int)blockDim.x);
+        else stage_mlp_blocks_w<MW>(m, w, blk);
+    }
+    static CCSD_DEV void eval(const float* blk, int nlin, const float* in, float* out) {
+        if constexpr (MW == CCSD_SMALLW) small_mlp_lds<MW>(blk, nlin, in, out);
+        else small_mlp_ldsw<MW>(blk, nlin, in, out);
+    }
+};
+template <int MW>
+CCSD_DEV void gemm_p_body(const float* __restrict__ rank2, const float* __restrict__ W,
+                          float* __restrict__ P, int rows, int E, int K, int wc, int wcat_off,
+                          int layer, const MlpD& mval, int cin, const float* __restrict__ acoef,
+                          const unsigned long long* __restrict__ offbits,
+                          const unsigned char* __restrict__ edges,
+                          const unsigned long long* __restrict__ cells, int kchunk) {
     __shared__ float As[T_BK * T_LD];
     __shared__ float Bs[T_BK * T_LD];
-    __shared__ float s_mv[CCSD_MAXLIN * CCSD_HWBLK];   // mlp_value as zero-padded 8x8 blocks (LDS broadcast reads)
+    __shared__ float s_mv[MvalBlocks<MW>::FLOATS];
     const int m0 = blockIdx.y * T_BM, n0 = blockIdx.x * T_BN;
     // split K (small batches: too few 64-row tiles to fill the chip): slice blockIdx.z sums k in [z kchunk, (z + 1) kchunk) into its own
     // copy of P (P + z rows wc); k_sum_splits adds the slices in a fixed order.  kchunk >= K with gridDim.z == 1: the whole sum, in place.
@@ -413,7 +428,7 @@ __global__ __launch_bounds__(256) void k_gemm_p(const float* __restrict__ rank2,
     const float* Wc = W + wcat_off;
     TileAcc acc;
     tile_zero(acc);
-    if (layer == 1) { stage_mlp_blocks(mval, W, s_mv, (int)threadIdx.x, (int)blockDim.x); __syncthreads(); }
+    if (layer == 1) { MvalBlocks<MW>::stage(mval, W, s_mv); __syncthreads(); }
     for (int k0 = kbeg; k0 < kend; k0 += T_BK) {
         for (int idx = threadIdx.x; idx < T_BM * T_BK; idx += blockDim.x) {
             const int r = idx / T_BK, kk = idx % T_BK, k = k0 + kk, row = m0 + r;
@@ -423,10 +438,10 @@ __global__ __launch_bounds__(256) void k_gemm_p(const float* __restrict__ rank2,
                 if (layer == 1) {
                     const int b = row / E, e = row % E;
                     const unsigned long long off = offbits[b];
-                    float in[CCSD_SMALLW], out[CCSD_SMALLW];
+                    float in[MW], out[MW];
 #pragma unroll
-                    for (int c = 0; c < CCSD_SMALLW; ++c) in[c] = c < cin ? acoef[((size_t)b * cin + c) * E + e] * v : 0.f;
-                    small_mlp_lds<CCSD_SMALLW>(s_mv, mval.n, in, out);
+                    for (int c = 0; c < MW; ++c) in[c] = c < cin ? acoef[((size_t)b * cin + c) * E + e] * v : 0.f;
+                    MvalBlocks<MW>::eval(s_mv, mval.n, in, out);
                     v = edge_on(off, edges, e) * out[0] * cell_on(off, cells, k);
                 }
             }
@@ -450,6 +465,16 @@ __global__ __launch_bounds__(256) void k_gemm_p(const float* __restrict__ rank2,
         }
     });
 }
+#define CCSD_GEMM_P_ARGS const float* __restrict__ rank2, const float* __restrict__ W, float* __restrict__ P, int rows, int E, int K, int wc,       \
+                         int wcat_off, int layer, MlpD mval, int cin, const float* __restrict__ acoef, const unsigned long long* __restrict__ offbits, \
+                         const unsigned char* __restrict__ edges, const unsigned long long* __restrict__ cells, int kchunk
+__global__ __launch_bounds__(256) void k_gemm_p(CCSD_GEMM_P_ARGS) {
+    gemm_p_body<CCSD_SMALLW>(rank2, W, P, rows, E, K, wc, wcat_off, layer, mval, cin, acoef, offbits, edges, cells, kchunk);
+}
+__global__ __launch_bounds__(256) void k_gemm_p_w(CCSD_GEMM_P_ARGS) {
+    gemm_p_body<CCSD_HWIDE>(rank2, W, P, rows, E, K, wc, wcat_off, layer, mval, cin, acoef, offbits, edges, cells, kchunk);
+}
+#undef CCSD_GEMM_P_ARGS
 // k_sum_splits: P[i] = parts[0][i] + parts[1][i] + ... (the K slices of k_gemm_p, always in this order: reproducible)
 __global__ void k_sum_splits(const float* __restrict__ parts, float* __restrict__ P, long long n, int S) {
     for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x) {
@@ -912,17 +937,18 @@ __global__ void k_edgecoef(const float* __restrict__ adj, float* __restrict__ ac
 // grid (ceil(K / cw), B), cw = 64 columns (32 when E > 128); one workgroup holds the [E][cw] column slab of Rin in LDS (dynamic: E cw floats).
 // A wave works on one edge row (two) at a time with its lanes on the columns: H_c[e][.] is wave-uniform, the slab reads conflict-free.
 // ---------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void k_hodge_value(const float* __restrict__ Rin, const float* __restrict__ H, int hstride,
-                                                     const float* __restrict__ acoef, const float* __restrict__ W, MlpD mval, int cin,
-                                                     float* __restrict__ Rout, int E, int K, int cw,
-                                                     const unsigned long long* __restrict__ offbits,
-                                                     const unsigned char* __restrict__ edges,
-                                                     const unsigned long long* __restrict__ cells) {
+template <int MW>
+CCSD_DEV void hodge_value_body(const float* __restrict__ Rin, const float* __restrict__ H, int hstride,
+                               const float* __restrict__ acoef, const float* __restrict__ W, const MlpD& mval, int cin,
+                               float* __restrict__ Rout, int E, int K, int cw,
+                               const unsigned long long* __restrict__ offbits,
+                               const unsigned char* __restrict__ edges,
+                               const unsigned long long* __restrict__ cells) {
     CCSD_DYN_SMEM(Rs);                                   // [E][cw]
-    __shared__ float s_mv[CCSD_MAXLIN * CCSD_HWBLK];
+    __shared__ float s_mv[MvalBlocks<MW>::FLOATS];
     const int b = blockIdx.y, k0 = blockIdx.x * cw, sh = cw == 64 ? 6 : 5;
     const float* Rb = Rin + (size_t)b * E * K;
-    stage_mlp_blocks(mval, W, s_mv, (int)threadIdx.x, (int)blockDim.x);
+    MvalBlocks<MW>::stage(mval, W, s_mv);
     for (int idx = threadIdx.x; idx < E * cw; idx += blockDim.x) {
         const int e = idx >> sh, kk = idx & (cw - 1);
         Rs[idx] = k0 + kk < K ? Rb[(size_t)e * K + k0 + kk] : 0.f;
@@ -932,9 +958,9 @@ __global__ __launch_bounds__(256) void k_hodge_value(const float* __restrict__ R
     for (int idx = threadIdx.x; idx < E * cw; idx += blockDim.x) {
         const int e = idx >> sh, kk = idx & (cw - 1), k = k0 + kk;
         if (k >= K) continue;
-        float in[CCSD_SMALLW], out[CCSD_SMALLW];
+        float in[MW], out[MW];
 #pragma unroll
-        for (int c = 0; c < CCSD_SMALLW; ++c) {
+        for (int c = 0; c < MW; ++c) {
             float v = 0.f;
             if (c < cin) {
                 if (H) {
@@ -946,10 +972,21 @@ __global__ __launch_bounds__(256) void k_hodge_value(const float* __restrict__ R
             }
             in[c] = v;
         }
-        small_mlp_lds<CCSD_SMALLW>(s_mv, mval.n, in, out);
+        MvalBlocks<MW>::eval(s_mv, mval.n, in, out);
         Rout[((size_t)b * E + e) * K + k] = edge_on(off, edges, e) * out[0] * cell_on(off, cells, k);
     }
 }
+#define CCSD_HODGE_VALUE_ARGS const float* __restrict__ Rin, const float* __restrict__ H, int hstride, const float* __restrict__ acoef,           \
+                              const float* __restrict__ W, MlpD mval, int cin, float* __restrict__ Rout, int E, int K, int cw,                     \
+                              const unsigned long long* __restrict__ offbits, const unsigned char* __restrict__ edges,                              \
+                              const unsigned long long* __restrict__ cells
+__global__ __launch_bounds__(256) void k_hodge_value(CCSD_HODGE_VALUE_ARGS) {
+    hodge_value_body<CCSD_SMALLW>(Rin, H, hstride, acoef, W, mval, cin, Rout, E, K, cw, offbits, edges, cells);
+}
+__global__ __launch_bounds__(256) void k_hodge_value_w(CCSD_HODGE_VALUE_ARGS) {
+    hodge_value_body<CCSD_HWIDE>(Rin, H, hstride, acoef, W, mval, cin, Rout, E, K, cw, offbits, edges, cells);
+}
+#undef CCSD_HODGE_VALUE_ARGS
 
 // ---------------------------------------------------------------------------------------------
 // k_hf_score: ScoreNetworkF.  Tile (edge rows m0.., cell columns n0..) of  H.F  on MFMA, then per

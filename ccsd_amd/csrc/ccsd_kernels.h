@@ -14,7 +14,8 @@
 //                    (+ ccsd_attn_stack.inc: the AttentionLayer stack)
 //   ccsd_k_lg.h      k_lg_*: the tiled graph-network path (graph-only plans above 64 nodes, plans without a k_xa LDS layout, one-hodge-layer
 //                    ScoreNetworkA_CC among them): ScoreNetworkX + ScoreNetworkA(_CC) over the HBM workspace, each graph tiled over many
-//                    workgroups (definitions compiled in ccsd_lg.hip)
+//                    workgroups (definitions compiled in ccsd_lg.hip; + ccsd_lg_fin.inc: the body of k_lg_fin and of k_lg_fin_w, which
+//                    ccsd_lgw.hip compiles)
 //   ccsd_k_update.h  k_normsum, k_langevin_apply, k_s4_apply, k_init_state, k_quantize, k_rank2_cells
 // The product library is built from several translation units compiled in parallel (ccsd_hip.hip: C ABI + the small kernels;
 // ccsd_r2*.hip / ccsd_xa.hip: the explicit instantiations of the two big kernel templates); the host emulation used by the

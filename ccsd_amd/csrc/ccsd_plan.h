@@ -12,7 +12,8 @@
 #define CCSD_MAXHLX 6
 #define CCSD_MAXFL 4      // HodgeNetworkLayers in ScoreNetworkF
 #define CCSD_MAXCN 4      // channels [F, HF, H^2 F, H^3 F] of ScoreNetworkF's input (cnum, cc_utils.py:961-979)
-#define CCSD_SMALLW 8     // widest per-thread MLP in the hodge branch
+#define CCSD_SMALLW 8     // widest per-thread MLP in the hodge branch (k_xa, k_r2), and the ceiling on its channel counts
+#define CCSD_HWIDE 16     // widest hidden Linear of the hodge branch's MLPs: above CCSD_SMALLW only the tiled graph-network route and the tiled rank-2 family serve
 #define CCSD_FW 16        // widest per-thread MLP in ScoreNetworkF's general path (fused kernel; hodge baseline mlp_hodge)
 #define CCSD_FWMAX 32     // ... in the tiled k_hf_score path
 #define CCSD_XA_MAXN 64   // k_xa: one graph per workgroup, its working set in one CU's LDS (node masks: one 64-bit word per graph)
@@ -35,11 +36,12 @@ struct MlpD {
     int pw[CCSD_MAXLIN], pb[CCSD_MAXLIN];
 };
 // (input, hidden, output) widths in 16-feature tiles the chain is instantiated for (index 0 = none)
-#define CCSD_NSHAPES 7
-static const int CCSD_CHAIN_SHAPES[CCSD_NSHAPES][3] = {{0, 0, 0}, {1, 1, 1}, {2, 3, 1}, {2, 4, 1}, {3, 5, 1}, {3, 6, 1}, {4, 7, 1}};
+#define CCSD_NSHAPES 8
+static const int CCSD_CHAIN_SHAPES[CCSD_NSHAPES][3] = {{0, 0, 0}, {1, 1, 1}, {2, 3, 1}, {2, 4, 1}, {3, 5, 1}, {3, 6, 1}, {4, 7, 1}, {4, 8, 1}};
 #define CCSD_CHAIN_EDGE 0x02u      /* shapes allowed per call site (bit = shape index) */
 #define CCSD_CHAIN_XFIN 0x24u
 #define CCSD_CHAIN_AFIN 0x78u
+#define CCSD_CHAIN_AFIN_LG 0x80u   /* the tiled route alone (k_lg_fin_w): ScoreNetworkA's final MLP with 57 .. 64 channels, PlanBuilder::afin_lg */
 static inline __host__ __device__ int pad16(int v) { return (v + 15) & ~15; }
 #define CCSD_MLP_WT 0x5754
 // dims of linear i of an MlpD
@@ -189,6 +191,25 @@ struct PlanBuilder {
     // out (route plans with two or more HodgeAdjAttentionLayers): mlp_attention of every layer but the last with packed copies for
     // mlp_chain_tile (k_lg_hd_dense).  Kept out of PlanD, and reserved behind everything else in the packed buffer: no plan k_xa serves moves
     MlpD hdm[CCSD_MAXHL + CCSD_MAXHLX] = {};
+    // out: some Linear of the hodge branch's MLPs is wider than CCSD_SMALLW (num_linears_h >= 2, hid = 9 .. 16).  Such a plan takes the route
+    // at any N, never k_xa or k_r2 (their per-thread small_mlp stays 8 wide), and hdm holds EVERY layer's mlp_attention: the last layer's
+    // diagonal runs the chain too (k_lg_hd_diag_w, k_lg_hodge1_w)
+    int h_wide = 0;
+    // out (wide plans whose PlanD::a_fin has no chained shape, 57 to 64 channels -- k_xa runs those through block_linear, and narrow plans
+    // with such a final MLP stay with it): the final MLP with packed copies in the route's own shape (CCSD_CHAIN_AFIN_LG, k_lg_fin_w)
+    MlpD afin_lg = {};
+    // the packed copies only route plans read, reserved behind everything else in the packed buffer (no plan k_xa serves moves)
+    void route_copies(const PlanD& p) {
+        if (h_wide && !p.a_fin.chain) {
+            afin_lg = p.a_fin; chainify(afin_lg, CCSD_CHAIN_AFIN_LG);
+            // (ccsd_lg_ineligible admitted the plan for this shape: launch_lg must never meet an unchained final MLP)
+            if (!afin_lg.chain) fail(CCSD_ERR_RUNTIME, "tiled graph-network route: no chained shape for the final MLP");
+        }
+        for (int l = 0; l + (h_wide ? 0 : 1) < p.h_L; ++l) {
+            hdm[l] = ccsd_hl(p, l).matt;
+            chainify(hdm[l], CCSD_CHAIN_EDGE);
+        }
+    }
     int take(int64_t n) {
         int o = cur;
         cur += (int)n;
@@ -302,7 +323,7 @@ static inline size_t lg_nmlp_lds(const PlanD& p) {
     for (int l = 0; l < p.a_L; ++l) if (lg_nmlp_lds_of(p.al[l].mc) > v) v = lg_nmlp_lds_of(p.al[l].mc);
     return v;
 }
-static inline const char* ccsd_lg_ineligible(const ccsd_config_t* c, const PlanD* p) {
+static inline const char* ccsd_lg_ineligible(const ccsd_config_t* c, const PlanD* p, int h_wide) {
     if (p->a_is_cc == 2 && (c->h_nhid > CCSD_LG_HBW || (c->h_num_layers > 1 && c->h_adim > CCSD_LG_HBW)))
         return "ScoreNetworkA_Base_CC with BaselineBlocks wider than 16";
     if (p->h_L > 1 && p->E > CCSD_LG_HD_MAXE) return "hodge stacks of two or more layers beyond E = 703 (the dense E x E hodge layer)";
@@ -315,7 +336,8 @@ static inline const char* ccsd_lg_ineligible(const ccsd_config_t* c, const PlanD
         if (a.mlp.chain != 1) return "edge MLPs wider than 16 features";
         if (a.adim > 64) return "attention dimensions above 64";
     }
-    if (!p->a_fin.chain) return "final MLPs wider than 64 input channels";
+    // (57 to 64 channels: the route's own shape, for the plans that have no other kernel -- wide hodge MLPs; any other such plan stays with k_xa)
+    if (!p->a_fin.chain && !(h_wide && p->a_fdim <= 64)) return "final MLPs wider than 64 input channels";
     if (lg_nmlp_lds(*p) > 160 * 1024) return "per-node MLPs whose 16-row activations exceed the 160 KB LDS of a CU";
     return nullptr;
 }
@@ -457,8 +479,11 @@ static inline size_t ccsd_build_plan(const ccsd_config_t* c, PlanD* p, PlanBuild
             const int hid = 2 * (h.cin > h.cout ? h.cin : h.cout);
             h.mval = pb.mlp(c->h_num_linears, h.cin, hid, 1);
             h.matt = pb.mlp(c->h_num_linears, h.cin, hid, h.cout);
-            if (h.cin > CCSD_SMALLW || hid > CCSD_SMALLW || h.cout > CCSD_SMALLW) {
-                pb.fail(CCSD_ERR_UNSUPPORTED, "hodge MLP wider than 8"); return 0; }
+            // (a single-Linear MLP has no Linear of width hid)
+            const int hidw = c->h_num_linears > 1 ? hid : 0;
+            if (h.cin > CCSD_SMALLW || hidw > CCSD_HWIDE || h.cout > CCSD_SMALLW) {
+                pb.fail(CCSD_ERR_UNSUPPORTED, "hodge MLP wider than 16"); return 0; }
+            if (hidw > CCSD_SMALLW) pb.h_wide = 1;
             hch += h.cout;
         }
         p->a_nch_hodge = hch;
@@ -508,10 +533,11 @@ static inline size_t ccsd_build_plan(const ccsd_config_t* c, PlanD* p, PlanBuild
     }
 
     // ---- route: tiled graph-network kernels (ccsd_k_lg.h) when k_xa cannot place the plan (N > 64, or no LDS layout below) or when forced
-    const char* lg_reason = ccsd_lg_ineligible(c, p);
+    const char* lg_reason = ccsd_lg_ineligible(c, p, pb.h_wide);
     if (big) {
         if (lg_reason) { pb.fail(CCSD_ERR_UNSUPPORTED, std::string("N > 64 needs the tiled graph-network route, which does not serve ") + lg_reason); return 0; }
         pb.lg = 1;
+        pb.route_copies(*p);
         p->ldn = round_ld(N);
         p->chan_rows = p->a_fdim;
         return nweights;            // (no k_xa layout: its LDS fields stay zero)
@@ -520,6 +546,16 @@ static inline size_t ccsd_build_plan(const ccsd_config_t* c, PlanD* p, PlanBuild
     if (p->hb_L > CCSD_MAXHL) {
         if (lg_reason) { pb.fail(CCSD_ERR_UNSUPPORTED, std::string("more than 2 HodgeBaselineLayers need the tiled graph-network route, which does not serve ") + lg_reason); return 0; }
         pb.lg = 1;
+        pb.route_copies(*p);
+        p->ldn = round_ld(N);
+        p->chan_rows = p->a_fdim;
+        return nweights;
+    }
+    // ScoreNetworkA_CC with hodge MLPs wider than 8: k_xa's (and k_r2's) per-thread small_mlp is 8 wide, only the route evaluates them
+    if (pb.h_wide) {
+        if (lg_reason) { pb.fail(CCSD_ERR_UNSUPPORTED, std::string("hodge MLPs wider than 8 need the tiled graph-network route, which does not serve ") + lg_reason); return 0; }
+        pb.lg = 1;
+        pb.route_copies(*p);
         p->ldn = round_ld(N);
         p->chan_rows = p->a_fdim;
         return nweights;
@@ -699,8 +735,7 @@ static inline size_t ccsd_build_plan(const ccsd_config_t* c, PlanD* p, PlanBuild
         if (!lg_reason) pb.lg = 1;         // no k_xa layout: the tiled route serves the plan
         else pb.fail(CCSD_ERR_UNSUPPORTED, std::string("graph-network working set exceeds the 160 KB LDS of a CU, and the tiled graph-network route does not serve ") + lg_reason);
     }
-    if (pb.lg && p->h_L > 1)
-        for (int l = 0; l + 1 < p->h_L; ++l) { pb.hdm[l] = ccsd_hl(*p, l).matt; pb.chainify(pb.hdm[l], CCSD_CHAIN_EDGE); }
+    if (pb.lg) pb.route_copies(*p);
     return nweights;
 }
 

@@ -185,7 +185,8 @@ enum {
     CCSD_QUERY_TILED_FUSE = 14,   /* 1: tiled rank-2 side, the Langevin corrector's rank2 work rides on the layer-0 projection pass */
     CCSD_QUERY_EW1_FUSE = 15,     /* 1: k_ew1 plans, the whole rank-2 side of a half-step rides on the layer-0 projection pass */
     CCSD_QUERY_H_GENERAL = 16,    /* 1: general hodge stack (R_l materialised layer by layer) */
-    CCSD_QUERY_GEO_EK = 17        /* general-path kernels: 0 run-time (E, K); 1 community_small, 2 zinc250k, 3 ENZYMES_small compiled in */
+    CCSD_QUERY_GEO_EK = 17,       /* general-path kernels: 0 run-time (E, K); 1 community_small, 2 zinc250k, 3 ENZYMES_small compiled in */
+    CCSD_QUERY_H_WIDE = 18        /* 1: ScoreNetworkA_CC hodge MLPs wider than 8 (16-wide kernels of the tiled route and the tiled rank-2 family) */
 };
 int ccsd_plan_query(const ccsd_plan_t* plan, int32_t what, int64_t* value);
 

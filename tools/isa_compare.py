@@ -9,7 +9,12 @@ unit whose assembly in DIR is newer than the tree's sources is not compiled agai
   same opcodes  equal line count and opcode multiset, and unchanged descriptor / register / scratch / LDS / occupancy lines
   different     anything else (also: present in one tree only)
 followed by the resource lines of the NEW tree's symbol and, where one of them moved, `[old -> new]` per moved figure.  It compares text;
-it knows nothing about particular instructions.
+it knows nothing about particular instructions.  Not part of the comparison: the number behind a compiler-local label's name -- every
+`.L<name><n>` (`.LBB<f>_<n>` and `.Lfunc_end<f>`, where <f> is the ordinal of the function inside its unit, but also `.Ltmp<n>`, `.LJTI<f>_<n>`
+and any other such label: their numbering is erased alike, while their positions and the code between them still count) and `BB<f>_<n>` in
+comments --, the column at which a comment starts, and the `.globl` / `.protected` / `.p2align` lines ahead of a function, which name that
+function and not the one before it.  So a kernel added in the middle of a unit leaves the functions behind it `identical` where their code is.
+A unit that only one of the trees has lists its symbols as present in that tree only.
 Exit status 1 when any symbol is `different`.
 """
 import argparse
@@ -19,7 +24,7 @@ import re
 import subprocess
 import sys
 
-UNITS = ["ccsd_hip", "ccsd_r2", "ccsd_r2b", "ccsd_r2c", "ccsd_r2d", "ccsd_xa", "ccsd_lg"]
+UNITS = ["ccsd_hip", "ccsd_r2", "ccsd_r2b", "ccsd_r2c", "ccsd_r2d", "ccsd_xa", "ccsd_lg", "ccsd_lgw"]
 CSRC = os.path.join("ccsd_amd", "csrc")
 STATS = ("NumVgprs", "NumAgprs", "TotalNumSgprs", "ScratchSize", "LDSByteSize", "Occupancy", "codeLenInByte")
 
@@ -32,6 +37,8 @@ def compile_all(trees, work, jobs):
         src_dir = os.path.join(tree, CSRC)
         newest = max(os.path.getmtime(os.path.join(d, f)) for d in (src_dir, os.path.join(tree, "include")) for f in os.listdir(d))
         for u in UNITS:
+            if not os.path.exists(os.path.join(tree, CSRC, u + ".hip")):      # (a unit only one of the trees has: its symbols are in one tree only)
+                continue
             out = os.path.join(work, tag, u + ".s")
             if not os.path.exists(out) or os.path.getmtime(out) < newest:
                 # relative source path, cwd = the tree: nothing in the assembly depends on where the tree lies
@@ -56,11 +63,21 @@ def compile_all(trees, work, jobs):
 def split_symbols(path):
     """-> ({symbol: {"body": [...], "desc": [...], "stats": {...}}}, [every line that belongs to no symbol])"""
     syms, rest = collections.OrderedDict(), []
+    if not os.path.exists(path):
+        return syms, rest
     cur, part = None, None            # part: "body" up to the symbol's .Lfunc_end, "desc" inside its .amdhsa_kernel block, "tail" behind (resource comments)
     for line in open(path):
         line = re.sub(r"__hip_cuid_[0-9a-f]+", "__hip_cuid", line.rstrip("\n"))      # (a hash of the unit's path and contents)
+        # compiler-local labels (.LBB<f>_<n>, .Lfunc_end<f>, BB<f>_<n> in comments) carry the ordinal <f> of their function in the unit: a
+        # kernel added ahead of a function renumbers them without changing a byte of its code
+        line = re.sub(r"(\.L[A-Za-z_]+|\bBB)\d+(?=_\d|:|-|\s|$)", r"\1", line)
+        line = re.sub(r"\s+;", " ;", line)            # (the comment column moves with the label's width)
         m = re.match(r"\s*\.type\s+(\S+),@function", line)
         if m:
+            # (the .protected / .globl / .p2align lines ahead of it name this function, not the one before)
+            prev = cur["desc"] if cur is not None else rest
+            while prev and re.match(r"\s*\.(protected|globl|weak|p2align|section\s+\.text)", prev[-1]):
+                prev.pop()
             cur, part = syms.setdefault(m.group(1), {"body": [], "desc": [], "stats": {}}), "body"
             continue
         if cur is None:
@@ -75,7 +92,7 @@ def split_symbols(path):
             part = "body" if ".end_amdhsa_kernel" in line else "desc"
         elif part == "body":
             cur["body"].append(line)
-            if re.match(r"\.Lfunc_end\d+:", line):
+            if re.match(r"\.Lfunc_end\d*:", line):
                 part = "tail"
         elif re.match(r"\s*\.(amdgpu_metadata|ident|addrsig)|\s*\.section\s+\S*\.note|\s*\.type\s", line):
             cur = None                 # (behind the last function, or a variable: no symbol's text)

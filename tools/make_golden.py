@@ -701,6 +701,52 @@ def kat_hodge_general():
     print("kat_hodge_general", {k: (v.shape, float(np.abs(v).max())) for k, v in out.items() if k.endswith("/out")})
 
 
+def kat_hodge_wide():
+    """ScoreNetworkA_CC whose hodge branch is up to 8 channels wide, so that the true MLPs mlp_value / mlp_attention (num_linears_h >= 2)
+    have hidden Linears 9 to 16 wide (hid = 2 max(cin, cout), hodge_attention.py:245-252), built by the reference's constructor; the graph
+    branch is kat_hodge_general's.  Tags: one layer with the full 16 (W1_n5), two layers with a ragged 10 (W2_n6), the qm9_CC geometry with
+    three Linears (W2_n9), three layers at E = 66 with hidden widths 12 and 16 (W3_n12: the general hodge stack), and the single-Linear
+    counterpart of W2_n9 (S2_n9), whose widest Linear is 8."""
+    from ccsd.src.models.ScoreNetwork_A_CC import ScoreNetworkA_CC
+
+    out, meta = {}, {}
+    base = dict(nhid=4, num_layers=2, num_linears=2, c_init=2, c_hid=2, c_final=2, adim=2, num_heads=2, conv="GCN",
+                conv_hodge="HCN", use_bn=False, is_cc=True, nhid_h=4, adim_h=4, num_heads_h=2)
+    cases = {
+        "W1_n5": (5, 10, 3, 4, dict(num_layers_h=1, num_linears_h=2, c_hid_h=8, c_final_h=8), [5, 4, 3]),
+        "W2_n6": (6, 2, 3, 4, dict(num_layers_h=2, num_linears_h=2, c_hid_h=5, c_final_h=3), [6, 4]),
+        "W2_n9": (9, 4, 3, 9, dict(num_layers_h=2, num_linears_h=3, c_hid_h=8, c_final_h=4), [9, 6, 2]),
+        "W3_n12": (12, 3, 3, 4, dict(c_init=3, num_layers_h=3, num_linears_h=2, c_hid_h=6, c_final_h=8), [12, 7]),
+        "S2_n9": (9, 4, 3, 9, dict(num_layers_h=2, num_linears_h=1, c_hid_h=8, c_final_h=4), [9, 5]),
+    }
+    torch.manual_seed(3141)
+    for tag, (N, Fd, dmin, dmax, hp, counts) in cases.items():
+        prm = dict(base, **hp, max_feat_num=Fd, max_node_num=N, d_min=dmin, d_max=dmax)
+        m = ScoreNetworkA_CC(**prm)
+        for k, p_ in m.named_parameters():
+            if k.endswith("bias"):
+                p_.data.normal_(0, 0.2)
+        m.eval()
+        B = len(counts)
+        flags = make_flags(B, N, counts)
+        x, adj, rank2 = masked_state(59, B, N, Fd, True, dmin, dmax, flags, 0.5)
+        for k, v in (("flags", flags), ("x", x), ("adj", adj), ("rank2", rank2)):
+            out[f"{tag}/{k}"] = v.numpy()
+        with torch.no_grad():
+            for k, v in m.state_dict().items():
+                out[f"{tag}/w/{k}"] = v.numpy()
+            out[f"{tag}/out"] = m(x, adj, rank2, flags).numpy()
+        meta[tag] = dict(prm, model_type="ScoreNetworkA_CC")
+    # (the N = 12 tag's K = 715 rows of Wcat and rank2 would carry the file past 1 MiB: it goes into a second one, named in "files")
+    second = {k: out.pop(k) for k in list(out) if k.startswith("W3_n12/")}
+    out["meta"] = json.dumps(meta)
+    out["files"] = json.dumps(["kat_hodge_wide.npz", "kat_hodge_wide.1.npz"])
+    np.savez_compressed(os.path.join(GOLD, "kat_hodge_wide.npz"), **out)
+    np.savez_compressed(os.path.join(GOLD, "kat_hodge_wide.1.npz"), **second)
+    out.update(second)
+    print("kat_hodge_wide", {k: (v.shape, float(np.abs(v).max())) for k, v in out.items() if k.endswith("/out")})
+
+
 def reference_variant_status():
     """What the reference itself does with the two config switches no shipped config sets: use_bn=True (layers.py:219-224,
     262-275: BatchNorm1d(hidden) applied to (B, N, hidden) / (B, N, N, hidden) activations) and conv_hodge="MLP"
@@ -1029,6 +1075,9 @@ def main():
     only = set(sys.argv[1:])
     if only == {"base_cc_route"}:
         base_cc_route()
+        return
+    if only == {"kat_hodge_wide"}:
+        kat_hodge_wide()
         return
     if only == {"grid_small_cc"}:
         grid_small_cc()
