@@ -24,7 +24,7 @@ EXPORTS = [
     "ccsd_plan_create", "ccsd_plan_destroy", "ccsd_weight_count", "ccsd_rank2_dims", "ccsd_workspace_bytes",
     "ccsd_last_error", "ccsd_score", "ccsd_init_state", "ccsd_corrector_norms", "ccsd_corrector_apply",
     "ccsd_predictor", "ccsd_s4_apply", "ccsd_sampler_run", "ccsd_quantize", "ccsd_rank2_cells", "ccsd_profile_kernel", "ccsd_profile_stride", "ccsd_profile_read", "ccsd_profile_launches", "ccsd_debug_stamps",
-    "ccsd_noise_draws", "ccsd_plan_query", "ccsd_sampler_run_ex",
+    "ccsd_noise_draws", "ccsd_plan_query", "ccsd_sampler_run_ex", "ccsd_finish",
 ]
 QUERIES = {"fused_r2": 0, "xa_variant": 1, "r2_lds_bytes": 2, "xa_lds_bytes": 3, "fused_loop": 4, "merged_r2": 5, "ew1": 6, "large_graph": 7,
            "r2_family": 8, "r2_instance": 9, "loop_form": 10, "h_full": 11, "hp_full": 12, "p0_narrow": 13, "tiled_fuse": 14, "ew1_fuse": 15,
@@ -58,6 +58,22 @@ class State(C.Structure):
 
 class Noise(C.Structure):
     _fields_ = [("zx", C.c_void_p), ("zadj", C.c_void_p), ("zrank2", C.c_void_p)]
+
+
+FINISH_ADJ_QUANTIZE, FINISH_ADJ_MOL = 0, 1
+
+
+class FinishDims(C.Structure):
+    _fields_ = [("B", C.c_int32), ("N", C.c_int32), ("F", C.c_int32), ("E", C.c_int32), ("K", C.c_int64),
+                ("d_min", C.c_int32), ("d_max", C.c_int32), ("adj_mode", C.c_int32), ("thr", C.c_float)]
+
+
+FINISH_OUTPUTS = ("adj_int", "degree", "degree_hist", "edge_hist", "n_nodes", "x_hist", "rank2_u8", "rank2_cell_bits",
+                  "rank2_cell_count", "rank2_cell_hist", "rank2_nnz")
+
+
+class FinishOut(C.Structure):
+    _fields_ = [(n, C.c_void_p) for n in FINISH_OUTPUTS]
 
 
 # ccsd_reduce_fn: int (*)(float* sums_dev, int32_t n, void* stream, void* user)
@@ -141,6 +157,8 @@ class Library:
         L.ccsd_noise_draws.restype = C.c_int
         L.ccsd_plan_query.argtypes = [vp, i32, P(i64)]
         L.ccsd_plan_query.restype = C.c_int
+        L.ccsd_finish.argtypes = [P(FinishDims), P(State), vp, P(FinishOut), vp]
+        L.ccsd_finish.restype = C.c_int
 
     def __getattr__(self, name):
         return getattr(self.c, name)

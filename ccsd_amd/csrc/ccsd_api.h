@@ -1651,3 +1651,65 @@ extern "C" int ccsd_rank2_cells(const float* rank2, int32_t B, int32_t E, int64_
     return CCSD_OK;
 }
 
+
+// ccsd_finish: quantised outputs, cell bitmask and per-complex descriptors of finished samples (plan-free).  The graph pass
+// (k_finish_graph) and the rank-2 pass (k_finish_rank2) are launched only when one of their outputs is requested.
+extern "C" int ccsd_finish(const ccsd_finish_dims_t* d, const ccsd_state_t* in, const float* flags, const ccsd_finish_out_t* out,
+                           void* stream) {
+    (void)flags;      // (no output depends on the node flags: finished samples are masked, masked slots count as isolated / empty)
+    if (!d || !in || !out) return set_err(CCSD_ERR_INVALID, "ccsd_finish: NULL argument");
+    const int B = d->B, N = d->N, F = d->F;
+    if (B < 1) return set_err(CCSD_ERR_INVALID, "ccsd_finish: B must be >= 1");
+    if (N < 2 || N > CCSD_FIN_MAXN) return set_err(CCSD_ERR_INVALID, "ccsd_finish: N = " + std::to_string(N) + " outside 2.." + std::to_string(CCSD_FIN_MAXN));
+    if (d->E != N * (N - 1) / 2)
+        return set_err(CCSD_ERR_INVALID, "ccsd_finish: E = " + std::to_string(d->E) + " is not N (N - 1) / 2 = " + std::to_string(N * (N - 1) / 2));
+    if (d->adj_mode != CCSD_FINISH_ADJ_QUANTIZE && d->adj_mode != CCSD_FINISH_ADJ_MOL) return set_err(CCSD_ERR_INVALID, "ccsd_finish: unknown adj_mode");
+    if (!(d->thr >= 0.f)) return set_err(CCSD_ERR_INVALID, "ccsd_finish: thr must be >= 0");
+    const bool want_adj = out->adj_int || out->degree || out->degree_hist || out->edge_hist;
+    const bool want_x = out->n_nodes || out->x_hist;
+    const bool want_r = out->rank2_u8 || out->rank2_cell_bits || out->rank2_cell_count || out->rank2_cell_hist || out->rank2_nnz;
+    if (want_adj && !in->adj) return set_err(CCSD_ERR_INVALID, "ccsd_finish: adjacency outputs requested without in->adj");
+    if (want_x && (!in->x || F < 1 || F > CCSD_FIN_MAXN))
+        return set_err(CCSD_ERR_INVALID, "ccsd_finish: x outputs need in->x and 1 <= F <= " + std::to_string(CCSD_FIN_MAXN));
+    if (want_r && !in->rank2) return set_err(CCSD_ERR_INVALID, "ccsd_finish: rank-2 outputs requested without in->rank2");
+    FinishTab tab;
+    memset(&tab, 0, sizeof tab);
+    int64_t K = 0;
+    if (want_r) {      // (every check comes before the first launch)
+        const int d_min = d->d_min, d_max = d->d_max;
+        if (d_min < 1 || d_max < d_min || d_max > N || d_max - d_min + 1 > CCSD_FIN_MAXBINS)
+            return set_err(CCSD_ERR_INVALID, "ccsd_finish: bad cell sizes d_min = " + std::to_string(d_min) + ", d_max = " + std::to_string(d_max));
+        for (int s = d_min; s <= d_max; ++s) {
+            K += ccsd_comb(N, s);
+            if (K > (1 << 24)) break;
+            tab.end[s - d_min] = (int)K;
+        }
+        tab.nb = d_max - d_min + 1;
+        if (K != d->K)
+            return set_err(CCSD_ERR_INVALID, "ccsd_finish: K = " + std::to_string((long long)d->K) + " is not sum C(N, d) for d = " + std::to_string(d_min) +
+                                                 ".." + std::to_string(d_max) + (K > (1 << 24) ? " (which exceeds 2^24)" : " = " + std::to_string((long long)K)));
+        if ((int64_t)d->E * K >= (int64_t(1) << 31)) return set_err(CCSD_ERR_INVALID, "ccsd_finish: E K must be below 2^31");
+        if (((uintptr_t)in->rank2 & 15) || ((uintptr_t)out->rank2_u8 & 3) || ((uintptr_t)out->rank2_cell_bits & 7))
+            return set_err(CCSD_ERR_INVALID, "ccsd_finish: rank2 must be 16-byte, rank2_u8 4-byte and rank2_cell_bits 8-byte aligned");
+        if (B > 65535) return set_err(CCSD_ERR_INVALID, "ccsd_finish: B must be at most 65535 with rank-2 outputs");
+    }
+    if (want_adj || want_x) {
+        CCSD_LAUNCH(k_finish_graph, dim3(B), dim3(CCSD_NTHREADS), 0, stream, want_x ? (const float*)in->x : (const float*)nullptr,
+                    want_adj ? (const float*)in->adj : (const float*)nullptr, N, F, d->adj_mode == CCSD_FINISH_ADJ_MOL ? -1.0f : d->thr,
+                    (long long*)out->adj_int, (int*)out->degree, (int*)out->degree_hist, (int*)out->edge_hist, (int*)out->n_nodes, (int*)out->x_hist);
+        LAUNCH_CHECK();
+    }
+    if (want_r) {
+        const int W = (int)((K + 63) / 64), nslab = (int)((K + CCSD_FIN_SLAB - 1) / CCSD_FIN_SLAB);
+        // the accumulated outputs start from zero (atomicOr / atomicAdd per workgroup)
+        if (out->rank2_cell_bits) RT_CHECK(rt_memset_async(out->rank2_cell_bits, 0, (size_t)B * W * 8, stream));
+        if (out->rank2_cell_count) RT_CHECK(rt_memset_async(out->rank2_cell_count, 0, (size_t)B * 4, stream));
+        if (out->rank2_cell_hist) RT_CHECK(rt_memset_async(out->rank2_cell_hist, 0, (size_t)B * tab.nb * 4, stream));
+        if (out->rank2_nnz) RT_CHECK(rt_memset_async(out->rank2_nnz, 0, (size_t)B * 4, stream));
+        CCSD_LAUNCH(k_finish_rank2, dim3(nslab, B), dim3(CCSD_NTHREADS), 0, stream, (const float*)in->rank2, (int)d->E, (int)K, d->thr, tab,
+                    (long long)B * d->E * K, (unsigned char*)out->rank2_u8, (unsigned long long*)out->rank2_cell_bits, (int*)out->rank2_cell_count,
+                    (int*)out->rank2_cell_hist, (int*)out->rank2_nnz);
+        LAUNCH_CHECK();
+    }
+    return CCSD_OK;
+}

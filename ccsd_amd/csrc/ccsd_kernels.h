@@ -17,6 +17,7 @@
 //                    workgroups (definitions compiled in ccsd_lg.hip; + ccsd_lg_fin.inc: the body of k_lg_fin and of k_lg_fin_w, which
 //                    ccsd_lgw.hip compiles)
 //   ccsd_k_update.h  k_normsum, k_langevin_apply, k_s4_apply, k_init_state, k_quantize, k_rank2_cells
+//   ccsd_k_finish.h  k_finish_rank2, k_finish_graph: quantised outputs, cell bitmask and per-complex descriptors in one pass per tensor
 // The product library is built from several translation units compiled in parallel (ccsd_hip.hip: C ABI + the small kernels;
 // ccsd_r2*.hip / ccsd_xa.hip: the explicit instantiations of the two big kernel templates); the host emulation used by the
 // CPU tests includes everything in one unit.  Reference file:line citations sit next to each restated formula.
@@ -27,4 +28,5 @@
 #include "ccsd_k_r2.h"
 #include "ccsd_k_xa.h"
 #include "ccsd_k_update.h"
+#include "ccsd_k_finish.h"
 #include "ccsd_k_lg.h"

@@ -298,6 +298,68 @@ class PCEngine:
         return bits, counts
 
 
+    def finish(self, x: Optional[torch.Tensor], adj: Optional[torch.Tensor], rank2: Optional[torch.Tensor] = None,
+               flags: Optional[torch.Tensor] = None, *, mol: bool = False, thr: float = 0.5, d_min: int = 0, d_max: int = 0,
+               dense_rank2: bool = True, descriptors: bool = True, dense_adj: bool = True) -> dict:
+        """The finish of a sampling run in one C call (ccsd_finish): one pass over (x, adj) and one over rank2.
+          adj_int (B,N,N) int64         quantize_mol(adj) if `mol` else quantize(adj, thr), as quantize()        [dense_adj]
+          degree, degree_hist (B,N), edge_hist (B,4), n_nodes (B,), x_hist (B,F) int32                            [descriptors]
+        and, with rank2 (B,E,K) and its cell sizes d_min..d_max,
+          rank2_int (B,E,K) uint8       quantize(rank2, thr)                                                       [dense_rank2]
+          rank2_cell_bits (B,ceil(K/64)) int64, rank2_cell_count (B,) int32      as rank2_cells()
+          rank2_cell_hist (B,d_max-d_min+1), rank2_nnz (B,) int32                                                  [descriptors]
+        A switched-off group is left out of the result and never computed.  No tensor of rank2's shape other than the uint8 output is
+        allocated.  x or adj may be None (their outputs are then left out)."""
+        ref = adj if adj is not None else x
+        if ref is None:
+            raise ValueError("finish: x or adj is required")
+        B, N = ref.shape[0], ref.shape[1]
+        dev = ref.device
+        x = None if x is None else x.contiguous()
+        adj = None if adj is None else adj.contiguous()
+        if adj is not None and (adj.dim() != 3 or tuple(adj.shape) != (B, N, N)):
+            raise ValueError(f"finish: adj must be (B, N, N), got {tuple(adj.shape)}")
+        if x is not None and (x.dim() != 3 or tuple(x.shape[:2]) != (B, N)):
+            raise ValueError(f"finish: x must be (B, N, F) with B, N = {B}, {N}, got {tuple(x.shape)}")
+        F = x.shape[2] if x is not None else 1
+        E, K = N * (N - 1) // 2, 0
+        res = {}
+
+        def new(name, shape, dtype):
+            res[name] = torch.empty(shape, dtype=dtype, device=dev)
+
+        if adj is not None:
+            if dense_adj:
+                new("adj_int", (B, N, N), torch.int64)
+            if descriptors:
+                new("degree", (B, N), torch.int32)
+                new("degree_hist", (B, N), torch.int32)
+                new("edge_hist", (B, 4), torch.int32)
+        if x is not None and descriptors:
+            new("n_nodes", (B,), torch.int32)
+            new("x_hist", (B, F), torch.int32)
+        if rank2 is not None:
+            rank2 = rank2.contiguous()
+            if rank2.dim() != 3 or rank2.shape[0] != B:
+                raise ValueError(f"finish: rank2 must be (B, E, K) with B = {B}, got {tuple(rank2.shape)}")
+            E, K = rank2.shape[1], rank2.shape[2]
+            if dense_rank2:
+                new("rank2_int", (B, E, K), torch.uint8)
+            new("rank2_cell_bits", (B, (K + 63) // 64), torch.int64)
+            new("rank2_cell_count", (B,), torch.int32)
+            if descriptors:
+                new("rank2_cell_hist", (B, max(d_max - d_min + 1, 1)), torch.int32)
+                new("rank2_nnz", (B,), torch.int32)
+        for name, t in (("x", x), ("adj", adj), ("rank2", rank2), ("flags", flags)):
+            if t is not None and (t.dtype != torch.float32 or t.device.type != self.device.type):
+                raise ValueError(f"finish: {name} must be float32 on {self.device}, got {t.dtype} {t.device}")
+        dims = _lib.FinishDims(B, N, F, E, K, int(d_min), int(d_max), _lib.FINISH_ADJ_MOL if mol else _lib.FINISH_ADJ_QUANTIZE, float(thr))
+        out = _lib.FinishOut(*[_ptr(res.get("rank2_int" if n == "rank2_u8" else n)) for n in _lib.FINISH_OUTPUTS])
+        st = _lib.State(_ptr(x), _ptr(adj), _ptr(rank2))
+        self.lib.check(self.lib.ccsd_finish(C.byref(dims), C.byref(st), _ptr(flags), C.byref(out), self._stream()))
+        return res
+
+
 def cells_from_bits(bits_row, N: int, d_min: int, d_max: int):
     """Cell tuples of one complex from its bitmask row, in the reference's enumeration order (get_cells,
     cc_utils.py:72-94: itertools.combinations(range(N), d) for d = d_min..d_max)."""

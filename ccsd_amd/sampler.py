@@ -274,7 +274,9 @@ class Sampler:
                       f"histogram ({self.node_counts_source})")
         self.node_counts = counts
 
-    def sample(self, save: bool = False, node_counts=None, rounds: Optional[int] = None) -> Dict[str, torch.Tensor]:
+    def sample(self, save: bool = False, node_counts=None, rounds: Optional[int] = None, dense_rank2: bool = True) -> Dict[str, torch.Tensor]:
+        """`dense_rank2=False` leaves the dense incidence tensors `rank2` and `rank2_int` out of the result and the saved file (the cell
+        bitmask and the descriptors describe the rank-2 cells); everything else is unchanged."""
         cfg = self.config
         self.load(node_counts)
         if node_counts is not None:
@@ -314,8 +316,14 @@ class Sampler:
         out: Dict[str, torch.Tensor] = {"x": x, "adj": adj, "flags": torch.cat(flags_all, dim=0)}
         quant = PCEngine(None, None, None, None, None, None, N=adj.shape[-1], F=1, is_cc=False, device=self.device0,
                          lib=self.extra.get("lib"))
+        # one call: quantize / quantize_mol (graph_utils.py:181-213), the sparse form of the rank-2 incidence matrix for cc_from_incidence
+        # (cc_utils.py:243-262) and the per-complex descriptors the evaluators histogram (stats.py:36, cc_utils.py:1208-1334)
+        datac = _get(cfg, "data")
+        fin = quant.finish(x, adj, rank2, out["flags"], mol=self.is_mol, thr=0.5, dense_rank2=dense_rank2,
+                           d_min=(_get(datac, "d_min") or _get(datat, "d_min") or 0) if self.is_cc else 0,
+                           d_max=(_get(datac, "d_max") or _get(datat, "d_max") or 0) if self.is_cc else 0)
         if self.is_mol:
-            samples_int = quant.quantize(adj, -1.0)                          # quantize_mol, graph_utils.py:195-213
+            samples_int = fin["adj_int"]                                     # quantize_mol, graph_utils.py:195-213
             samples_int = samples_int - 1
             samples_int[samples_int == -1] = 3                               # 0,1,2,3 (no,S,D,T) -> 3,0,1,2 (sampler.py:1219-1220)
             out["adj_int"] = samples_int
@@ -323,12 +331,16 @@ class Sampler:
             xi = torch.where(x > 0.5, 1, 0)
             out["x_onehot"] = torch.concat([xi, 1 - xi.sum(dim=-1, keepdim=True)], dim=-1)
         else:
-            out["adj_int"] = quant.quantize(adj, 0.5)                        # quantize, graph_utils.py:181-192
+            out["adj_int"] = fin["adj_int"]                                  # quantize, graph_utils.py:181-192
+        for k in ("n_nodes", "degree", "degree_hist", "edge_hist", "x_hist"):
+            out[k] = fin[k]
         if self.is_cc:
-            out["rank2"] = rank2
-            out["rank2_int"] = quant.quantize(rank2, 0.5).to(torch.uint8)
+            if dense_rank2:
+                out["rank2"] = rank2
+                out["rank2_int"] = fin["rank2_int"]
             # sparse form for cc_from_incidence (cc_utils.py:243-262): which of the K candidate cells exist, per complex
-            out["rank2_cell_bits"], out["rank2_cell_count"] = quant.rank2_cells(rank2, 0.5)
+            for k in ("rank2_cell_bits", "rank2_cell_count", "rank2_cell_hist", "rank2_nnz"):
+                out[k] = fin[k]
         out["sampling_time"] = torch.tensor(sampling_time)
         self.result = out
         if save and self.rank == 0:          # every rank holds the gathered samples; rank 0 writes them

@@ -30,6 +30,10 @@
  *                              utils/loader.py:649-650)
  * ccsd_quantize                quantize_mol / quantize (graph_utils.py:181-213)
  * ccsd_rank2_cells             the rank-2 part of cc_from_incidence's input, as a cell bitmask (cc_utils.py:243-262)
+ * ccsd_finish                  everything after the last predictor step in one pass per tensor: quantize / quantize_mol of adj and
+ *                              quantize of rank2 (sampler.py:1216-1225, 520-535), the cell bitmask, and the per-complex integers the
+ *                              evaluators histogram (degree_worker, evaluation/stats.py:36; rank1_distrib_worker /
+ *                              rank2_distrib_worker, cc_utils.py:1208-1334)
  */
 #ifndef CCSD_HIP_H
 #define CCSD_HIP_H
@@ -271,6 +275,40 @@ int ccsd_quantize(const float* in_dev, int64_t n, float thr, int64_t* out_dev, v
  * (B,E,K) fp32 device-to-host copy after sampling by ~K/8 bytes per complex. */
 int ccsd_rank2_cells(const float* rank2_dev, int32_t B, int32_t E, int64_t K, float thr, uint64_t* bits_dev,
                      int32_t* counts_dev, void* stream);
+
+/* The finish of a sampling run: one streaming pass over rank2 and one over (x, adj) give the quantised tensors, the cell bitmask and
+ * the per-complex descriptors.  Plan-free, like ccsd_quantize and ccsd_rank2_cells, whose results it reproduces bit for bit. */
+enum { CCSD_FINISH_ADJ_QUANTIZE = 0,   /* adj_int = quantize(adj, thr)   (graph_utils.py:181-192) */
+       CCSD_FINISH_ADJ_MOL = 1 };      /* adj_int = quantize_mol(adj)    (graph_utils.py:195-213) */
+typedef struct {
+    int32_t B, N, F, E;        /* E must be N (N - 1) / 2; 2 <= N <= 512, F <= 512 */
+    int64_t K;                 /* must be sum C(N, d), d = d_min..d_max (get_rank2_dim, cc_utils.py:269-283); ignored without rank-2 outputs */
+    int32_t d_min, d_max;
+    int32_t adj_mode;          /* CCSD_FINISH_ADJ_* */
+    float thr;                 /* threshold of quantize() for rank2 and, in CCSD_FINISH_ADJ_QUANTIZE mode, for adj (the harness: 0.5) */
+} ccsd_finish_dims_t;
+/* Every pointer is nullable: NULL = that output is not produced; a pass none of whose outputs is requested is not launched.
+ * All dev.  The four accumulated rank-2 outputs are cleared by the call itself. */
+typedef struct {
+    int64_t* adj_int;            /* (B,N,N)  quantize / quantize_mol of adj, as ccsd_quantize (sampler.py:1216, 520) */
+    int32_t* degree;             /* (B,N)    number of j != i with adj_int[i][j] != 0: G.degree() of adjs_to_graphs (graph_utils.py:216-251) */
+    int32_t* degree_hist;        /* (B,N)    bin d = node slots of degree d; bins 1.. = nx.degree_histogram(G) of degree_worker
+                                  *          (evaluation/stats.py:36; adjs_to_graphs drops isolated nodes, so bin 0 -- isolated and masked slots -- has no twin) */
+    int32_t* edge_hist;          /* (B,4)    pairs i < j by adj_int[i][j]: the rank-1 cells (and their bond types) rank1_distrib_worker counts
+                                  *          (cc_utils.py:1208-1243, 217-238) */
+    int32_t* n_nodes;            /* (B,)     rows of x with a non-zero entry: the rank-0 cells of cc_from_incidence (cc_utils.py:199-213) */
+    int32_t* x_hist;             /* (B,F)    nodes with x[i][f] > 0.5: column sums of the one-hot atom types (sampler.py:1222-1225) */
+    uint8_t* rank2_u8;           /* (B,E,K)  quantize(rank2, thr) (sampler.py:1216 / graph_utils.py:181-192), one byte per entry */
+    uint64_t* rank2_cell_bits;   /* (B, ceil(K/64))  as ccsd_rank2_cells (cc_utils.py:243-262) */
+    int32_t* rank2_cell_count;   /* (B,)     as ccsd_rank2_cells */
+    int32_t* rank2_cell_hist;    /* (B, d_max - d_min + 1)  rank-2 cells per size: rank2_distrib_worker's histogram (cc_utils.py:1315-1334) */
+    int32_t* rank2_nnz;          /* (B,)     entries of rank2 that are >= thr */
+} ccsd_finish_out_t;
+/* in->rank2 == NULL: a graph-only call (the rank-2 outputs must be NULL).  flags_dev (B,N), nullable: accepted for symmetry with the
+ * other entry points; no output depends on it (finished samples are masked).  Returns CCSD_ERR_INVALID with a message when E or K do
+ * not belong to (N, d_min, d_max). */
+int ccsd_finish(const ccsd_finish_dims_t* dims, const ccsd_state_t* in, const float* flags_dev,
+                const ccsd_finish_out_t* out, void* stream);
 
 /* Measurement hooks (bench.py): time every launch of selected kernels with HIP events on the launch stream.
  * kernel_id: 0 k_xa, 1 k_gemm_p, 2 k_hf_score, 3 k_gemm_h, 4 k_langevin_apply, 5 k_r2, 6 k_s4_apply, 7 k_ew1; each call adds one kernel to the

@@ -351,9 +351,11 @@ def g5_pc_runs(name, ck, is_cc, B, counts, sampler_cfg, cases, seed, min_dist=0.
     raise RuntimeError("no seed with the requested threshold margin")
 
 
-def _g5_pc_runs(name, ck, is_cc, B, counts, sampler_cfg, cases, seed, summarize_large=False):
+def _g5_pc_runs(name, ck, is_cc, B, counts, sampler_cfg, cases, seed, summarize_large=False, flags=None, keep=None):
     """G4/G5: end-to-end sampler runs; inputs are regenerated from the seed by the consumer
     (prior + every in-loop draw come from torch's global CPU generator in reference order).
+    `flags`: the node flags to run with (default: make_flags(B, N, counts)).  `keep`: a dict that receives the final tensors of every
+    case, {case: {"x", "adj", "rank2"}}; no fixture file is written then (f1_finish / d1_qm9_cc_n1000 reduce them to descriptors).
     sampler_cfg may carry `probability_flow` (default False) and `sde_override` = {part: sde dict} replacing the
     checkpoint's SDE for that part (subVP has no shipped checkpoint: the weights are just weights, the SDE
     arithmetic is what the case pins)."""
@@ -361,7 +363,7 @@ def _g5_pc_runs(name, ck, is_cc, B, counts, sampler_cfg, cases, seed, summarize_
     N, Fd = cfg["data"]["max_node_num"], cfg["data"]["max_feat_num"]
     d_min, d_max = (cfg["data"]["d_min"], cfg["data"]["d_max"]) if is_cc else (None, None)
     models = build_models(ck, is_cc)
-    flags = make_flags(B, N, counts)
+    flags = make_flags(B, N, counts) if flags is None else flags
     out = {"flags": flags.numpy(), "seed": seed, "rng_probe": rng_probe(seed),
            "sampler": json.dumps(sampler_cfg)}
     for case, (num_scales, max_steps) in cases.items():
@@ -395,6 +397,8 @@ def _g5_pc_runs(name, ck, is_cc, B, counts, sampler_cfg, cases, seed, summarize_
         res = [r.clone() if isinstance(r, torch.Tensor) else r for r in res]  # quantize_mol mutates CPU inputs
         for p, v in zip(parts, res):
             out[f"{case}/{p}"] = v.numpy().copy()
+        if keep is not None:
+            keep[case] = {p: out[f"{case}/{p}"] for p in parts}
         out[f"{case}/nfe"] = np.array(res[len(parts)])
         traj = res[-1]
         out[f"{case}/traj_len"] = np.array(len(traj))
@@ -408,8 +412,143 @@ def _g5_pc_runs(name, ck, is_cc, B, counts, sampler_cfg, cases, seed, summarize_
         out[f"{case}/min_thr_dist"] = np.array((res[1][..., None] - thr).abs().min().item())
         print("g5", name, case, "adj absmax", float(res[1].abs().max()), "min thr dist", float(out[f"{case}/min_thr_dist"]))
     dist = min(float(out[f"{case}/min_thr_dist"]) for case in cases)
-    save_golden(f"g5_{name}.npz", out, summarize_large)
+    if keep is None:
+        save_golden(f"g5_{name}.npz", out, summarize_large)
     return dist
+
+
+def ref_descriptors(x, adj, rank2, d_min, d_max, mol):
+    """Per-complex integer descriptors of finished samples, by the reference's own functions: the quantities its evaluators reduce to
+    histograms (degree_worker, stats.py:36; rank1_distrib_worker / rank2_distrib_worker, cc_utils.py:1208-1334).
+      degree_hist (B, N)  nx.degree_histogram of adjs_to_graphs(quantize(adj), True) (graph_utils.py:216-251), zero padded; degree_len (B,) its length
+      edge_hist (B, 4)    pairs i < j by value of quantize_mol(adj) (mol) / quantize(adj)
+      n_nodes (B,)        rows of x with any non-zero entry (cc_from_incidence's node rule, cc_utils.py:199-213)
+      x_hist (B, F)       nodes with x[i, f] > 0.5
+      cell_hist (B, d_max - d_min + 1)   columns of quantize(rank2) with any() set (cc_utils.py:247-249), by the size of get_cells' cell
+      rank2_nnz (B,)      entries of quantize(rank2) that are set"""
+    import networkx as nx
+
+    x, adj = torch.as_tensor(x), torch.as_tensor(adj)
+    B, N = adj.shape[0], adj.shape[-1]
+    graphs = ref_gu.adjs_to_graphs(ref_gu.quantize(adj), True)
+    out = {"degree_hist": np.zeros((B, N), np.int32), "degree_len": np.zeros(B, np.int32)}
+    for b, G in enumerate(graphs):
+        h = nx.degree_histogram(G)
+        out["degree_hist"][b, :len(h)] = h
+        out["degree_len"][b] = len(h)
+    q = torch.as_tensor(ref_gu.quantize_mol(adj.clone())) if mol else ref_gu.quantize(adj).to(torch.int64)
+    iu = np.triu_indices(N, 1)
+    out["edge_hist"] = np.stack([np.bincount(q[b].numpy()[iu], minlength=4) for b in range(B)]).astype(np.int32)
+    out["n_nodes"] = np.array([sum(int(x[b, i, :].any().item()) for i in range(N)) for b in range(B)], np.int32)
+    out["x_hist"] = (x > 0.5).sum(dim=1).numpy().astype(np.int32)
+    if rank2 is not None:
+        cells = ref_cc.get_cells(N, d_min, d_max)[0]
+        size = np.array([len(c) for c in cells])
+        qr = ref_gu.quantize(torch.as_tensor(rank2))
+        active = qr.bool().any(dim=1).numpy()
+        out["cell_hist"] = np.stack([np.bincount(size[active[b]] - d_min, minlength=d_max - d_min + 1) for b in range(B)]).astype(np.int32)
+        out["rank2_nnz"] = qr.sum(dim=(1, 2)).numpy().astype(np.int32)
+    return out
+
+
+# f1_finish.npz: name -> (checkpoint table, is_cc, B, node counts, sampler, cases, seed, mol): the g5 runs whose finished tensors it reads
+F1_RUNS = {
+    "ccsd_qm9_CC": (CHECKPOINTS, True, ["k10", "k50", "n1000_first3"], True),
+    "ccsd_qm9_CC_full1000": (CHECKPOINTS, True, ["n1000"], True),
+    "ccsd_community_small_CC": (CHECKPOINTS, True, ["k5", "n1000_first2"], False),
+    "ccsd_ego_small_CC": (SHIPPED, True, ["k6", "n1000_first2"], False),
+    "gdss_zinc250k": (CHECKPOINTS, False, ["k5"], True),
+    "gdss_grid": (SHIPPED, False, ["n1000_first3"], False),
+}
+
+
+def f1_finish():
+    """The reference's descriptors (ref_descriptors) of the reference's finished samples of the g5_* fixtures.  Where a g5 file holds a
+    tensor only as a summary (ego_small_CC's rank2, grid's adj) the run is repeated here from the fixture's seed, checked against the
+    summary's sha256, and f1 keeps what the descriptors depend on: the bits of quantize(rank2) (np.packbits) / quantize_mol(adj) as int8."""
+    import hashlib
+
+    ego = dict(predictor="Euler", corrector="None", snr=0.0, scale_eps=0.0, n_steps=1)
+    grid = dict(predictor="Reverse", corrector="Langevin", snr=0.1, scale_eps=0.7, n_steps=1)
+    rerun = {"ccsd_ego_small_CC": ([18, 9], ego, {"k6": (6, None), "n1000_first2": (None, 2)}),
+             "gdss_grid": ([361, 144], grid, {"n1000_first3": (None, 3)})}
+    out, meta = {}, {}
+    for name, (table, is_cc, cases, mol) in F1_RUNS.items():
+        g = np.load(os.path.join(GOLD, f"g5_{name}.npz"))
+        ckname = "ccsd_qm9_CC" if name == "ccsd_qm9_CC_full1000" else name
+        ck = refshim.load_reference_ckpt(table[ckname][0])
+        data = ck["model_config"]["data"]
+        d_min, d_max = (int(data["d_min"]), int(data["d_max"])) if is_cc else (0, 0)
+        kept = {}
+        if name in rerun:
+            counts, smp, cs = rerun[name]
+            _g5_pc_runs(name, ck, is_cc, 2, counts, smp, cs, int(g["seed"]), keep=kept)
+        meta[name] = {"is_cc": is_cc, "mol": mol, "d_min": d_min, "d_max": d_max, "cases": cases, "N": int(data["max_node_num"])}
+        for case in cases:
+            t = {}
+            for p in ["x", "adj"] + (["rank2"] if is_cc else []):
+                key = f"{case}/{p}"
+                if key in g.files:
+                    t[p] = g[key]
+                else:
+                    t[p] = kept[case][p]
+                    assert hashlib.sha256(np.ascontiguousarray(t[p]).tobytes()).hexdigest() == str(g[key + "/sha256"]), (name, key)
+                    if p == "rank2":
+                        out[f"{name}/{case}/rank2_bits"] = np.packbits(ref_gu.quantize(torch.as_tensor(t[p])).numpy().astype(np.uint8))
+                        out[f"{name}/{case}/rank2_shape"] = np.array(t[p].shape)
+                    else:
+                        out[f"{name}/{case}/adj_qmol"] = ref_gu.quantize_mol(torch.as_tensor(t[p]).clone()).astype(np.int8)
+            for k, v in ref_descriptors(t["x"], t["adj"], t.get("rank2"), d_min, d_max, mol).items():
+                out[f"{name}/{case}/{k}"] = v
+        print("f1", name, cases)
+    out["meta"] = np.array(json.dumps(meta))
+    path = os.path.join(GOLD, "f1_finish.npz")
+    np.savez_compressed(path, **out)
+    assert os.path.getsize(path) <= MAX_FIXTURE, os.path.getsize(path)
+    print("wrote f1_finish", os.path.getsize(path))
+
+
+def d1_qm9_cc_n1000(B=256, seed=42, raw=None):
+    """d1_qm9_CC_n1000.npz: ONE reference run of the shipped qm9_CC sampling set-up -- checkpoints/QM9/ccsd_qm9_CC.pth, the sampler block of
+    config/sample_qm9_CC.yaml, all 1000 scales, B complexes, flags drawn as the harness draws them without the dataset blobs
+    (ccsd_amd.sampler.init_flags on the shipped QM9 node-count histogram after np.random.seed(seed)), every draw from torch's CPU
+    generator after torch.manual_seed(seed) -- reduced to the flags and ref_descriptors of the final tensors.  The host time the run took
+    is recorded in the metadata.  `raw`: a path that also receives the final tensors (not a fixture; for inspection)."""
+    import time
+
+    import yaml
+
+    from ccsd_amd import sampler as S
+    from ccsd_amd.loader import AttrDict
+
+    with open(os.path.join(refshim.REFERENCE_ROOT, "config", "sample_qm9_CC.yaml")) as f:
+        y = yaml.safe_load(f)
+    smp = dict(y["sampler"])
+    ck = refshim.load_reference_ckpt(CHECKPOINTS["ccsd_qm9_CC"][0])
+    data = ck["model_config"]["data"]
+    with open(S._COUNTS) as f:
+        hist = json.load(f)["QM9"]["test_histogram"]
+    np.random.seed(seed)
+    flags = S.init_flags(hist, AttrDict({"data": {"max_node_num": int(data["max_node_num"])}}), B, is_cc=True)
+    kept = {}
+    t0 = time.perf_counter()
+    _g5_pc_runs("d1", ck, True, B, None, smp, {"n1000": (None, None)}, seed, flags=flags, keep=kept)
+    seconds = time.perf_counter() - t0
+    t = kept["n1000"]
+    if raw:
+        np.savez_compressed(raw, flags=flags.numpy(), **t)
+    out = ref_descriptors(t["x"], t["adj"], t["rank2"], int(data["d_min"]), int(data["d_max"]), True)
+    out["flags"] = flags.numpy().astype(np.float32)
+    out["meta"] = np.array(json.dumps({
+        "checkpoint": CHECKPOINTS["ccsd_qm9_CC"][0], "sampler": smp, "num_scales": int(ck["model_config"]["sde"]["adj"]["num_scales"]),
+        "B": B, "numpy_seed": seed, "torch_seed": seed, "eps": 1e-4, "denoise": True,
+        "flags": "ccsd_amd.sampler.init_flags(QM9 test_histogram of ccsd_amd/data/node_counts.json) after np.random.seed(numpy_seed)",
+        "reference_run_seconds": round(seconds, 1), "host_threads": torch.get_num_threads(),
+        "d_min": int(data["d_min"]), "d_max": int(data["d_max"])}))
+    path = os.path.join(GOLD, "d1_qm9_CC_n1000.npz")
+    np.savez_compressed(path, **out)
+    assert os.path.getsize(path) <= MAX_FIXTURE
+    print("wrote d1_qm9_CC_n1000", os.path.getsize(path), "bytes;", round(seconds, 1), "s of reference time")
 
 
 def kat_small_models():
@@ -1073,6 +1212,13 @@ def base_cc_route():
 
 def main():
     only = set(sys.argv[1:])
+    if only == {"f1"}:
+        f1_finish()
+        return
+    if only == {"d1"}:
+        # ~a quarter of an hour of reference CPU time was the estimate; the fixture's metadata holds what it took
+        d1_qm9_cc_n1000(raw=os.environ.get("CCSD_D1_RAW"))
+        return
     if only == {"base_cc_route"}:
         base_cc_route()
         return
