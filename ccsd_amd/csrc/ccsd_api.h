@@ -1713,3 +1713,106 @@ extern "C" int ccsd_finish(const ccsd_finish_dims_t* d, const ccsd_state_t* in, 
     }
     return CCSD_OK;
 }
+
+// ccsd_cluster_hist: the clustering-coefficient histogram of every graph (k_cluster_hist; plan-free, same quantiser arguments as ccsd_finish)
+extern "C" int ccsd_cluster_hist(const float* adj, int32_t B, int32_t N, int32_t adj_mode, float thr, const double* edges, int32_t bins,
+                                 int32_t* tri2, int32_t* cluster_hist, void* stream) {
+    if (!adj) return set_err(CCSD_ERR_INVALID, "ccsd_cluster_hist: NULL adj");
+    if (B < 1) return set_err(CCSD_ERR_INVALID, "ccsd_cluster_hist: B must be >= 1");
+    if (N < 2 || N > CCSD_FIN_MAXN) return set_err(CCSD_ERR_INVALID, "ccsd_cluster_hist: N = " + std::to_string(N) + " outside 2.." + std::to_string(CCSD_FIN_MAXN));
+    if (bins < 1 || bins > CCSD_CLUSTER_MAX_BINS)
+        return set_err(CCSD_ERR_INVALID, "ccsd_cluster_hist: bins = " + std::to_string(bins) + " outside 1.." + std::to_string(CCSD_CLUSTER_MAX_BINS));
+    if (adj_mode != CCSD_FINISH_ADJ_QUANTIZE && adj_mode != CCSD_FINISH_ADJ_MOL) return set_err(CCSD_ERR_INVALID, "ccsd_cluster_hist: unknown adj_mode");
+    if (!(thr >= 0.f)) return set_err(CCSD_ERR_INVALID, "ccsd_cluster_hist: thr must be >= 0");
+    if (!edges) return set_err(CCSD_ERR_INVALID, "ccsd_cluster_hist: NULL edges");
+    if (!tri2 && !cluster_hist) return CCSD_OK;
+    CCSD_LAUNCH(k_cluster_hist, dim3(B), dim3(CCSD_NTHREADS), 0, stream, adj, (int)N, adj_mode == CCSD_FINISH_ADJ_MOL ? -1.0f : thr, edges, (int)bins,
+                (int*)tri2, (int*)cluster_hist);
+    LAUNCH_CHECK();
+    return CCSD_OK;
+}
+
+// Workspace of ccsd_mmd: the two transposed fp64 operands (rows padded to the pair kernel's tile), their mass flags and lengths, and
+// one fp64 partial per tile of each of the three pair reductions.
+struct MmdWs {
+    size_t op1, op2, part, mass1, len1, mass2, len2, bytes;
+    int np1, np2, T1, T2;
+};
+static MmdWs carve_mmd(int64_t n1, int64_t n2, int64_t L) {
+    MmdWs w;
+    w.T1 = (int)((n1 + CCSD_EVAL_TILE - 1) / CCSD_EVAL_TILE);
+    w.T2 = (int)((n2 + CCSD_EVAL_TILE - 1) / CCSD_EVAL_TILE);
+    w.np1 = w.T1 * CCSD_EVAL_TILE;
+    w.np2 = w.T2 * CCSD_EVAL_TILE;
+    size_t o = 0;
+    w.op1 = o; o += (size_t)L * w.np1 * 8;
+    w.op2 = o; o += (size_t)L * w.np2 * 8;
+    w.part = o; o += ((size_t)w.T1 * w.T1 + (size_t)w.T2 * w.T2 + (size_t)w.T1 * w.T2) * 8;
+    w.mass1 = o; o += (size_t)w.np1 * 4;
+    w.len1 = o; o += (size_t)w.np1 * 4;
+    w.mass2 = o; o += (size_t)w.np2 * 4;
+    w.len2 = o; o += (size_t)w.np2 * 4;
+    w.bytes = o;
+    return w;
+}
+// (the limits are the public header's: CCSD_MMD_MAX_ROWS, CCSD_MMD_MAX_BINS, CCSD_CLUSTER_MAX_BINS)
+static_assert(CCSD_CLUSTER_MAX_BINS == CCSD_EVAL_MAXBINS, "the header's bin limit is k_cluster_hist's LDS histogram");
+static bool mmd_dims_ok(int64_t n1, int64_t n2, int64_t L) {
+    return n1 >= 1 && n2 >= 1 && L >= 1 && n1 <= CCSD_MMD_MAX_ROWS && n2 <= CCSD_MMD_MAX_ROWS && L <= CCSD_MMD_MAX_BINS;
+}
+
+extern "C" size_t ccsd_mmd_workspace_bytes(int32_t n1, int32_t n2, int32_t L) {
+    if (!mmd_dims_ok(n1, n2, L)) {
+        set_err(CCSD_ERR_INVALID, "ccsd_mmd_workspace_bytes: n1, n2 must be in 1.." + std::to_string(CCSD_MMD_MAX_ROWS) + " and L in 1.." + std::to_string(CCSD_MMD_MAX_BINS));
+        return 0;
+    }
+    return carve_mmd(n1, n2, L).bytes;
+}
+
+// ccsd_mmd: compute_mmd (mmd.py:230-257) of two sets of histograms: k_mmd_prep per set, k_mmd_pairs for disc(1, 1), disc(2, 2) (both by
+// symmetry) and disc(1, 2), k_mmd_final.  out (4 doubles, device) = disc(1, 1), disc(2, 2), disc(1, 2), mmd.
+extern "C" int ccsd_mmd(const void* h1, int32_t n1, const int32_t* lens1, const void* h2, int32_t n2, const int32_t* lens2, int32_t L,
+                        int32_t dtype, int32_t kind, int32_t flags, double sigma, double distance_scaling, void* workspace, size_t ws_bytes,
+                        double* out, void* stream) {
+    if (n1 < 1 || n2 < 1) return set_err(CCSD_ERR_INVALID, "ccsd_mmd: n1 = " + std::to_string(n1) + ", n2 = " + std::to_string(n2) + ": every set needs n >= 1 rows");
+    if (L < 1) return set_err(CCSD_ERR_INVALID, "ccsd_mmd: L = " + std::to_string(L) + " must be >= 1");
+    if (!mmd_dims_ok(n1, n2, L)) return set_err(CCSD_ERR_INVALID, "ccsd_mmd: n above " + std::to_string(CCSD_MMD_MAX_ROWS) + " or L above " + std::to_string(CCSD_MMD_MAX_BINS));
+    if (!h1 || !h2 || !out) return set_err(CCSD_ERR_INVALID, "ccsd_mmd: NULL argument");
+    if (dtype != CCSD_MMD_INT32 && dtype != CCSD_MMD_FP64) return set_err(CCSD_ERR_INVALID, "ccsd_mmd: unknown dtype");
+    if (kind != CCSD_MMD_EMD && kind != CCSD_MMD_TV && kind != CCSD_MMD_L2) return set_err(CCSD_ERR_INVALID, "ccsd_mmd: unknown kind");
+    if (flags & ~(CCSD_MMD_IS_HIST | CCSD_MMD_DEGREE | CCSD_MMD_F32_PMF)) return set_err(CCSD_ERR_INVALID, "ccsd_mmd: unknown flag");
+    if (kind == CCSD_MMD_EMD && !(flags & CCSD_MMD_IS_HIST))
+        return set_err(CCSD_ERR_INVALID, "ccsd_mmd: the EMD kind needs is_hist (rows of unequal mass have no closed form on the line metric)");
+    if (!(sigma > 0.0)) return set_err(CCSD_ERR_INVALID, "ccsd_mmd: sigma must be > 0");
+    if (kind == CCSD_MMD_EMD && !(distance_scaling > 0.0)) return set_err(CCSD_ERR_INVALID, "ccsd_mmd: distance_scaling must be > 0");
+    const MmdWs w = carve_mmd(n1, n2, L);
+    if (!workspace || ws_bytes < w.bytes) return set_err(CCSD_ERR_WORKSPACE, "ccsd_mmd: workspace too small");
+    if ((uintptr_t)workspace & 7) return set_err(CCSD_ERR_INVALID, "ccsd_mmd: workspace must be 8-byte aligned");
+    static_assert((int)CCSD_MMD_EMD == (int)EVAL_EMD && (int)CCSD_MMD_TV == (int)EVAL_TV && (int)CCSD_MMD_L2 == (int)EVAL_L2 &&
+                  (int)CCSD_MMD_IS_HIST == (int)EVAL_F_HIST && (int)CCSD_MMD_DEGREE == (int)EVAL_F_DEGREE &&
+                  (int)CCSD_MMD_F32_PMF == (int)EVAL_F_F32PMF, "the header's constants are the kernels'");
+    char* base = (char*)workspace;
+    double *op1 = (double*)(base + w.op1), *op2 = (double*)(base + w.op2), *part = (double*)(base + w.part);
+    int *m1 = (int*)(base + w.mass1), *l1 = (int*)(base + w.len1), *m2 = (int*)(base + w.mass2), *l2 = (int*)(base + w.len2);
+    // (k_mmd_prep: 256 rows per workgroup; the emulation's one thread takes them in turn)
+    CCSD_LAUNCH(k_mmd_prep, dim3((w.np1 + 255) / 256), dim3(256), 0, stream, h1, (int)(dtype == CCSD_MMD_FP64), (const int*)lens1, (int)n1, w.np1,
+                (int)L, (int)kind, (int)flags, op1, m1, l1);
+    LAUNCH_CHECK();
+    CCSD_LAUNCH(k_mmd_prep, dim3((w.np2 + 255) / 256), dim3(256), 0, stream, h2, (int)(dtype == CCSD_MMD_FP64), (const int*)lens2, (int)n2, w.np2,
+                (int)L, (int)kind, (int)flags, op2, m2, l2);
+    LAUNCH_CHECK();
+    const double two_s2 = 2 * sigma * sigma;
+    const int c11 = w.T1 * w.T1, c22 = w.T2 * w.T2, c12 = w.T1 * w.T2;
+    CCSD_LAUNCH(k_mmd_pairs, dim3(w.T1, w.T1), dim3(CCSD_NTHREADS), 0, stream, (const double*)op1, (const int*)m1, (const int*)l1, (int)n1, w.np1,
+                (const double*)op1, (const int*)m1, (const int*)l1, (int)n1, w.np1, (int)L, (int)kind, distance_scaling, two_s2, 1, part);
+    LAUNCH_CHECK();
+    CCSD_LAUNCH(k_mmd_pairs, dim3(w.T2, w.T2), dim3(CCSD_NTHREADS), 0, stream, (const double*)op2, (const int*)m2, (const int*)l2, (int)n2, w.np2,
+                (const double*)op2, (const int*)m2, (const int*)l2, (int)n2, w.np2, (int)L, (int)kind, distance_scaling, two_s2, 1, part + c11);
+    LAUNCH_CHECK();
+    CCSD_LAUNCH(k_mmd_pairs, dim3(w.T2, w.T1), dim3(CCSD_NTHREADS), 0, stream, (const double*)op1, (const int*)m1, (const int*)l1, (int)n1, w.np1,
+                (const double*)op2, (const int*)m2, (const int*)l2, (int)n2, w.np2, (int)L, (int)kind, distance_scaling, two_s2, 0, part + c11 + c22);
+    LAUNCH_CHECK();
+    CCSD_LAUNCH(k_mmd_final, dim3(1), dim3(CCSD_NTHREADS), 0, stream, (const double*)part, c11, c22, c12, (double)n1, (double)n2, out);
+    LAUNCH_CHECK();
+    return CCSD_OK;
+}

@@ -18,6 +18,8 @@
 //                    ccsd_lgw.hip compiles)
 //   ccsd_k_update.h  k_normsum, k_langevin_apply, k_s4_apply, k_init_state, k_quantize, k_rank2_cells
 //   ccsd_k_finish.h  k_finish_rank2, k_finish_graph: quantised outputs, cell bitmask and per-complex descriptors in one pass per tensor
+//   ccsd_k_eval.h    k_cluster_hist, k_mmd_prep, k_mmd_pairs, k_mmd_final: clustering-coefficient histograms and the fp64 MMD of two
+//                    sets of histograms (the evaluation of finished samples)
 // The product library is built from several translation units compiled in parallel (ccsd_hip.hip: C ABI + the small kernels;
 // ccsd_r2*.hip / ccsd_xa.hip: the explicit instantiations of the two big kernel templates); the host emulation used by the
 // CPU tests includes everything in one unit.  Reference file:line citations sit next to each restated formula.
@@ -29,4 +31,5 @@
 #include "ccsd_k_xa.h"
 #include "ccsd_k_update.h"
 #include "ccsd_k_finish.h"
+#include "ccsd_k_eval.h"
 #include "ccsd_k_lg.h"

@@ -61,6 +61,7 @@ class PCEngine:
         self.handle = handle
         self._ws: Optional[torch.Tensor] = None
         self._ws_B = 0
+        self._edges: dict = {}          # (bins, device) -> np.linspace(0, 1, bins + 1) on the device (cluster_hist)
 
     def __del__(self):
         h = getattr(self, "handle", None)
@@ -358,6 +359,66 @@ class PCEngine:
         st = _lib.State(_ptr(x), _ptr(adj), _ptr(rank2))
         self.lib.check(self.lib.ccsd_finish(C.byref(dims), C.byref(st), _ptr(flags), C.byref(out), self._stream()))
         return res
+
+    def cluster_hist(self, adj: torch.Tensor, *, mol: bool = False, thr: float = 0.5, bins: int = 100, tri2: bool = True) -> dict:
+        """Clustering-coefficient histogram per graph (ccsd_cluster_hist): clustering_worker of the reference (evaluation/stats.py:206-220)
+        on adjs_to_graphs of the quantised adjacency, with finish()'s quantiser (`mol`, `thr`).  adj (B,N,N) float32, SYMMETRIC.
+          cluster_hist (B,bins) int32   np.histogram(nx.clustering(G).values(), bins, range=(0, 1))
+          tri2 (B,N) int32              twice the triangles through each node                                      [tri2]
+        The bin edges are numpy's own: np.linspace(0.0, 1.0, bins + 1), uploaded once per `bins`."""
+        if adj.dim() != 3 or adj.shape[1] != adj.shape[2]:
+            raise ValueError(f"cluster_hist: adj must be (B, N, N), got {tuple(adj.shape)}")
+        if adj.dtype != torch.float32 or adj.device.type != self.device.type:
+            raise ValueError(f"cluster_hist: adj must be float32 on {self.device}, got {adj.dtype} {adj.device}")
+        adj = adj.contiguous()
+        B, N = adj.shape[0], adj.shape[1]
+        bins = int(bins)
+        if not 1 <= bins <= _lib.CLUSTER_MAX_BINS:
+            raise ValueError(f"cluster_hist: bins = {bins} outside 1..{_lib.CLUSTER_MAX_BINS}")
+        key = (bins, adj.device)
+        if key not in self._edges:
+            self._edges[key] = torch.from_numpy(np.linspace(0.0, 1.0, bins + 1)).to(adj.device)
+        edges = self._edges[key]
+        res = {"cluster_hist": torch.empty((B, bins), dtype=torch.int32, device=adj.device)}
+        if tri2:
+            res["tri2"] = torch.empty((B, N), dtype=torch.int32, device=adj.device)
+        self.lib.check(self.lib.ccsd_cluster_hist(_ptr(adj), B, N, _lib.FINISH_ADJ_MOL if mol else _lib.FINISH_ADJ_QUANTIZE, float(thr),
+                                                  _ptr(edges), bins, _ptr(res.get("tri2")), _ptr(res["cluster_hist"]), self._stream()))
+        return res
+
+    def mmd(self, s1: torch.Tensor, s2: torch.Tensor, kind: str = "emd", *, is_hist: bool = True, degree: bool = False,
+            f32_pmf: bool = False, sigma: float = 1.0, distance_scaling: float = 1.0, lens1: Optional[torch.Tensor] = None,
+            lens2: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """compute_mmd of the reference (evaluation/mmd.py:230-257) on the device (ccsd_mmd): s1 (n1,L), s2 (n2,L) int32 or float64
+        histograms with one row per sample -> a float64 device tensor [disc(1,1), disc(2,2), disc(1,2), mmd].  kind: "emd"
+        (gaussian_emd), "tv" (gaussian_tv), "l2" (gaussian).  degree: the rows are finish()'s degree_hist (bin 0 is no node of the
+        reference's graphs).  f32_pmf: normalise in float32, as numpy does for float32 histograms.  lens1 / lens2 (n,) int32: the
+        lengths of the original arrays of a ragged set (they matter only to the EMD of rows without mass).  Nothing is synchronised."""
+        kinds = {"emd": _lib.MMD_EMD, "tv": _lib.MMD_TV, "l2": _lib.MMD_L2}
+        if kind not in kinds:
+            raise ValueError(f"mmd: kind must be one of {sorted(kinds)}, got {kind!r}")
+        if s1.dim() != 2 or s2.dim() != 2 or s1.shape[1] != s2.shape[1]:
+            raise ValueError(f"mmd: s1 and s2 must be (n1, L) and (n2, L), got {tuple(s1.shape)} and {tuple(s2.shape)}")
+        if s1.dtype != s2.dtype or s1.dtype not in (torch.int32, torch.float64):
+            raise ValueError(f"mmd: s1 and s2 must both be int32 or both float64, got {s1.dtype} and {s2.dtype}")
+        for name, t in (("s1", s1), ("s2", s2), ("lens1", lens1), ("lens2", lens2)):
+            if t is not None and t.device.type != self.device.type:
+                raise ValueError(f"mmd: {name} must be on {self.device}, got {t.device}")
+        for name, t, s in (("lens1", lens1, s1), ("lens2", lens2, s2)):
+            if t is not None and (t.dtype != torch.int32 or tuple(t.shape) != (s.shape[0],)):
+                raise ValueError(f"mmd: {name} must be int32 of shape ({s.shape[0]},), got {t.dtype} {tuple(t.shape)}")
+        s1, s2 = s1.contiguous(), s2.contiguous()
+        lens1 = None if lens1 is None else lens1.contiguous()
+        lens2 = None if lens2 is None else lens2.contiguous()
+        n1, n2, L = s1.shape[0], s2.shape[0], s1.shape[1]
+        out = torch.empty(4, dtype=torch.float64, device=s1.device)
+        nbytes = self.lib.ccsd_mmd_workspace_bytes(n1, n2, L)
+        ws = torch.empty(max(nbytes, 8) // 8 + 1, dtype=torch.float64, device=s1.device)        # (8-byte aligned)
+        flags = (_lib.MMD_IS_HIST if is_hist else 0) | (_lib.MMD_DEGREE if degree else 0) | (_lib.MMD_F32_PMF if f32_pmf else 0)
+        self.lib.check(self.lib.ccsd_mmd(_ptr(s1), n1, _ptr(lens1), _ptr(s2), n2, _ptr(lens2), L,
+                                         _lib.MMD_FP64 if s1.dtype == torch.float64 else _lib.MMD_INT32, kinds[kind], flags, float(sigma),
+                                         float(distance_scaling), _ptr(ws), ws.numel() * 8, _ptr(out), self._stream()))
+        return out
 
 
 def cells_from_bits(bits_row, N: int, d_min: int, d_max: int):

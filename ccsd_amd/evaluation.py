@@ -1,0 +1,242 @@
+"""Evaluation of finished samples on the GPU: the reference's MMD scores against a held-out set.
+
+Mirrors, under the reference's names, the part of ccsd/src/evaluation/{mmd,stats}.py and ccsd/src/utils/cc_utils.py:1208-1474 that
+needs no external program:
+
+  compute_mmd with gaussian_emd / gaussian_tv / gaussian          (mmd.py:27-257)       -> PCEngine.mmd (ccsd_mmd)
+  degree_stats, clustering_stats, eval_torch_batch                (stats.py:60-310, 547-570)
+  rank1_distrib_stats, rank2_distrib_stats, eval_CC_batch         (cc_utils.py:1208-1474, eval_CC_list)
+
+The reference builds networkx graphs / toponetx complexes on the host and solves one pyemd linear program per pair of histograms.
+Here a sample set is a dict of per-sample integer DESCRIPTORS on the device -- `describe()`: the descriptor outputs of
+PCEngine.finish plus `cluster_hist` -- and every score is one ccsd_mmd call on them.  There is no CPU fallback: methods that need an
+external program or a solver this build does not have raise NotImplementedError (UNSUPPORTED); their histograms, computed elsewhere,
+can still be scored through compute_mmd.
+"""
+from __future__ import annotations
+
+from typing import Dict, Optional, Sequence
+
+import numpy as np
+import torch
+
+from .engine import PCEngine
+
+
+class KernelSelector:
+    """Names one of the reference's kernels (mmd.py:69-131) for compute_mmd.  The kernel values are computed on the device inside
+    ccsd_mmd, pair tile by pair tile; the selector itself computes nothing."""
+
+    def __init__(self, name: str, kind: str):
+        self.__name__, self.kind = name, kind
+
+    def __repr__(self) -> str:
+        return f"<kernel selector {self.__name__}>"
+
+    def __call__(self, *a, **k):
+        raise TypeError(f"{self.__name__} selects a kernel of compute_mmd; it is evaluated on the device, not called per pair")
+
+
+gaussian_emd = KernelSelector("gaussian_emd", "emd")
+gaussian_tv = KernelSelector("gaussian_tv", "tv")
+gaussian = KernelSelector("gaussian", "l2")
+
+UNSUPPORTED = {
+    "orbit": "orbit counts come from the external orca program (evaluation/stats.py:343-379)",
+    "spectral": "needs a symmetric eigenvalue solver on the device (evaluation/stats.py:125-137): not part of this build yet",
+    "hodge_laplacian_spectrum": "needs a symmetric eigenvalue solver on the device (cc_utils.py:994-1060): not part of this build yet",
+    "nspdk": "needs the EDeN graph vectoriser (evaluation/eden.py, mmd.py:331-337)",
+    "rank0_distrib": "the node label it histograms is data-set specific (cc_utils.py:1098-1205)",
+}
+
+_engines: dict = {}
+
+
+def _engine(device=None, lib=None) -> PCEngine:
+    """The plan-free entry points (finish, cluster_hist, mmd) hang off a PCEngine; one per (device, library)."""
+    device = torch.device(device if device is not None else "cuda")
+    key = (str(device), id(lib))
+    if key not in _engines:
+        _engines[key] = PCEngine(None, None, None, None, None, None, N=2, F=1, is_cc=False, device=device, lib=lib)
+    return _engines[key]
+
+
+def _as_rows(samples, device):
+    """A sample set -> (rows (n, L) int32 / float64 tensor on `device`, lens (n,) numpy, the set's numpy dtype kind).  Accepts a 2-D array /
+    tensor or a sequence of 1-D arrays / tensors of differing lengths (zero padded, as process_tensor does, mmd.py:380-395)."""
+    if isinstance(samples, torch.Tensor) and samples.dim() == 2:
+        f32 = samples.dtype == torch.float32
+        t = samples if samples.dtype == torch.int32 else samples.to(torch.int32 if not samples.dtype.is_floating_point else torch.float64)
+        if not samples.dtype.is_floating_point and samples.dtype != torch.int32 and samples.numel() and int(samples.abs().max()) >= 2 ** 31:
+            raise ValueError("compute_mmd: integer histograms must fit int32")
+        return t.to(device), np.full(t.shape[0], t.shape[1], np.int32), ("f32" if f32 else "f" if t.dtype == torch.float64 else "i")
+    rows = [np.asarray(s.detach().cpu() if isinstance(s, torch.Tensor) else s) for s in samples]
+    if any(r.ndim != 1 for r in rows):
+        raise ValueError("compute_mmd: a sample set is a 2-D array or a sequence of 1-D arrays")
+    n = len(rows)
+    lens = np.array([len(r) for r in rows], np.int32)
+    floating = any(r.dtype.kind == "f" for r in rows)
+    f32 = n > 0 and all(r.dtype == np.float32 for r in rows)
+    out = np.zeros((n, int(lens.max()) if n else 0), np.float64 if floating else np.int64)
+    for i, r in enumerate(rows):
+        out[i, :len(r)] = r
+    if not floating:
+        if out.size and np.abs(out).max() >= 2 ** 31:
+            raise ValueError("compute_mmd: integer histograms must fit int32")
+        out = out.astype(np.int32)
+    return torch.from_numpy(out).to(device), lens, ("f32" if f32 else "f" if floating else "i")
+
+
+def _pad(t: torch.Tensor, L: int) -> torch.Tensor:
+    return t if t.shape[1] == L else torch.nn.functional.pad(t, (0, L - t.shape[1]))
+
+
+def mmd_terms(samples1, samples2, kernel: KernelSelector = gaussian_emd, is_hist: bool = True, sigma: float = 1.0,
+              distance_scaling: float = 1.0, *, degree: bool = False, f32_pmf: Optional[bool] = None, device=None, lib=None) -> torch.Tensor:
+    """[disc(1,1), disc(2,2), disc(1,2), mmd] as a float64 device tensor; nothing is synchronised.  f32_pmf=None: taken from the
+    inputs (float32 histograms are normalised in float32 by numpy, so by compute_mmd of the reference)."""
+    if not isinstance(kernel, KernelSelector):
+        raise TypeError("compute_mmd: kernel must be gaussian_emd, gaussian_tv or gaussian of ccsd_amd.evaluation")
+    eng = _engine(device, lib)
+    s1, l1, k1 = _as_rows(samples1, eng.device)
+    s2, l2, k2 = _as_rows(samples2, eng.device)
+    if s1.dtype != s2.dtype:
+        s1, s2 = s1.to(torch.float64), s2.to(torch.float64)
+    L = max(s1.shape[1], s2.shape[1])
+    s1, s2 = _pad(s1, L), _pad(s2, L)
+    ragged = bool((l1 != L).any() or (l2 != L).any()) and not degree
+    lens = [torch.from_numpy(l).to(eng.device) if ragged else None for l in (l1, l2)]
+    if f32_pmf is None:
+        f32_pmf = k1 == "f32" and k2 == "f32"
+    return eng.mmd(s1, s2, kernel.kind, is_hist=is_hist, degree=degree, f32_pmf=bool(f32_pmf and is_hist), sigma=sigma,
+                   distance_scaling=distance_scaling, lens1=lens[0], lens2=lens[1])
+
+
+def compute_mmd(samples1, samples2, kernel: KernelSelector = gaussian_emd, is_hist: bool = True, sigma: float = 1.0,
+                distance_scaling: float = 1.0, **kw) -> float:
+    """compute_mmd of the reference (mmd.py:230-257).  samples1 / samples2: 2-D arrays or lists of 1-D arrays of differing lengths,
+    numpy or torch, integer or floating point."""
+    return float(mmd_terms(samples1, samples2, kernel, is_hist, sigma, distance_scaling, **kw)[3].item())
+
+
+# ---------------------------------------------------------------------------------------------
+# descriptors
+# ---------------------------------------------------------------------------------------------
+def describe(adj: torch.Tensor, x: Optional[torch.Tensor] = None, rank2: Optional[torch.Tensor] = None, *, mol: bool = False,
+             thr: float = 0.5, bins: int = 100, d_min: int = 0, d_max: int = 0, device=None, lib=None) -> Dict[str, torch.Tensor]:
+    """The descriptor dict of a batch: PCEngine.finish's descriptors (degree, degree_hist, edge_hist; n_nodes, x_hist with x;
+    rank2_cell_bits / _count / _hist, rank2_nnz with rank2) plus cluster_hist (B, bins) and tri2 (B, N).  adj: (B, N, N), raw samples,
+    quantised samples or a 0/1 data set (any real or integer dtype)."""
+    eng = _engine(device if device is not None else (adj.device if adj.device.type == "cuda" else None), lib)
+    mv = lambda t: None if t is None else t.to(device=eng.device, dtype=torch.float32).contiguous()
+    adj, x, rank2 = mv(adj), mv(x), mv(rank2)
+    out = eng.finish(x, adj, rank2, None, mol=mol, thr=thr, d_min=d_min, d_max=d_max, dense_rank2=False, dense_adj=False)
+    out.update(eng.cluster_hist(adj, mol=mol, thr=thr, bins=bins))
+    return out
+
+
+def _descriptors(obj, need: Sequence[str], **kw) -> Dict[str, torch.Tensor]:
+    if isinstance(obj, dict):
+        missing = [k for k in need if k not in obj]
+        if missing:
+            raise KeyError(f"descriptor dict lacks {missing}; describe() produces them")
+        return obj
+    return describe(torch.as_tensor(obj), **kw)
+
+
+def _dev_kw(kw):
+    return {k: kw[k] for k in ("device", "lib") if k in kw}
+
+
+def degree_stats(ref, pred, kernel: KernelSelector = gaussian_emd, **kw) -> float:
+    """degree_stats (stats.py:60-122): MMD of the degree histograms.  ref / pred: adjacency batches or descriptor dicts.  The graphs
+    of adjs_to_graphs hold no isolated node and at least one node, so no predicted graph is ever dropped as empty."""
+    a, b = _descriptors(ref, ["degree_hist"], **kw), _descriptors(pred, ["degree_hist"], **kw)
+    return compute_mmd(a["degree_hist"], b["degree_hist"], kernel, degree=True, **_dev_kw(kw))
+
+
+def clustering_stats(ref, pred, kernel: KernelSelector = gaussian_emd, bins: int = 100, **kw) -> float:
+    """clustering_stats (stats.py:223-310): sigma = 0.1 and, for the kernel that takes it, distance_scaling = bins."""
+    a, b = _descriptors(ref, ["cluster_hist"], bins=bins, **kw), _descriptors(pred, ["cluster_hist"], bins=bins, **kw)
+    for d in (a, b):
+        if d["cluster_hist"].shape[1] != bins:
+            raise ValueError(f"clustering_stats: cluster_hist has {d['cluster_hist'].shape[1]} bins, not {bins}")
+    return compute_mmd(a["cluster_hist"], b["cluster_hist"], kernel, sigma=1.0 / 10,
+                       distance_scaling=bins if kernel is gaussian_emd else 1.0, **_dev_kw(kw))
+
+
+def _cc_keep(desc: Dict[str, torch.Tensor], n: Optional[int], drop_empty: bool) -> torch.Tensor:
+    """Row indices eval_CC_list scores: the first n complexes (cc_nb_eval slices first), minus -- predictions only -- the complexes
+    with no node, edge or cell (is_empty_cc, cc_utils.py:982-991)."""
+    cells = desc["edge_hist"][:, 1:].sum(-1)
+    if "n_nodes" in desc:
+        cells = cells + desc["n_nodes"]
+    if "rank2_cell_hist" in desc:
+        cells = cells + desc["rank2_cell_hist"].sum(-1)
+    idx = torch.arange(cells.shape[0], device=cells.device)[:n]
+    return idx[cells[:n] > 0] if drop_empty else idx
+
+
+def rank1_distrib_stats(ref_desc, pred_desc, worker_kwargs, kernel: KernelSelector = gaussian_emd, cc_nb_eval: Optional[int] = None, **kw) -> float:
+    """rank1_distrib_stats (cc_utils.py:1235-1312): histogram of the rank-1 cells' integer values over min_edge_val..max_edge_val,
+    from edge_hist (pairs by quantised value; value 0 is no cell and never counts)."""
+    lo, hi = int(worker_kwargs["min_edge_val"]), int(worker_kwargs["max_edge_val"])
+    sets = []
+    for desc, drop in ((ref_desc, False), (pred_desc, True)):
+        eh = desc["edge_hist"].index_select(0, _cc_keep(desc, cc_nb_eval, drop))
+        h = torch.zeros((eh.shape[0], hi - lo + 1), dtype=torch.int32, device=eh.device)
+        for v in range(max(lo, 1), min(hi, eh.shape[1] - 1) + 1):
+            h[:, v - lo] = eh[:, v]
+        sets.append(h)
+    return compute_mmd(sets[0], sets[1], kernel, f32_pmf=True, **_dev_kw(kw))        # (the worker's histograms are float32)
+
+
+def rank2_distrib_stats(ref_desc, pred_desc, worker_kwargs=None, kernel: KernelSelector = gaussian_emd, cc_nb_eval: Optional[int] = None, **kw) -> float:
+    """rank2_distrib_stats (cc_utils.py:1337-1406): histogram of the rank-2 cells by size d_min..d_max = rank2_cell_hist."""
+    sets = [desc["rank2_cell_hist"].index_select(0, _cc_keep(desc, cc_nb_eval, drop)) for desc, drop in ((ref_desc, False), (pred_desc, True))]
+    if worker_kwargs is not None and "d_min" in worker_kwargs:
+        nb = int(worker_kwargs["d_max"]) - int(worker_kwargs["d_min"]) + 1
+        if any(s.shape[1] != nb for s in sets):
+            raise ValueError(f"rank2_distrib_stats: rank2_cell_hist does not have d_max - d_min + 1 = {nb} bins")
+    return compute_mmd(sets[0], sets[1], kernel, f32_pmf=True, **_dev_kw(kw))        # (the worker's histograms are float32)
+
+
+METHOD_NAME_TO_FUNC = {"degree": degree_stats, "cluster": clustering_stats}
+CC_METHOD_NAME_TO_FUNC = {"rank1_distrib": rank1_distrib_stats, "rank2_distrib": rank2_distrib_stats}
+
+
+def _check_methods(methods, table):
+    for m in methods:
+        if m in UNSUPPORTED:
+            raise NotImplementedError(f"evaluation method {m!r}: {UNSUPPORTED[m]}")
+        if m not in table:
+            raise KeyError(f"unknown evaluation method {m!r}; available: {sorted(table)}")
+
+
+def eval_torch_batch(ref_batch, pred_batch, methods: Optional[Sequence[str]] = None, kernels: Optional[dict] = None, *,
+                     mol: bool = False, thr: float = 0.5, bins: int = 100, **kw) -> Dict[str, float]:
+    """eval_torch_batch / eval_graph_list (stats.py:480-570): {method: round(score, 6)}.  ref_batch / pred_batch: adjacency batches
+    (B, N, N) or descriptor dicts.  Default methods: "degree", "cluster" -- the reference's third default, "orbit", needs the orca
+    program and has to be asked for by name to get its NotImplementedError.  Default kernel: gaussian_emd for both."""
+    methods = ["degree", "cluster"] if methods is None else list(methods)
+    _check_methods(methods, METHOD_NAME_TO_FUNC)
+    kernels = kernels or {}
+    dkw = dict(mol=mol, thr=thr, bins=bins, **_dev_kw(kw))
+    ref = _descriptors(ref_batch, ["degree_hist", "cluster_hist"], **dkw)
+    pred = _descriptors(pred_batch, ["degree_hist", "cluster_hist"], **dkw)
+    out = {}
+    for m in methods:
+        extra = {"bins": bins} if m == "cluster" else {}
+        out[m] = round(METHOD_NAME_TO_FUNC[m](ref, pred, kernels.get(m, gaussian_emd), **extra, **_dev_kw(kw)), 6)
+    return out
+
+
+def eval_CC_batch(ref_desc, pred_desc, worker_kwargs, methods: Optional[Sequence[str]] = None, kernels: Optional[dict] = None,
+                  cc_nb_eval: Optional[int] = 1000, **kw) -> Dict[str, float]:
+    """eval_CC_list (cc_utils.py:1418-1474) on descriptor dicts: {method: round(score, 6)}.  Default methods: "rank1_distrib",
+    "rank2_distrib" (the reference's other two defaults raise NotImplementedError when asked for, see UNSUPPORTED)."""
+    methods = ["rank1_distrib", "rank2_distrib"] if methods is None else list(methods)
+    _check_methods(methods, CC_METHOD_NAME_TO_FUNC)
+    kernels = kernels or {}
+    return {m: round(CC_METHOD_NAME_TO_FUNC[m](ref_desc, pred_desc, worker_kwargs, kernels.get(m, gaussian_emd), cc_nb_eval=cc_nb_eval,
+                                               **_dev_kw(kw)), 6) for m in methods}

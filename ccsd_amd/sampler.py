@@ -353,6 +353,48 @@ class Sampler:
         return out
 
 
+    def evaluate(self, result, ref, methods: Optional[List[str]] = None, cc_methods: Optional[List[str]] = None, bins: int = 100,
+                 cc_nb_eval: Optional[int] = 1000) -> Dict[str, float]:
+        """Score a finished run against a held-out set on the GPU (ccsd_amd/evaluation.py): what the reference prints after
+        sampling from eval_graph_list and eval_CC_list (sampler.py:253-262, 565-583), for the methods this build computes.
+        `result`: what sample() returned.  `ref`: an adjacency batch (B, N, N) of the held-out graphs, a descriptor dict
+        (evaluation.describe), or the path of an .npz that sample(save=True) wrote.  Returns {method: round(score, 6)}: "degree" and
+        "cluster" and, for combinatorial complexes whose two sides hold the descriptors, "rank1_distrib" and "rank2_distrib"
+        (data.min_edge_val / data.max_edge_val of the config; default 1..3 for molecules, 1..1 otherwise).  sample() itself is
+        untouched: nothing here runs unless it is called.  In a sharded run every rank holds the gathered samples and rank 0 alone
+        evaluates; the other ranks return {}."""
+        from . import evaluation as ev
+
+        if self.rank != 0:
+            return {}
+        lib = self.extra.get("lib")
+        kw = dict(device=self.device0, lib=lib)
+
+        keep = ("adj", "degree_hist", "edge_hist", "n_nodes", "rank2_cell_hist", "cluster_hist")
+
+        def side(obj):
+            if isinstance(obj, (str, os.PathLike)):
+                with np.load(obj) as z:           # (only the kept keys are decompressed: the dense rank2 of a saved run is never read)
+                    obj = {k: torch.from_numpy(z[k]) for k in keep if k in z.files}
+            if isinstance(obj, dict):
+                desc = {k: (v if isinstance(v, torch.Tensor) else torch.as_tensor(v)).to(self.device0) for k, v in obj.items() if k in keep}
+                if "cluster_hist" not in desc or desc["cluster_hist"].shape[1] != bins or "degree_hist" not in desc or "edge_hist" not in desc:
+                    if "adj" not in desc:
+                        raise KeyError("evaluate: a descriptor dict needs degree_hist, edge_hist and cluster_hist, or adj to compute them from")
+                    desc.update(ev.describe(desc["adj"], mol=self.is_mol, bins=bins, **kw))
+                return desc
+            return ev.describe(torch.as_tensor(obj), mol=self.is_mol, bins=bins, **kw)
+
+        pred, held = side(result), side(ref)
+        out = ev.eval_torch_batch(held, pred, methods, bins=bins, **kw)
+        if self.is_cc:
+            data = _get(self.config, "data")
+            wk = {"min_edge_val": _get(data, "min_edge_val", 1), "max_edge_val": _get(data, "max_edge_val", 3 if self.is_mol else 1)}
+            have = ["rank1_distrib"] + (["rank2_distrib"] if "rank2_cell_hist" in pred and "rank2_cell_hist" in held else [])
+            out.update(ev.eval_CC_batch(held, pred, wk, have if cc_methods is None else cc_methods, cc_nb_eval=cc_nb_eval, **kw))
+        return out
+
+
 # the reference's four class names (sampler.py:92, 369, 684, 1061) and its factory (sampler.py:1438-1468)
 class Sampler_Graph(Sampler):
     IS_MOL, APPLIES_EMA = False, True

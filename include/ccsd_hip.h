@@ -34,6 +34,11 @@
  *                              quantize of rank2 (sampler.py:1216-1225, 520-535), the cell bitmask, and the per-complex integers the
  *                              evaluators histogram (degree_worker, evaluation/stats.py:36; rank1_distrib_worker /
  *                              rank2_distrib_worker, cc_utils.py:1208-1334)
+ * ccsd_cluster_hist            clustering_worker on adjs_to_graphs(adj): np.histogram of nx.clustering per graph
+ *                              (evaluation/stats.py:206-220; graph_utils.py:216-251)
+ * ccsd_mmd                     compute_mmd with gaussian_emd / gaussian_tv / gaussian: the scores of degree_stats, clustering_stats,
+ *                              rank1_distrib_stats, rank2_distrib_stats (evaluation/mmd.py:27-257; evaluation/stats.py:60-310;
+ *                              cc_utils.py:1235-1406); ccsd_mmd_workspace_bytes sizes its workspace
  */
 #ifndef CCSD_HIP_H
 #define CCSD_HIP_H
@@ -309,6 +314,44 @@ typedef struct {
  * not belong to (N, d_min, d_max). */
 int ccsd_finish(const ccsd_finish_dims_t* dims, const ccsd_state_t* in, const float* flags_dev,
                 const ccsd_finish_out_t* out, void* stream);
+
+/* The clustering-coefficient histogram of every graph of adj_dev (B,N,N), 2 <= N <= 512: clustering_worker (evaluation/stats.py:206-220)
+ * on adjs_to_graphs (graph_utils.py:216-251).  An edge i -- j is a non-zero quantised entry adj[i][j], j != i, with the quantiser of
+ * ccsd_finish (adj_mode, thr); row i alone is read for node i: adj must be SYMMETRIC.  Nodes without an edge are not counted, a graph
+ * without any edge counts as one node in bin 0.
+ * edges_dev: bins + 1 doubles, the host's np.linspace(0.0, 1.0, bins + 1) (1 <= bins <= 1024): a coefficient c = t2 / (d (d - 1)) (fp64,
+ * IEEE division) goes to the largest bin i with edges[i] <= c, the last bin closed at 1, exactly as np.histogram places it.
+ * tri2_dev (B,N) int32: t2 = twice the triangles through each node; cluster_hist_dev (B,bins) int32.  Both nullable.
+ * CCSD_ERR_INVALID with a message for N outside 2..512 or bins outside 1..CCSD_CLUSTER_MAX_BINS (the histogram of a graph is kept in LDS). */
+#define CCSD_CLUSTER_MAX_BINS 1024
+int ccsd_cluster_hist(const float* adj_dev, int32_t B, int32_t N, int32_t adj_mode, float thr, const double* edges_dev, int32_t bins,
+                      int32_t* tri2_dev, int32_t* cluster_hist_dev, void* stream);
+
+/* compute_mmd (evaluation/mmd.py:230-257) of two sets of histograms, in fp64 and bit-reproducible from call to call:
+ *   mmd = disc(1,1) + disc(2,2) - 2 disc(1,2),  disc = mean over all pairs of exp(-dist(x, y)^2 / (2 sigma^2)). */
+enum { CCSD_MMD_EMD = 0,    /* gaussian_emd: dist = EMD on the ground distance toeplitz(range(L)) / distance_scaling, computed as
+                             *   sum |cdf_x - cdf_y| / distance_scaling (exact on a line metric); needs CCSD_MMD_IS_HIST */
+       CCSD_MMD_TV = 1,     /* gaussian_tv:  dist = 0.5 sum |x - y| */
+       CCSD_MMD_L2 = 2 };   /* gaussian:     dist = sqrt(sum (x - y)^2) */
+enum { CCSD_MMD_INT32 = 0, CCSD_MMD_FP64 = 1 };
+enum { CCSD_MMD_IS_HIST = 1,   /* compute_mmd's is_hist: every row with a non-zero sum is divided by it */
+       CCSD_MMD_DEGREE = 2,    /* rows are degree_hist of ccsd_finish: bin 0 is cleared (isolated and masked slots are no nodes of the
+                                *   reference's graphs), a row that is then empty becomes [1], and the row's length is its last non-zero bin + 1 */
+       CCSD_MMD_F32_PMF = 4 }; /* the division of CCSD_MMD_IS_HIST is rounded to fp32, as numpy does for the float32 histograms of
+                                *   rank1_distrib_worker / rank2_distrib_worker */
+/* h1_dev (n1,L), h2_dev (n2,L): int32 or fp64 rows (dtype), shorter histograms zero padded to the common L.  lens1_dev (n1,), lens2_dev
+ * (n2,) int32, nullable: the length of each row's original array (default L).  A length matters only to the EMD of a row of sum zero
+ * against one that has mass: pyemd's default extra_mass_penalty makes that distance (max(len_x, len_y) - 1) / distance_scaling; two
+ * rows of sum zero are at distance 0.  workspace_dev: at least ccsd_mmd_workspace_bytes(n1, n2, L) bytes, 8-byte aligned.
+ * out_dev: 4 doubles = disc(1,1), disc(2,2), disc(1,2), mmd.
+ * Limits: 1 <= n1, n2 <= CCSD_MMD_MAX_ROWS, 1 <= L <= CCSD_MMD_MAX_BINS; CCSD_ERR_INVALID with a message outside them (ccsd_mmd_workspace_bytes
+ * then returns 0).  The workspace grows as 8 L (n1 + n2) bytes for the operands plus 8 bytes per 64 x 64 tile of pairs. */
+#define CCSD_MMD_MAX_ROWS (1 << 20)
+#define CCSD_MMD_MAX_BINS (1 << 16)
+size_t ccsd_mmd_workspace_bytes(int32_t n1, int32_t n2, int32_t L);
+int ccsd_mmd(const void* h1_dev, int32_t n1, const int32_t* lens1_dev, const void* h2_dev, int32_t n2, const int32_t* lens2_dev, int32_t L,
+             int32_t dtype, int32_t kind, int32_t flags, double sigma, double distance_scaling, void* workspace_dev, size_t ws_bytes,
+             double* out_dev, void* stream);
 
 /* Measurement hooks (bench.py): time every launch of selected kernels with HIP events on the launch stream.
  * kernel_id: 0 k_xa, 1 k_gemm_p, 2 k_hf_score, 3 k_gemm_h, 4 k_langevin_apply, 5 k_r2, 6 k_s4_apply, 7 k_ew1; each call adds one kernel to the

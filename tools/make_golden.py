@@ -508,6 +508,260 @@ def f1_finish():
     print("wrote f1_finish", os.path.getsize(path))
 
 
+# ---------------------------------------------------------------------------------------------
+# e1_eval.npz: the reference's evaluators on small graph sets and histogram sets (`python tools/make_golden.py eval`)
+# ---------------------------------------------------------------------------------------------
+def _pyemd_stand_in(record):
+    """pyemd is not installed here.  Stand-in module with pyemd.emd's documented behaviour: the minimum-cost flow between the two
+    histograms on the caller's distance matrix, by scipy.optimize.linprog, plus |mass_x - mass_y| times extra_mass_penalty, whose
+    default (-1) means max(distance_matrix).  record["tl"].mode == "closed": the closed form on a line metric instead of the program
+    (sum |cdf_x - cdf_y| times the unit distance), with the same extra-mass rule; used to measure the difference between the two."""
+    import types
+
+    from scipy.optimize import linprog
+
+    def emd(x, y, D, extra_mass_penalty=-1.0):
+        x, y, D = np.asarray(x, np.float64), np.asarray(y, np.float64), np.asarray(D, np.float64)
+        n = len(x)
+        pen = D.max() if extra_mass_penalty == -1.0 else extra_mass_penalty
+        mx, my = x.sum(), y.sum()
+        extra = abs(mx - my) * pen
+        if min(mx, my) == 0.0:
+            return float(extra)
+        if getattr(record["tl"], "mode", "lp") == "closed":
+            assert abs(mx - my) < 1e-6, (x, y)           # (pmfs normalised in float32 miss mass 1 by ~1e-8: the closed form is then approximate)
+            unit = D[0, 1] if n > 1 else 0.0
+            return float(np.abs(np.cumsum(x) - np.cumsum(y)).sum() * unit + extra)
+        A_ub = np.zeros((2 * n, n * n))
+        for i in range(n):
+            A_ub[i, i * n:(i + 1) * n] = 1.0
+            A_ub[n + i, i::n] = 1.0
+        res = linprog(D.reshape(-1), A_ub=A_ub, b_ub=np.concatenate([x, y]), A_eq=np.ones((1, n * n)), b_eq=[min(mx, my)],
+                      bounds=(0, None), method="highs")
+        assert res.status == 0, res.message
+        record["programs"] = record.get("programs", 0) + 1
+        return float(res.fun + extra)
+
+    m = types.ModuleType("pyemd")
+    m.emd = emd
+    return m
+
+
+class _StandInCC:
+    """The two members of a toponetx CombinatorialComplex that rank1_distrib_worker, rank2_distrib_worker and is_empty_cc read,
+    filled from per-complex counts: n_nodes rank-0 cells, edge_hist[v] rank-1 cells of value v >= 1, cell_hist[s - d_min] rank-2 cells of size s."""
+
+    def __init__(self, n_nodes, edge_hist, cell_hist, d_min):
+        import types
+
+        r1 = {}
+        for v in range(1, len(edge_hist)):
+            for i in range(int(edge_hist[v])):
+                r1[frozenset((("e", v, i), ("f", v, i)))] = {"label": v}
+        r2 = {}
+        for b, c in enumerate(cell_hist):
+            for i in range(int(c)):
+                r2[frozenset([("c", b, i, j) for j in range(d_min + b)])] = {}
+        self.cells = types.SimpleNamespace(hyperedge_dict={0: {frozenset([i]): {} for i in range(int(n_nodes))}, 1: r1, 2: r2})
+
+    def number_of_cells(self):
+        return sum(len(v) for v in self.cells.hyperedge_dict.values())
+
+
+def e1_graph_sets():
+    """name -> (adjacency (B, N, N) int8, mol): the graphs of the clustering cases of tests/eval_cases.py."""
+    from itertools import combinations
+
+    rng = np.random.default_rng(20261018)
+
+    def sym(B, N, p, masked=0, values=(1,)):
+        a = np.zeros((B, N, N), np.int8)
+        for b in range(B):
+            n = N - masked * b
+            u = np.triu((rng.random((n, n)) < p), 1)
+            v = rng.choice(np.array(values, np.int8), size=(n, n))
+            a[b, :n, :n] = u * v
+            a[b] = a[b] + a[b].T
+        return a
+
+    def hub(N, inner):
+        a = np.zeros((1, N, N), np.int8)
+        a[0, 0, 1:] = a[0, 1:, 0] = 1
+        for i, j in list(combinations(range(1, N), 2))[:inner]:
+            a[0, i, j] = a[0, j, i] = 1
+        return a
+
+    sets = {"c07": (hub(6, 7), False),                                  # degree 5, 7 triangles: c = 0.7 -> bin 69 of 100
+            "n17": (hub(17, 42), False),                                # degree 16, 42 triangles: c = 0.35 -> bin 34
+            "k65": ((1 - np.eye(65, dtype=np.int8))[None], False),      # crosses a mask word; every c = 1 -> bin 99
+            "n2": (np.array([[[0, 1], [1, 0]], [[0, 0], [0, 0]], [[1, 1], [1, 1]]], np.int8), False),
+            "r65": (sym(3, 65, 0.3, masked=7), False),
+            "r130": (sym(2, 130, 0.3, masked=11), False),
+            "n512": (sym(2, 512, 0.05, masked=40), False),
+            "mol9": (sym(4, 9, 0.45, masked=1, values=(1, 2, 3)), True)}
+    small = np.zeros((4, 5, 5), np.int8)                                # edgeless; a single edge; a triangle + tail with a non-zero diagonal; diagonal only
+    small[1, 1, 3] = small[1, 3, 1] = 1
+    for i, j in ((0, 1), (1, 2), (0, 2), (2, 3)):
+        small[2, i, j] = small[2, j, i] = 1
+    small[2][np.diag_indices(5)] = 1
+    small[3][np.diag_indices(5)] = 1
+    sets["small5"] = (small, False)
+    d = sym(3, 12, 0.4)
+    d[:, np.arange(12), np.arange(12)] = 1
+    sets["diag12"] = (d, False)
+    # the two sets eval_graph_list scores against each other (the second holds an edgeless graph)
+    sets["eval_ref"] = (sym(12, 12, 0.35, masked=0), False)
+    pred = sym(9, 12, 0.55, masked=1)
+    pred[8] = 0
+    sets["eval_pred"] = (pred, False)
+    return sets
+
+
+def e1_mmd_sets():
+    """name -> (rows1, rows2, emd): lists of 1-D histograms; emd = whether the linear programs are affordable at this size."""
+    rng = np.random.default_rng(1018)
+
+    def rows(n, L, ragged=False, dtype=np.int64, zero=()):
+        out = []
+        for i in range(n):
+            l = int(rng.integers(1, L + 1)) if ragged else L
+            r = rng.integers(0, 6, l).astype(dtype)
+            if not r.any():
+                r[0] = 1
+            if i in zero:
+                r[:] = 0
+            out.append(r)
+        return out
+
+    return {"a": (rows(3, 2), rows(1, 2), True),
+            "l1": (rows(3, 1), rows(2, 1), True),
+            "ragged": (rows(5, 11, ragged=True), rows(3, 9, ragged=True), True),
+            "zero_one": (rows(4, 7, dtype=np.float32, zero=(1,)), rows(3, 7, dtype=np.float32), True),      # (float32: the rank-2 worker's dtype)
+            "zero_both": (rows(4, 6, ragged=True, zero=(0, 2)), rows(3, 8, ragged=True, zero=(1,)), True),
+            "n65": (rows(65, 33), rows(3, 33), True),
+            "n130": (rows(130, 100), rows(64, 100), False),
+            "l512": (rows(3, 512), rows(1, 512), False),
+            "l200": (rows(3, 200, ragged=True), rows(3, 200), False)}
+
+
+def e1_eval():
+    """e1_eval.npz: the reference's own clustering_worker, degree_worker, compute_mmd with gaussian_tv / gaussian / gaussian_emd,
+    eval_graph_list and eval_CC_list on small inputs.  gaussian_emd runs on the stand-in pyemd above; meta holds the largest
+    difference between its linear programs and the closed form, per kernel value and per score."""
+    import time
+
+    import threading
+
+    record = {"tl": threading.local()}          # (disc() runs the kernel on a thread pool: the mode is per thread)
+    sys.modules["pyemd"] = _pyemd_stand_in(record)
+    from ccsd.src.evaluation import mmd as ref_mmd
+    from ccsd.src.evaluation import stats as ref_stats
+
+    ref_mmd.pyemd = sys.modules["pyemd"]
+    t0 = time.time()
+    out, meta = {}, {"graph_sets": {}, "mmd_sets": {}, "scores": {}, "lp_vs_closed": {}, "lp_vs_closed_kernel": 0.0, "lp_vs_closed_score": 0.0}
+
+    def k_closed(x, y, **kw):        # gaussian_emd with the closed form behind pyemd.emd
+        record["tl"].mode = "closed"
+        try:
+            return ref_mmd.gaussian_emd(x, y, **kw)
+        finally:
+            record["tl"].mode = "lp"
+
+    def k_emd(x, y, **kw):           # gaussian_emd under both stand-ins: the program's value is the one returned
+        kc = k_closed(x, y, **kw)
+        kl = ref_mmd.gaussian_emd(x, y, **kw)
+        meta["lp_vs_closed_kernel"] = max(meta["lp_vs_closed_kernel"], abs(float(kl) - float(kc)))
+        return kl
+
+    def closed(fn):
+        return fn(k_closed)
+
+    def emd_score(fn, tag):
+        """fn(kernel) -> score: with the linear programs (returned) and with the closed form; meta["lp_vs_closed"][tag] = the largest
+        |program - closed form| over the kernel values of this score, lp_vs_closed_kernel / _score the largest over all scores."""
+        before, meta["lp_vs_closed_kernel"] = meta["lp_vs_closed_kernel"], 0.0
+        lp = float(fn(k_emd))
+        meta["lp_vs_closed"][tag] = meta["lp_vs_closed_kernel"]
+        meta["lp_vs_closed_kernel"] = max(before, meta["lp_vs_closed_kernel"])
+        meta["lp_vs_closed_score"] = max(meta["lp_vs_closed_score"], abs(lp - float(closed(fn))))
+        return lp
+
+    # ---- graphs: clustering_worker / degree_worker per graph
+    graphs = {}
+    for name, (adj, mol) in e1_graph_sets().items():
+        out[f"graphs/{name}/adj"] = adj
+        meta["graph_sets"][name] = {"mol": mol, "N": int(adj.shape[1]), "B": int(adj.shape[0])}
+        q = ref_gu.quantize_mol(torch.as_tensor(adj, dtype=torch.float32)) if mol else ref_gu.quantize(torch.as_tensor(adj, dtype=torch.float32)).numpy()
+        G = ref_gu.adjs_to_graphs(np.asarray(q, np.float32))
+        graphs[name] = G
+        for bins in (10, 100):
+            out[f"graphs/{name}/cluster_hist{bins}"] = np.stack([ref_stats.clustering_worker((g, bins)) for g in G]).astype(np.int32)
+        dh = np.zeros((len(G), adj.shape[1]), np.int32)
+        dl = np.zeros(len(G), np.int32)
+        for b, g in enumerate(G):
+            h = ref_stats.degree_worker(g)
+            dh[b, :len(h)], dl[b] = h, len(h)
+        out[f"graphs/{name}/degree_hist"], out[f"graphs/{name}/degree_len"] = dh, dl
+    # ---- eval_graph_list on two graph sets
+    gr, gp = graphs["eval_ref"], graphs["eval_pred"]
+    sc = meta["scores"]
+    sc["degree/emd"] = emd_score(lambda k: ref_stats.degree_stats(gr, gp, k), "degree/emd")
+    sc["cluster/emd"] = emd_score(lambda k: ref_stats.clustering_stats(gr, gp, k), "cluster/emd")
+    sc["cluster10/emd"] = emd_score(lambda k: ref_stats.clustering_stats(gr, gp, k, bins=10), "cluster10/emd")
+    sc["degree/tv"] = float(ref_stats.degree_stats(gr, gp, ref_mmd.gaussian_tv))
+    sc["cluster/tv"] = float(ref_stats.clustering_stats(gr, gp, ref_mmd.gaussian_tv))
+    meta["eval_graph_list"] = ref_stats.eval_graph_list(gr, gp, methods=["degree", "cluster"], kernels={"degree": k_emd, "cluster": k_emd})
+    # ---- compute_mmd on histogram sets
+    for name, (r1, r2, with_emd) in e1_mmd_sets().items():
+        for side, rows in (("1", r1), ("2", r2)):
+            L = max(len(r) for r in rows)
+            pad = np.zeros((len(rows), L), rows[0].dtype)
+            for i, r in enumerate(rows):
+                pad[i, :len(r)] = r
+            out[f"mmd/{name}/rows{side}"], out[f"mmd/{name}/lens{side}"] = pad, np.array([len(r) for r in rows], np.int32)
+        meta["mmd_sets"][name] = {"emd": with_emd, "dtype": str(r1[0].dtype)}
+        for sigma, scale in ((1.0, 1.0), (0.1, 100.0)):
+            tag = f"mmd/{name}/s{sigma:g}_d{scale:g}"
+            sc[tag + "/tv"] = float(ref_mmd.compute_mmd(r1, r2, kernel=ref_mmd.gaussian_tv, sigma=sigma))
+            sc[tag + "/l2"] = float(ref_mmd.compute_mmd(r1, r2, kernel=ref_mmd.gaussian, sigma=sigma))
+            if with_emd:
+                sc[tag + "/emd"] = emd_score(lambda k: ref_mmd.compute_mmd(r1, r2, kernel=k, sigma=sigma, distance_scaling=scale), tag + "/emd")
+        # raw vectors (orbit_stats_all's call: is_hist=False, sigma=30)
+        f1_, f2_ = [r.astype(np.float64) * 7.5 for r in r1], [r.astype(np.float64) * 7.5 for r in r2]
+        sc[f"mmd/{name}/raw_s30/l2"] = float(ref_mmd.compute_mmd(f1_, f2_, kernel=ref_mmd.gaussian, is_hist=False, sigma=30.0))
+        print("e1 mmd", name, round(time.time() - t0, 1), "s", record.get("programs", 0), "programs")
+    # ---- eval_CC_list over the descriptors of f1_finish.npz (qm9_CC: bonds 1..3, cells of 3..9 nodes)
+    f1 = np.load(os.path.join(GOLD, "f1_finish.npz"))
+    d_min, d_max = 3, 9
+    cc_sets = {"ref": [("ccsd_qm9_CC", "k10"), ("ccsd_qm9_CC", "k50")], "pred": [("ccsd_qm9_CC", "n1000_first3"), ("ccsd_qm9_CC_full1000", "n1000")]}
+    wk = {"min_edge_val": 1, "max_edge_val": 3, "edge_label": "label", "d_min": d_min, "d_max": d_max}
+    desc = {side: {k: np.concatenate([f1[f"{n}/{c}/{k}"] for n, c in parts]) for k in ("n_nodes", "edge_hist", "cell_hist")} for side, parts in cc_sets.items()}
+    meta["cc_sets"], meta["cc_worker_kwargs"] = cc_sets, wk
+
+    def ccs(d, extra_empty):
+        cc = [_StandInCC(d["n_nodes"][b], d["edge_hist"][b], d["cell_hist"][b], d_min) for b in range(len(d["n_nodes"]))]
+        return cc + [_StandInCC(0, [0, 0, 0, 0], [0] * (d_max - d_min + 1), d_min)] * extra_empty
+
+    kern = {"rank1_distrib": k_emd, "rank2_distrib": k_emd}
+    for tag, er, ep, nb in (("plain", 0, 0, 1000), ("empties", 1, 1, 1000), ("first5", 0, 0, 5)):
+        # ("empties": one complex without any cell appended to each side -- kept in the reference set, dropped from the predictions)
+        meta[f"eval_CC_list/{tag}"] = ref_cc.eval_CC_list(ccs(desc["ref"], er), ccs(desc["pred"], ep), wk, methods=["rank1_distrib", "rank2_distrib"],
+                                                          kernels=kern, cc_nb_eval=nb)
+        sc[f"cc/{tag}/rank2/emd"] = emd_score(lambda k: ref_cc.rank2_distrib_stats(ccs(desc["ref"], er)[:nb], ccs(desc["pred"], ep)[:nb], wk, k), f"cc/{tag}/rank2/emd")
+        sc[f"cc/{tag}/rank1/emd"] = emd_score(lambda k: ref_cc.rank1_distrib_stats(ccs(desc["ref"], er)[:nb], ccs(desc["pred"], ep)[:nb], wk, k), f"cc/{tag}/rank1/emd")
+    meta["programs"] = record.get("programs", 0)
+    meta["seconds"] = round(time.time() - t0, 1)
+    meta["note"] = ("gaussian_emd ran on a stand-in pyemd (scipy.optimize.linprog on the reference's distance matrix, extra mass at pyemd's "
+                    "documented default penalty max(distance_matrix)); lp_vs_closed_* = largest |program - closed form| seen here")
+    out["meta"] = np.array(json.dumps(plain(meta)))
+    path = os.path.join(GOLD, "e1_eval.npz")
+    np.savez_compressed(path, **out)
+    assert os.path.getsize(path) <= MAX_FIXTURE, os.path.getsize(path)
+    print("wrote e1_eval", os.path.getsize(path), "bytes;", meta["programs"], "programs,", meta["seconds"], "s; lp vs closed form:",
+          meta["lp_vs_closed_kernel"], "(kernel)", meta["lp_vs_closed_score"], "(score)")
+
+
 def d1_qm9_cc_n1000(B=256, seed=42, raw=None):
     """d1_qm9_CC_n1000.npz: ONE reference run of the shipped qm9_CC sampling set-up -- checkpoints/QM9/ccsd_qm9_CC.pth, the sampler block of
     config/sample_qm9_CC.yaml, all 1000 scales, B complexes, flags drawn as the harness draws them without the dataset blobs
@@ -1214,6 +1468,9 @@ def main():
     only = set(sys.argv[1:])
     if only == {"f1"}:
         f1_finish()
+        return
+    if only == {"eval"}:
+        e1_eval()
         return
     if only == {"d1"}:
         # ~a quarter of an hour of reference CPU time was the estimate; the fixture's metadata holds what it took
