@@ -92,14 +92,29 @@ CCSD_DEV float elu1(float v) {
     return v > 0.f ? v : ex;
 }
 CCSD_DEV float elu1_sel(float v) { return elu1(v); }
-// t / d and t % d for 0 <= t < 2^22 and small d without the ~40-instruction integer division:
-// (t + 0.5) * (1/d) is never within 0.5/d of an integer, far more than the fp32 rounding of the product.
+// t / d and t % d without the ~40-instruction integer division.  EXACT DOMAIN: 0 <= t <= 2^22 - 1, 1 <= d <= 2^24 (any such d).
+// Proof: t + 0.5 and d are exact in fp32; inv and the product round once each, so the computed value is (t + 0.5) / d * (1 + eps)
+// with |eps| < 2^-23 (1 + 2^-25).  (t + 0.5) / d = (2 t + 1) / (2 d) lies at least 0.5 / d from every integer, and the error
+// (t + 0.5) / d * |eps| stays below that iff (t + 0.5) (1 + 2^-25) < 2^22, which t <= 2^22 - 1 gives.  Beyond it the truncation may
+// land one off (the first miss over d < 2000: t = 4243964 = 2^22 + 49660 at d = 255; tests/test_probe.py walks the edge), so a
+// site must bound its t: every site indexes a block that lives in the workgroup's LDS (at most 40960 floats).  Indices into a
+// complex's tensors in global memory do not qualify: see flat_split.
 struct FastDiv {
     int d; float inv;
     CCSD_DEV explicit FastDiv(int dd) : d(dd), inv(1.0f / (float)dd) {}
     CCSD_DEV int div(int t) const { return (int)(((float)t + 0.5f) * inv); }
     CCSD_DEV void divmod(int t, int& q, int& r) const { q = div(t); r = t - q * d; }
 };
+// (e, k) of element t = e K + k of a complex's flattened (E, K) block: the split of a flat Philox group's first element in
+// k_noise_norm, k_langevin_apply and k_ew1.  Exact for every 0 <= t < 2^31, K >= 1 (E K passes FastDiv's 2^22 from N = 43 on:
+// 903 x 12341): unsigned integer division -- a multiply-high and a shift where K is a compile-time constant (GEO_EK), otherwise
+// the reciprocal of the uniform K is set up once per thread and each split costs a multiply-high and two corrections, next to the
+// ~100 instructions of the group's Philox rounds.
+CCSD_DEV void flat_split(int t, int K, int& e, int& k) {
+    const unsigned q = (unsigned)t / (unsigned)K;
+    e = (int)q;
+    k = (int)((unsigned)t - q * (unsigned)K);
+}
 
 template <bool V> struct BoolTag { static constexpr bool v = V; };
 

@@ -73,7 +73,7 @@ __global__ __launch_bounds__(512, 4) void k_r2(const PlanD* __restrict__ plan, c
     __shared__ int s_hdone;              // H-tile tasks finished (phase 1 -> 2 hand-over)
 #endif
     const float* Fg = ra.rank2 + (size_t)b * E * K;
-    const FastDiv dK(K);
+    const FastDiv dK(K);                                  // t < E K: the block is LDS-resident here (E ldk floats of sF), far inside FastDiv's 2^22
     constexpr bool ST = AFFINE && !GEN1 && MT == 3 && RS == 1;   // E = 33..36: two full row tiles + one 4-row strip
     constexpr int MTF = ST ? MT - 1 : MT;                 // full 16-row tiles
     constexpr int E0 = 16 * MTF;                          // first strip row (ST)
@@ -149,7 +149,7 @@ __global__ __launch_bounds__(512, 4) void k_r2(const PlanD* __restrict__ plan, c
             const float4* N4 = reinterpret_cast<const float4*>(Ng);
             const float4* Z4 = reinterpret_cast<const float4*>(nc.zr ? nc.zr + (size_t)b * EK : Fg);
             const int n4 = EK >> 2;
-            const FastDiv dK2(K >> 1);                        // pair index -> (row, pair within the row)
+            const FastDiv dK2(K >> 1);                        // pair index -> (row, pair within the row); 2 i4 < E K / 2, the LDS-resident block again
             auto phase0 = [&](auto LB_, auto CF_, auto ZN_) {
                 constexpr int LB = decltype(LB_)::value;      // float4 loads per thread and batch
                 constexpr bool CF = decltype(CF_)::value;     // fused corrector apply: the raw scores are loaded alongside

@@ -82,13 +82,12 @@ __global__ void k_noise_norm(NoiseArgs na, MaskTab mt, int E_, int K_, float* __
     const int E = EC ? EC : E_, K = KC ? KC : K_;
     const int b = blockIdx.y, EK = E * K, ng = (EK + 3) >> 2;
     const int g0 = blockIdx.x * CCSD_NN_CH, g1 = g0 + CCSD_NN_CH < ng ? g0 + CCSD_NN_CH : ng;
-    const FastDiv dK(K);
     float acc = 0.f;
     for (int g = g0 + threadIdx.x; g < g1; g += blockDim.x) {
         float z[4];
         raw_noise_rflat4(na, b, g, EK, z);
         int e, k;
-        dK.divmod(4 * g, e, k);
+        flat_split(4 * g, K, e, k);
         float m[4];
         group_masks(mt, b, E, K, e, k, m);
 #pragma unroll
@@ -128,7 +127,6 @@ __global__ void k_langevin_apply(LangArgs a, NoiseArgs na, MaskTab mt) {
     langevin_coef(a.lc, 0, &c1x, &c2x);
     langevin_coef(a.lc, 1, &c1a, &c2a);
     if (a.is_cc) langevin_coef(a.lc, 2, &c1r, &c2r);
-    const FastDiv dK(a.K > 0 ? a.K : 1);
     for (long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x; t < total; t += (long long)gridDim.x * blockDim.x) {
         if (t < nre) {                                           // (the rank2 groups come first: the bulk of the work, aligned)
             const int b = (int)(t / ng), g = (int)(t - (long long)b * ng);
@@ -148,7 +146,7 @@ __global__ void k_langevin_apply(LangArgs a, NoiseArgs na, MaskTab mt) {
             }
             raw_noise_rflat4(na, b, g, EK, z);
             int e, k;
-            dK.divmod(4 * g, e, k);
+            flat_split(4 * g, a.K, e, k);
             float o[4], m[4];
             group_masks(mt, b, a.E, a.K, e, k, m);
 #pragma unroll
@@ -199,7 +197,6 @@ __global__ void k_ew1(Ew1Args a, NoiseArgs na) {
     if (EC) { a.E = EC; a.K = KC; }
     const int b = blockIdx.y, EK = a.E * a.K, ng = (EK + 3) >> 2;
     const int g0 = blockIdx.x * CCSD_NN_CH, g1 = g0 + CCSD_NN_CH < ng ? g0 + CCSD_NN_CH : ng;
-    const FastDiv dK(a.K);
     const bool vec = (EK & 3) == 0;
     float c1 = 0.f, c2 = 0.f;
     // (Ew1Args carries the rank2 target's scalars only: slot 2 of the LangCoef is the one that is read)
@@ -216,7 +213,7 @@ __global__ void k_ew1(Ew1Args a, NoiseArgs na) {
             for (int s = 0; s < 4; ++s) v[s] = 4 * g + s < EK ? a.r[base + s] : 0.f;
         }
         int e, k;
-        dK.divmod(4 * g, e, k);
+        flat_split(4 * g, a.K, e, k);
         float m[4];                                                            // flags_left * flags_right, cc_utils.py:590
         group_masks(a.mt, b, a.E, a.K, e, k, m);
         float o[4], mu[4], w1[4], nt[4];

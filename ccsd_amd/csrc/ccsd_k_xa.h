@@ -86,7 +86,7 @@ CCSD_DEV void wave_prio(int p) {
 
 // clamp(rowsum(A with unit diagonal), 1)^-1/2 for `nc` channels   (DenseGCNConv, layers.py:139-145)
 CCSD_DEV void gcn_dinv(const float* a, float* dinv, int nc, int N) {
-    const FastDiv dN(N);
+    const FastDiv dN(N);                 // t < nc N, a slice of the workgroup's LDS
     for (int t = threadIdx.x; t < nc * N; t += blockDim.x) {
         int c, i;
         dN.divmod(t, c, i);
@@ -229,6 +229,9 @@ __global__ __launch_bounds__((VAR == XA_PLAIN9 || VAR == XA_BAKED9 || !XA_4WAVES
     float* s_dinv = sm + p.o_an;
     float* s_red = sm + (xa.do_a ? p.o_red : p.o_xcat);   // block reductions: a region that is idle at the end of the launch
     float* s_R = sm + p.o_c0;            // shared region: GCN scratch | MLP hidden activations | dense hodge layer
+    // FastDiv sites of this kernel (these four and the per-layer ones below and in ccsd_attn_stack.inc): every t they split counts the
+    // elements of one region of the workgroup's LDS layout (at most 40960 floats) or of one complex's channel stack (channels x N x N
+    // with N <= 64: 2^12 per channel, so a thousand channels would still fit), inside FastDiv's domain t <= 2^22 - 1
     const FastDiv dN(N), dNN(NN), dF(F), dE(E > 0 ? E : 1);
     const float* wp = xa.wp;
 #ifdef CCSD_EMU

@@ -196,6 +196,21 @@ def case_planner_rejections(lib, device, monkeypatch):
     assert eng.query("loop_form") == 1 and eng.query("tiled_fuse") == 0 and eng.query("fused_loop") == 0
 
 
+# ---- the node counts between the crossover and the shipped N = 49 at which E K > 2^22 made FastDiv(K) split flat Philox groups
+# into the wrong row (206, 125 and 15 groups per complex: tests/test_probe.py); k_noise_norm and k_langevin_apply run on every step
+# of the un-fused Langevin loop these plans take
+SPLIT_NODE_COUNTS = (44, 45, 47)
+
+
+def case_split_shape_production_loop(lib, device, N):
+    """grid_at(N), Reverse + Langevin (snr 0.1, scale_eps 0.7), one step, B = 3 with node counts [N, 2, N] -- a full complex followed
+    by a near-empty one, and a full one last in the batch -- through parity_cases.case_production_loop_vs_oracle: the oracle replays
+    the draws ccsd_noise_draws exports (k_init_state splits flat groups by integer division), so a group the loop's kernels split
+    into the wrong row shows as a difference; the step-wise driver (ccsd_corrector_norms / ccsd_corrector_apply) bit for bit."""
+    pc.case_production_loop_vs_oracle(f"grid_small_CC@{N}", lib, device, 3, [N, 2, N], 1, "Reverse", "Langevin", 0.1, 0.7,
+                                      source=grid_at(N), expect_route={"large_graph": 1, "loop_form": 1})
+
+
 # ---- the real checkpoint at N = 49 (GPU suite: one rank2 forward takes minutes on the emulation)
 def case_grid_forwards(lib, device):
     """g1: x and adj (and their score scaling at t = 0.5) against the reference's outputs; rank2 through its summary: the fixture's

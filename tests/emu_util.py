@@ -24,3 +24,26 @@ def emu_library() -> _lib.Library:
                                    SRC, "-o", OUT])
         _emu = _lib.Library(OUT, is_hip=False)
     return _emu
+
+
+PROBE_SRC = os.path.join(ROOT, "tests", "emu", "ccsd_probe.cpp")
+_probe = {}
+
+
+def probe_library(csrc: str = CSRC, defines=()):
+    """tests/emu/ccsd_probe.cpp built against the kernel source in `csrc` (ctypes handle): the device helpers of the noise stream
+    on the host.  Another `csrc` / `defines` builds a library of its own beside it (a kernel source to compare against)."""
+    import ctypes
+    import hashlib
+
+    key = (os.path.abspath(csrc), tuple(defines))
+    if key not in _probe:
+        tag = "" if key == (CSRC, ()) else "_" + hashlib.sha1(repr(key).encode()).hexdigest()[:10]
+        out = os.path.join(ROOT, "tests", "emu", "_build", f"libccsd_probe{tag}.so")
+        deps = [PROBE_SRC] + glob.glob(os.path.join(csrc, "*.h"))
+        os.makedirs(os.path.dirname(out), exist_ok=True)
+        if not os.path.exists(out) or any(os.path.getmtime(d) > os.path.getmtime(out) for d in deps):
+            subprocess.check_call(["g++", "-O2", "-std=c++17", "-DCCSD_EMU", *[f"-D{d}" for d in defines], "-fPIC", "-shared",
+                                   "-Wno-unknown-pragmas", "-I", csrc, PROBE_SRC, "-o", out])
+        _probe[key] = ctypes.CDLL(out)
+    return _probe[key]

@@ -668,6 +668,37 @@ def case_zinc5b_production_loop(lib, device):
                                    sm["scale_eps"], seed=29, expect_fused=True, source=(meta, parts))
 
 
+def zinc5b_at(N, d_min, d_max):
+    """The zinc250k_CC substitute's architecture (zinc5b_setup) at another geometry: every weight from the fixture, the four hodge
+    weights whose row count is K repeated cyclically to K(N, d_min, d_max) rows and scaled by sqrt(8436 / K) (the projections keep
+    their magnitude): a same-architecture network with arbitrary weights, in the checkpoint layout."""
+    _, meta5, sd, _, _ = zinc5b_setup()
+    _, Fd, _, _, _, K0 = meta5["dims"]
+    E, K = rank2_dim(N, d_min, d_max)
+    geo = dict(max_node_num=N, d_min=d_min, d_max=d_max)
+    meta = {"is_cc": True, "config": {"data": {"max_node_num": N, "max_feat_num": Fd, "d_min": d_min, "d_max": d_max},
+                                      "sde": {p: dict(meta5["sde"][p], num_scales=1000) for p in ("x", "adj", "rank2")}}}
+    parts = {}
+    for p in ("x", "adj", "rank2"):
+        meta[f"params_{p}"] = dict(meta5["params"][p], **{k: v for k, v in geo.items() if k in meta5["params"][p]})
+        parts[p] = {}
+        for k, v in sd[p].items():
+            if v.dim() == 2 and v.shape[0] == K0:
+                v = v[torch.arange(K) % K0] * (K0 / K) ** 0.5
+            parts[p][k] = v.clone().requires_grad_(True)
+    return meta, parts, meta5["sampler"]
+
+
+def case_ew1_odd_k_production_loop(lib, device, N=30, d_min=3, d_max=4):
+    """k_ew1 itself at a block beyond 2^22 elements: the zinc250k_CC substitute's architecture at N = 30, d = 3..4 (E = 435, K = 31465,
+    E K = 13 687 275; FastDiv(K) split 28 of its flat groups into the wrong row).  K is odd, so the rank-2 side does not ride on the
+    projection GEMM (ew1_fuse 0) and k_ew1 runs every pass.  Reverse + Langevin, one step, B = 3 with node counts [N, 2, N]."""
+    meta, parts, sm = zinc5b_at(N, d_min, d_max)
+    assert rank2_dim(N, d_min, d_max)[1] % 2 == 1
+    case_production_loop_vs_oracle(f"zinc250k_CC_5b@{N}", lib, device, 3, [N, 2, N], 1, sm["predictor"], sm["corrector"], sm["snr"],
+                                   sm["scale_eps"], seed=29, source=(meta, parts), expect_route={"ew1": 1, "ew1_fuse": 0})
+
+
 def case_fused_r2_nonaffine_shapes(lib, device):
     """Non-affine ScoreNetworkF (2-linear HodgeNetworkLayers / 2-layer head: the reference-built nets of kat_small_models, whose
     weights do not depend on N) at N = 7, 8, 11 -- E = 21, 28, 55, i.e. two and four 16-row tiles: the plan must select the
