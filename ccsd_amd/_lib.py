@@ -26,6 +26,8 @@ EXPORTS = [
     "ccsd_predictor", "ccsd_s4_apply", "ccsd_sampler_run", "ccsd_quantize", "ccsd_rank2_cells", "ccsd_profile_kernel", "ccsd_profile_stride", "ccsd_profile_read", "ccsd_profile_launches", "ccsd_debug_stamps",
     "ccsd_noise_draws", "ccsd_plan_query", "ccsd_sampler_run_ex", "ccsd_finish",
     "ccsd_cluster_hist", "ccsd_mmd_workspace_bytes", "ccsd_mmd",
+    "ccsd_eig_workspace_bytes", "ccsd_eigvalsh", "ccsd_spectral_workspace_bytes", "ccsd_spectral_hist",
+    "ccsd_hodge_workspace_bytes", "ccsd_hodge_spectrum",
 ]
 QUERIES = {"fused_r2": 0, "xa_variant": 1, "r2_lds_bytes": 2, "xa_lds_bytes": 3, "fused_loop": 4, "merged_r2": 5, "ew1": 6, "large_graph": 7,
            "r2_family": 8, "r2_instance": 9, "loop_form": 10, "h_full": 11, "hp_full": 12, "p0_narrow": 13, "tiled_fuse": 14, "ew1_fuse": 15,
@@ -66,6 +68,7 @@ MMD_EMD, MMD_TV, MMD_L2 = 0, 1, 2
 MMD_INT32, MMD_FP64 = 0, 1
 MMD_IS_HIST, MMD_DEGREE, MMD_F32_PMF = 1, 2, 4
 CLUSTER_MAX_BINS, MMD_MAX_ROWS, MMD_MAX_BINS = 1024, 1 << 20, 1 << 16      # CCSD_CLUSTER_MAX_BINS, CCSD_MMD_MAX_ROWS, CCSD_MMD_MAX_BINS
+EIG_MAXN, EIG_MAX_SWEEPS = 512, 30                                        # CCSD_EIG_MAXN; the sweep cap of k_eigvalsh
 
 
 class FinishDims(C.Structure):
@@ -170,6 +173,18 @@ class Library:
         L.ccsd_mmd_workspace_bytes.restype = sz
         L.ccsd_mmd.argtypes = [vp, i32, vp, vp, i32, vp, i32, i32, i32, i32, C.c_double, C.c_double, vp, sz, vp, vp]
         L.ccsd_mmd.restype = C.c_int
+        L.ccsd_eig_workspace_bytes.argtypes = [i32, i32]
+        L.ccsd_eig_workspace_bytes.restype = sz
+        L.ccsd_eigvalsh.argtypes = [vp, i32, i32, vp, vp, vp, sz, vp]
+        L.ccsd_eigvalsh.restype = C.c_int
+        L.ccsd_spectral_workspace_bytes.argtypes = [i32, i32]
+        L.ccsd_spectral_workspace_bytes.restype = sz
+        L.ccsd_spectral_hist.argtypes = [vp, i32, i32, i32, f32, vp, i32, vp, vp, vp, vp, sz, vp]
+        L.ccsd_spectral_hist.restype = C.c_int
+        L.ccsd_hodge_workspace_bytes.argtypes = [i32, i32]
+        L.ccsd_hodge_workspace_bytes.restype = sz
+        L.ccsd_hodge_spectrum.argtypes = [vp, vp, i32, i32, i32, i32, i32, f32, vp, vp, vp, sz, vp]
+        L.ccsd_hodge_spectrum.restype = C.c_int
 
     def __getattr__(self, name):
         return getattr(self.c, name)

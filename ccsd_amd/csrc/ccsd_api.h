@@ -1816,3 +1816,155 @@ extern "C" int ccsd_mmd(const void* h1, int32_t n1, const int32_t* lens1, const 
     LAUNCH_CHECK();
     return CCSD_OK;
 }
+
+// ---------------- spectra (ccsd_k_eig.h) ----------------
+static_assert(CCSD_EIG_MAXN == 512 && CCSD_EIG_MAX_SWEEPS == 30, "the public header states these limits in words");
+// The workspace-resident placement of k_eigvalsh: a bounded grid of workgroups, one slab each -- the size does not grow with B.
+static int eig_grid(int B, int n) { return n <= CCSD_EIG_LDS_MAXN || B < CCSD_EIG_MAX_GRID ? B : CCSD_EIG_MAX_GRID; }
+static size_t eig_slab_bytes(int B, int n) {
+    return n <= CCSD_EIG_LDS_MAXN ? 0 : (size_t)eig_grid(B, n) * n * (n | 1) * 8;
+}
+static std::string eig_too_large(const char* who, const char* what, int n) {
+    return std::string(who) + ": " + what + " = " + std::to_string(n) + " is above CCSD_EIG_MAXN = " + std::to_string(CCSD_EIG_MAXN) +
+           ": the solver is a Jacobi iteration of O(n^3) per sweep with one matrix per compute unit, which larger matrices are out of reach of";
+}
+// one launch of k_eigvalsh over matrices of order <= nmax (every argument checked by the caller)
+static int eig_launch(const double* a, int B, int nmax, long long a_stride, int lda, const int* n_arr, void* slabs, double* w, float* w32,
+                      int* sweeps, const double* edges, int bins, int* hist, void* stream) {
+    const int threads = CCSD_NTHREADS == 1 ? 1 : nmax <= 64 ? 256 : CCSD_EIG_THREADS;
+    if (nmax <= CCSD_EIG_LDS_MAXN) {
+        const size_t lds = (size_t)nmax * (nmax | 1) * 8;
+        // (the kernel's static arrays take another 18 KB: the attribute is raised as soon as the two together could pass 64 KB)
+        if (lds + 20 * 1024 > 64 * 1024) RT_CHECK(rt_set_max_dyn_smem((const void*)k_eigvalsh<true>, lds));
+        CCSD_LAUNCH(k_eigvalsh<true>, dim3(B), dim3(threads), lds, stream, a, B, nmax, a_stride, lda, n_arr, (double*)nullptr, w, w32, sweeps,
+                    edges, bins, hist);
+    } else {
+        CCSD_LAUNCH(k_eigvalsh<false>, dim3(eig_grid(B, nmax)), dim3(threads), 0, stream, a, B, nmax, a_stride, lda, n_arr, (double*)slabs, w,
+                    w32, sweeps, edges, bins, hist);
+    }
+    LAUNCH_CHECK();
+    return CCSD_OK;
+}
+
+extern "C" size_t ccsd_eig_workspace_bytes(int32_t B, int32_t n) {
+    if (B < 1 || n < 1 || n > CCSD_EIG_MAXN) {
+        set_err(CCSD_ERR_INVALID, "ccsd_eig_workspace_bytes: B must be >= 1 and n in 1.." + std::to_string(CCSD_EIG_MAXN));
+        return 0;
+    }
+    return eig_slab_bytes(B, n);
+}
+
+// ccsd_eigvalsh: the eigenvalues of B symmetric n x n fp64 matrices, ascending (k_eigvalsh; plan-free)
+extern "C" int ccsd_eigvalsh(const double* a, int32_t B, int32_t n, double* w, int32_t* sweeps, void* workspace, size_t ws_bytes,
+                             void* stream) {
+    if (!a || !w) return set_err(CCSD_ERR_INVALID, "ccsd_eigvalsh: NULL argument");
+    if (B < 1) return set_err(CCSD_ERR_INVALID, "ccsd_eigvalsh: B must be >= 1");
+    if (n < 1) return set_err(CCSD_ERR_INVALID, "ccsd_eigvalsh: n = " + std::to_string(n) + " must be >= 1");
+    if (n > CCSD_EIG_MAXN) return set_err(CCSD_ERR_UNSUPPORTED, eig_too_large("ccsd_eigvalsh", "n", n));
+    const size_t need = eig_slab_bytes(B, n);
+    if (need && (!workspace || ws_bytes < need)) return set_err(CCSD_ERR_WORKSPACE, "ccsd_eigvalsh: workspace too small");
+    if (need && ((uintptr_t)workspace & 7)) return set_err(CCSD_ERR_INVALID, "ccsd_eigvalsh: workspace must be 8-byte aligned");
+    return eig_launch(a, B, n, (long long)n * n, n, nullptr, workspace, w, nullptr, (int*)sweeps, nullptr, 0, nullptr, stream);
+}
+
+// Workspace of ccsd_spectral_hist: the fp64 Laplacians (B, N, N), the eigenvalues (B, N) when the caller does not take them, the
+// orders (B,) likewise, and the solver's slabs.
+struct SpectralWs {
+    size_t lap, eig, neff, slabs, bytes;
+};
+static SpectralWs carve_spectral(int64_t B, int64_t N) {
+    SpectralWs w;
+    size_t o = 0;
+    w.lap = o; o += (size_t)B * N * N * 8;
+    w.eig = o; o += (size_t)B * N * 8;
+    w.neff = o; o += ((size_t)B * 4 + 7) & ~(size_t)7;
+    w.slabs = o; o += eig_slab_bytes((int)B, (int)N);
+    w.bytes = o;
+    return w;
+}
+extern "C" size_t ccsd_spectral_workspace_bytes(int32_t B, int32_t N) {
+    if (B < 1 || N < 2 || N > CCSD_FIN_MAXN) {
+        set_err(CCSD_ERR_INVALID, "ccsd_spectral_workspace_bytes: B must be >= 1 and N in 2.." + std::to_string(CCSD_FIN_MAXN));
+        return 0;
+    }
+    return carve_spectral(B, N).bytes;
+}
+
+// ccsd_spectral_hist: spectral_worker (evaluation/stats.py:125-137) of every graph: k_norm_laplacian, then k_eigvalsh with the
+// histogram in its epilogue
+extern "C" int ccsd_spectral_hist(const float* adj, int32_t B, int32_t N, int32_t adj_mode, float thr, const double* edges, int32_t bins,
+                                  int32_t* hist, double* eig, int32_t* n_eff, void* workspace, size_t ws_bytes, void* stream) {
+    static_assert(CCSD_FIN_MAXN <= CCSD_EIG_MAXN, "every graph ccsd_finish takes has a Laplacian the solver takes");
+    if (!adj) return set_err(CCSD_ERR_INVALID, "ccsd_spectral_hist: NULL adj");
+    if (B < 1) return set_err(CCSD_ERR_INVALID, "ccsd_spectral_hist: B must be >= 1");
+    if (N < 2 || N > CCSD_FIN_MAXN) return set_err(CCSD_ERR_INVALID, "ccsd_spectral_hist: N = " + std::to_string(N) + " outside 2.." + std::to_string(CCSD_FIN_MAXN));
+    if (bins < 1 || bins > CCSD_CLUSTER_MAX_BINS)
+        return set_err(CCSD_ERR_INVALID, "ccsd_spectral_hist: bins = " + std::to_string(bins) + " outside 1.." + std::to_string(CCSD_CLUSTER_MAX_BINS));
+    if (adj_mode != CCSD_FINISH_ADJ_QUANTIZE && adj_mode != CCSD_FINISH_ADJ_MOL) return set_err(CCSD_ERR_INVALID, "ccsd_spectral_hist: unknown adj_mode");
+    if (!(thr >= 0.f)) return set_err(CCSD_ERR_INVALID, "ccsd_spectral_hist: thr must be >= 0");
+    if (!edges) return set_err(CCSD_ERR_INVALID, "ccsd_spectral_hist: NULL edges");
+    if (!hist && !eig && !n_eff) return CCSD_OK;
+    const SpectralWs w = carve_spectral(B, N);
+    if (!workspace || ws_bytes < w.bytes) return set_err(CCSD_ERR_WORKSPACE, "ccsd_spectral_hist: workspace too small");
+    if ((uintptr_t)workspace & 7) return set_err(CCSD_ERR_INVALID, "ccsd_spectral_hist: workspace must be 8-byte aligned");
+    char* base = (char*)workspace;
+    double* lap = (double*)(base + w.lap);
+    int* ne = n_eff ? (int*)n_eff : (int*)(base + w.neff);
+    CCSD_LAUNCH(k_norm_laplacian, dim3(B), dim3(CCSD_NTHREADS), 0, stream, adj, (int)N, adj_mode == CCSD_FINISH_ADJ_MOL ? -1.0f : thr, lap, ne);
+    LAUNCH_CHECK();
+    if (!hist && !eig) return CCSD_OK;
+    return eig_launch(lap, B, N, (long long)N * N, N, ne, base + w.slabs, eig ? eig : (double*)(base + w.eig), nullptr, nullptr, edges,
+                      hist ? (int)bins : 0, (int*)hist, stream);
+}
+
+// the number of candidate cells of sizes d_min..d_max, or -1 above 2^24 (the limit of ccsd_finish)
+static int64_t hodge_cells(int N, int d_min, int d_max) {
+    int64_t K = 0;
+    for (int s = d_min; s <= d_max; ++s) {
+        K += ccsd_comb(N, s);
+        if (K > (1 << 24)) return -1;
+    }
+    return K;
+}
+extern "C" size_t ccsd_hodge_workspace_bytes(int32_t B, int32_t N) {
+    const int64_t E = (int64_t)N * (N - 1) / 2;
+    if (B < 1 || N < 2) {
+        set_err(CCSD_ERR_INVALID, "ccsd_hodge_workspace_bytes: B must be >= 1 and N >= 2");
+        return 0;
+    }
+    if (E > CCSD_EIG_MAXN) {
+        set_err(CCSD_ERR_UNSUPPORTED, eig_too_large("ccsd_hodge_workspace_bytes", ("N = " + std::to_string(N) + ": E = N (N - 1) / 2").c_str(), (int)E));
+        return 0;
+    }
+    return (size_t)B * E * E * 8 + eig_slab_bytes(B, (int)E);
+}
+
+// ccsd_hodge_spectrum: hodge_laplacian_spectrum_worker (cc_utils.py:994-1060) of every complex: k_hodge_laplacian, then k_eigvalsh
+extern "C" int ccsd_hodge_spectrum(const float* adj, const uint64_t* cell_bits, int32_t B, int32_t N, int32_t d_min, int32_t d_max,
+                                   int32_t adj_mode, float thr, float* spectrum, int32_t* sweeps, void* workspace, size_t ws_bytes,
+                                   void* stream) {
+    if (!adj || !cell_bits || !spectrum) return set_err(CCSD_ERR_INVALID, "ccsd_hodge_spectrum: NULL argument");
+    if (B < 1) return set_err(CCSD_ERR_INVALID, "ccsd_hodge_spectrum: B must be >= 1");
+    if (N < 2) return set_err(CCSD_ERR_INVALID, "ccsd_hodge_spectrum: N = " + std::to_string(N) + " must be >= 2");
+    const int64_t E64 = (int64_t)N * (N - 1) / 2;
+    if (E64 > CCSD_EIG_MAXN)
+        return set_err(CCSD_ERR_UNSUPPORTED, eig_too_large("ccsd_hodge_spectrum", ("N = " + std::to_string(N) + ": E = N (N - 1) / 2").c_str(), (int)E64));
+    static_assert(CCSD_EIG_HODGE_MAXN * (CCSD_EIG_HODGE_MAXN - 1) / 2 <= CCSD_EIG_MAXN &&
+                  (CCSD_EIG_HODGE_MAXN + 1) * CCSD_EIG_HODGE_MAXN / 2 > CCSD_EIG_MAXN, "k_hodge_laplacian's node list holds every N with E <= CCSD_EIG_MAXN");
+    if (d_min < 1 || d_max < d_min || d_max > N)
+        return set_err(CCSD_ERR_INVALID, "ccsd_hodge_spectrum: bad cell sizes d_min = " + std::to_string(d_min) + ", d_max = " + std::to_string(d_max));
+    if (adj_mode != CCSD_FINISH_ADJ_QUANTIZE && adj_mode != CCSD_FINISH_ADJ_MOL) return set_err(CCSD_ERR_INVALID, "ccsd_hodge_spectrum: unknown adj_mode");
+    if (!(thr >= 0.f)) return set_err(CCSD_ERR_INVALID, "ccsd_hodge_spectrum: thr must be >= 0");
+    const int64_t K = hodge_cells(N, d_min, d_max);
+    if (K < 0) return set_err(CCSD_ERR_INVALID, "ccsd_hodge_spectrum: sum C(N, d) for d = d_min..d_max exceeds 2^24");
+    const int E = (int)E64;
+    const size_t hbytes = (size_t)B * E * E * 8, need = hbytes + eig_slab_bytes(B, E);
+    if (!workspace || ws_bytes < need) return set_err(CCSD_ERR_WORKSPACE, "ccsd_hodge_spectrum: workspace too small");
+    if ((uintptr_t)workspace & 7) return set_err(CCSD_ERR_INVALID, "ccsd_hodge_spectrum: workspace must be 8-byte aligned");
+    double* H = (double*)workspace;
+    RT_CHECK(rt_memset_async(H, 0, hbytes, stream));              // (k_hodge_laplacian adds onto zeros)
+    CCSD_LAUNCH(k_hodge_laplacian, dim3(B), dim3(CCSD_NTHREADS), 0, stream, adj, (const unsigned long long*)cell_bits, (int)N, (int)d_min,
+                (int)d_max, (int)K, adj_mode == CCSD_FINISH_ADJ_MOL ? -1.0f : thr, H);
+    LAUNCH_CHECK();
+    return eig_launch(H, B, E, (long long)E * E, E, nullptr, (char*)workspace + hbytes, nullptr, spectrum, (int*)sweeps, nullptr, 0, nullptr, stream);
+}

@@ -20,6 +20,8 @@
 //   ccsd_k_finish.h  k_finish_rank2, k_finish_graph: quantised outputs, cell bitmask and per-complex descriptors in one pass per tensor
 //   ccsd_k_eval.h    k_cluster_hist, k_mmd_prep, k_mmd_pairs, k_mmd_final: clustering-coefficient histograms and the fp64 MMD of two
 //                    sets of histograms (the evaluation of finished samples)
+//   ccsd_k_eig.h     k_eigvalsh, k_norm_laplacian, k_hodge_laplacian: a batched symmetric eigenvalue solver (parallel Jacobi) and the
+//                    two matrices whose spectra the reference scores (normalised graph Laplacian, hodge Laplacian F F^T)
 // The product library is built from several translation units compiled in parallel (ccsd_hip.hip: C ABI + the small kernels;
 // ccsd_r2*.hip / ccsd_xa.hip: the explicit instantiations of the two big kernel templates); the host emulation used by the
 // CPU tests includes everything in one unit.  Reference file:line citations sit next to each restated formula.
@@ -32,4 +34,5 @@
 #include "ccsd_k_update.h"
 #include "ccsd_k_finish.h"
 #include "ccsd_k_eval.h"
+#include "ccsd_k_eig.h"
 #include "ccsd_k_lg.h"

@@ -6,6 +6,7 @@ and state update is done by the HIP kernels behind include/ccsd_hip.h.
 from __future__ import annotations
 
 import ctypes as C
+import math
 from typing import List, Optional, Sequence, Tuple
 
 import numpy as np
@@ -61,7 +62,7 @@ class PCEngine:
         self.handle = handle
         self._ws: Optional[torch.Tensor] = None
         self._ws_B = 0
-        self._edges: dict = {}          # (bins, device) -> np.linspace(0, 1, bins + 1) on the device (cluster_hist)
+        self._edges: dict = {}          # (bins, device) -> np.linspace(0, 1, bins + 1) on the device (cluster_hist); ("spectral", bins, device) -> spectral_hist's
 
     def __del__(self):
         h = getattr(self, "handle", None)
@@ -419,6 +420,102 @@ class PCEngine:
                                          _lib.MMD_FP64 if s1.dtype == torch.float64 else _lib.MMD_INT32, kinds[kind], flags, float(sigma),
                                          float(distance_scaling), _ptr(ws), ws.numel() * 8, _ptr(out), self._stream()))
         return out
+
+    def _scratch(self, nbytes: int, device) -> torch.Tensor:
+        return torch.empty(max(int(nbytes), 8) // 8 + 1, dtype=torch.float64, device=device)        # (8-byte aligned)
+
+    def eigvalsh(self, a: torch.Tensor, *, sweeps: bool = False):
+        """Eigenvalues of symmetric matrices, ascending (ccsd_eigvalsh: a batched Jacobi solver; what numpy.linalg.eigvalsh gives, to
+        a small multiple of n 2^-53 ||A||_F).  a: (B, n, n) or (n, n) float64 on the device, 1 <= n <= 512; it is not modified.
+        sweeps=True also returns the (B,) int32 sweep counts (negative: the sweep cap ended the iteration).  Nothing is synchronised."""
+        single = a.dim() == 2
+        if single:
+            a = a.unsqueeze(0)
+        if a.dim() != 3 or a.shape[1] != a.shape[2]:
+            raise ValueError(f"eigvalsh: a must be (B, n, n), got {tuple(a.shape)}")
+        if a.dtype != torch.float64 or a.device.type != self.device.type:
+            raise ValueError(f"eigvalsh: a must be float64 on {self.device}, got {a.dtype} {a.device}")
+        a = a.contiguous()
+        B, n = a.shape[0], a.shape[1]
+        w = torch.empty((B, n), dtype=torch.float64, device=a.device)
+        sw = torch.empty((B,), dtype=torch.int32, device=a.device)
+        if B and n:
+            nbytes = self.lib.ccsd_eig_workspace_bytes(B, min(n, _lib.EIG_MAXN))
+            ws = self._scratch(nbytes, a.device)
+            self.lib.check(self.lib.ccsd_eigvalsh(_ptr(a), B, n, _ptr(w), _ptr(sw), _ptr(ws), ws.numel() * 8, self._stream()))
+        if single:
+            w, sw = w[0], sw[0]
+        return (w, sw) if sweeps else w
+
+    def spectral_hist(self, adj: torch.Tensor, *, mol: bool = False, thr: float = 0.5, bins: int = 200, eig: bool = False) -> dict:
+        """Histogram of the normalised Laplacian's eigenvalues per graph (ccsd_spectral_hist): spectral_worker of the reference
+        (evaluation/stats.py:125-137) on adjs_to_graphs of the quantised adjacency, with finish()'s quantiser (`mol`, `thr`; in mol
+        mode the bond orders are the edge weights).  adj (B,N,N) float32, SYMMETRIC.
+          spectral_hist (B,bins) int32   np.histogram(eigvalsh(L), bins, range=(-1e-5, 2)) -- counts; compute_mmd normalises them
+          spectral_eig (B,N) float64, spectral_n (B,) int32    the n eigenvalues ascending, then zeros                [eig]
+        Eigenvalues are clamped to [0, 2] before binning: an eigenvalue 2 of a bipartite component that a solver rounds above 2 still
+        counts in the last bin (the reference drops it).  The bin edges are np.linspace(-1e-5, 2, bins + 1), uploaded once per `bins`.
+        The call allocates its workspace, which holds every Laplacian: 8 B N^2 bytes (2 GB for 1024 graphs of N = 512) -- split a
+        large batch of large graphs into several calls."""
+        if adj.dim() != 3 or adj.shape[1] != adj.shape[2]:
+            raise ValueError(f"spectral_hist: adj must be (B, N, N), got {tuple(adj.shape)}")
+        if adj.dtype != torch.float32 or adj.device.type != self.device.type:
+            raise ValueError(f"spectral_hist: adj must be float32 on {self.device}, got {adj.dtype} {adj.device}")
+        adj = adj.contiguous()
+        B, N = adj.shape[0], adj.shape[1]
+        bins = int(bins)
+        if not 1 <= bins <= _lib.CLUSTER_MAX_BINS:
+            raise ValueError(f"spectral_hist: bins = {bins} outside 1..{_lib.CLUSTER_MAX_BINS}")
+        key = ("spectral", bins, adj.device)
+        if key not in self._edges:
+            self._edges[key] = torch.from_numpy(np.linspace(-1e-5, 2, bins + 1)).to(adj.device)
+        edges = self._edges[key]
+        res = {"spectral_hist": torch.empty((B, bins), dtype=torch.int32, device=adj.device)}
+        if eig:
+            res["spectral_eig"] = torch.empty((B, N), dtype=torch.float64, device=adj.device)
+            res["spectral_n"] = torch.empty((B,), dtype=torch.int32, device=adj.device)
+        nbytes = self.lib.ccsd_spectral_workspace_bytes(B, N)
+        if nbytes == 0:
+            self.lib.check(_lib.ERR_INVALID)
+        ws = self._scratch(nbytes, adj.device)
+        self.lib.check(self.lib.ccsd_spectral_hist(_ptr(adj), B, N, _lib.FINISH_ADJ_MOL if mol else _lib.FINISH_ADJ_QUANTIZE, float(thr),
+                                                   _ptr(edges), bins, _ptr(res["spectral_hist"]), _ptr(res.get("spectral_eig")),
+                                                   _ptr(res.get("spectral_n")), _ptr(ws), ws.numel() * 8, self._stream()))
+        return res
+
+    def hodge_spectrum(self, adj: torch.Tensor, cell_bits: torch.Tensor, *, d_min: int, d_max: int, mol: bool = False, thr: float = 0.5,
+                       sweeps: bool = False):
+        """Eigenvalues of the hodge Laplacian F F^T per complex (ccsd_hodge_spectrum): hodge_laplacian_spectrum_worker of the reference
+        (cc_utils.py:994-1060) on the complex cc_from_incidence builds from the quantised sample.  adj (B,N,N) float32 (finish()'s
+        quantiser `mol`, `thr`), cell_bits (B, ceil(K/64)) int64 = finish()'s rank2_cell_bits for the cell sizes d_min..d_max.
+        -> (B,E) float32, ascending, E = N (N - 1) / 2; exact zeros for a complex without a cell.  E > 512 raises NotImplementedError.
+        sweeps=True also returns the solver's (B,) int32 sweep counts.  The call allocates its workspace, which holds every H:
+        8 B E^2 bytes (296 MB for 1024 complexes at E = 190) -- split a large batch into several calls."""
+        if adj.dim() != 3 or adj.shape[1] != adj.shape[2]:
+            raise ValueError(f"hodge_spectrum: adj must be (B, N, N), got {tuple(adj.shape)}")
+        if adj.dtype != torch.float32 or adj.device.type != self.device.type:
+            raise ValueError(f"hodge_spectrum: adj must be float32 on {self.device}, got {adj.dtype} {adj.device}")
+        adj = adj.contiguous()
+        B, N = adj.shape[0], adj.shape[1]
+        E = N * (N - 1) // 2
+        d_min, d_max = int(d_min), int(d_max)
+        if not 1 <= d_min <= d_max <= N:
+            raise ValueError(f"hodge_spectrum: bad cell sizes d_min = {d_min}, d_max = {d_max} for N = {N}")
+        K = sum(math.comb(N, d) for d in range(d_min, d_max + 1))
+        if cell_bits.dtype != torch.int64 or cell_bits.device.type != self.device.type or tuple(cell_bits.shape) != (B, (K + 63) // 64):
+            raise ValueError(f"hodge_spectrum: cell_bits must be int64 of shape ({B}, {(K + 63) // 64}) on {self.device}, "
+                             f"got {cell_bits.dtype} {tuple(cell_bits.shape)} {cell_bits.device}")
+        cell_bits = cell_bits.contiguous()
+        nbytes = self.lib.ccsd_hodge_workspace_bytes(B, N)
+        if nbytes == 0:
+            self.lib.check(_lib.ERR_UNSUPPORTED if E > _lib.EIG_MAXN else _lib.ERR_INVALID)
+        out = torch.empty((B, E), dtype=torch.float32, device=adj.device)
+        sw = torch.empty((B,), dtype=torch.int32, device=adj.device)
+        ws = self._scratch(nbytes, adj.device)
+        self.lib.check(self.lib.ccsd_hodge_spectrum(_ptr(adj), _ptr(cell_bits), B, N, d_min, d_max,
+                                                    _lib.FINISH_ADJ_MOL if mol else _lib.FINISH_ADJ_QUANTIZE, float(thr), _ptr(out), _ptr(sw),
+                                                    _ptr(ws), ws.numel() * 8, self._stream()))
+        return (out, sw) if sweeps else out
 
 
 def cells_from_bits(bits_row, N: int, d_min: int, d_max: int):

@@ -6,12 +6,15 @@ needs no external program:
   compute_mmd with gaussian_emd / gaussian_tv / gaussian          (mmd.py:27-257)       -> PCEngine.mmd (ccsd_mmd)
   degree_stats, clustering_stats, eval_torch_batch                (stats.py:60-310, 547-570)
   rank1_distrib_stats, rank2_distrib_stats, eval_CC_batch         (cc_utils.py:1208-1474, eval_CC_list)
+  spectral_stats                                                  (stats.py:125-203)    -> PCEngine.spectral_hist (ccsd_spectral_hist)
+  hodge_laplacian_spectrum_stats                                  (cc_utils.py:994-1098) -> PCEngine.hodge_spectrum (ccsd_hodge_spectrum)
 
 The reference builds networkx graphs / toponetx complexes on the host and solves one pyemd linear program per pair of histograms.
 Here a sample set is a dict of per-sample integer DESCRIPTORS on the device -- `describe()`: the descriptor outputs of
-PCEngine.finish plus `cluster_hist` -- and every score is one ccsd_mmd call on them.  There is no CPU fallback: methods that need an
-external program or a solver this build does not have raise NotImplementedError (UNSUPPORTED); their histograms, computed elsewhere,
-can still be scored through compute_mmd.
+PCEngine.finish plus `cluster_hist` -- and every score is one ccsd_mmd call on them.  The two spectral scores need an eigenvalue
+solver (ccsd_eigvalsh, a batched Jacobi iteration on the device) and cost O(N^3) per sample where the others cost O(N^2): they are
+opt-in, `spectra=True`.  There is no CPU fallback: methods that need an external program raise NotImplementedError (UNSUPPORTED);
+their histograms, computed elsewhere, can still be scored through compute_mmd.
 """
 from __future__ import annotations
 
@@ -43,8 +46,8 @@ gaussian = KernelSelector("gaussian", "l2")
 
 UNSUPPORTED = {
     "orbit": "orbit counts come from the external orca program (evaluation/stats.py:343-379)",
-    "spectral": "needs a symmetric eigenvalue solver on the device (evaluation/stats.py:125-137): not part of this build yet",
-    "hodge_laplacian_spectrum": "needs a symmetric eigenvalue solver on the device (cc_utils.py:994-1060): not part of this build yet",
+    "spectral": "runs a symmetric eigenvalue solver per graph (evaluation/stats.py:125-137) and is opt-in: pass spectra=True",
+    "hodge_laplacian_spectrum": "runs a symmetric eigenvalue solver per complex (cc_utils.py:994-1060) and is opt-in: pass spectra=True",
     "nspdk": "needs the EDeN graph vectoriser (evaluation/eden.py, mmd.py:331-337)",
     "rank0_distrib": "the node label it histograms is data-set specific (cc_utils.py:1098-1205)",
 }
@@ -123,15 +126,21 @@ def compute_mmd(samples1, samples2, kernel: KernelSelector = gaussian_emd, is_hi
 # descriptors
 # ---------------------------------------------------------------------------------------------
 def describe(adj: torch.Tensor, x: Optional[torch.Tensor] = None, rank2: Optional[torch.Tensor] = None, *, mol: bool = False,
-             thr: float = 0.5, bins: int = 100, d_min: int = 0, d_max: int = 0, device=None, lib=None) -> Dict[str, torch.Tensor]:
+             thr: float = 0.5, bins: int = 100, d_min: int = 0, d_max: int = 0, spectra: bool = False, device=None,
+             lib=None) -> Dict[str, torch.Tensor]:
     """The descriptor dict of a batch: PCEngine.finish's descriptors (degree, degree_hist, edge_hist; n_nodes, x_hist with x;
     rank2_cell_bits / _count / _hist, rank2_nnz with rank2) plus cluster_hist (B, bins) and tri2 (B, N).  adj: (B, N, N), raw samples,
-    quantised samples or a 0/1 data set (any real or integer dtype)."""
+    quantised samples or a 0/1 data set (any real or integer dtype).  spectra=True adds spectral_hist (B, 200) int32 and, with rank2,
+    hodge_spectrum (B, E) float32 (PCEngine.spectral_hist / hodge_spectrum: an eigenvalue solve per sample)."""
     eng = _engine(device if device is not None else (adj.device if adj.device.type == "cuda" else None), lib)
     mv = lambda t: None if t is None else t.to(device=eng.device, dtype=torch.float32).contiguous()
     adj, x, rank2 = mv(adj), mv(x), mv(rank2)
     out = eng.finish(x, adj, rank2, None, mol=mol, thr=thr, d_min=d_min, d_max=d_max, dense_rank2=False, dense_adj=False)
     out.update(eng.cluster_hist(adj, mol=mol, thr=thr, bins=bins))
+    if spectra:
+        out.update(eng.spectral_hist(adj, mol=mol, thr=thr))
+        if rank2 is not None:
+            out["hodge_spectrum"] = eng.hodge_spectrum(adj, out["rank2_cell_bits"], d_min=d_min, d_max=d_max, mol=mol, thr=thr)
     return out
 
 
@@ -163,6 +172,33 @@ def clustering_stats(ref, pred, kernel: KernelSelector = gaussian_emd, bins: int
             raise ValueError(f"clustering_stats: cluster_hist has {d['cluster_hist'].shape[1]} bins, not {bins}")
     return compute_mmd(a["cluster_hist"], b["cluster_hist"], kernel, sigma=1.0 / 10,
                        distance_scaling=bins if kernel is gaussian_emd else 1.0, **_dev_kw(kw))
+
+
+SPECTRAL_BINS = 200          # spectral_worker's np.histogram(eigs, bins=200, range=(-1e-5, 2)) (stats.py:135)
+
+
+def _spectral_rows(obj, kw) -> torch.Tensor:
+    """spectral_hist of a side: taken from a descriptor dict that has it, computed from its `adj` (or from a raw batch) otherwise."""
+    if isinstance(obj, dict) and "spectral_hist" in obj:
+        return obj["spectral_hist"]
+    if isinstance(obj, dict) and "adj" not in obj:
+        raise KeyError("descriptor dict lacks spectral_hist and the adj to compute it from; describe(..., spectra=True) produces it")
+    adj = obj["adj"] if isinstance(obj, dict) else torch.as_tensor(obj)
+    eng = _engine(kw.get("device") if kw.get("device") is not None else (adj.device if adj.device.type == "cuda" else None), kw.get("lib"))
+    adj = adj.to(device=eng.device, dtype=torch.float32).contiguous()
+    return eng.spectral_hist(adj, mol=kw.get("mol", False), thr=kw.get("thr", 0.5))["spectral_hist"]
+
+
+def spectral_stats(ref, pred, kernel: KernelSelector = gaussian_emd, **kw) -> float:
+    """spectral_stats (stats.py:140-203): MMD of the 200-bin histograms of the normalised Laplacian's eigenvalues, sigma = 1 and no
+    distance scaling.  ref / pred: adjacency batches or descriptor dicts (spectral_hist, or adj to compute it from).  The graphs of
+    adjs_to_graphs hold at least one node, so no predicted graph is dropped.  Eigenvalues are clamped to [0, 2] before binning
+    (PCEngine.spectral_hist): the one deliberate difference from the reference."""
+    a, b = _spectral_rows(ref, kw), _spectral_rows(pred, kw)
+    for h in (a, b):
+        if h.shape[1] != SPECTRAL_BINS:
+            raise ValueError(f"spectral_stats: spectral_hist has {h.shape[1]} bins, not {SPECTRAL_BINS}")
+    return compute_mmd(a, b, kernel, **_dev_kw(kw))
 
 
 def _cc_keep(desc: Dict[str, torch.Tensor], n: Optional[int], drop_empty: bool) -> torch.Tensor:
@@ -201,42 +237,91 @@ def rank2_distrib_stats(ref_desc, pred_desc, worker_kwargs=None, kernel: KernelS
     return compute_mmd(sets[0], sets[1], kernel, f32_pmf=True, **_dev_kw(kw))        # (the worker's histograms are float32)
 
 
+def _hodge_rows(desc, worker_kwargs, kw) -> torch.Tensor:
+    """hodge_spectrum of a descriptor dict: taken from it, or computed from its `adj` and `rank2_cell_bits` (the cell sizes
+    d_min..d_max come from worker_kwargs, as in the reference)."""
+    if "hodge_spectrum" in desc:
+        return desc["hodge_spectrum"]
+    missing = [k for k in ("adj", "rank2_cell_bits") if k not in desc]
+    if missing:
+        raise KeyError(f"descriptor dict lacks hodge_spectrum and {missing} to compute it from; describe(..., spectra=True) produces it")
+    adj = desc["adj"]
+    eng = _engine(kw.get("device") if kw.get("device") is not None else (adj.device if adj.device.type == "cuda" else None), kw.get("lib"))
+    adj = adj.to(device=eng.device, dtype=torch.float32).contiguous()
+    if "N" in worker_kwargs and int(worker_kwargs["N"]) != adj.shape[1]:
+        raise ValueError(f"hodge_laplacian_spectrum_stats: worker_kwargs N = {worker_kwargs['N']} but adj has {adj.shape[1]} nodes")
+    return eng.hodge_spectrum(adj, desc["rank2_cell_bits"].to(eng.device), d_min=int(worker_kwargs["d_min"]), d_max=int(worker_kwargs["d_max"]),
+                              mol=kw.get("mol", False), thr=kw.get("thr", 0.5))
+
+
+def hodge_laplacian_spectrum_stats(ref_desc, pred_desc, worker_kwargs, kernel: KernelSelector = gaussian_emd,
+                                   cc_nb_eval: Optional[int] = None, **kw) -> float:
+    """hodge_laplacian_spectrum_stats (cc_utils.py:1025-1098): MMD of the float32 eigenvalue vectors of F F^T (length E; zeros for a
+    complex without rank-2 cells), each normalised by its sum like a histogram (compute_mmd's is_hist default).  The descriptor dicts
+    hold hodge_spectrum, or adj and rank2_cell_bits to compute it from (worker_kwargs: d_min, d_max)."""
+    sets = [_hodge_rows(desc, worker_kwargs, kw).index_select(0, _cc_keep(desc, cc_nb_eval, drop))
+            for desc, drop in ((ref_desc, False), (pred_desc, True))]
+    return compute_mmd(sets[0], sets[1], kernel, **_dev_kw(kw))                      # (float32 rows: the f32_pmf path)
+
+
 METHOD_NAME_TO_FUNC = {"degree": degree_stats, "cluster": clustering_stats}
 CC_METHOD_NAME_TO_FUNC = {"rank1_distrib": rank1_distrib_stats, "rank2_distrib": rank2_distrib_stats}
+# the methods that run the eigenvalue solver: accepted only with spectra=True
+SPECTRA_METHOD_NAME_TO_FUNC = {"spectral": spectral_stats}
+SPECTRA_CC_METHOD_NAME_TO_FUNC = {"hodge_laplacian_spectrum": hodge_laplacian_spectrum_stats}
 
 
-def _check_methods(methods, table):
+def _check_methods(methods, table, spectra=False):
     for m in methods:
-        if m in UNSUPPORTED:
+        if m in table:
+            continue
+        opted_in = spectra and (m in SPECTRA_METHOD_NAME_TO_FUNC or m in SPECTRA_CC_METHOD_NAME_TO_FUNC)      # (the other evaluator's method)
+        if m in UNSUPPORTED and not opted_in:
             raise NotImplementedError(f"evaluation method {m!r}: {UNSUPPORTED[m]}")
-        if m not in table:
-            raise KeyError(f"unknown evaluation method {m!r}; available: {sorted(table)}")
+        raise KeyError(f"unknown evaluation method {m!r}; available: {sorted(table)}")
 
 
 def eval_torch_batch(ref_batch, pred_batch, methods: Optional[Sequence[str]] = None, kernels: Optional[dict] = None, *,
-                     mol: bool = False, thr: float = 0.5, bins: int = 100, **kw) -> Dict[str, float]:
+                     mol: bool = False, thr: float = 0.5, bins: int = 100, spectra: bool = False, **kw) -> Dict[str, float]:
     """eval_torch_batch / eval_graph_list (stats.py:480-570): {method: round(score, 6)}.  ref_batch / pred_batch: adjacency batches
     (B, N, N) or descriptor dicts.  Default methods: "degree", "cluster" -- the reference's third default, "orbit", needs the orca
-    program and has to be asked for by name to get its NotImplementedError.  Default kernel: gaussian_emd for both."""
+    program and has to be asked for by name to get its NotImplementedError.  Default kernel: gaussian_emd for both.
+    spectra=True also accepts "spectral" in `methods` (it is never a default) and computes spectral_hist for a side given as a raw
+    batch; without it the name raises NotImplementedError."""
     methods = ["degree", "cluster"] if methods is None else list(methods)
-    _check_methods(methods, METHOD_NAME_TO_FUNC)
+    table = dict(METHOD_NAME_TO_FUNC, **SPECTRA_METHOD_NAME_TO_FUNC) if spectra else METHOD_NAME_TO_FUNC
+    _check_methods(methods, table, spectra)
     kernels = kernels or {}
+    want_spec = "spectral" in methods
     dkw = dict(mol=mol, thr=thr, bins=bins, **_dev_kw(kw))
-    ref = _descriptors(ref_batch, ["degree_hist", "cluster_hist"], **dkw)
-    pred = _descriptors(pred_batch, ["degree_hist", "cluster_hist"], **dkw)
+    need = ["degree_hist", "cluster_hist"] + (["spectral_hist"] if want_spec else [])
+    sides = []
+    for obj in (ref_batch, pred_batch):
+        if isinstance(obj, dict) and want_spec and "spectral_hist" not in obj and "adj" in obj:
+            obj = dict(obj, spectral_hist=_spectral_rows(obj, dict(mol=mol, thr=thr, **_dev_kw(kw))))
+        sides.append(_descriptors(obj, need, **dkw, **({"spectra": True} if want_spec else {})))
+    ref, pred = sides
     out = {}
     for m in methods:
         extra = {"bins": bins} if m == "cluster" else {}
-        out[m] = round(METHOD_NAME_TO_FUNC[m](ref, pred, kernels.get(m, gaussian_emd), **extra, **_dev_kw(kw)), 6)
+        out[m] = round(table[m](ref, pred, kernels.get(m, gaussian_emd), **extra, **_dev_kw(kw)), 6)
     return out
 
 
 def eval_CC_batch(ref_desc, pred_desc, worker_kwargs, methods: Optional[Sequence[str]] = None, kernels: Optional[dict] = None,
-                  cc_nb_eval: Optional[int] = 1000, **kw) -> Dict[str, float]:
+                  cc_nb_eval: Optional[int] = 1000, *, spectra: bool = False, mol: bool = False, thr: float = 0.5, **kw) -> Dict[str, float]:
     """eval_CC_list (cc_utils.py:1418-1474) on descriptor dicts: {method: round(score, 6)}.  Default methods: "rank1_distrib",
-    "rank2_distrib" (the reference's other two defaults raise NotImplementedError when asked for, see UNSUPPORTED)."""
+    "rank2_distrib" (the reference's other two defaults raise NotImplementedError when asked for, see UNSUPPORTED).
+    spectra=True also accepts "hodge_laplacian_spectrum" in `methods` (it is never a default): a side without hodge_spectrum has it
+    computed from its adj and rank2_cell_bits with the quantiser `mol`, `thr` and worker_kwargs' d_min, d_max.  Without spectra=True
+    the name raises NotImplementedError."""
     methods = ["rank1_distrib", "rank2_distrib"] if methods is None else list(methods)
-    _check_methods(methods, CC_METHOD_NAME_TO_FUNC)
+    table = dict(CC_METHOD_NAME_TO_FUNC, **SPECTRA_CC_METHOD_NAME_TO_FUNC) if spectra else CC_METHOD_NAME_TO_FUNC
+    _check_methods(methods, table, spectra)
     kernels = kernels or {}
-    return {m: round(CC_METHOD_NAME_TO_FUNC[m](ref_desc, pred_desc, worker_kwargs, kernels.get(m, gaussian_emd), cc_nb_eval=cc_nb_eval,
-                                               **_dev_kw(kw)), 6) for m in methods}
+    out = {}
+    for m in methods:
+        extra = dict(mol=mol, thr=thr) if m in SPECTRA_CC_METHOD_NAME_TO_FUNC else {}
+        out[m] = round(table[m](ref_desc, pred_desc, worker_kwargs, kernels.get(m, gaussian_emd), cc_nb_eval=cc_nb_eval, **extra,
+                                **_dev_kw(kw)), 6)
+    return out

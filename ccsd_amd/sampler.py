@@ -354,14 +354,16 @@ class Sampler:
 
 
     def evaluate(self, result, ref, methods: Optional[List[str]] = None, cc_methods: Optional[List[str]] = None, bins: int = 100,
-                 cc_nb_eval: Optional[int] = 1000) -> Dict[str, float]:
+                 cc_nb_eval: Optional[int] = 1000, spectra: bool = False) -> Dict[str, float]:
         """Score a finished run against a held-out set on the GPU (ccsd_amd/evaluation.py): what the reference prints after
         sampling from eval_graph_list and eval_CC_list (sampler.py:253-262, 565-583), for the methods this build computes.
         `result`: what sample() returned.  `ref`: an adjacency batch (B, N, N) of the held-out graphs, a descriptor dict
         (evaluation.describe), or the path of an .npz that sample(save=True) wrote.  Returns {method: round(score, 6)}: "degree" and
         "cluster" and, for combinatorial complexes whose two sides hold the descriptors, "rank1_distrib" and "rank2_distrib"
         (data.min_edge_val / data.max_edge_val of the config; default 1..3 for molecules, 1..1 otherwise).  sample() itself is
-        untouched: nothing here runs unless it is called.  In a sharded run every rank holds the gathered samples and rank 0 alone
+        untouched: nothing here runs unless it is called.  spectra=True adds the two scores that run an eigenvalue solver per
+        sample: "spectral" and, for combinatorial complexes, "hodge_laplacian_spectrum" -- both computed from `adj` and
+        `rank2_cell_bits`, so results of sample(dense_rank2=False) and saved .npz files serve as well.  In a sharded run every rank holds the gathered samples and rank 0 alone
         evaluates; the other ranks return {}."""
         from . import evaluation as ev
 
@@ -370,7 +372,8 @@ class Sampler:
         lib = self.extra.get("lib")
         kw = dict(device=self.device0, lib=lib)
 
-        keep = ("adj", "degree_hist", "edge_hist", "n_nodes", "rank2_cell_hist", "cluster_hist")
+        keep = ("adj", "degree_hist", "edge_hist", "n_nodes", "rank2_cell_hist", "cluster_hist") + (
+            ("rank2_cell_bits", "spectral_hist", "hodge_spectrum") if spectra else ())
 
         def side(obj):
             if isinstance(obj, (str, os.PathLike)):
@@ -386,12 +389,20 @@ class Sampler:
             return ev.describe(torch.as_tensor(obj), mol=self.is_mol, bins=bins, **kw)
 
         pred, held = side(result), side(ref)
-        out = ev.eval_torch_batch(held, pred, methods, bins=bins, **kw)
+        if spectra and methods is None:
+            methods = ["degree", "cluster", "spectral"]
+        out = ev.eval_torch_batch(held, pred, methods, bins=bins, mol=self.is_mol, spectra=spectra, **kw)
         if self.is_cc:
             data = _get(self.config, "data")
             wk = {"min_edge_val": _get(data, "min_edge_val", 1), "max_edge_val": _get(data, "max_edge_val", 3 if self.is_mol else 1)}
             have = ["rank1_distrib"] + (["rank2_distrib"] if "rank2_cell_hist" in pred and "rank2_cell_hist" in held else [])
-            out.update(ev.eval_CC_batch(held, pred, wk, have if cc_methods is None else cc_methods, cc_nb_eval=cc_nb_eval, **kw))
+            if spectra:
+                datat = _get(self.configt, "data")                   # (the cell sizes sample() hands to finish())
+                wk.update(d_min=_get(data, "d_min") or _get(datat, "d_min") or 0, d_max=_get(data, "d_max") or _get(datat, "d_max") or 0)
+                if all("hodge_spectrum" in d or ("adj" in d and "rank2_cell_bits" in d) for d in (pred, held)):
+                    have.append("hodge_laplacian_spectrum")
+            out.update(ev.eval_CC_batch(held, pred, wk, have if cc_methods is None else cc_methods, cc_nb_eval=cc_nb_eval, spectra=spectra,
+                                        mol=self.is_mol, **kw))
         return out
 
 

@@ -39,6 +39,12 @@
  * ccsd_mmd                     compute_mmd with gaussian_emd / gaussian_tv / gaussian: the scores of degree_stats, clustering_stats,
  *                              rank1_distrib_stats, rank2_distrib_stats (evaluation/mmd.py:27-257; evaluation/stats.py:60-310;
  *                              cc_utils.py:1235-1406); ccsd_mmd_workspace_bytes sizes its workspace
+ * ccsd_eigvalsh                the eigenvalues of many small dense symmetric fp64 matrices (what scipy.linalg.eigvalsh /
+ *                              torch.linalg.eigvalsh are called for in the two workers below); ccsd_eig_workspace_bytes sizes its workspace
+ * ccsd_spectral_hist           spectral_worker: the histogram of the normalised Laplacian's eigenvalues per graph
+ *                              (evaluation/stats.py:125-137); ccsd_spectral_workspace_bytes sizes its workspace
+ * ccsd_hodge_spectrum          hodge_laplacian_spectrum_worker: the eigenvalues of F F^T of the complex's rank-1 / rank-2 incidence
+ *                              matrix (cc_utils.py:994-1060); ccsd_hodge_workspace_bytes sizes its workspace
  */
 #ifndef CCSD_HIP_H
 #define CCSD_HIP_H
@@ -352,6 +358,56 @@ size_t ccsd_mmd_workspace_bytes(int32_t n1, int32_t n2, int32_t L);
 int ccsd_mmd(const void* h1_dev, int32_t n1, const int32_t* lens1_dev, const void* h2_dev, int32_t n2, const int32_t* lens2_dev, int32_t L,
              int32_t dtype, int32_t kind, int32_t flags, double sigma, double distance_scaling, void* workspace_dev, size_t ws_bytes,
              double* out_dev, void* stream);
+
+/* The eigenvalues of B symmetric n x n fp64 matrices a_dev (B,n,n), 1 <= n <= CCSD_EIG_MAXN, ascending into w_dev (B,n): a parallel
+ * cyclic two-sided Jacobi iteration, one workgroup per matrix, eigenvalues only.  a_dev is not modified; only its upper triangle
+ * decides the rotations, a SYMMETRIC matrix is the contract.  The eigenvalues agree with LAPACK's to a small multiple of
+ * n 2^-53 ||A||_F each; two calls give the same bits.
+ * sweeps_dev (B,) int32, nullable: the sweeps used (0 for a diagonal matrix), or -30 when the compile-time cap of 30 sweeps ended
+ * the iteration (not seen on any input; a converging matrix takes 5 to 9).
+ * Up to n = 128 the matrix lives in LDS and no workspace is needed (ccsd_eig_workspace_bytes returns 0, workspace_dev may be NULL).
+ * Above, it lives in a slab of workspace_dev, one slab per workgroup of a bounded grid that walks the batch:
+ * ccsd_eig_workspace_bytes(B, n) = min(B, 256) n (n | 1) 8 bytes, 8-byte aligned.
+ * n > CCSD_EIG_MAXN returns CCSD_ERR_UNSUPPORTED with the reason (O(n^3) per sweep on one compute unit), other bad dimensions CCSD_ERR_INVALID.
+ * Range: the stopping test squares the entries without scaling, so ||A||_F^2 has to be a normal fp64 number -- entries between about
+ * 1e-150 and 1e+150 in magnitude, zeros aside; outside that range the diagonal comes back unsolved with sweeps = 0.  Scale first. */
+#define CCSD_EIG_MAXN 512
+size_t ccsd_eig_workspace_bytes(int32_t B, int32_t n);
+int ccsd_eigvalsh(const double* a_dev, int32_t B, int32_t n, double* w_dev, int32_t* sweeps_dev, void* workspace_dev, size_t ws_bytes,
+                  void* stream);
+
+/* spectral_worker (evaluation/stats.py:125-137) of every graph of adj_dev (B,N,N), 2 <= N <= 512, with the quantiser of ccsd_finish
+ * (adj_mode, thr; the diagonal is ignored, row i alone is read for node i: adj must be SYMMETRIC).  Per graph: the weights are the
+ * quantised entries (0/1, or bond orders 1..3 in CCSD_FINISH_ADJ_MOL mode), nodes without an edge are removed, a graph without any
+ * edge is one node; L = I - D^-1/2 A D^-1/2 in fp64; its n_eff eigenvalues; np.histogram(eigenvalues, bins, range=(edges[0], edges[bins])).
+ * edges_dev: bins + 1 doubles, the host's np.linspace(-1e-5, 2, bins + 1) (the reference: bins = 200; 1 <= bins <= 1024): an
+ * eigenvalue goes to the largest bin i with edges[i] <= v, the last bin closed, as np.histogram places it.
+ * ONE deliberate difference from the reference: every eigenvalue is clamped to [0, edges[bins]] before it is binned.  [0, 2] is the
+ * exact range of this spectrum, a bipartite component has the eigenvalue 2 exactly, and LAPACK returns it as 2 - 2e-16, 2.0 or
+ * 2 + 4e-16 depending on the graph; np.histogram drops the last of these.  Here the eigenvalue always counts in the last bin.
+ * hist_dev (B,bins) int32 counts; eig_dev (B,N) fp64: the n_eff eigenvalues ascending, the rest zero; n_eff_dev (B,) int32.  Each nullable.
+ * workspace_dev: at least ccsd_spectral_workspace_bytes(B, N) bytes, 8-byte aligned.  It holds every Laplacian of the batch, so it GROWS
+ * with B: 8 B N^2 bytes plus the solver's slabs -- 16 MB for 1024 graphs of N = 45, 2 GB for 1024 graphs of N = 512.  Split a large
+ * batch into several calls to bound it; the rows of the outputs are independent. */
+size_t ccsd_spectral_workspace_bytes(int32_t B, int32_t N);
+int ccsd_spectral_hist(const float* adj_dev, int32_t B, int32_t N, int32_t adj_mode, float thr, const double* edges_dev, int32_t bins,
+                       int32_t* hist_dev, double* eig_dev, int32_t* n_eff_dev, void* workspace_dev, size_t ws_bytes, void* stream);
+
+/* hodge_laplacian_spectrum_worker (cc_utils.py:994-1060) of every complex: the eigenvalues of H = F F^T, where F (E,K) is the incidence
+ * matrix CC_to_incidence_matrices returns for the complex cc_from_incidence builds from the quantised sample: F[e][k] = 1 iff cell k
+ * is present (bit k of cell_bits_dev (B, ceil(K/64)), as ccsd_finish / ccsd_rank2_cells write it; K = sum of C(N, d), d = d_min..d_max, in
+ * get_cells order), both nodes of edge e lie in cell k, and edge e is in the quantised adjacency (adj_dev (B,N,N) with the quantiser of
+ * ccsd_finish; symmetric).  H is built in exact integer arithmetic, solved in fp64, and rounded to fp32 once:
+ * spectrum_dev (B,E) float32, ascending, E = N (N - 1) / 2; a complex without a cell gives exact zeros.  sweeps_dev (B,) int32, nullable: as ccsd_eigvalsh.
+ * workspace_dev: at least ccsd_hodge_workspace_bytes(B, N) bytes, 8-byte aligned.  It holds every H of the batch, so it GROWS with B:
+ * 8 B E^2 bytes plus the solver's slabs -- 296 MB for 1024 complexes at E = 190, 2 GB at E = 496.  Split a large batch into several
+ * calls to bound it; the rows of the output are independent.
+ * E > CCSD_EIG_MAXN (N > 32) returns CCSD_ERR_UNSUPPORTED with the reason (ccsd_hodge_workspace_bytes then returns 0): the E = 703 and
+ * E = 1176 complexes are out of reach of a Jacobi iteration on one compute unit. */
+size_t ccsd_hodge_workspace_bytes(int32_t B, int32_t N);
+int ccsd_hodge_spectrum(const float* adj_dev, const uint64_t* cell_bits_dev, int32_t B, int32_t N, int32_t d_min, int32_t d_max,
+                        int32_t adj_mode, float thr, float* spectrum_dev, int32_t* sweeps_dev, void* workspace_dev, size_t ws_bytes,
+                        void* stream);
 
 /* Measurement hooks (bench.py): time every launch of selected kernels with HIP events on the launch stream.
  * kernel_id: 0 k_xa, 1 k_gemm_p, 2 k_hf_score, 3 k_gemm_h, 4 k_langevin_apply, 5 k_r2, 6 k_s4_apply, 7 k_ew1; each call adds one kernel to the

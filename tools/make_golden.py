@@ -762,6 +762,306 @@ def e1_eval():
           meta["lp_vs_closed_kernel"], "(kernel)", meta["lp_vs_closed_score"], "(score)")
 
 
+# ---------------------------------------------------------------------------------------------
+# e2_spectrum.npz: the reference's two spectral evaluators on small sets (`python tools/make_golden.py spectrum`)
+# ---------------------------------------------------------------------------------------------
+class _StandInComplex:
+    """toponetx's CombinatorialComplex as far as cc_from_incidence, CC_to_incidence_matrices, is_empty_cc and the workers of
+    eval_CC_list use it: add_cell(cell, rank, **attributes) files the attributes under cells.hyperedge_dict[rank][frozenset(cell)].
+    (Whether toponetx adds the nodes of a higher cell that were never added as rank-0 cells does not matter here: every set below keeps
+    the nodes of its edges and cells among its rank-0 cells, which are the first n indices -- what masked samples look like.)"""
+
+    def __init__(self):
+        import types
+
+        self.cells = types.SimpleNamespace(hyperedge_dict={})
+
+    def add_cell(self, cell, rank, **attr):
+        self.cells.hyperedge_dict.setdefault(rank, {})[frozenset(cell)] = attr
+
+    def number_of_cells(self):
+        return sum(len(v) for v in self.cells.hyperedge_dict.values())
+
+
+def e2_graph_sets():
+    """name -> (adjacency (B, N, N) int8, mol, exact): `exact` sets are compared count by count (no bipartite component, margin checked)."""
+    e1 = e1_graph_sets()
+    sets = {k: (e1[k][0], e1[k][1], True) for k in ("mol9", "r65", "diag12")}
+
+    def sym(rng, B, N, p, masked=0):
+        a = np.zeros((B, N, N), np.int8)
+        for b in range(B):
+            n = N - masked * b
+            u = np.triu((rng.random((n, n)) < p), 1)
+            a[b, :n, :n] = u
+            a[b] = a[b] + a[b].T
+        return a
+
+    # (seeds: the first of 0, 1, 2, ... whose set passes the margin and bipartite checks of e2_spectrum, searched there)
+    sets["n125"] = (lambda rng: sym(rng, 2, 125, 0.08, masked=9), False, True)
+    sets["s12a"] = (lambda rng: sym(rng, 4, 12, 0.4, masked=1), False, True)
+    sets["s12b"] = (lambda rng: sym(rng, 3, 12, 0.6, masked=2), False, True)
+    # bipartite landmarks (eigenvalue 2 exactly): path, even cycle, star, 3 x 4 grid, and a path beside a cycle (two components)
+    N = 12
+    bip = np.zeros((5, N, N), np.int8)
+
+    def edge(b, i, j):
+        bip[b, i, j] = bip[b, j, i] = 1
+
+    for i in range(5):
+        edge(0, i, i + 1)
+    for i in range(8):
+        edge(1, i, (i + 1) % 8)
+    for i in range(1, 7):
+        edge(2, 0, i)
+    for r in range(3):
+        for c in range(4):
+            if c < 3:
+                edge(3, 4 * r + c, 4 * r + c + 1)
+            if r < 2:
+                edge(3, 4 * r + c, 4 * r + c + 4)
+    for i in range(3):
+        edge(4, i, i + 1)
+    for i in range(6):
+        edge(4, 4 + i, 4 + (i + 1) % 6)
+    sets["bip"] = (bip, False, False)
+    return sets
+
+
+def e2_complex_sets():
+    """name -> (N, d_min, d_max, node counts of the ref side, of the pred side, seed)."""
+    return {"e10": (5, 3, 4, [5, 4, 5], [5, 3], 1), "e36": (9, 3, 5, [9, 8, 7], [9, 6, 9], 2), "e66": (12, 3, 4, [12, 10], [11, 12], 3),
+            "e190": (20, 3, 3, [20, 17], [18, 20], 4)}
+
+
+def e2_spectrum():
+    """e2_spectrum.npz: spectral_worker / spectral_stats / eval_graph_list on graph sets and hodge_laplacian_spectrum_worker /
+    hodge_laplacian_spectrum_stats / eval_CC_list on complex sets, from the reference itself (networkx, scipy, torch on the host;
+    gaussian_emd on the stand-in pyemd, the complexes on _StandInComplex)."""
+    import threading
+    import time
+    from itertools import combinations
+
+    import networkx as nx
+    from scipy.linalg import eigvalsh as sp_eigvalsh
+
+    record = {"tl": threading.local()}
+    stand_in = _pyemd_stand_in(record)
+    raw_emd, memo, lock = stand_in.emd, {}, threading.Lock()
+
+    def emd(x, y, D, extra_mass_penalty=-1.0):       # (the same pair of rows comes back in eval_*_list: one program per pair)
+        key = (getattr(record["tl"], "mode", "lp"), np.asarray(x).tobytes(), np.asarray(y).tobytes(), float(np.asarray(D).max()))
+        with lock:
+            if key in memo:
+                return memo[key]
+        v = raw_emd(x, y, D, extra_mass_penalty)
+        with lock:
+            memo[key] = v
+        return v
+
+    stand_in.emd = emd
+    sys.modules["pyemd"] = stand_in
+    from ccsd.src.evaluation import mmd as ref_mmd
+    from ccsd.src.evaluation import stats as ref_stats
+
+    ref_mmd.pyemd = stand_in
+    ref_cc.CombinatorialComplex = _StandInComplex
+    t0 = time.time()
+    out = {}
+    meta = {"graph_sets": {}, "complex_sets": {}, "scores": {}, "lp_vs_closed": {}, "f32_vs_f64": {}, "lp_vs_closed_kernel": 0.0}
+
+    def k_closed(x, y, **kw):
+        record["tl"].mode = "closed"
+        try:
+            return ref_mmd.gaussian_emd(x, y, **kw)
+        finally:
+            record["tl"].mode = "lp"
+
+    def k_emd(x, y, **kw):
+        kc = k_closed(x, y, **kw)
+        kl = ref_mmd.gaussian_emd(x, y, **kw)
+        meta["lp_vs_closed_kernel"] = max(meta["lp_vs_closed_kernel"], abs(float(kl) - float(kc)))
+        return kl
+
+    def emd_score(fn, tag):
+        before, meta["lp_vs_closed_kernel"] = meta["lp_vs_closed_kernel"], 0.0
+        lp = float(fn(k_emd))
+        meta["lp_vs_closed"][tag] = meta["lp_vs_closed_kernel"]
+        meta["lp_vs_closed_kernel"] = max(before, meta["lp_vs_closed_kernel"])
+        return lp
+
+    # ---- graphs
+    BINS, RANGE = 200, (-1e-5, 2)
+    interior = np.linspace(RANGE[0], RANGE[1], BINS + 1)[1:-1]
+
+    def restated(adj, mol):
+        """(counts, eigenvalues, n_eff) per graph in float64 with the clamp to [0, 2]: the definition of include/ccsd_hip.h."""
+        cs, es, ns = [], [], []
+        for a in adj:
+            w = a.astype(np.float64) * (1 - np.eye(len(a)))
+            if not mol:
+                w = (w != 0).astype(np.float64)
+            keep = w.sum(1) > 0
+            w = w[keep][:, keep]
+            if not keep.any():
+                ev_ = np.zeros(1)
+            else:
+                d = w.sum(1)
+                ev_ = np.linalg.eigvalsh(np.eye(len(d)) - w / np.sqrt(d[:, None] * d[None, :]))
+            ev_ = np.clip(ev_, 0.0, 2.0)
+            cs.append(np.histogram(ev_, bins=BINS, range=RANGE)[0])
+            es.append(np.pad(ev_, (0, len(a) - len(ev_))))
+            ns.append(len(ev_))
+        return np.stack(cs).astype(np.int32), np.stack(es), np.array(ns, np.int32)
+
+    def reference_graphs(adj, mol):
+        q = ref_gu.quantize_mol(torch.as_tensor(adj, dtype=torch.float32)) if mol else ref_gu.quantize(torch.as_tensor(adj, dtype=torch.float32)).numpy()
+        return ref_gu.adjs_to_graphs(np.asarray(q, np.float32))
+
+    def reference_spectra(G, N):
+        counts, eigs, n_eff = [], [], []
+        for g in G:
+            e = sp_eigvalsh(nx.normalized_laplacian_matrix(g).todense())           # spectral_worker's own first line
+            c = np.histogram(e, bins=BINS, range=RANGE, density=False)[0]
+            pmf = ref_stats.spectral_worker(g)
+            assert np.array_equal(pmf, c / c.sum())
+            counts.append(c)
+            eigs.append(np.pad(e, (0, N - len(e))))
+            n_eff.append(len(e))
+        return np.stack(counts).astype(np.int32), np.stack(eigs), np.array(n_eff, np.int32)
+
+    def margin_ok(G, eigs, n_eff):
+        gap = min(np.abs(e[:n, None] - interior[None]).min() for e, n in zip(eigs, n_eff))
+        bip = any(nx.is_bipartite(g.subgraph(c)) and len(c) > 1 for g in G for c in nx.connected_components(g))
+        return gap, bip
+
+    graphs = {}
+    for name, (adj, mol, exact) in e2_graph_sets().items():
+        seed = None
+        if callable(adj):
+            make = adj
+            for seed in range(1000):
+                adj = make(np.random.default_rng(20261019 + seed))
+                G = reference_graphs(adj, mol)
+                gap, bip = margin_ok(G, *reference_spectra(G, adj.shape[1])[1:])
+                if gap >= 1e-9 and not bip:
+                    break
+            else:
+                raise RuntimeError(name)
+        G = reference_graphs(adj, mol)
+        counts, eigs, n_eff = reference_spectra(G, adj.shape[1])
+        gap, bip = margin_ok(G, eigs, n_eff)
+        if exact and (gap < 1e-9 or bip):
+            print("e2:", name, "fails the margin / bipartite check (gap", gap, "bipartite", bip, "): not compared count by count")
+            exact = False
+        rc, re_, rn = restated(adj, mol)
+        assert np.array_equal(rn, n_eff), name
+        if exact:
+            assert np.array_equal(rc, counts), name
+        graphs[name] = G
+        out[f"graphs/{name}/adj"] = adj
+        out[f"graphs/{name}/counts"], out[f"graphs/{name}/eig"], out[f"graphs/{name}/n_eff"] = counts, eigs, n_eff
+        if not exact:
+            out[f"graphs/{name}/expected_counts"] = rc
+        meta["graph_sets"][name] = {"mol": mol, "N": int(adj.shape[1]), "B": int(adj.shape[0]), "exact": bool(exact), "seed": seed,
+                                    "edge_margin": float(gap), "bipartite_component": bool(bip),
+                                    "restated_vs_reference_eig": float(np.abs(re_ - np.clip(eigs, 0, 2)).max()),
+                                    # informational: did np.histogram keep every eigenvalue of the reference (a top eigenvalue above 2 is dropped)
+                                    "reference_kept_all": [bool(c.sum() == n) for c, n in zip(counts, n_eff)]}
+        print("e2 graphs", name, "gap", gap, "bipartite", bip, round(time.time() - t0, 1), "s")
+    meta["edge_margin_required"] = 1e-9
+    meta["edge_margin_ok"] = all(v["edge_margin"] >= 1e-9 for v in meta["graph_sets"].values() if v["exact"])
+    assert meta["edge_margin_ok"]
+    sc = meta["scores"]
+    for a, b in (("s12a", "s12b"), ("mol9", "s12b")):
+        gr, gp = graphs[a], graphs[b]
+        sc[f"spectral/{a}_{b}/emd"] = emd_score(lambda k: ref_stats.spectral_stats(gr, gp, k), f"spectral/{a}_{b}/emd")
+        sc[f"spectral/{a}_{b}/tv"] = float(ref_stats.spectral_stats(gr, gp, ref_mmd.gaussian_tv))
+        print("e2 spectral", a, b, round(time.time() - t0, 1), "s", record.get("programs", 0), "programs")
+    meta["eval_graph_list"] = ref_stats.eval_graph_list(graphs["s12a"], graphs["s12b"], methods=["degree", "cluster", "spectral"],
+                                                        kernels={"degree": k_emd, "cluster": k_emd, "spectral": k_emd})
+    for m in ("degree", "cluster"):
+        meta["lp_vs_closed"][f"eval_graph_list/{m}"] = meta["lp_vs_closed_kernel"]
+    # ---- complexes
+    def make_side(rng, N, d_min, d_max, counts):
+        cells = [c for d in range(d_min, d_max + 1) for c in combinations(range(N), d)]
+        edges = {e: i for i, e in enumerate(combinations(range(N), 2))}
+        E, K = len(edges), len(cells)
+        x = np.zeros((len(counts), N, 1), np.int8)
+        adj = np.zeros((len(counts), N, N), np.int8)
+        r2 = np.zeros((len(counts), E, K), np.int8)
+        for b, n in enumerate(counts):
+            x[b, :n] = 1
+            u = np.triu(rng.random((n, n)) < 0.55, 1)
+            adj[b, :n, :n] = u + u.T
+            ok = [k for k, c in enumerate(cells) if max(c) < n]
+            for k in rng.choice(ok, size=min(len(ok), int(rng.integers(2, 7))), replace=False) if b != 1 else []:
+                # (a present cell is a column with any entry: the entries sit on the cell's own edges, present in the graph or not)
+                rows = [edges[e] for e in combinations(cells[k], 2)]
+                r2[b, rng.choice(rows, size=int(rng.integers(1, len(rows) + 1)), replace=False), k] = 1
+        return x, adj, r2
+
+    def to_ccs(x, adj, r2, d_min, d_max, empties=0):
+        ccs = [ref_cc.cc_from_incidence([x[b].astype(np.float32), adj[b].astype(np.float32), r2[b].astype(np.float32)], d_min, d_max)
+               for b in range(len(x))]
+        return ccs + [_StandInComplex() for _ in range(empties)]
+
+    def f64_rows(ccs, d_min, d_max, N):
+        rows = []
+        for cc in ccs:
+            F = ref_cc.CC_to_incidence_matrices(cc, d_min, d_max)[2]
+            if F.size:
+                F = np.asarray(ref_cc.pad_rank2(F, node_number=N, d_min=d_min, d_max=d_max), np.float64)
+                rows.append(np.linalg.eigvalsh(F @ F.T))
+            else:
+                rows.append(np.zeros(N * (N - 1) // 2))
+        return rows
+
+    for name, (N, d_min, d_max, n_ref, n_pred, seed) in e2_complex_sets().items():
+        rng = np.random.default_rng(20261019 + seed)
+        wk = {"min_edge_val": 1, "max_edge_val": 1, "edge_label": "label", "d_min": d_min, "d_max": d_max, "N": N}
+        sides = {"ref": make_side(rng, N, d_min, d_max, n_ref), "pred": make_side(rng, N, d_min, d_max, n_pred)}
+        worst = 0.0
+        for side, (x, adj, r2) in sides.items():
+            ccs = to_ccs(x, adj, r2, d_min, d_max)
+            spec = np.stack([ref_cc.hodge_laplacian_spectrum_worker(cc, d_min, d_max, N) for cc in ccs])
+            assert spec.dtype == np.float32 and spec.shape == (len(x), N * (N - 1) // 2)
+            f64 = np.stack(f64_rows(ccs, d_min, d_max, N))
+            worst = max(worst, float(np.abs(spec.astype(np.float64) - f64).max()))
+            out[f"cc/{name}/{side}/x"], out[f"cc/{name}/{side}/adj"], out[f"cc/{name}/{side}/rank2"] = x, adj, r2
+            out[f"cc/{name}/{side}/spectrum"] = spec
+        meta["f32_vs_f64"][f"cc/{name}/eig"] = worst
+        meta["complex_sets"][name] = {"N": N, "d_min": d_min, "d_max": d_max, "E": N * (N - 1) // 2, "worker_kwargs": wk}
+        kern = {m: k_emd for m in ("hodge_laplacian_spectrum", "rank1_distrib", "rank2_distrib")}
+        for tag, er, ep, nb in (("plain", 0, 0, 1000), ("empties", 1, 1, 1000), ("first2", 0, 0, 2)):
+            cr, cp = to_ccs(*sides["ref"], d_min, d_max, er)[:nb], to_ccs(*sides["pred"], d_min, d_max, ep)[:nb]
+            key = f"cc/{name}/{tag}/hodge/emd"
+            sc[key] = emd_score(lambda k: ref_cc.hodge_laplacian_spectrum_stats(cr, cp, wk, k, is_parallel=False), key)
+            sc[f"cc/{name}/{tag}/hodge/tv"] = float(ref_cc.hodge_laplacian_spectrum_stats(cr, cp, wk, ref_mmd.gaussian_tv, is_parallel=False))
+            # the same scores from float64 eigenvalues rounded to float32 once
+            rows = [[r.astype(np.float32) for r in f64_rows(c, d_min, d_max, N)] for c in (cr, [c for c in cp if not ref_cc.is_empty_cc(c)])]
+            alt = float(ref_mmd.compute_mmd(rows[0], rows[1], kernel=k_emd))
+            alt_tv = float(ref_mmd.compute_mmd(rows[0], rows[1], kernel=ref_mmd.gaussian_tv))
+            meta["f32_vs_f64"][key] = abs(alt - sc[key])
+            meta["f32_vs_f64"][f"cc/{name}/{tag}/hodge/tv"] = abs(alt_tv - sc[f"cc/{name}/{tag}/hodge/tv"])
+            meta[f"eval_CC_list/{name}/{tag}"] = ref_cc.eval_CC_list(to_ccs(*sides["ref"], d_min, d_max, er), to_ccs(*sides["pred"], d_min, d_max, ep), wk,
+                                                                     methods=list(kern), kernels=kern, cc_nb_eval=nb)
+            for m in ("rank1_distrib", "rank2_distrib"):
+                meta["lp_vs_closed"][f"eval_CC_list/{name}/{tag}/{m}"] = meta["lp_vs_closed_kernel"]
+        print("e2 complexes", name, round(time.time() - t0, 1), "s", record.get("programs", 0), "programs")
+    meta["programs"] = record.get("programs", 0)
+    meta["seconds"] = round(time.time() - t0, 1)
+    meta["note"] = ("gaussian_emd ran on a stand-in pyemd (scipy.optimize.linprog), the complexes on a stand-in CombinatorialComplex; lp_vs_closed = "
+                    "largest |program - closed form| per score; f32_vs_f64 = largest difference between the reference's float32 eigenvalues (and "
+                    "scores) and the same from float64 numpy.linalg.eigvalsh; edge_margin = smallest distance of a reference eigenvalue to an "
+                    "interior bin edge")
+    out["meta"] = np.array(json.dumps(plain(meta)))
+    path = os.path.join(GOLD, "e2_spectrum.npz")
+    np.savez_compressed(path, **out)
+    assert os.path.getsize(path) <= MAX_FIXTURE, os.path.getsize(path)
+    print("wrote e2_spectrum", os.path.getsize(path), "bytes;", meta["programs"], "programs,", meta["seconds"], "s")
+
+
 def d1_qm9_cc_n1000(B=256, seed=42, raw=None):
     """d1_qm9_CC_n1000.npz: ONE reference run of the shipped qm9_CC sampling set-up -- checkpoints/QM9/ccsd_qm9_CC.pth, the sampler block of
     config/sample_qm9_CC.yaml, all 1000 scales, B complexes, flags drawn as the harness draws them without the dataset blobs
@@ -1471,6 +1771,9 @@ def main():
         return
     if only == {"eval"}:
         e1_eval()
+        return
+    if only == {"spectrum"}:
+        e2_spectrum()
         return
     if only == {"d1"}:
         # ~a quarter of an hour of reference CPU time was the estimate; the fixture's metadata holds what it took
