@@ -1635,336 +1635,5 @@ extern "C" int ccsd_sampler_run_ex(ccsd_plan_t* pl, int32_t B, const float* flag
                        stream, options ? options->reduce : nullptr, options ? options->user : nullptr);
 }
 
-extern "C" int ccsd_quantize(const float* in, int64_t n, float thr, int64_t* out, void* stream) {
-    if (!in || !out || n < 0) return set_err(CCSD_ERR_INVALID, "bad argument");
-    if (n == 0) return CCSD_OK;
-    CCSD_LAUNCH(k_quantize, dim3(grid_for(n, 256)), dim3(CCSD_NTHREADS), 0, stream, in, (long long)n, thr, (long long*)out);
-    LAUNCH_CHECK();
-    return CCSD_OK;
-}
-
-extern "C" int ccsd_rank2_cells(const float* rank2, int32_t B, int32_t E, int64_t K, float thr, uint64_t* bits, int32_t* counts,
-                                void* stream) {
-    if (!rank2 || !bits || !counts || B < 1 || E < 1 || K < 1 || K > (1 << 24)) return set_err(CCSD_ERR_INVALID, "bad argument");
-    CCSD_LAUNCH(k_rank2_cells, dim3(B), dim3(CCSD_NTHREADS), 0, stream, rank2, (int)E, (int)K, thr, (unsigned long long*)bits, (int*)counts);
-    LAUNCH_CHECK();
-    return CCSD_OK;
-}
-
-
-// ccsd_finish: quantised outputs, cell bitmask and per-complex descriptors of finished samples (plan-free).  The graph pass
-// (k_finish_graph) and the rank-2 pass (k_finish_rank2) are launched only when one of their outputs is requested.
-extern "C" int ccsd_finish(const ccsd_finish_dims_t* d, const ccsd_state_t* in, const float* flags, const ccsd_finish_out_t* out,
-                           void* stream) {
-    (void)flags;      // (no output depends on the node flags: finished samples are masked, masked slots count as isolated / empty)
-    if (!d || !in || !out) return set_err(CCSD_ERR_INVALID, "ccsd_finish: NULL argument");
-    const int B = d->B, N = d->N, F = d->F;
-    if (B < 1) return set_err(CCSD_ERR_INVALID, "ccsd_finish: B must be >= 1");
-    if (N < 2 || N > CCSD_FIN_MAXN) return set_err(CCSD_ERR_INVALID, "ccsd_finish: N = " + std::to_string(N) + " outside 2.." + std::to_string(CCSD_FIN_MAXN));
-    if (d->E != N * (N - 1) / 2)
-        return set_err(CCSD_ERR_INVALID, "ccsd_finish: E = " + std::to_string(d->E) + " is not N (N - 1) / 2 = " + std::to_string(N * (N - 1) / 2));
-    if (d->adj_mode != CCSD_FINISH_ADJ_QUANTIZE && d->adj_mode != CCSD_FINISH_ADJ_MOL) return set_err(CCSD_ERR_INVALID, "ccsd_finish: unknown adj_mode");
-    if (!(d->thr >= 0.f)) return set_err(CCSD_ERR_INVALID, "ccsd_finish: thr must be >= 0");
-    const bool want_adj = out->adj_int || out->degree || out->degree_hist || out->edge_hist;
-    const bool want_x = out->n_nodes || out->x_hist;
-    const bool want_r = out->rank2_u8 || out->rank2_cell_bits || out->rank2_cell_count || out->rank2_cell_hist || out->rank2_nnz;
-    if (want_adj && !in->adj) return set_err(CCSD_ERR_INVALID, "ccsd_finish: adjacency outputs requested without in->adj");
-    if (want_x && (!in->x || F < 1 || F > CCSD_FIN_MAXN))
-        return set_err(CCSD_ERR_INVALID, "ccsd_finish: x outputs need in->x and 1 <= F <= " + std::to_string(CCSD_FIN_MAXN));
-    if (want_r && !in->rank2) return set_err(CCSD_ERR_INVALID, "ccsd_finish: rank-2 outputs requested without in->rank2");
-    FinishTab tab;
-    memset(&tab, 0, sizeof tab);
-    int64_t K = 0;
-    if (want_r) {      // (every check comes before the first launch)
-        const int d_min = d->d_min, d_max = d->d_max;
-        if (d_min < 1 || d_max < d_min || d_max > N || d_max - d_min + 1 > CCSD_FIN_MAXBINS)
-            return set_err(CCSD_ERR_INVALID, "ccsd_finish: bad cell sizes d_min = " + std::to_string(d_min) + ", d_max = " + std::to_string(d_max));
-        for (int s = d_min; s <= d_max; ++s) {
-            K += ccsd_comb(N, s);
-            if (K > (1 << 24)) break;
-            tab.end[s - d_min] = (int)K;
-        }
-        tab.nb = d_max - d_min + 1;
-        if (K != d->K)
-            return set_err(CCSD_ERR_INVALID, "ccsd_finish: K = " + std::to_string((long long)d->K) + " is not sum C(N, d) for d = " + std::to_string(d_min) +
-                                                 ".." + std::to_string(d_max) + (K > (1 << 24) ? " (which exceeds 2^24)" : " = " + std::to_string((long long)K)));
-        if ((int64_t)d->E * K >= (int64_t(1) << 31)) return set_err(CCSD_ERR_INVALID, "ccsd_finish: E K must be below 2^31");
-        if (((uintptr_t)in->rank2 & 15) || ((uintptr_t)out->rank2_u8 & 3) || ((uintptr_t)out->rank2_cell_bits & 7))
-            return set_err(CCSD_ERR_INVALID, "ccsd_finish: rank2 must be 16-byte, rank2_u8 4-byte and rank2_cell_bits 8-byte aligned");
-        if (B > 65535) return set_err(CCSD_ERR_INVALID, "ccsd_finish: B must be at most 65535 with rank-2 outputs");
-    }
-    if (want_adj || want_x) {
-        CCSD_LAUNCH(k_finish_graph, dim3(B), dim3(CCSD_NTHREADS), 0, stream, want_x ? (const float*)in->x : (const float*)nullptr,
-                    want_adj ? (const float*)in->adj : (const float*)nullptr, N, F, d->adj_mode == CCSD_FINISH_ADJ_MOL ? -1.0f : d->thr,
-                    (long long*)out->adj_int, (int*)out->degree, (int*)out->degree_hist, (int*)out->edge_hist, (int*)out->n_nodes, (int*)out->x_hist);
-        LAUNCH_CHECK();
-    }
-    if (want_r) {
-        const int W = (int)((K + 63) / 64), nslab = (int)((K + CCSD_FIN_SLAB - 1) / CCSD_FIN_SLAB);
-        // the accumulated outputs start from zero (atomicOr / atomicAdd per workgroup)
-        if (out->rank2_cell_bits) RT_CHECK(rt_memset_async(out->rank2_cell_bits, 0, (size_t)B * W * 8, stream));
-        if (out->rank2_cell_count) RT_CHECK(rt_memset_async(out->rank2_cell_count, 0, (size_t)B * 4, stream));
-        if (out->rank2_cell_hist) RT_CHECK(rt_memset_async(out->rank2_cell_hist, 0, (size_t)B * tab.nb * 4, stream));
-        if (out->rank2_nnz) RT_CHECK(rt_memset_async(out->rank2_nnz, 0, (size_t)B * 4, stream));
-        CCSD_LAUNCH(k_finish_rank2, dim3(nslab, B), dim3(CCSD_NTHREADS), 0, stream, (const float*)in->rank2, (int)d->E, (int)K, d->thr, tab,
-                    (long long)B * d->E * K, (unsigned char*)out->rank2_u8, (unsigned long long*)out->rank2_cell_bits, (int*)out->rank2_cell_count,
-                    (int*)out->rank2_cell_hist, (int*)out->rank2_nnz);
-        LAUNCH_CHECK();
-    }
-    return CCSD_OK;
-}
-
-// ccsd_cluster_hist: the clustering-coefficient histogram of every graph (k_cluster_hist; plan-free, same quantiser arguments as ccsd_finish)
-extern "C" int ccsd_cluster_hist(const float* adj, int32_t B, int32_t N, int32_t adj_mode, float thr, const double* edges, int32_t bins,
-                                 int32_t* tri2, int32_t* cluster_hist, void* stream) {
-    if (!adj) return set_err(CCSD_ERR_INVALID, "ccsd_cluster_hist: NULL adj");
-    if (B < 1) return set_err(CCSD_ERR_INVALID, "ccsd_cluster_hist: B must be >= 1");
-    if (N < 2 || N > CCSD_FIN_MAXN) return set_err(CCSD_ERR_INVALID, "ccsd_cluster_hist: N = " + std::to_string(N) + " outside 2.." + std::to_string(CCSD_FIN_MAXN));
-    if (bins < 1 || bins > CCSD_CLUSTER_MAX_BINS)
-        return set_err(CCSD_ERR_INVALID, "ccsd_cluster_hist: bins = " + std::to_string(bins) + " outside 1.." + std::to_string(CCSD_CLUSTER_MAX_BINS));
-    if (adj_mode != CCSD_FINISH_ADJ_QUANTIZE && adj_mode != CCSD_FINISH_ADJ_MOL) return set_err(CCSD_ERR_INVALID, "ccsd_cluster_hist: unknown adj_mode");
-    if (!(thr >= 0.f)) return set_err(CCSD_ERR_INVALID, "ccsd_cluster_hist: thr must be >= 0");
-    if (!edges) return set_err(CCSD_ERR_INVALID, "ccsd_cluster_hist: NULL edges");
-    if (!tri2 && !cluster_hist) return CCSD_OK;
-    CCSD_LAUNCH(k_cluster_hist, dim3(B), dim3(CCSD_NTHREADS), 0, stream, adj, (int)N, adj_mode == CCSD_FINISH_ADJ_MOL ? -1.0f : thr, edges, (int)bins,
-                (int*)tri2, (int*)cluster_hist);
-    LAUNCH_CHECK();
-    return CCSD_OK;
-}
-
-// Workspace of ccsd_mmd: the two transposed fp64 operands (rows padded to the pair kernel's tile), their mass flags and lengths, and
-// one fp64 partial per tile of each of the three pair reductions.
-struct MmdWs {
-    size_t op1, op2, part, mass1, len1, mass2, len2, bytes;
-    int np1, np2, T1, T2;
-};
-static MmdWs carve_mmd(int64_t n1, int64_t n2, int64_t L) {
-    MmdWs w;
-    w.T1 = (int)((n1 + CCSD_EVAL_TILE - 1) / CCSD_EVAL_TILE);
-    w.T2 = (int)((n2 + CCSD_EVAL_TILE - 1) / CCSD_EVAL_TILE);
-    w.np1 = w.T1 * CCSD_EVAL_TILE;
-    w.np2 = w.T2 * CCSD_EVAL_TILE;
-    size_t o = 0;
-    w.op1 = o; o += (size_t)L * w.np1 * 8;
-    w.op2 = o; o += (size_t)L * w.np2 * 8;
-    w.part = o; o += ((size_t)w.T1 * w.T1 + (size_t)w.T2 * w.T2 + (size_t)w.T1 * w.T2) * 8;
-    w.mass1 = o; o += (size_t)w.np1 * 4;
-    w.len1 = o; o += (size_t)w.np1 * 4;
-    w.mass2 = o; o += (size_t)w.np2 * 4;
-    w.len2 = o; o += (size_t)w.np2 * 4;
-    w.bytes = o;
-    return w;
-}
-// (the limits are the public header's: CCSD_MMD_MAX_ROWS, CCSD_MMD_MAX_BINS, CCSD_CLUSTER_MAX_BINS)
-static_assert(CCSD_CLUSTER_MAX_BINS == CCSD_EVAL_MAXBINS, "the header's bin limit is k_cluster_hist's LDS histogram");
-static bool mmd_dims_ok(int64_t n1, int64_t n2, int64_t L) {
-    return n1 >= 1 && n2 >= 1 && L >= 1 && n1 <= CCSD_MMD_MAX_ROWS && n2 <= CCSD_MMD_MAX_ROWS && L <= CCSD_MMD_MAX_BINS;
-}
-
-extern "C" size_t ccsd_mmd_workspace_bytes(int32_t n1, int32_t n2, int32_t L) {
-    if (!mmd_dims_ok(n1, n2, L)) {
-        set_err(CCSD_ERR_INVALID, "ccsd_mmd_workspace_bytes: n1, n2 must be in 1.." + std::to_string(CCSD_MMD_MAX_ROWS) + " and L in 1.." + std::to_string(CCSD_MMD_MAX_BINS));
-        return 0;
-    }
-    return carve_mmd(n1, n2, L).bytes;
-}
-
-// ccsd_mmd: compute_mmd (mmd.py:230-257) of two sets of histograms: k_mmd_prep per set, k_mmd_pairs for disc(1, 1), disc(2, 2) (both by
-// symmetry) and disc(1, 2), k_mmd_final.  out (4 doubles, device) = disc(1, 1), disc(2, 2), disc(1, 2), mmd.
-extern "C" int ccsd_mmd(const void* h1, int32_t n1, const int32_t* lens1, const void* h2, int32_t n2, const int32_t* lens2, int32_t L,
-                        int32_t dtype, int32_t kind, int32_t flags, double sigma, double distance_scaling, void* workspace, size_t ws_bytes,
-                        double* out, void* stream) {
-    if (n1 < 1 || n2 < 1) return set_err(CCSD_ERR_INVALID, "ccsd_mmd: n1 = " + std::to_string(n1) + ", n2 = " + std::to_string(n2) + ": every set needs n >= 1 rows");
-    if (L < 1) return set_err(CCSD_ERR_INVALID, "ccsd_mmd: L = " + std::to_string(L) + " must be >= 1");
-    if (!mmd_dims_ok(n1, n2, L)) return set_err(CCSD_ERR_INVALID, "ccsd_mmd: n above " + std::to_string(CCSD_MMD_MAX_ROWS) + " or L above " + std::to_string(CCSD_MMD_MAX_BINS));
-    if (!h1 || !h2 || !out) return set_err(CCSD_ERR_INVALID, "ccsd_mmd: NULL argument");
-    if (dtype != CCSD_MMD_INT32 && dtype != CCSD_MMD_FP64) return set_err(CCSD_ERR_INVALID, "ccsd_mmd: unknown dtype");
-    if (kind != CCSD_MMD_EMD && kind != CCSD_MMD_TV && kind != CCSD_MMD_L2) return set_err(CCSD_ERR_INVALID, "ccsd_mmd: unknown kind");
-    if (flags & ~(CCSD_MMD_IS_HIST | CCSD_MMD_DEGREE | CCSD_MMD_F32_PMF)) return set_err(CCSD_ERR_INVALID, "ccsd_mmd: unknown flag");
-    if (kind == CCSD_MMD_EMD && !(flags & CCSD_MMD_IS_HIST))
-        return set_err(CCSD_ERR_INVALID, "ccsd_mmd: the EMD kind needs is_hist (rows of unequal mass have no closed form on the line metric)");
-    if (!(sigma > 0.0)) return set_err(CCSD_ERR_INVALID, "ccsd_mmd: sigma must be > 0");
-    if (kind == CCSD_MMD_EMD && !(distance_scaling > 0.0)) return set_err(CCSD_ERR_INVALID, "ccsd_mmd: distance_scaling must be > 0");
-    const MmdWs w = carve_mmd(n1, n2, L);
-    if (!workspace || ws_bytes < w.bytes) return set_err(CCSD_ERR_WORKSPACE, "ccsd_mmd: workspace too small");
-    if ((uintptr_t)workspace & 7) return set_err(CCSD_ERR_INVALID, "ccsd_mmd: workspace must be 8-byte aligned");
-    static_assert((int)CCSD_MMD_EMD == (int)EVAL_EMD && (int)CCSD_MMD_TV == (int)EVAL_TV && (int)CCSD_MMD_L2 == (int)EVAL_L2 &&
-                  (int)CCSD_MMD_IS_HIST == (int)EVAL_F_HIST && (int)CCSD_MMD_DEGREE == (int)EVAL_F_DEGREE &&
-                  (int)CCSD_MMD_F32_PMF == (int)EVAL_F_F32PMF, "the header's constants are the kernels'");
-    char* base = (char*)workspace;
-    double *op1 = (double*)(base + w.op1), *op2 = (double*)(base + w.op2), *part = (double*)(base + w.part);
-    int *m1 = (int*)(base + w.mass1), *l1 = (int*)(base + w.len1), *m2 = (int*)(base + w.mass2), *l2 = (int*)(base + w.len2);
-    // (k_mmd_prep: 256 rows per workgroup; the emulation's one thread takes them in turn)
-    CCSD_LAUNCH(k_mmd_prep, dim3((w.np1 + 255) / 256), dim3(256), 0, stream, h1, (int)(dtype == CCSD_MMD_FP64), (const int*)lens1, (int)n1, w.np1,
-                (int)L, (int)kind, (int)flags, op1, m1, l1);
-    LAUNCH_CHECK();
-    CCSD_LAUNCH(k_mmd_prep, dim3((w.np2 + 255) / 256), dim3(256), 0, stream, h2, (int)(dtype == CCSD_MMD_FP64), (const int*)lens2, (int)n2, w.np2,
-                (int)L, (int)kind, (int)flags, op2, m2, l2);
-    LAUNCH_CHECK();
-    const double two_s2 = 2 * sigma * sigma;
-    const int c11 = w.T1 * w.T1, c22 = w.T2 * w.T2, c12 = w.T1 * w.T2;
-    CCSD_LAUNCH(k_mmd_pairs, dim3(w.T1, w.T1), dim3(CCSD_NTHREADS), 0, stream, (const double*)op1, (const int*)m1, (const int*)l1, (int)n1, w.np1,
-                (const double*)op1, (const int*)m1, (const int*)l1, (int)n1, w.np1, (int)L, (int)kind, distance_scaling, two_s2, 1, part);
-    LAUNCH_CHECK();
-    CCSD_LAUNCH(k_mmd_pairs, dim3(w.T2, w.T2), dim3(CCSD_NTHREADS), 0, stream, (const double*)op2, (const int*)m2, (const int*)l2, (int)n2, w.np2,
-                (const double*)op2, (const int*)m2, (const int*)l2, (int)n2, w.np2, (int)L, (int)kind, distance_scaling, two_s2, 1, part + c11);
-    LAUNCH_CHECK();
-    CCSD_LAUNCH(k_mmd_pairs, dim3(w.T2, w.T1), dim3(CCSD_NTHREADS), 0, stream, (const double*)op1, (const int*)m1, (const int*)l1, (int)n1, w.np1,
-                (const double*)op2, (const int*)m2, (const int*)l2, (int)n2, w.np2, (int)L, (int)kind, distance_scaling, two_s2, 0, part + c11 + c22);
-    LAUNCH_CHECK();
-    CCSD_LAUNCH(k_mmd_final, dim3(1), dim3(CCSD_NTHREADS), 0, stream, (const double*)part, c11, c22, c12, (double)n1, (double)n2, out);
-    LAUNCH_CHECK();
-    return CCSD_OK;
-}
-
-// ---------------- spectra (ccsd_k_eig.h) ----------------
-static_assert(CCSD_EIG_MAXN == 512 && CCSD_EIG_MAX_SWEEPS == 30, "the public header states these limits in words");
-// The workspace-resident placement of k_eigvalsh: a bounded grid of workgroups, one slab each -- the size does not grow with B.
-static int eig_grid(int B, int n) { return n <= CCSD_EIG_LDS_MAXN || B < CCSD_EIG_MAX_GRID ? B : CCSD_EIG_MAX_GRID; }
-static size_t eig_slab_bytes(int B, int n) {
-    return n <= CCSD_EIG_LDS_MAXN ? 0 : (size_t)eig_grid(B, n) * n * (n | 1) * 8;
-}
-static std::string eig_too_large(const char* who, const char* what, int n) {
-    return std::string(who) + ": " + what + " = " + std::to_string(n) + " is above CCSD_EIG_MAXN = " + std::to_string(CCSD_EIG_MAXN) +
-           ": the solver is a Jacobi iteration of O(n^3) per sweep with one matrix per compute unit, which larger matrices are out of reach of";
-}
-// one launch of k_eigvalsh over matrices of order <= nmax (every argument checked by the caller)
-static int eig_launch(const double* a, int B, int nmax, long long a_stride, int lda, const int* n_arr, void* slabs, double* w, float* w32,
-                      int* sweeps, const double* edges, int bins, int* hist, void* stream) {
-    const int threads = CCSD_NTHREADS == 1 ? 1 : nmax <= 64 ? 256 : CCSD_EIG_THREADS;
-    if (nmax <= CCSD_EIG_LDS_MAXN) {
-        const size_t lds = (size_t)nmax * (nmax | 1) * 8;
-        // (the kernel's static arrays take another 18 KB: the attribute is raised as soon as the two together could pass 64 KB)
-        if (lds + 20 * 1024 > 64 * 1024) RT_CHECK(rt_set_max_dyn_smem((const void*)k_eigvalsh<true>, lds));
-        CCSD_LAUNCH(k_eigvalsh<true>, dim3(B), dim3(threads), lds, stream, a, B, nmax, a_stride, lda, n_arr, (double*)nullptr, w, w32, sweeps,
-                    edges, bins, hist);
-    } else {
-        CCSD_LAUNCH(k_eigvalsh<false>, dim3(eig_grid(B, nmax)), dim3(threads), 0, stream, a, B, nmax, a_stride, lda, n_arr, (double*)slabs, w,
-                    w32, sweeps, edges, bins, hist);
-    }
-    LAUNCH_CHECK();
-    return CCSD_OK;
-}
-
-extern "C" size_t ccsd_eig_workspace_bytes(int32_t B, int32_t n) {
-    if (B < 1 || n < 1 || n > CCSD_EIG_MAXN) {
-        set_err(CCSD_ERR_INVALID, "ccsd_eig_workspace_bytes: B must be >= 1 and n in 1.." + std::to_string(CCSD_EIG_MAXN));
-        return 0;
-    }
-    return eig_slab_bytes(B, n);
-}
-
-// ccsd_eigvalsh: the eigenvalues of B symmetric n x n fp64 matrices, ascending (k_eigvalsh; plan-free)
-extern "C" int ccsd_eigvalsh(const double* a, int32_t B, int32_t n, double* w, int32_t* sweeps, void* workspace, size_t ws_bytes,
-                             void* stream) {
-    if (!a || !w) return set_err(CCSD_ERR_INVALID, "ccsd_eigvalsh: NULL argument");
-    if (B < 1) return set_err(CCSD_ERR_INVALID, "ccsd_eigvalsh: B must be >= 1");
-    if (n < 1) return set_err(CCSD_ERR_INVALID, "ccsd_eigvalsh: n = " + std::to_string(n) + " must be >= 1");
-    if (n > CCSD_EIG_MAXN) return set_err(CCSD_ERR_UNSUPPORTED, eig_too_large("ccsd_eigvalsh", "n", n));
-    const size_t need = eig_slab_bytes(B, n);
-    if (need && (!workspace || ws_bytes < need)) return set_err(CCSD_ERR_WORKSPACE, "ccsd_eigvalsh: workspace too small");
-    if (need && ((uintptr_t)workspace & 7)) return set_err(CCSD_ERR_INVALID, "ccsd_eigvalsh: workspace must be 8-byte aligned");
-    return eig_launch(a, B, n, (long long)n * n, n, nullptr, workspace, w, nullptr, (int*)sweeps, nullptr, 0, nullptr, stream);
-}
-
-// Workspace of ccsd_spectral_hist: the fp64 Laplacians (B, N, N), the eigenvalues (B, N) when the caller does not take them, the
-// orders (B,) likewise, and the solver's slabs.
-struct SpectralWs {
-    size_t lap, eig, neff, slabs, bytes;
-};
-static SpectralWs carve_spectral(int64_t B, int64_t N) {
-    SpectralWs w;
-    size_t o = 0;
-    w.lap = o; o += (size_t)B * N * N * 8;
-    w.eig = o; o += (size_t)B * N * 8;
-    w.neff = o; o += ((size_t)B * 4 + 7) & ~(size_t)7;
-    w.slabs = o; o += eig_slab_bytes((int)B, (int)N);
-    w.bytes = o;
-    return w;
-}
-extern "C" size_t ccsd_spectral_workspace_bytes(int32_t B, int32_t N) {
-    if (B < 1 || N < 2 || N > CCSD_FIN_MAXN) {
-        set_err(CCSD_ERR_INVALID, "ccsd_spectral_workspace_bytes: B must be >= 1 and N in 2.." + std::to_string(CCSD_FIN_MAXN));
-        return 0;
-    }
-    return carve_spectral(B, N).bytes;
-}
-
-// ccsd_spectral_hist: spectral_worker (evaluation/stats.py:125-137) of every graph: k_norm_laplacian, then k_eigvalsh with the
-// histogram in its epilogue
-extern "C" int ccsd_spectral_hist(const float* adj, int32_t B, int32_t N, int32_t adj_mode, float thr, const double* edges, int32_t bins,
-                                  int32_t* hist, double* eig, int32_t* n_eff, void* workspace, size_t ws_bytes, void* stream) {
-    static_assert(CCSD_FIN_MAXN <= CCSD_EIG_MAXN, "every graph ccsd_finish takes has a Laplacian the solver takes");
-    if (!adj) return set_err(CCSD_ERR_INVALID, "ccsd_spectral_hist: NULL adj");
-    if (B < 1) return set_err(CCSD_ERR_INVALID, "ccsd_spectral_hist: B must be >= 1");
-    if (N < 2 || N > CCSD_FIN_MAXN) return set_err(CCSD_ERR_INVALID, "ccsd_spectral_hist: N = " + std::to_string(N) + " outside 2.." + std::to_string(CCSD_FIN_MAXN));
-    if (bins < 1 || bins > CCSD_CLUSTER_MAX_BINS)
-        return set_err(CCSD_ERR_INVALID, "ccsd_spectral_hist: bins = " + std::to_string(bins) + " outside 1.." + std::to_string(CCSD_CLUSTER_MAX_BINS));
-    if (adj_mode != CCSD_FINISH_ADJ_QUANTIZE && adj_mode != CCSD_FINISH_ADJ_MOL) return set_err(CCSD_ERR_INVALID, "ccsd_spectral_hist: unknown adj_mode");
-    if (!(thr >= 0.f)) return set_err(CCSD_ERR_INVALID, "ccsd_spectral_hist: thr must be >= 0");
-    if (!edges) return set_err(CCSD_ERR_INVALID, "ccsd_spectral_hist: NULL edges");
-    if (!hist && !eig && !n_eff) return CCSD_OK;
-    const SpectralWs w = carve_spectral(B, N);
-    if (!workspace || ws_bytes < w.bytes) return set_err(CCSD_ERR_WORKSPACE, "ccsd_spectral_hist: workspace too small");
-    if ((uintptr_t)workspace & 7) return set_err(CCSD_ERR_INVALID, "ccsd_spectral_hist: workspace must be 8-byte aligned");
-    char* base = (char*)workspace;
-    double* lap = (double*)(base + w.lap);
-    int* ne = n_eff ? (int*)n_eff : (int*)(base + w.neff);
-    CCSD_LAUNCH(k_norm_laplacian, dim3(B), dim3(CCSD_NTHREADS), 0, stream, adj, (int)N, adj_mode == CCSD_FINISH_ADJ_MOL ? -1.0f : thr, lap, ne);
-    LAUNCH_CHECK();
-    if (!hist && !eig) return CCSD_OK;
-    return eig_launch(lap, B, N, (long long)N * N, N, ne, base + w.slabs, eig ? eig : (double*)(base + w.eig), nullptr, nullptr, edges,
-                      hist ? (int)bins : 0, (int*)hist, stream);
-}
-
-// the number of candidate cells of sizes d_min..d_max, or -1 above 2^24 (the limit of ccsd_finish)
-static int64_t hodge_cells(int N, int d_min, int d_max) {
-    int64_t K = 0;
-    for (int s = d_min; s <= d_max; ++s) {
-        K += ccsd_comb(N, s);
-        if (K > (1 << 24)) return -1;
-    }
-    return K;
-}
-extern "C" size_t ccsd_hodge_workspace_bytes(int32_t B, int32_t N) {
-    const int64_t E = (int64_t)N * (N - 1) / 2;
-    if (B < 1 || N < 2) {
-        set_err(CCSD_ERR_INVALID, "ccsd_hodge_workspace_bytes: B must be >= 1 and N >= 2");
-        return 0;
-    }
-    if (E > CCSD_EIG_MAXN) {
-        set_err(CCSD_ERR_UNSUPPORTED, eig_too_large("ccsd_hodge_workspace_bytes", ("N = " + std::to_string(N) + ": E = N (N - 1) / 2").c_str(), (int)E));
-        return 0;
-    }
-    return (size_t)B * E * E * 8 + eig_slab_bytes(B, (int)E);
-}
-
-// ccsd_hodge_spectrum: hodge_laplacian_spectrum_worker (cc_utils.py:994-1060) of every complex: k_hodge_laplacian, then k_eigvalsh
-extern "C" int ccsd_hodge_spectrum(const float* adj, const uint64_t* cell_bits, int32_t B, int32_t N, int32_t d_min, int32_t d_max,
-                                   int32_t adj_mode, float thr, float* spectrum, int32_t* sweeps, void* workspace, size_t ws_bytes,
-                                   void* stream) {
-    if (!adj || !cell_bits || !spectrum) return set_err(CCSD_ERR_INVALID, "ccsd_hodge_spectrum: NULL argument");
-    if (B < 1) return set_err(CCSD_ERR_INVALID, "ccsd_hodge_spectrum: B must be >= 1");
-    if (N < 2) return set_err(CCSD_ERR_INVALID, "ccsd_hodge_spectrum: N = " + std::to_string(N) + " must be >= 2");
-    const int64_t E64 = (int64_t)N * (N - 1) / 2;
-    if (E64 > CCSD_EIG_MAXN)
-        return set_err(CCSD_ERR_UNSUPPORTED, eig_too_large("ccsd_hodge_spectrum", ("N = " + std::to_string(N) + ": E = N (N - 1) / 2").c_str(), (int)E64));
-    static_assert(CCSD_EIG_HODGE_MAXN * (CCSD_EIG_HODGE_MAXN - 1) / 2 <= CCSD_EIG_MAXN &&
-                  (CCSD_EIG_HODGE_MAXN + 1) * CCSD_EIG_HODGE_MAXN / 2 > CCSD_EIG_MAXN, "k_hodge_laplacian's node list holds every N with E <= CCSD_EIG_MAXN");
-    if (d_min < 1 || d_max < d_min || d_max > N)
-        return set_err(CCSD_ERR_INVALID, "ccsd_hodge_spectrum: bad cell sizes d_min = " + std::to_string(d_min) + ", d_max = " + std::to_string(d_max));
-    if (adj_mode != CCSD_FINISH_ADJ_QUANTIZE && adj_mode != CCSD_FINISH_ADJ_MOL) return set_err(CCSD_ERR_INVALID, "ccsd_hodge_spectrum: unknown adj_mode");
-    if (!(thr >= 0.f)) return set_err(CCSD_ERR_INVALID, "ccsd_hodge_spectrum: thr must be >= 0");
-    const int64_t K = hodge_cells(N, d_min, d_max);
-    if (K < 0) return set_err(CCSD_ERR_INVALID, "ccsd_hodge_spectrum: sum C(N, d) for d = d_min..d_max exceeds 2^24");
-    const int E = (int)E64;
-    const size_t hbytes = (size_t)B * E * E * 8, need = hbytes + eig_slab_bytes(B, E);
-    if (!workspace || ws_bytes < need) return set_err(CCSD_ERR_WORKSPACE, "ccsd_hodge_spectrum: workspace too small");
-    if ((uintptr_t)workspace & 7) return set_err(CCSD_ERR_INVALID, "ccsd_hodge_spectrum: workspace must be 8-byte aligned");
-    double* H = (double*)workspace;
-    RT_CHECK(rt_memset_async(H, 0, hbytes, stream));              // (k_hodge_laplacian adds onto zeros)
-    CCSD_LAUNCH(k_hodge_laplacian, dim3(B), dim3(CCSD_NTHREADS), 0, stream, adj, (const unsigned long long*)cell_bits, (int)N, (int)d_min,
-                (int)d_max, (int)K, adj_mode == CCSD_FINISH_ADJ_MOL ? -1.0f : thr, H);
-    LAUNCH_CHECK();
-    return eig_launch(H, B, E, (long long)E * E, E, nullptr, (char*)workspace + hbytes, nullptr, spectrum, (int*)sweeps, nullptr, 0, nullptr, stream);
-}
+// the plan-free entry points (operations on finished samples): a file of their own, sharing set_err, grid_for and the check macros
+#include "ccsd_api_samples.h"

@@ -1,0 +1,351 @@
+// ccsd_api_samples.h -- host side of the PLAN-FREE entry points of include/ccsd_hip.h: the operations on finished samples, which take
+// tensors and sizes and never a ccsd_plan_t (ccsd_quantize, ccsd_rank2_cells, ccsd_finish, ccsd_cluster_hist, ccsd_mmd, ccsd_eigvalsh,
+// ccsd_spectral_hist, ccsd_hodge_spectrum and their *_workspace_bytes).  Included by ccsd_api.h as its last line; of what stands above it
+// there, this file uses set_err, grid_for, RT_CHECK and LAUNCH_CHECK only.
+//
+// One definition per rule: check_batch (B, N, the quantiser), check_hist (bins, edges), check_scratch (workspace), no_bytes, quant_thr,
+// cell_count.
+// Every check of an entry point comes before its first launch.
+#pragma once
+
+// ---------------- the shared argument rules ----------------
+// B >= 1, the quantiser of ccsd_finish (adj_mode, thr) and -- fin_n -- the node count of the graphs ccsd_finish takes
+static int check_batch(const char* who, int B, int N, int adj_mode, float thr, bool fin_n = true) {
+    const std::string w = std::string(who) + ": ";
+    if (B < 1) return set_err(CCSD_ERR_INVALID, w + "B must be >= 1");
+    if (fin_n && (N < 2 || N > CCSD_FIN_MAXN)) return set_err(CCSD_ERR_INVALID, w + "N = " + std::to_string(N) + " outside 2.." + std::to_string(CCSD_FIN_MAXN));
+    if (adj_mode != CCSD_FINISH_ADJ_QUANTIZE && adj_mode != CCSD_FINISH_ADJ_MOL) return set_err(CCSD_ERR_INVALID, w + "unknown adj_mode");
+    if (!(thr >= 0.f)) return set_err(CCSD_ERR_INVALID, w + "thr must be >= 0");
+    return CCSD_OK;
+}
+// the histogram of k_cluster_hist / k_eigvalsh's epilogue: bins + 1 edges on the device (the limit is the public header's)
+static_assert(CCSD_CLUSTER_MAX_BINS == CCSD_EVAL_MAXBINS, "the header's bin limit is k_cluster_hist's LDS histogram");
+static int check_hist(const char* who, const double* edges, int bins) {
+    if (bins < 1 || bins > CCSD_CLUSTER_MAX_BINS)
+        return set_err(CCSD_ERR_INVALID, std::string(who) + ": bins = " + std::to_string(bins) + " outside 1.." + std::to_string(CCSD_CLUSTER_MAX_BINS));
+    if (!edges) return set_err(CCSD_ERR_INVALID, std::string(who) + ": NULL edges");
+    return CCSD_OK;
+}
+// a caller's scratch of `need` bytes (need = 0: none is read)
+static int check_scratch(const char* who, const void* workspace, size_t ws_bytes, size_t need) {
+    if (!need) return CCSD_OK;
+    if (!workspace || ws_bytes < need) return set_err(CCSD_ERR_WORKSPACE, std::string(who) + ": workspace too small");
+    if ((uintptr_t)workspace & 7) return set_err(CCSD_ERR_INVALID, std::string(who) + ": workspace must be 8-byte aligned");
+    return CCSD_OK;
+}
+// a *_workspace_bytes function refuses its sizes: the reason is left for ccsd_last_error, the size is 0
+static size_t no_bytes(int st, const std::string& m) { set_err(st, m); return 0; }
+// the threshold argument of the quantising kernels: negative selects quantize_mol's 0/1/2/3 bins
+static float quant_thr(int adj_mode, float thr) { return adj_mode == CCSD_FINISH_ADJ_MOL ? -1.0f : thr; }
+// K = sum C(N, d) over d = d_min..d_max, the number of candidate cells, or -1 above 2^24 (the limit of ccsd_finish); `end`: the running
+// sum per size (FinishTab::end)
+static int64_t cell_count(int N, int d_min, int d_max, int* end = nullptr) {
+    int64_t K = 0;
+    for (int s = d_min; s <= d_max; ++s) {
+        K += ccsd_comb(N, s);
+        if (K > (1 << 24)) return -1;
+        if (end) end[s - d_min] = (int)K;
+    }
+    return K;
+}
+
+// ---------------- quantised outputs and descriptors (ccsd_k_update.h, ccsd_k_finish.h) ----------------
+extern "C" int ccsd_quantize(const float* in, int64_t n, float thr, int64_t* out, void* stream) {
+    if (!in || !out || n < 0) return set_err(CCSD_ERR_INVALID, "bad argument");
+    if (n == 0) return CCSD_OK;
+    CCSD_LAUNCH(k_quantize, dim3(grid_for(n, 256)), dim3(CCSD_NTHREADS), 0, stream, in, (long long)n, thr, (long long*)out);
+    LAUNCH_CHECK();
+    return CCSD_OK;
+}
+
+extern "C" int ccsd_rank2_cells(const float* rank2, int32_t B, int32_t E, int64_t K, float thr, uint64_t* bits, int32_t* counts,
+                                void* stream) {
+    if (!rank2 || !bits || !counts || B < 1 || E < 1 || K < 1 || K > (1 << 24)) return set_err(CCSD_ERR_INVALID, "bad argument");
+    CCSD_LAUNCH(k_rank2_cells, dim3(B), dim3(CCSD_NTHREADS), 0, stream, rank2, (int)E, (int)K, thr, (unsigned long long*)bits, (int*)counts);
+    LAUNCH_CHECK();
+    return CCSD_OK;
+}
+
+// ccsd_finish: quantised outputs, cell bitmask and per-complex descriptors of finished samples.  The graph pass (k_finish_graph) and
+// the rank-2 pass (k_finish_rank2) are launched only when one of their outputs is requested.
+extern "C" int ccsd_finish(const ccsd_finish_dims_t* d, const ccsd_state_t* in, const float* flags, const ccsd_finish_out_t* out,
+                           void* stream) {
+    (void)flags;      // (no output depends on the node flags: finished samples are masked, masked slots count as isolated / empty)
+    if (!d || !in || !out) return set_err(CCSD_ERR_INVALID, "ccsd_finish: NULL argument");
+    const int B = d->B, N = d->N, F = d->F;
+    if (int st = check_batch("ccsd_finish", B, N, d->adj_mode, d->thr)) return st;
+    if (d->E != N * (N - 1) / 2)
+        return set_err(CCSD_ERR_INVALID, "ccsd_finish: E = " + std::to_string(d->E) + " is not N (N - 1) / 2 = " + std::to_string(N * (N - 1) / 2));
+    const bool want_adj = out->adj_int || out->degree || out->degree_hist || out->edge_hist;
+    const bool want_x = out->n_nodes || out->x_hist;
+    const bool want_r = out->rank2_u8 || out->rank2_cell_bits || out->rank2_cell_count || out->rank2_cell_hist || out->rank2_nnz;
+    if (want_adj && !in->adj) return set_err(CCSD_ERR_INVALID, "ccsd_finish: adjacency outputs requested without in->adj");
+    if (want_x && (!in->x || F < 1 || F > CCSD_FIN_MAXN))
+        return set_err(CCSD_ERR_INVALID, "ccsd_finish: x outputs need in->x and 1 <= F <= " + std::to_string(CCSD_FIN_MAXN));
+    if (want_r && !in->rank2) return set_err(CCSD_ERR_INVALID, "ccsd_finish: rank-2 outputs requested without in->rank2");
+    FinishTab tab;
+    memset(&tab, 0, sizeof tab);
+    int64_t K = 0;
+    if (want_r) {
+        const int d_min = d->d_min, d_max = d->d_max;
+        if (d_min < 1 || d_max < d_min || d_max > N || d_max - d_min + 1 > CCSD_FIN_MAXBINS)
+            return set_err(CCSD_ERR_INVALID, "ccsd_finish: bad cell sizes d_min = " + std::to_string(d_min) + ", d_max = " + std::to_string(d_max));
+        K = cell_count(N, d_min, d_max, tab.end);
+        tab.nb = d_max - d_min + 1;
+        if (K < 0 || K != d->K)
+            return set_err(CCSD_ERR_INVALID, "ccsd_finish: K = " + std::to_string((long long)d->K) + " is not sum C(N, d) for d = " + std::to_string(d_min) +
+                                                 ".." + std::to_string(d_max) + (K < 0 ? " (which exceeds 2^24)" : " = " + std::to_string((long long)K)));
+        if ((int64_t)d->E * K >= (int64_t(1) << 31)) return set_err(CCSD_ERR_INVALID, "ccsd_finish: E K must be below 2^31");
+        if (((uintptr_t)in->rank2 & 15) || ((uintptr_t)out->rank2_u8 & 3) || ((uintptr_t)out->rank2_cell_bits & 7))
+            return set_err(CCSD_ERR_INVALID, "ccsd_finish: rank2 must be 16-byte, rank2_u8 4-byte and rank2_cell_bits 8-byte aligned");
+        if (B > 65535) return set_err(CCSD_ERR_INVALID, "ccsd_finish: B must be at most 65535 with rank-2 outputs");
+    }
+    if (want_adj || want_x) {
+        CCSD_LAUNCH(k_finish_graph, dim3(B), dim3(CCSD_NTHREADS), 0, stream, want_x ? (const float*)in->x : (const float*)nullptr,
+                    want_adj ? (const float*)in->adj : (const float*)nullptr, N, F, quant_thr(d->adj_mode, d->thr),
+                    (long long*)out->adj_int, (int*)out->degree, (int*)out->degree_hist, (int*)out->edge_hist, (int*)out->n_nodes, (int*)out->x_hist);
+        LAUNCH_CHECK();
+    }
+    if (want_r) {
+        const int W = (int)((K + 63) / 64), nslab = (int)((K + CCSD_FIN_SLAB - 1) / CCSD_FIN_SLAB);
+        // the accumulated outputs start from zero (atomicOr / atomicAdd per workgroup)
+        if (out->rank2_cell_bits) RT_CHECK(rt_memset_async(out->rank2_cell_bits, 0, (size_t)B * W * 8, stream));
+        if (out->rank2_cell_count) RT_CHECK(rt_memset_async(out->rank2_cell_count, 0, (size_t)B * 4, stream));
+        if (out->rank2_cell_hist) RT_CHECK(rt_memset_async(out->rank2_cell_hist, 0, (size_t)B * tab.nb * 4, stream));
+        if (out->rank2_nnz) RT_CHECK(rt_memset_async(out->rank2_nnz, 0, (size_t)B * 4, stream));
+        CCSD_LAUNCH(k_finish_rank2, dim3(nslab, B), dim3(CCSD_NTHREADS), 0, stream, (const float*)in->rank2, (int)d->E, (int)K, d->thr, tab,
+                    (long long)B * d->E * K, (unsigned char*)out->rank2_u8, (unsigned long long*)out->rank2_cell_bits, (int*)out->rank2_cell_count,
+                    (int*)out->rank2_cell_hist, (int*)out->rank2_nnz);
+        LAUNCH_CHECK();
+    }
+    return CCSD_OK;
+}
+
+// ---------------- clustering histograms and the MMD (ccsd_k_eval.h) ----------------
+// ccsd_cluster_hist: the clustering-coefficient histogram of every graph (k_cluster_hist; same quantiser arguments as ccsd_finish)
+extern "C" int ccsd_cluster_hist(const float* adj, int32_t B, int32_t N, int32_t adj_mode, float thr, const double* edges, int32_t bins,
+                                 int32_t* tri2, int32_t* cluster_hist, void* stream) {
+    if (!adj) return set_err(CCSD_ERR_INVALID, "ccsd_cluster_hist: NULL adj");
+    if (int st = check_batch("ccsd_cluster_hist", B, N, adj_mode, thr)) return st;
+    if (int st = check_hist("ccsd_cluster_hist", edges, bins)) return st;
+    if (!tri2 && !cluster_hist) return CCSD_OK;
+    CCSD_LAUNCH(k_cluster_hist, dim3(B), dim3(CCSD_NTHREADS), 0, stream, adj, (int)N, quant_thr(adj_mode, thr), edges, (int)bins, (int*)tri2,
+                (int*)cluster_hist);
+    LAUNCH_CHECK();
+    return CCSD_OK;
+}
+
+// Workspace of ccsd_mmd: the two transposed fp64 operands (rows padded to the pair kernel's tile), one fp64 partial per tile of each of
+// the three pair reductions, then the mass flags and lengths of each set.
+struct MmdSet {      // one set of rows: its offsets in the workspace; rows, padded rows, tiles
+    size_t op, mass, len;
+    int n, np, T;
+};
+struct MmdWs {
+    MmdSet s[2];
+    size_t part, bytes;
+};
+static MmdWs carve_mmd(int64_t n1, int64_t n2, int64_t L) {
+    MmdWs w;
+    size_t o = 0;
+    w.s[0].n = (int)n1, w.s[1].n = (int)n2;
+    for (MmdSet& s : w.s) {
+        s.T = (s.n + CCSD_EVAL_TILE - 1) / CCSD_EVAL_TILE;
+        s.np = s.T * CCSD_EVAL_TILE;
+        s.op = o; o += (size_t)L * s.np * 8;
+    }
+    const size_t T1 = w.s[0].T, T2 = w.s[1].T;
+    w.part = o; o += (T1 * T1 + T2 * T2 + T1 * T2) * 8;
+    for (MmdSet& s : w.s) {
+        s.mass = o; o += (size_t)s.np * 4;
+        s.len = o; o += (size_t)s.np * 4;
+    }
+    w.bytes = o;
+    return w;
+}
+// (the limits are the public header's: CCSD_MMD_MAX_ROWS, CCSD_MMD_MAX_BINS)
+static bool mmd_dims_ok(int64_t n1, int64_t n2, int64_t L) {
+    return n1 >= 1 && n2 >= 1 && L >= 1 && n1 <= CCSD_MMD_MAX_ROWS && n2 <= CCSD_MMD_MAX_ROWS && L <= CCSD_MMD_MAX_BINS;
+}
+
+extern "C" size_t ccsd_mmd_workspace_bytes(int32_t n1, int32_t n2, int32_t L) {
+    if (!mmd_dims_ok(n1, n2, L))
+        return no_bytes(CCSD_ERR_INVALID, "ccsd_mmd_workspace_bytes: n1, n2 must be in 1.." + std::to_string(CCSD_MMD_MAX_ROWS) + " and L in 1.." + std::to_string(CCSD_MMD_MAX_BINS));
+    return carve_mmd(n1, n2, L).bytes;
+}
+
+// ccsd_mmd: compute_mmd (mmd.py:230-257) of two sets of histograms: k_mmd_prep per set, k_mmd_pairs for disc(1, 1), disc(2, 2) (both by
+// symmetry) and disc(1, 2), k_mmd_final.  out (4 doubles, device) = disc(1, 1), disc(2, 2), disc(1, 2), mmd.
+extern "C" int ccsd_mmd(const void* h1, int32_t n1, const int32_t* lens1, const void* h2, int32_t n2, const int32_t* lens2, int32_t L,
+                        int32_t dtype, int32_t kind, int32_t flags, double sigma, double distance_scaling, void* workspace, size_t ws_bytes,
+                        double* out, void* stream) {
+    if (n1 < 1 || n2 < 1) return set_err(CCSD_ERR_INVALID, "ccsd_mmd: n1 = " + std::to_string(n1) + ", n2 = " + std::to_string(n2) + ": every set needs n >= 1 rows");
+    if (L < 1) return set_err(CCSD_ERR_INVALID, "ccsd_mmd: L = " + std::to_string(L) + " must be >= 1");
+    if (!mmd_dims_ok(n1, n2, L)) return set_err(CCSD_ERR_INVALID, "ccsd_mmd: n above " + std::to_string(CCSD_MMD_MAX_ROWS) + " or L above " + std::to_string(CCSD_MMD_MAX_BINS));
+    if (!h1 || !h2 || !out) return set_err(CCSD_ERR_INVALID, "ccsd_mmd: NULL argument");
+    if (dtype != CCSD_MMD_INT32 && dtype != CCSD_MMD_FP64) return set_err(CCSD_ERR_INVALID, "ccsd_mmd: unknown dtype");
+    if (kind != CCSD_MMD_EMD && kind != CCSD_MMD_TV && kind != CCSD_MMD_L2) return set_err(CCSD_ERR_INVALID, "ccsd_mmd: unknown kind");
+    if (flags & ~(CCSD_MMD_IS_HIST | CCSD_MMD_DEGREE | CCSD_MMD_F32_PMF)) return set_err(CCSD_ERR_INVALID, "ccsd_mmd: unknown flag");
+    if (kind == CCSD_MMD_EMD && !(flags & CCSD_MMD_IS_HIST))
+        return set_err(CCSD_ERR_INVALID, "ccsd_mmd: the EMD kind needs is_hist (rows of unequal mass have no closed form on the line metric)");
+    if (!(sigma > 0.0)) return set_err(CCSD_ERR_INVALID, "ccsd_mmd: sigma must be > 0");
+    if (kind == CCSD_MMD_EMD && !(distance_scaling > 0.0)) return set_err(CCSD_ERR_INVALID, "ccsd_mmd: distance_scaling must be > 0");
+    const MmdWs w = carve_mmd(n1, n2, L);
+    if (int st = check_scratch("ccsd_mmd", workspace, ws_bytes, w.bytes)) return st;
+    static_assert((int)CCSD_MMD_EMD == (int)EVAL_EMD && (int)CCSD_MMD_TV == (int)EVAL_TV && (int)CCSD_MMD_L2 == (int)EVAL_L2 &&
+                  (int)CCSD_MMD_IS_HIST == (int)EVAL_F_HIST && (int)CCSD_MMD_DEGREE == (int)EVAL_F_DEGREE &&
+                  (int)CCSD_MMD_F32_PMF == (int)EVAL_F_F32PMF, "the header's constants are the kernels'");
+    char* base = (char*)workspace;
+    for (int i = 0; i < 2; ++i) {      // (k_mmd_prep: 256 rows per workgroup; the emulation's one thread takes them in turn)
+        const MmdSet& s = w.s[i];
+        CCSD_LAUNCH(k_mmd_prep, dim3((s.np + 255) / 256), dim3(256), 0, stream, i ? h2 : h1, (int)(dtype == CCSD_MMD_FP64),
+                    (const int*)(i ? lens2 : lens1), s.n, s.np, (int)L, (int)kind, (int)flags, (double*)(base + s.op), (int*)(base + s.mass),
+                    (int*)(base + s.len));
+        LAUNCH_CHECK();
+    }
+    // disc(1, 1), disc(2, 2) -- a set against itself takes the symmetric half --, disc(1, 2): one partial per pair of tiles, b's tiles along grid x
+    const MmdSet* const sets[3][2] = {{&w.s[0], &w.s[0]}, {&w.s[1], &w.s[1]}, {&w.s[0], &w.s[1]}};
+    double* const part = (double*)(base + w.part);
+    int c[3], done = 0;
+    for (int p = 0; p < 3; done += c[p++]) {
+        const MmdSet &a = *sets[p][0], &b = *sets[p][1];
+        c[p] = a.T * b.T;
+        CCSD_LAUNCH(k_mmd_pairs, dim3(b.T, a.T), dim3(CCSD_NTHREADS), 0, stream, (const double*)(base + a.op), (const int*)(base + a.mass),
+                    (const int*)(base + a.len), a.n, a.np, (const double*)(base + b.op), (const int*)(base + b.mass), (const int*)(base + b.len),
+                    b.n, b.np, (int)L, (int)kind, distance_scaling, 2 * sigma * sigma, (int)(&a == &b), part + done);
+        LAUNCH_CHECK();
+    }
+    CCSD_LAUNCH(k_mmd_final, dim3(1), dim3(CCSD_NTHREADS), 0, stream, (const double*)part, c[0], c[1], c[2], (double)n1, (double)n2, out);
+    LAUNCH_CHECK();
+    return CCSD_OK;
+}
+
+// ---------------- spectra (ccsd_k_eig.h) ----------------
+static_assert(CCSD_EIG_MAXN == 512 && CCSD_EIG_MAX_SWEEPS == 30, "the public header states these limits in words");
+// The workspace-resident placement of k_eigvalsh: a bounded grid of workgroups, one slab each -- the size does not grow with B.
+static int eig_grid(int B, int n) { return n <= CCSD_EIG_LDS_MAXN || B < CCSD_EIG_MAX_GRID ? B : CCSD_EIG_MAX_GRID; }
+static size_t eig_slab_bytes(int B, int n) {
+    return n <= CCSD_EIG_LDS_MAXN ? 0 : (size_t)eig_grid(B, n) * n * (n | 1) * 8;
+}
+static std::string eig_too_large(const char* who, const char* what, int n) {
+    return std::string(who) + ": " + what + " = " + std::to_string(n) + " is above CCSD_EIG_MAXN = " + std::to_string(CCSD_EIG_MAXN) +
+           ": the solver is a Jacobi iteration of O(n^3) per sweep with one matrix per compute unit, which larger matrices are out of reach of";
+}
+// one launch of k_eigvalsh over matrices of order <= nmax (every argument checked by the caller)
+static int eig_launch(const double* a, int B, int nmax, long long a_stride, int lda, const int* n_arr, void* slabs, double* w, float* w32,
+                      int* sweeps, const double* edges, int bins, int* hist, void* stream) {
+    const int threads = CCSD_NTHREADS == 1 ? 1 : nmax <= 64 ? 256 : CCSD_EIG_THREADS;
+    if (nmax <= CCSD_EIG_LDS_MAXN) {
+        const size_t lds = (size_t)nmax * (nmax | 1) * 8;
+        // (the kernel's static arrays take another 18 KB: the attribute is raised as soon as the two together could pass 64 KB)
+        if (lds + 20 * 1024 > 64 * 1024) RT_CHECK(rt_set_max_dyn_smem((const void*)k_eigvalsh<true>, lds));
+        CCSD_LAUNCH(k_eigvalsh<true>, dim3(B), dim3(threads), lds, stream, a, B, nmax, a_stride, lda, n_arr, (double*)nullptr, w, w32, sweeps,
+                    edges, bins, hist);
+    } else {
+        CCSD_LAUNCH(k_eigvalsh<false>, dim3(eig_grid(B, nmax)), dim3(threads), 0, stream, a, B, nmax, a_stride, lda, n_arr, (double*)slabs, w,
+                    w32, sweeps, edges, bins, hist);
+    }
+    LAUNCH_CHECK();
+    return CCSD_OK;
+}
+
+extern "C" size_t ccsd_eig_workspace_bytes(int32_t B, int32_t n) {
+    if (B < 1 || n < 1 || n > CCSD_EIG_MAXN)
+        return no_bytes(CCSD_ERR_INVALID, "ccsd_eig_workspace_bytes: B must be >= 1 and n in 1.." + std::to_string(CCSD_EIG_MAXN));
+    return eig_slab_bytes(B, n);
+}
+
+// ccsd_eigvalsh: the eigenvalues of B symmetric n x n fp64 matrices, ascending (k_eigvalsh)
+extern "C" int ccsd_eigvalsh(const double* a, int32_t B, int32_t n, double* w, int32_t* sweeps, void* workspace, size_t ws_bytes,
+                             void* stream) {
+    if (!a || !w) return set_err(CCSD_ERR_INVALID, "ccsd_eigvalsh: NULL argument");
+    if (B < 1) return set_err(CCSD_ERR_INVALID, "ccsd_eigvalsh: B must be >= 1");
+    if (n < 1) return set_err(CCSD_ERR_INVALID, "ccsd_eigvalsh: n = " + std::to_string(n) + " must be >= 1");
+    if (n > CCSD_EIG_MAXN) return set_err(CCSD_ERR_UNSUPPORTED, eig_too_large("ccsd_eigvalsh", "n", n));
+    if (int st = check_scratch("ccsd_eigvalsh", workspace, ws_bytes, eig_slab_bytes(B, n))) return st;
+    return eig_launch(a, B, n, (long long)n * n, n, nullptr, workspace, w, nullptr, (int*)sweeps, nullptr, 0, nullptr, stream);
+}
+
+// Workspace of ccsd_spectral_hist: the fp64 Laplacians (B, N, N), the eigenvalues (B, N) when the caller does not take them, the
+// orders (B,) likewise, and the solver's slabs.
+struct SpectralWs {
+    size_t lap, eig, neff, slabs, bytes;
+};
+static SpectralWs carve_spectral(int64_t B, int64_t N) {
+    SpectralWs w;
+    size_t o = 0;
+    w.lap = o; o += (size_t)B * N * N * 8;
+    w.eig = o; o += (size_t)B * N * 8;
+    w.neff = o; o += ((size_t)B * 4 + 7) & ~(size_t)7;
+    w.slabs = o; o += eig_slab_bytes((int)B, (int)N);
+    w.bytes = o;
+    return w;
+}
+extern "C" size_t ccsd_spectral_workspace_bytes(int32_t B, int32_t N) {
+    if (B < 1 || N < 2 || N > CCSD_FIN_MAXN)
+        return no_bytes(CCSD_ERR_INVALID, "ccsd_spectral_workspace_bytes: B must be >= 1 and N in 2.." + std::to_string(CCSD_FIN_MAXN));
+    return carve_spectral(B, N).bytes;
+}
+
+// ccsd_spectral_hist: spectral_worker (evaluation/stats.py:125-137) of every graph: k_norm_laplacian, then k_eigvalsh with the
+// histogram in its epilogue
+extern "C" int ccsd_spectral_hist(const float* adj, int32_t B, int32_t N, int32_t adj_mode, float thr, const double* edges, int32_t bins,
+                                  int32_t* hist, double* eig, int32_t* n_eff, void* workspace, size_t ws_bytes, void* stream) {
+    static_assert(CCSD_FIN_MAXN <= CCSD_EIG_MAXN, "every graph ccsd_finish takes has a Laplacian the solver takes");
+    if (!adj) return set_err(CCSD_ERR_INVALID, "ccsd_spectral_hist: NULL adj");
+    if (int st = check_batch("ccsd_spectral_hist", B, N, adj_mode, thr)) return st;
+    if (int st = check_hist("ccsd_spectral_hist", edges, bins)) return st;
+    if (!hist && !eig && !n_eff) return CCSD_OK;
+    const SpectralWs w = carve_spectral(B, N);
+    if (int st = check_scratch("ccsd_spectral_hist", workspace, ws_bytes, w.bytes)) return st;
+    char* base = (char*)workspace;
+    double* lap = (double*)(base + w.lap);
+    int* ne = n_eff ? (int*)n_eff : (int*)(base + w.neff);
+    CCSD_LAUNCH(k_norm_laplacian, dim3(B), dim3(CCSD_NTHREADS), 0, stream, adj, (int)N, quant_thr(adj_mode, thr), lap, ne);
+    LAUNCH_CHECK();
+    if (!hist && !eig) return CCSD_OK;
+    return eig_launch(lap, B, N, (long long)N * N, N, ne, base + w.slabs, eig ? eig : (double*)(base + w.eig), nullptr, nullptr, edges,
+                      hist ? (int)bins : 0, (int*)hist, stream);
+}
+
+// The node rule of the hodge entry points is their own, not ccsd_finish's 2..CCSD_FIN_MAXN: N >= 2 (CCSD_ERR_INVALID), then the solver's
+// limit on E = N (N - 1) / 2 (CCSD_ERR_UNSUPPORTED).  Fills *E on success.
+static_assert(CCSD_EIG_HODGE_MAXN * (CCSD_EIG_HODGE_MAXN - 1) / 2 <= CCSD_EIG_MAXN &&
+              (CCSD_EIG_HODGE_MAXN + 1) * CCSD_EIG_HODGE_MAXN / 2 > CCSD_EIG_MAXN, "k_hodge_laplacian's node list holds every N with E <= CCSD_EIG_MAXN");
+static int hodge_edges(const char* who, int N, int* E) {
+    if (N < 2) return set_err(CCSD_ERR_INVALID, std::string(who) + ": N = " + std::to_string(N) + " must be >= 2");
+    const int64_t E64 = (int64_t)N * (N - 1) / 2;
+    if (E64 > CCSD_EIG_MAXN)
+        return set_err(CCSD_ERR_UNSUPPORTED, eig_too_large(who, ("N = " + std::to_string(N) + ": E = N (N - 1) / 2").c_str(), (int)E64));
+    *E = (int)E64;
+    return CCSD_OK;
+}
+
+extern "C" size_t ccsd_hodge_workspace_bytes(int32_t B, int32_t N) {
+    int E = 0;
+    if (B < 1 || N < 2) return no_bytes(CCSD_ERR_INVALID, "ccsd_hodge_workspace_bytes: B must be >= 1 and N >= 2");
+    if (hodge_edges("ccsd_hodge_workspace_bytes", N, &E)) return 0;
+    return (size_t)B * E * E * 8 + eig_slab_bytes(B, E);      // the fp64 hodge Laplacians (B, E, E), then the solver's slabs
+}
+
+// ccsd_hodge_spectrum: hodge_laplacian_spectrum_worker (cc_utils.py:994-1060) of every complex: k_hodge_laplacian, then k_eigvalsh
+extern "C" int ccsd_hodge_spectrum(const float* adj, const uint64_t* cell_bits, int32_t B, int32_t N, int32_t d_min, int32_t d_max,
+                                   int32_t adj_mode, float thr, float* spectrum, int32_t* sweeps, void* workspace, size_t ws_bytes,
+                                   void* stream) {
+    if (!adj || !cell_bits || !spectrum) return set_err(CCSD_ERR_INVALID, "ccsd_hodge_spectrum: NULL argument");
+    if (int st = check_batch("ccsd_hodge_spectrum", B, N, adj_mode, thr, /*fin_n=*/false)) return st;
+    int E = 0;
+    if (int st = hodge_edges("ccsd_hodge_spectrum", N, &E)) return st;
+    if (d_min < 1 || d_max < d_min || d_max > N)
+        return set_err(CCSD_ERR_INVALID, "ccsd_hodge_spectrum: bad cell sizes d_min = " + std::to_string(d_min) + ", d_max = " + std::to_string(d_max));
+    const int64_t K = cell_count(N, d_min, d_max);
+    if (K < 0) return set_err(CCSD_ERR_INVALID, "ccsd_hodge_spectrum: sum C(N, d) for d = d_min..d_max exceeds 2^24");
+    const size_t hbytes = (size_t)B * E * E * 8;
+    if (int st = check_scratch("ccsd_hodge_spectrum", workspace, ws_bytes, hbytes + eig_slab_bytes(B, E))) return st;
+    double* H = (double*)workspace;
+    RT_CHECK(rt_memset_async(H, 0, hbytes, stream));              // (k_hodge_laplacian adds onto zeros)
+    CCSD_LAUNCH(k_hodge_laplacian, dim3(B), dim3(CCSD_NTHREADS), 0, stream, adj, (const unsigned long long*)cell_bits, (int)N, (int)d_min,
+                (int)d_max, (int)K, quant_thr(adj_mode, thr), H);
+    LAUNCH_CHECK();
+    return eig_launch(H, B, E, (long long)E * E, E, nullptr, (char*)workspace + hbytes, nullptr, spectrum, (int*)sweeps, nullptr, 0, nullptr, stream);
+}

@@ -22,6 +22,8 @@
 //                    sets of histograms (the evaluation of finished samples)
 //   ccsd_k_eig.h     k_eigvalsh, k_norm_laplacian, k_hodge_laplacian: a batched symmetric eigenvalue solver (parallel Jacobi) and the
 //                    two matrices whose spectra the reference scores (normalised graph Laplacian, hodge Laplacian F F^T)
+//   ccsd_api.h       host side of the C ABI: plan, route, workspace, launchers, the sampler loop; its last line includes
+//   ccsd_api_samples.h   the host side of the plan-free entry points (ccsd_quantize .. ccsd_hodge_spectrum: operations on finished samples)
 // The product library is built from several translation units compiled in parallel (ccsd_hip.hip: C ABI + the small kernels;
 // ccsd_r2*.hip / ccsd_xa.hip: the explicit instantiations of the two big kernel templates); the host emulation used by the
 // CPU tests includes everything in one unit.  Reference file:line citations sit next to each restated formula.

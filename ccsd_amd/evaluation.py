@@ -3,15 +3,16 @@
 Mirrors, under the reference's names, the part of ccsd/src/evaluation/{mmd,stats}.py and ccsd/src/utils/cc_utils.py:1208-1474 that
 needs no external program:
 
-  compute_mmd with gaussian_emd / gaussian_tv / gaussian          (mmd.py:27-257)       -> PCEngine.mmd (ccsd_mmd)
+  compute_mmd with gaussian_emd / gaussian_tv / gaussian          (mmd.py:27-257)       -> SampleOps.mmd (ccsd_mmd)
   degree_stats, clustering_stats, eval_torch_batch                (stats.py:60-310, 547-570)
   rank1_distrib_stats, rank2_distrib_stats, eval_CC_batch         (cc_utils.py:1208-1474, eval_CC_list)
-  spectral_stats                                                  (stats.py:125-203)    -> PCEngine.spectral_hist (ccsd_spectral_hist)
-  hodge_laplacian_spectrum_stats                                  (cc_utils.py:994-1098) -> PCEngine.hodge_spectrum (ccsd_hodge_spectrum)
+  spectral_stats                                                  (stats.py:125-203)    -> SampleOps.spectral_hist (ccsd_spectral_hist)
+  hodge_laplacian_spectrum_stats                                  (cc_utils.py:994-1098) -> SampleOps.hodge_spectrum (ccsd_hodge_spectrum)
 
 The reference builds networkx graphs / toponetx complexes on the host and solves one pyemd linear program per pair of histograms.
 Here a sample set is a dict of per-sample integer DESCRIPTORS on the device -- `describe()`: the descriptor outputs of
-PCEngine.finish plus `cluster_hist` -- and every score is one ccsd_mmd call on them.  The two spectral scores need an eigenvalue
+SampleOps.finish plus `cluster_hist` -- and every score is one ccsd_mmd call on them (ccsd_amd/samples.py: the plan-free calls; no
+network plan is built here).  The two spectral scores need an eigenvalue
 solver (ccsd_eigvalsh, a batched Jacobi iteration on the device) and cost O(N^3) per sample where the others cost O(N^2): they are
 opt-in, `spectra=True`.  There is no CPU fallback: methods that need an external program raise NotImplementedError (UNSUPPORTED);
 their histograms, computed elsewhere, can still be scored through compute_mmd.
@@ -23,7 +24,7 @@ from typing import Dict, Optional, Sequence
 import numpy as np
 import torch
 
-from .engine import PCEngine
+from .samples import SampleOps
 
 
 class KernelSelector:
@@ -52,16 +53,16 @@ UNSUPPORTED = {
     "rank0_distrib": "the node label it histograms is data-set specific (cc_utils.py:1098-1205)",
 }
 
-_engines: dict = {}
+_sample_ops: dict = {}
 
 
-def _engine(device=None, lib=None) -> PCEngine:
-    """The plan-free entry points (finish, cluster_hist, mmd) hang off a PCEngine; one per (device, library)."""
+def _ops(device=None, lib=None) -> SampleOps:
+    """One SampleOps (it keeps the uploaded bin edges) per (device, library)."""
     device = torch.device(device if device is not None else "cuda")
     key = (str(device), id(lib))
-    if key not in _engines:
-        _engines[key] = PCEngine(None, None, None, None, None, None, N=2, F=1, is_cc=False, device=device, lib=lib)
-    return _engines[key]
+    if key not in _sample_ops:
+        _sample_ops[key] = SampleOps(device, lib)
+    return _sample_ops[key]
 
 
 def _as_rows(samples, device):
@@ -100,7 +101,7 @@ def mmd_terms(samples1, samples2, kernel: KernelSelector = gaussian_emd, is_hist
     inputs (float32 histograms are normalised in float32 by numpy, so by compute_mmd of the reference)."""
     if not isinstance(kernel, KernelSelector):
         raise TypeError("compute_mmd: kernel must be gaussian_emd, gaussian_tv or gaussian of ccsd_amd.evaluation")
-    eng = _engine(device, lib)
+    eng = _ops(device, lib)
     s1, l1, k1 = _as_rows(samples1, eng.device)
     s2, l2, k2 = _as_rows(samples2, eng.device)
     if s1.dtype != s2.dtype:
@@ -128,11 +129,11 @@ def compute_mmd(samples1, samples2, kernel: KernelSelector = gaussian_emd, is_hi
 def describe(adj: torch.Tensor, x: Optional[torch.Tensor] = None, rank2: Optional[torch.Tensor] = None, *, mol: bool = False,
              thr: float = 0.5, bins: int = 100, d_min: int = 0, d_max: int = 0, spectra: bool = False, device=None,
              lib=None) -> Dict[str, torch.Tensor]:
-    """The descriptor dict of a batch: PCEngine.finish's descriptors (degree, degree_hist, edge_hist; n_nodes, x_hist with x;
+    """The descriptor dict of a batch: SampleOps.finish's descriptors (degree, degree_hist, edge_hist; n_nodes, x_hist with x;
     rank2_cell_bits / _count / _hist, rank2_nnz with rank2) plus cluster_hist (B, bins) and tri2 (B, N).  adj: (B, N, N), raw samples,
     quantised samples or a 0/1 data set (any real or integer dtype).  spectra=True adds spectral_hist (B, 200) int32 and, with rank2,
-    hodge_spectrum (B, E) float32 (PCEngine.spectral_hist / hodge_spectrum: an eigenvalue solve per sample)."""
-    eng = _engine(device if device is not None else (adj.device if adj.device.type == "cuda" else None), lib)
+    hodge_spectrum (B, E) float32 (SampleOps.spectral_hist / hodge_spectrum: an eigenvalue solve per sample)."""
+    eng = _ops(device if device is not None else (adj.device if adj.device.type == "cuda" else None), lib)
     mv = lambda t: None if t is None else t.to(device=eng.device, dtype=torch.float32).contiguous()
     adj, x, rank2 = mv(adj), mv(x), mv(rank2)
     out = eng.finish(x, adj, rank2, None, mol=mol, thr=thr, d_min=d_min, d_max=d_max, dense_rank2=False, dense_adj=False)
@@ -184,7 +185,7 @@ def _spectral_rows(obj, kw) -> torch.Tensor:
     if isinstance(obj, dict) and "adj" not in obj:
         raise KeyError("descriptor dict lacks spectral_hist and the adj to compute it from; describe(..., spectra=True) produces it")
     adj = obj["adj"] if isinstance(obj, dict) else torch.as_tensor(obj)
-    eng = _engine(kw.get("device") if kw.get("device") is not None else (adj.device if adj.device.type == "cuda" else None), kw.get("lib"))
+    eng = _ops(kw.get("device") if kw.get("device") is not None else (adj.device if adj.device.type == "cuda" else None), kw.get("lib"))
     adj = adj.to(device=eng.device, dtype=torch.float32).contiguous()
     return eng.spectral_hist(adj, mol=kw.get("mol", False), thr=kw.get("thr", 0.5))["spectral_hist"]
 
@@ -193,7 +194,7 @@ def spectral_stats(ref, pred, kernel: KernelSelector = gaussian_emd, **kw) -> fl
     """spectral_stats (stats.py:140-203): MMD of the 200-bin histograms of the normalised Laplacian's eigenvalues, sigma = 1 and no
     distance scaling.  ref / pred: adjacency batches or descriptor dicts (spectral_hist, or adj to compute it from).  The graphs of
     adjs_to_graphs hold at least one node, so no predicted graph is dropped.  Eigenvalues are clamped to [0, 2] before binning
-    (PCEngine.spectral_hist): the one deliberate difference from the reference."""
+    (SampleOps.spectral_hist): the one deliberate difference from the reference."""
     a, b = _spectral_rows(ref, kw), _spectral_rows(pred, kw)
     for h in (a, b):
         if h.shape[1] != SPECTRAL_BINS:
@@ -246,7 +247,7 @@ def _hodge_rows(desc, worker_kwargs, kw) -> torch.Tensor:
     if missing:
         raise KeyError(f"descriptor dict lacks hodge_spectrum and {missing} to compute it from; describe(..., spectra=True) produces it")
     adj = desc["adj"]
-    eng = _engine(kw.get("device") if kw.get("device") is not None else (adj.device if adj.device.type == "cuda" else None), kw.get("lib"))
+    eng = _ops(kw.get("device") if kw.get("device") is not None else (adj.device if adj.device.type == "cuda" else None), kw.get("lib"))
     adj = adj.to(device=eng.device, dtype=torch.float32).contiguous()
     if "N" in worker_kwargs and int(worker_kwargs["N"]) != adj.shape[1]:
         raise ValueError(f"hodge_laplacian_spectrum_stats: worker_kwargs N = {worker_kwargs['N']} but adj has {adj.shape[1]} nodes")

@@ -36,7 +36,7 @@ import numpy as np
 import torch
 
 from . import loader
-from .engine import PCEngine
+from .samples import SampleOps
 from .loader import AttrDict, _get
 
 _COUNTS = os.path.join(os.path.dirname(os.path.abspath(__file__)), "data", "node_counts.json")
@@ -314,8 +314,7 @@ class Sampler:
         x, adj = (torch.cat([o[k] for o in outs], dim=0) for k in (0, 1))
         rank2 = torch.cat([o[2] for o in outs], dim=0) if self.is_cc else None
         out: Dict[str, torch.Tensor] = {"x": x, "adj": adj, "flags": torch.cat(flags_all, dim=0)}
-        quant = PCEngine(None, None, None, None, None, None, N=adj.shape[-1], F=1, is_cc=False, device=self.device0,
-                         lib=self.extra.get("lib"))
+        quant = SampleOps(self.device0, self.extra.get("lib"))
         # one call: quantize / quantize_mol (graph_utils.py:181-213), the sparse form of the rank-2 incidence matrix for cc_from_incidence
         # (cc_utils.py:243-262) and the per-complex descriptors the evaluators histogram (stats.py:36, cc_utils.py:1208-1334)
         datac = _get(cfg, "data")

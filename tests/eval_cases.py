@@ -18,8 +18,7 @@ import pytest
 import torch
 
 from ccsd_amd import evaluation as ev
-from ccsd_amd.engine import PCEngine
-from tests.helpers import load_golden
+from tests.helpers import load_golden, sample_ops
 
 TOL = 1e-12
 GRAPH_SETS = ("c07", "n17", "k65", "n2", "r65", "r130", "n512", "mol9", "small5", "diag12", "eval_ref", "eval_pred")
@@ -33,10 +32,6 @@ def e1():
         z = load_golden("e1_eval.npz")
         _e1["z"], _e1["meta"] = z, json.loads(str(z["meta"]))
     return _e1["z"], _e1["meta"]
-
-
-def engine(lib, dev, N=2):
-    return PCEngine(None, None, None, None, None, None, N=N, F=1, is_cc=False, device=dev, lib=lib)
 
 
 # ---- clustering ---------------------------------------------------------------------------------------------------------------------
@@ -70,7 +65,7 @@ def cluster_run(lib, dev, name, bins):
     if key not in _cluster_runs:
         z, meta = e1()
         adj = torch.from_numpy(z[f"graphs/{name}/adj"].astype(np.float32)).to(dev)
-        res = engine(lib, dev).cluster_hist(adj, mol=meta["graph_sets"][name]["mol"], bins=bins)
+        res = sample_ops(lib, dev).cluster_hist(adj, mol=meta["graph_sets"][name]["mol"], bins=bins)
         _cluster_runs[key] = {k: v.cpu().numpy() for k, v in res.items()}
     return _cluster_runs[key]
 
@@ -107,7 +102,7 @@ def case_cluster_raw_and_null(lib, dev):
     import ctypes as C
 
     z, meta = e1()
-    eng = engine(lib, dev)
+    eng = sample_ops(lib, dev)
     adj = z["graphs/r65/adj"].astype(np.float32)
     rng = np.random.default_rng(65)
     raw = np.where(adj != 0, 0.5 + rng.random(adj.shape), 0.5 * rng.random(adj.shape)).astype(np.float32)
@@ -135,7 +130,7 @@ def case_cluster_raw_and_null(lib, dev):
 
 
 def case_bad_dims(lib, dev):
-    eng = engine(lib, dev)
+    eng = sample_ops(lib, dev)
     with pytest.raises(ValueError, match=r"N = 1 outside 2\.\.512"):
         eng.cluster_hist(torch.zeros(1, 1, 1, device=dev))
     with pytest.raises(ValueError, match=r"N = 513 outside 2\.\.512"):
@@ -230,7 +225,7 @@ def mmd_set(name):
 def case_mmd_restatement(lib, dev, name):
     """All three kinds and the raw-vector call (gaussian, is_hist=False, sigma=30) against the float64 restatement, and two calls bit-equal."""
     r1, l1, r2, l2 = mmd_set(name)
-    eng = engine(lib, dev)
+    eng = sample_ops(lib, dev)
     t = lambda a: torch.from_numpy(a).to(dev)
     for kind, sigma, scale in MMD_KINDS:
         want = numpy_mmd(r1, l1, r2, l2, kind, True, sigma, scale)
@@ -259,7 +254,7 @@ def case_mmd_identical(lib, dev, name):
     r1, l1, _, _ = mmd_set(name)
     t = torch.from_numpy(r1).to(dev)
     for kind in ("emd", "tv", "l2"):
-        got = engine(lib, dev).mmd(t, t, kind, sigma=0.1, distance_scaling=100.0, lens1=torch.from_numpy(l1).to(dev), lens2=torch.from_numpy(l1).to(dev))
+        got = sample_ops(lib, dev).mmd(t, t, kind, sigma=0.1, distance_scaling=100.0, lens1=torch.from_numpy(l1).to(dev), lens2=torch.from_numpy(l1).to(dev))
         assert abs(got[3].item()) <= TOL and abs(got[0].item() - got[2].item()) <= TOL, (name, kind, got)
 
 

@@ -1,4 +1,4 @@
-"""Shared cases for ccsd_finish / PCEngine.finish (k_finish_rank2, k_finish_graph): run by tests/test_finish.py over the host emulation
+"""Shared cases for ccsd_finish / SampleOps.finish (k_finish_rank2, k_finish_graph): run by tests/test_finish.py over the host emulation
 and by tests/test_gpu_finish.py on the device.  Every comparison is between integers and exact.
 
 Geometries: the smallest that reach each hazard of the rank-2 pass -- K < 64 with B E K not a multiple of 4 (n5), K % 64 != 0 and K % 4 = 2
@@ -12,8 +12,8 @@ import numpy as np
 import pytest
 import torch
 
-from ccsd_amd.engine import PCEngine, cells_from_bits
-from tests.helpers import load_golden
+from ccsd_amd.samples import cells_from_bits
+from tests.helpers import load_golden, sample_ops
 
 # name -> (B, N, F, d_min, d_max); d_min = 0: graph-only
 GEOMETRIES = {
@@ -38,10 +38,6 @@ def special_values():
         t = np.float32(t)
         out += [np.nextafter(t, np.float32(-10)), t, np.nextafter(t, np.float32(10))]
     return np.array(out, np.float32)
-
-
-def engine(lib, dev, N):
-    return PCEngine(None, None, None, None, None, None, N=N, F=1, is_cc=False, device=dev, lib=lib)
 
 
 _inputs = {}
@@ -90,7 +86,7 @@ def run(lib, dev, name, mol):
     if key not in _runs:
         B, N, F, d_min, d_max = GEOMETRIES[name]
         t = inputs(name)
-        eng = engine(lib, dev, N)
+        eng = sample_ops(lib, dev)
         mv = lambda v: None if v is None else v.to(dev)
         res = eng.finish(mv(t["x"]), mv(t["adj"]), mv(t["rank2"]), mv(t["flags"]), mol=mol, d_min=d_min, d_max=d_max)
         _runs[key] = {k: v.cpu() for k, v in res.items()}
@@ -101,7 +97,7 @@ def case_bitwise(lib, dev, name):
     """Test 1: adj_int, rank2_int, the cell bitmask and the cell counts against ccsd_quantize / ccsd_rank2_cells."""
     B, N, F, d_min, d_max = GEOMETRIES[name]
     t = inputs(name)
-    eng = engine(lib, dev, N)
+    eng = sample_ops(lib, dev)
     adj = t["adj"].to(dev)
     for mol in (False, True):
         got = run(lib, dev, name, mol)
@@ -189,7 +185,7 @@ def case_reference_fixture(lib, dev, name, case):
         else:   # kept by f1 as the bits of quantize(rank2)
             shape = tuple(f1[pre + "rank2_shape"].tolist())
             rank2 = torch.from_numpy(np.unpackbits(f1[pre + "rank2_bits"])[:int(np.prod(shape))].reshape(shape).astype(np.float32))
-    eng = engine(lib, dev, m["N"])
+    eng = sample_ops(lib, dev)
     mv = lambda v: None if v is None else v.to(dev)
     got = {k: v.cpu().numpy() for k, v in eng.finish(mv(x), mv(adj), mv(rank2), None, mol=m["mol"], d_min=m["d_min"], d_max=m["d_max"],
                                                      dense_rank2=False, dense_adj=False).items()}
@@ -215,7 +211,7 @@ def case_null_outputs(lib, dev, name="n9"):
     """Test 4: a graph-only call, dense_rank2=False and descriptors only give the same values for what remains."""
     B, N, F, d_min, d_max = GEOMETRIES[name]
     t = inputs(name)
-    eng = engine(lib, dev, N)
+    eng = sample_ops(lib, dev)
     x, adj, rank2, flags = (t[k].to(dev) for k in ("x", "adj", "rank2", "flags"))
     full = run(lib, dev, name, True)
     graph = eng.finish(x, adj, None, flags, mol=True)
@@ -235,7 +231,7 @@ def case_null_outputs(lib, dev, name="n9"):
 
 def case_bad_dims(lib, dev):
     """K that is not sum C(N, d), E that is not N (N - 1) / 2: ValueError with the library's message, nothing launched."""
-    eng = engine(lib, dev, 5)
+    eng = sample_ops(lib, dev)
     t = inputs("n5")
     x, adj, rank2 = (t[k].to(dev) for k in ("x", "adj", "rank2"))
     with pytest.raises(ValueError, match=r"K = 15 is not sum C\(N, d\) for d = 3\.\.5 = 16"):
@@ -246,3 +242,85 @@ def case_bad_dims(lib, dev):
         eng.finish(x, adj, rank2[:, :9].contiguous(), None, d_min=3, d_max=4)
     with pytest.raises(ValueError, match="bad cell sizes"):
         eng.finish(x, adj, rank2, None, d_min=0, d_max=4)
+
+
+# ---- the operations on finished samples build no network plan
+def sample_calls(eng, ev_kw=None):
+    """Every SampleOps method on `eng` at N = 5, d = 3..4 (E = 10, K = 15), B = 3 with the second complex without a cell, and eigvalsh at
+    n = 3 -> {name: tensor}.  With ev_kw, evaluation.describe(..., spectra=True) and evaluation.compute_mmd as well."""
+    B, N, F, d_min, d_max = GEOMETRIES["n5"]
+    dev = eng.device
+    t = {k: v.clone().to(dev) for k, v in inputs("n5").items()}           # (the shared inputs stay as they are)
+    x, flags, rank2 = t["x"], t["flags"], t["rank2"]
+    adj = (t["adj"] + t["adj"].transpose(1, 2)) / 2                        # cluster_hist and the spectra take a symmetric adjacency
+    rank2[1] = 0.0
+    assert rank2.shape == (3, 10, 15)
+    cell = dict(d_min=d_min, d_max=d_max)
+    out = {"quantize": eng.quantize(adj, -1.0), "quantize_rank2": eng.quantize(rank2, 0.5)}
+    out["cells_bits"], out["cells_count"] = eng.rank2_cells(rank2, 0.5)
+    fin = eng.finish(x, adj, rank2, flags, mol=True, **cell)
+    assert int(fin["rank2_cell_count"][1]) == 0 and int(fin["rank2_cell_count"][2]) > 0
+    out.update({"finish/" + k: v for k, v in fin.items()})
+    out.update(eng.cluster_hist(adj, mol=True))
+    out["mmd"] = eng.mmd(fin["degree_hist"], fin["degree_hist"][:2].contiguous(), "emd", degree=True)
+    a = torch.tensor([[[2.0, -1.0, 0.0], [-1.0, 2.0, -1.0], [0.0, -1.0, 2.0]], [[1.0, 0.5, 0.25], [0.5, -3.0, 0.0], [0.25, 0.0, 0.0]]],
+                     dtype=torch.float64, device=dev)
+    out["eig"], out["eig_sweeps"] = eng.eigvalsh(a, sweeps=True)
+    out.update(eng.spectral_hist(adj, mol=True, eig=True))
+    out["hodge"], out["hodge_sweeps"] = eng.hodge_spectrum(adj, fin["rank2_cell_bits"], mol=True, sweeps=True, **cell)
+    assert not out["hodge"][1].any() and out["hodge"][2].any()            # exact zeros for the complex without a cell
+    if ev_kw is not None:
+        from ccsd_amd import evaluation as ev
+
+        desc = ev.describe(adj, x, rank2, mol=True, spectra=True, **cell, **ev_kw)
+        out.update({"describe/" + k: v for k, v in desc.items()})
+        out["compute_mmd"] = torch.tensor(ev.compute_mmd(fin["degree_hist"], fin["degree_hist"][:2], degree=True, **ev_kw), dtype=torch.float64)
+    return {k: v.cpu() for k, v in out.items()}
+
+
+def case_no_plan(lib, dev, monkeypatch):
+    """SampleOps, evaluation.describe and evaluation.compute_mmd run with ccsd_plan_create out of reach, and give what the same calls
+    give on a PCEngine that owns a plan (created before the entry point is taken away)."""
+    from ccsd_amd import evaluation as ev
+    from ccsd_amd.engine import PCEngine
+
+    real = PCEngine(None, None, None, None, None, None, N=5, F=1, is_cc=False, device=dev, lib=lib)
+    assert real.handle and real.query("loop_form") >= 0                   # (it owns a plan, and the plan answers)
+    want = sample_calls(real)
+    fin = {k[len("finish/"):]: v for k, v in want.items() if k.startswith("finish/")}
+    for k in ("degree", "degree_hist", "edge_hist", "n_nodes", "x_hist", "rank2_cell_bits", "rank2_cell_count", "rank2_cell_hist", "rank2_nnz"):
+        want["describe/" + k] = fin[k]
+    for k in ("cluster_hist", "tri2", "spectral_hist"):
+        want["describe/" + k] = want[k]
+    want["describe/hodge_spectrum"] = want["hodge"]
+    want["compute_mmd"] = want["mmd"][3]
+
+    def no_plan(*a):
+        raise AssertionError("ccsd_plan_create called by an operation on finished samples")
+
+    monkeypatch.setattr(lib.c, "ccsd_plan_create", no_plan)
+    monkeypatch.setattr(ev, "_sample_ops", {})
+    got = sample_calls(sample_ops(lib, dev), ev_kw=dict(device=dev, lib=lib))
+    assert set(got) == set(want), set(got) ^ set(want)
+    for k, w in want.items():
+        assert got[k].dtype == w.dtype and torch.equal(got[k], w), k
+
+
+def case_sample_builds_no_plan_for_the_finish(lib, tmp_path):
+    """Sampler.sample() through the harness of tests/test_harness.py creates the plans its sampling function needs and none for the
+    finish: ONE ccsd_plan_create for sample_qm9_CC.  Before SampleOps the count, measured on the commit before it with this very
+    counter, was 2 (the second one the plan of the dummy engine that finish() hung off)."""
+    from tests.test_harness import QM9_CC_YAML, run_harness
+
+    real, calls = lib.c.ccsd_plan_create, []
+
+    def counting(*a):
+        calls.append(1)
+        return real(*a)
+
+    lib.c.ccsd_plan_create = counting
+    try:
+        out, _ = run_harness(tmp_path, lib, None, "sample_qm9_CC", QM9_CC_YAML, max_steps=2)
+    finally:
+        lib.c.ccsd_plan_create = real
+    assert "rank2_cell_hist" in out and len(calls) == 2 - 1, len(calls)

@@ -35,6 +35,13 @@ def load_ckpt_np(name):
     return meta, parts
 
 
+def sample_ops(lib, dev):
+    """The plan-free operations on finished samples (quantize, finish, cluster_hist, mmd, the spectra) over `lib` on `dev`."""
+    from ccsd_amd.samples import SampleOps
+
+    return SampleOps(dev, lib)
+
+
 def rng_matches(g):
     """The goldens regenerate inputs/noise from torch's CPU generator; check that this torch
     build reproduces the stream the fixtures were made with."""

@@ -13,7 +13,7 @@ from ccsd_amd import loader, solver
 from ccsd_amd.engine import PCEngine
 from ccsd_amd.plan import rank2_dim
 from oracle import ccsd_oracle as O
-from tests.helpers import load_ckpt_np, load_golden, make_flags, parse_case, rng_matches
+from tests.helpers import load_ckpt_np, load_golden, make_flags, parse_case, rng_matches, sample_ops
 
 # float tolerance of the path (BASELINE.json north_star: scores within 1e-4 relative).  Two checks per tensor:
 #  (1) max |got - ref| <= RTOL * max|ref|            -- relative to the tensor's scale, since entries pass through zero;
@@ -313,7 +313,7 @@ def case_pc_sampler_identical_seed(gname, ckpt, case, lib, device):
     adj = res[1].cpu()
     assert np.array_equal(O.quantize_mol(adj), g[f"{case}/quantize_mol_adj"])
     assert np.array_equal(O.quantize(adj).numpy(), g[f"{case}/quantize_adj"])
-    eng = PCEngine(None, None, None, None, None, None, N=adj.shape[-1], F=1, is_cc=False, device=device, lib=lib)
+    eng = sample_ops(lib, device)
     assert np.array_equal(eng.quantize(res[1], -1.0).cpu().numpy(), g[f"{case}/quantize_mol_adj"])
     assert np.array_equal(eng.quantize(res[1], 0.5).cpu().numpy(), g[f"{case}/quantize_adj"].astype(np.int64))
     if "rank2" in names:
@@ -767,7 +767,7 @@ def case_rank2_cells(lib, device):
 
     from ccsd_amd.engine import cells_from_bits
 
-    eng = PCEngine(None, None, None, None, None, None, N=9, F=1, is_cc=False, device=device, lib=lib)
+    eng = sample_ops(lib, device)
     torch.manual_seed(3)
     for (N, d_min, d_max) in ((9, 3, 9), (5, 3, 4), (12, 3, 4)):
         E, K = rank2_dim(N, d_min, d_max)
@@ -923,7 +923,7 @@ def case_zinc5b(lib, device):
     for t in (0.5, 1.5, 2.5):
         safe &= (ref - t).abs() > tol
     assert safe.double().mean().item() > 0.99
-    q = PCEngine(None, None, None, None, None, None, N=N, F=1, is_cc=False, device=device, lib=lib).quantize(res[1], -1.0).cpu()
+    q = sample_ops(lib, device).quantize(res[1], -1.0).cpu()
     assert torch.equal(q[safe], torch.from_numpy(g["k3/quantize_mol_adj"])[safe])
 
 

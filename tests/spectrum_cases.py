@@ -24,8 +24,7 @@ import torch
 
 from ccsd_amd import _lib
 from ccsd_amd import evaluation as ev
-from ccsd_amd.engine import PCEngine
-from tests.helpers import load_golden
+from tests.helpers import load_golden, sample_ops
 
 TOL = 1e-12
 SOLVER_SIZES = (1, 2, 3, 7, 63, 64, 65, 77, 128, 129, 190)      # (77: dynamic + static LDS first pass 64 KB together)
@@ -39,10 +38,6 @@ def e2():
         z = load_golden("e2_spectrum.npz")
         _e2["z"], _e2["meta"] = z, json.loads(str(z["meta"]))
     return _e2["z"], _e2["meta"]
-
-
-def engine(lib, dev):
-    return PCEngine(None, None, None, None, None, None, N=2, F=1, is_cc=False, device=dev, lib=lib)
 
 
 # ---- solver -------------------------------------------------------------------------------------------------------------------------
@@ -120,7 +115,7 @@ def check_solver(eng, dev, a, kind, diagonal=False, twice=True):
 
 
 def case_solver(lib, dev, n, B=5, kinds=None, twice=True):
-    eng = engine(lib, dev)
+    eng = sample_ops(lib, dev)
     worst = {}
     for kind, a in solver_matrices(n, B).items():
         if kinds is None or kind in kinds:
@@ -135,12 +130,12 @@ def case_solver_trap(lib, dev):
     pins the early exit and the sort only.  The rotation's large-|theta| branch is reached by the "trap" kind of solver_matrices at
     n >= 3, where the tiny entry sits in a pair of the first round while the rest of the matrix keeps the sweep going."""
     a = np.array([[[0.0, 1e-200], [1e-200, 1.0]], [[5.0, 1e-200], [1e-200, 4.0]]])
-    w = engine(lib, dev).eigvalsh(torch.from_numpy(a).to(dev)).cpu().numpy()
+    w = sample_ops(lib, dev).eigvalsh(torch.from_numpy(a).to(dev)).cpu().numpy()
     assert np.array_equal(w, [[0.0, 1.0], [4.0, 5.0]]), w
 
 
 def case_solver_bad_dims(lib, dev):
-    eng = engine(lib, dev)
+    eng = sample_ops(lib, dev)
     a = torch.zeros((1, 4, 4), dtype=torch.float64, device=dev)
     w = torch.zeros((1, 4), dtype=torch.float64, device=dev)
     p = lambda t: C.c_void_p(t.data_ptr())
@@ -170,7 +165,7 @@ def case_solver_batch_walk(lib, dev):
     rng = np.random.default_rng(129)
     a = rng.standard_normal((B, n, n)) * (1.0 + np.arange(B))[:, None, None]
     a = (a + a.transpose(0, 2, 1)) / 2
-    w, sw = engine(lib, dev).eigvalsh(torch.from_numpy(a).to(dev), sweeps=True)
+    w, sw = sample_ops(lib, dev).eigvalsh(torch.from_numpy(a).to(dev), sweeps=True)
     w, sw = w.cpu().numpy(), sw.cpu().numpy()
     bound = SOLVER_FACTOR * n * 2.0 ** -53 * np.sqrt((a * a).sum((1, 2)))
     assert (np.abs(w - np.linalg.eigvalsh(a)).max(1) <= bound).all()
@@ -209,7 +204,7 @@ def spectral_run(lib, dev, name):
     if key not in _spectral_runs:
         z, meta = e2()
         adj = torch.from_numpy(z[f"graphs/{name}/adj"].astype(np.float32)).to(dev)
-        res = engine(lib, dev).spectral_hist(adj, mol=meta["graph_sets"][name]["mol"], eig=True)
+        res = sample_ops(lib, dev).spectral_hist(adj, mol=meta["graph_sets"][name]["mol"], eig=True)
         _spectral_runs[key] = {k: v.cpu().numpy() for k, v in res.items()}
     return _spectral_runs[key]
 
@@ -271,7 +266,7 @@ def case_spectral_landmarks(lib, dev):
 def case_spectral_small(lib, dev):
     """Edgeless graph -> one count in bin 0; a single edge -> bins 0 and 199; isolated and masked nodes are not counted; a diagonal of
     ones is ignored; raw samples give the counts of their quantised form; mol mode weighs by bond order."""
-    eng = engine(lib, dev)
+    eng = sample_ops(lib, dev)
     a = np.zeros((5, 6, 6), np.float32)
     a[1, 1, 4] = a[1, 4, 1] = 1                                                    # a single edge among isolated nodes
     for i, j in ((0, 1), (1, 2), (0, 2), (2, 3)):                                  # triangle + tail, nodes 4 and 5 masked
@@ -310,7 +305,7 @@ def case_spectral_above_lds(lib, dev):
 
     adj = np.concatenate([e1()[0]["graphs/r130/adj"]] * 2)[:3].astype(np.float32)
     adj[2, 100:, :] = adj[2, :, 100:] = 0                                              # a third graph with another order
-    res = engine(lib, dev).spectral_hist(torch.from_numpy(adj).to(dev), eig=True)
+    res = sample_ops(lib, dev).spectral_hist(torch.from_numpy(adj).to(dev), eig=True)
     h, e, n = (res[k].cpu().numpy() for k in ("spectral_hist", "spectral_eig", "spectral_n"))
     counts, eig, n_eff = numpy_spectral(adj, False)
     assert np.array_equal(n, n_eff) and len(set(n.tolist())) == 3 and n.max() > 128
@@ -321,7 +316,7 @@ def case_spectral_above_lds(lib, dev):
 
 
 def case_spectral_bad_dims(lib, dev):
-    eng = engine(lib, dev)
+    eng = sample_ops(lib, dev)
     p = lambda t: C.c_void_p(t.data_ptr())
     adj = torch.zeros((1, 4, 4), dtype=torch.float32, device=dev)
     edges = torch.from_numpy(np.linspace(-1e-5, 2, 201)).to(dev)
@@ -396,13 +391,13 @@ def case_hodge(lib, dev, name):
     # a second call: the same bits (H is built without atomics, the solver sums in a fixed order)
     info, x, adj, rank2, _ = hodge_inputs(name, "ref")
     d = hodge_run(lib, dev, name, "ref")
-    again = engine(lib, dev).hodge_spectrum(torch.from_numpy(adj).to(dev), d["rank2_cell_bits"], d_min=info["d_min"], d_max=info["d_max"])
+    again = sample_ops(lib, dev).hodge_spectrum(torch.from_numpy(adj).to(dev), d["rank2_cell_bits"], d_min=info["d_min"], d_max=info["d_max"])
     assert torch.equal(again, d["hodge_spectrum"])
 
 
 def case_hodge_small(lib, dev):
     """One, two and N nodes; a cell whose edges are partly absent from the graph; sweeps reported."""
-    eng = engine(lib, dev)
+    eng = sample_ops(lib, dev)
     N, d_min, d_max = 5, 3, 4
     cells = [c for d in range(d_min, d_max + 1) for c in combinations(range(N), d)]
     E, K = 10, len(cells)
@@ -432,7 +427,7 @@ def case_hodge_small(lib, dev):
 
 def case_hodge_too_large(lib, dev):
     """E > 512 (N = 33: E = 528): CCSD_ERR_UNSUPPORTED from C, NotImplementedError naming the size from Python."""
-    eng = engine(lib, dev)
+    eng = sample_ops(lib, dev)
     p = lambda t: C.c_void_p(t.data_ptr())
     adj = torch.zeros((1, 33, 33), dtype=torch.float32, device=dev)
     bits = torch.zeros((1, (math.comb(33, 3) + 63) // 64), dtype=torch.int64, device=dev)
@@ -472,8 +467,8 @@ def case_spectral_scores(lib, dev):
     t = lambda name: torch.from_numpy(z[f"graphs/{name}/adj"].astype(np.float32)).to(dev)
     for a, b in (("s12a", "s12b"), ("mol9", "s12b")):
         mol = meta["graph_sets"][a]["mol"]
-        ra = engine(lib, dev).spectral_hist(t(a), mol=mol)
-        rb = engine(lib, dev).spectral_hist(t(b))
+        ra = sample_ops(lib, dev).spectral_hist(t(a), mol=mol)
+        rb = sample_ops(lib, dev).spectral_hist(t(b))
         key = f"spectral/{a}_{b}"
         # (the emd scores say little about the histograms: with sigma = 1 and no distance scaling the kernel of two distinct 200-bin
         # histograms is ~0, so the score is ~1/n1 + 1/n2 = 0.58333 for both pairs.  The tv scores and the exact counts carry the check.)

@@ -122,3 +122,44 @@ def test_unshipped_switches_fail_like_the_reference():
 
     m = loader.load_model(dict(st["bn_f"]["params"]))
     assert m.params["use_bn"] is True
+
+
+# The four workspace sizes of the plan-free entry points: ((arguments), bytes, ccsd_last_error of a refused size).  The literals were
+# RECORDED from the emulation library of the commit before these entry points moved to ccsd_api_samples.h -- not computed by the code under
+# test: the layouts must stay byte for byte.  n = 128 | 129 lie on the two sides of CCSD_EIG_LDS_MAXN (E = 120 | 136 for N = 16 | 17), and
+# B = 3 is above the emulation's slab grid (CCSD_EIG_MAX_GRID = 2 there), where the slabs stop growing with B.
+_EIG_ERR = "ccsd_eig_workspace_bytes: B must be >= 1 and n in 1..512"
+_MMD_ERR = "ccsd_mmd_workspace_bytes: n1, n2 must be in 1..1048576 and L in 1..65536"
+_SPECTRAL_ERR = "ccsd_spectral_workspace_bytes: B must be >= 1 and N in 2..512"
+_HODGE_ERR = "ccsd_hodge_workspace_bytes: B must be >= 1 and N >= 2"
+WORKSPACE_BYTES = {
+    "ccsd_mmd_workspace_bytes": [
+        ((1, 1, 1), 2072, None), ((3, 2, 5), 6168, None), ((64, 65, 10), 16952, None), ((200, 130, 100), 362280, None),
+        ((0, 3, 5), 0, _MMD_ERR), ((3, 3, 0), 0, _MMD_ERR), ((1048577, 1, 1), 0, _MMD_ERR), ((1, 1, 65537), 0, _MMD_ERR),
+    ],
+    "ccsd_eig_workspace_bytes": [
+        ((1, 1), 0, None), ((5, 128), 0, None), ((1, 129), 133128, None), ((2, 129), 266256, None), ((3, 129), 266256, None),
+        ((7, 512), 4202496, None), ((0, 4), 0, _EIG_ERR), ((1, 0), 0, _EIG_ERR), ((1, 513), 0, _EIG_ERR),
+    ],
+    "ccsd_spectral_workspace_bytes": [
+        ((1, 2), 56, None), ((3, 5), 736, None), ((4, 128), 528400, None), ((1, 129), 267296, None), ((3, 129), 668752, None),
+        ((5, 512), 14708760, None), ((0, 5), 0, _SPECTRAL_ERR), ((1, 1), 0, _SPECTRAL_ERR), ((1, 513), 0, _SPECTRAL_ERR),
+    ],
+    "ccsd_hodge_workspace_bytes": [
+        ((1, 2), 8, None), ((3, 5), 2400, None), ((2, 16), 230400, None), ((1, 17), 297024, None), ((3, 17), 742016, None),
+        ((2, 32), 7880448, None), ((0, 5), 0, _HODGE_ERR), ((1, 1), 0, _HODGE_ERR),
+        ((1, 33), 0, "ccsd_hodge_workspace_bytes: N = 33: E = N (N - 1) / 2 = 528 is above CCSD_EIG_MAXN = 512: the solver is a Jacobi iteration "
+                     "of O(n^3) per sweep with one matrix per compute unit, which larger matrices are out of reach of"),
+    ],
+}
+
+
+@pytest.mark.parametrize("fn", list(WORKSPACE_BYTES))
+def test_emu_workspace_bytes_are_the_recorded_ones(fn):
+    from tests.emu_util import emu_library
+
+    emu = emu_library()
+    for args, want, err in WORKSPACE_BYTES[fn]:
+        assert getattr(emu, fn)(*args) == want, (fn, args)
+        if err is not None:
+            assert emu.ccsd_last_error().decode() == err, (fn, args)

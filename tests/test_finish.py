@@ -37,6 +37,14 @@ def test_emu_bad_dims(lib):
     fc.case_bad_dims(lib, DEV)
 
 
+def test_emu_sample_ops_need_no_plan(lib, monkeypatch):
+    fc.case_no_plan(lib, DEV, monkeypatch)
+
+
+def test_emu_sample_builds_no_plan_for_the_finish(lib, tmp_path):
+    fc.case_sample_builds_no_plan_for_the_finish(lib, tmp_path)
+
+
 def test_special_values_straddle_every_threshold():
     sp = fc.special_values()
     assert len(sp) == 11 and (sp[:2] == 0).all() and bool(fc.np.signbit(sp[0]))

@@ -1,4 +1,4 @@
-"""Sampler.sample() finishes through PCEngine.finish (one C call): every key it returned before keeps the value the three separate
+"""Sampler.sample() finishes through SampleOps.finish (one C call): every key it returned before keeps the value the three separate
 calls -- quantize, quantize(...).to(uint8), rank2_cells -- give on the same tensors, the descriptors are new keys, and
 dense_rank2=False drops exactly the dense incidence tensors.  CPU: over the host emulation, with the machinery of tests/test_harness.py."""
 import os
@@ -6,9 +6,9 @@ import os
 import numpy as np
 import torch
 
-from ccsd_amd.engine import PCEngine
 from tests.emu_util import emu_library
 from tests.finish_cases import numpy_descriptors
+from tests.helpers import sample_ops
 from tests.test_harness import ENZYMES_YAML, QM9_CC_YAML, run_harness
 
 OLD_MOL_CC = {"adj_int", "adj_onehot", "x_onehot", "rank2", "rank2_int", "rank2_cell_bits", "rank2_cell_count", "flags", "x", "adj",
@@ -19,7 +19,7 @@ NEW_CC = {"rank2_cell_hist", "rank2_nnz"}
 
 def separate_calls(lib, out, mol):
     """What sample() computed before this feature, on the tensors it returned."""
-    q = PCEngine(None, None, None, None, None, None, N=out["adj"].shape[-1], F=1, is_cc=False, device="cpu", lib=lib)
+    q = sample_ops(lib, "cpu")
     want = {}
     if mol:
         s = q.quantize(out["adj"], -1.0) - 1

@@ -37,11 +37,11 @@ def test_production_loop_matches_the_reference_in_distribution(capsys):
     x, adj, rank2 = fn(*models, flags)[:3]
     torch.cuda.synchronize()
     assert torch.isfinite(adj).all() and torch.isfinite(rank2).all()
-    from tests.finish_cases import engine
     from ccsd_amd import _lib
+    from tests.helpers import sample_ops
 
-    res = engine(_lib.get_library(), DEV, N).finish(x, adj, rank2, flags, mol=True, d_min=d_min, d_max=d_max, dense_rank2=False,
-                                                    dense_adj=False)
+    res = sample_ops(_lib.get_library(), DEV).finish(x, adj, rank2, flags, mol=True, d_min=d_min, d_max=d_max, dense_rank2=False,
+                                                     dense_adj=False)
     got = {k: v.cpu().numpy() for k, v in res.items()}
     got["cell_hist"] = got["rank2_cell_hist"]
     bins = dc.nonempty_bins(d)

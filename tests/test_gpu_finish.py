@@ -38,6 +38,10 @@ def test_bad_dims(lib):
     fc.case_bad_dims(lib, DEV)
 
 
+def test_sample_ops_need_no_plan(lib, monkeypatch):
+    fc.case_no_plan(lib, DEV, monkeypatch)
+
+
 def test_no_int64_temporary(lib):
     """At N = 38, d = 3, B = 2 the device peak rises by at most the bytes of the returned tensors plus 1 MB (the three separate calls
     exceed that by the int64 copy of rank2, 8 B E K bytes).  A condition on the allocations, not a measurement."""
@@ -45,7 +49,7 @@ def test_no_int64_temporary(lib):
     E, K = N * (N - 1) // 2, 8436
     gen = torch.Generator(device=DEV).manual_seed(3)
     x, adj, rank2 = (torch.randn(s, device=DEV, generator=gen) for s in ((B, N, F), (B, N, N), (B, E, K)))
-    eng = fc.engine(lib, DEV, N)
+    eng = fc.sample_ops(lib, DEV)
     torch.cuda.synchronize()
     torch.cuda.reset_peak_memory_stats()
     before = torch.cuda.memory_allocated()

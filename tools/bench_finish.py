@@ -1,5 +1,5 @@
 """Time of the finish of one sampled chunk -- everything Sampler.sample() does to the final tensors -- through the one-call path
-(PCEngine.finish: k_finish_graph + k_finish_rank2) against the three-call sequence it replaces (quantize(adj), quantize(rank2).to(uint8),
+(SampleOps.finish: k_finish_graph + k_finish_rank2) against the three-call sequence it replaces (quantize(adj), quantize(rank2).to(uint8),
 rank2_cells(rank2)), in the same process on the same tensors, at three shapes:
 
     qm9_CC                     N =  9, d 3..9  (E =  36, K =   466), B = 1024
@@ -27,7 +27,7 @@ import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
-from ccsd_amd.engine import PCEngine  # noqa: E402
+from ccsd_amd.samples import SampleOps  # noqa: E402
 
 SHAPES = {       # name -> (B, N, F, d_min, d_max, molecule)
     "qm9_CC": (1024, 9, 4, 3, 9, True),
@@ -69,7 +69,7 @@ def bench(name, a, lib, dev, gpu):
     x = torch.rand((B, N, F), device=dev, generator=gen)
     adj = torch.rand((B, N, N), device=dev, generator=gen) * 3.2
     rank2 = torch.rand((B, E, K), device=dev, generator=gen) * 0.56
-    eng = PCEngine(None, None, None, None, None, None, N=N, F=1, is_cc=False, device=dev, lib=lib)
+    eng = SampleOps(dev, lib)
     new = lambda: eng.finish(x, adj, rank2, None, mol=mol, d_min=d_min, d_max=d_max)
     old = lambda: three_calls(eng, adj, rank2, mol)
     r2 = lambda: eng.finish(None, adj, rank2, None, mol=mol, d_min=d_min, d_max=d_max, dense_adj=False, descriptors=False)

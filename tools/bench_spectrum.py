@@ -99,7 +99,7 @@ def main():
     torch.set_num_threads(1)              # (the pool's threads are the parallelism: one matrix per call)
     pool = ThreadPoolExecutor(a.threads)
     name = torch.cuda.get_device_name(0) if gpu else ("host emulation" if a.emulate else None)
-    eng = ev._engine(dev, lib) if run else None
+    eng = ev._ops(dev, lib) if run else None
     lines = []
 
     def emit(rec):
