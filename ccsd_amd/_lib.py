@@ -25,7 +25,7 @@ EXPORTS = [
     "ccsd_last_error", "ccsd_score", "ccsd_init_state", "ccsd_corrector_norms", "ccsd_corrector_apply",
     "ccsd_predictor", "ccsd_s4_apply", "ccsd_sampler_run", "ccsd_quantize", "ccsd_rank2_cells", "ccsd_profile_kernel", "ccsd_profile_stride", "ccsd_profile_read", "ccsd_profile_launches", "ccsd_debug_stamps",
     "ccsd_noise_draws", "ccsd_plan_query", "ccsd_sampler_run_ex", "ccsd_finish",
-    "ccsd_cluster_hist", "ccsd_mmd_workspace_bytes", "ccsd_mmd",
+    "ccsd_cluster_hist", "ccsd_orbit_counts", "ccsd_mmd_workspace_bytes", "ccsd_mmd",
     "ccsd_eig_workspace_bytes", "ccsd_eigvalsh", "ccsd_spectral_workspace_bytes", "ccsd_spectral_hist",
     "ccsd_hodge_workspace_bytes", "ccsd_hodge_spectrum",
 ]
@@ -68,6 +68,7 @@ MMD_EMD, MMD_TV, MMD_L2 = 0, 1, 2
 MMD_INT32, MMD_FP64 = 0, 1
 MMD_IS_HIST, MMD_DEGREE, MMD_F32_PMF = 1, 2, 4
 CLUSTER_MAX_BINS, MMD_MAX_ROWS, MMD_MAX_BINS = 1024, 1 << 20, 1 << 16      # CCSD_CLUSTER_MAX_BINS, CCSD_MMD_MAX_ROWS, CCSD_MMD_MAX_BINS
+ORBITS = 15                                                               # CCSD_ORBITS: ORCA's orbits of the graphlets on 2..4 nodes
 EIG_MAXN, EIG_MAX_SWEEPS = 512, 30                                        # CCSD_EIG_MAXN; the sweep cap of k_eigvalsh
 
 
@@ -169,6 +170,8 @@ class Library:
         L.ccsd_finish.restype = C.c_int
         L.ccsd_cluster_hist.argtypes = [vp, i32, i32, i32, f32, vp, i32, vp, vp, vp]
         L.ccsd_cluster_hist.restype = C.c_int
+        L.ccsd_orbit_counts.argtypes = [vp, i32, i32, i32, f32, vp, vp, vp, vp]
+        L.ccsd_orbit_counts.restype = C.c_int
         L.ccsd_mmd_workspace_bytes.argtypes = [i32, i32, i32]
         L.ccsd_mmd_workspace_bytes.restype = sz
         L.ccsd_mmd.argtypes = [vp, i32, vp, vp, i32, vp, i32, i32, i32, i32, C.c_double, C.c_double, vp, sz, vp, vp]

@@ -1,5 +1,5 @@
 // ccsd_api_samples.h -- host side of the PLAN-FREE entry points of include/ccsd_hip.h: the operations on finished samples, which take
-// tensors and sizes and never a ccsd_plan_t (ccsd_quantize, ccsd_rank2_cells, ccsd_finish, ccsd_cluster_hist, ccsd_mmd, ccsd_eigvalsh,
+// tensors and sizes and never a ccsd_plan_t (ccsd_quantize, ccsd_rank2_cells, ccsd_finish, ccsd_cluster_hist, ccsd_orbit_counts, ccsd_mmd, ccsd_eigvalsh,
 // ccsd_spectral_hist, ccsd_hodge_spectrum and their *_workspace_bytes).  Included by ccsd_api.h as its last line; of what stands above it
 // there, this file uses set_err, grid_for, RT_CHECK and LAUNCH_CHECK only.
 //
@@ -131,6 +131,19 @@ extern "C" int ccsd_cluster_hist(const float* adj, int32_t B, int32_t N, int32_t
     if (!tri2 && !cluster_hist) return CCSD_OK;
     CCSD_LAUNCH(k_cluster_hist, dim3(B), dim3(CCSD_NTHREADS), 0, stream, adj, (int)N, quant_thr(adj_mode, thr), edges, (int)bins, (int*)tri2,
                 (int*)cluster_hist);
+    LAUNCH_CHECK();
+    return CCSD_OK;
+}
+
+// ccsd_orbit_counts: the 4-node graphlet orbit counts of every graph (k_orbit_counts, ccsd_k_orbit.h; same quantiser arguments as ccsd_finish)
+static_assert(CCSD_ORBITS == CCSD_NORBITS, "the header's orbit count is k_orbit_counts' row length");
+extern "C" int ccsd_orbit_counts(const float* adj, int32_t B, int32_t N, int32_t adj_mode, float thr, int64_t* node_orbits,
+                                 int64_t* graph_orbits, int32_t* orbit_nodes, void* stream) {
+    if (!adj) return set_err(CCSD_ERR_INVALID, "ccsd_orbit_counts: NULL adj");
+    if (int st = check_batch("ccsd_orbit_counts", B, N, adj_mode, thr)) return st;
+    if (!node_orbits && !graph_orbits && !orbit_nodes) return CCSD_OK;
+    CCSD_LAUNCH(k_orbit_counts, dim3(B), dim3(CCSD_NTHREADS), 0, stream, adj, (int)N, quant_thr(adj_mode, thr), (long long*)node_orbits,
+                (long long*)graph_orbits, (int*)orbit_nodes);
     LAUNCH_CHECK();
     return CCSD_OK;
 }

@@ -20,6 +20,8 @@
 //   ccsd_k_finish.h  k_finish_rank2, k_finish_graph: quantised outputs, cell bitmask and per-complex descriptors in one pass per tensor
 //   ccsd_k_eval.h    k_cluster_hist, k_mmd_prep, k_mmd_pairs, k_mmd_final: clustering-coefficient histograms and the fp64 MMD of two
 //                    sets of histograms (the evaluation of finished samples)
+//   ccsd_k_orbit.h   k_orbit_counts: the 4-node graphlet orbit counts per node and per graph from the same bit-mask rows, by a closed
+//                    form (what the reference's "orbit" score reads from the external orca program)
 //   ccsd_k_eig.h     k_eigvalsh, k_norm_laplacian, k_hodge_laplacian: a batched symmetric eigenvalue solver (parallel Jacobi) and the
 //                    two matrices whose spectra the reference scores (normalised graph Laplacian, hodge Laplacian F F^T)
 //   ccsd_api.h       host side of the C ABI: plan, route, workspace, launchers, the sampler loop; its last line includes
@@ -36,5 +38,6 @@
 #include "ccsd_k_update.h"
 #include "ccsd_k_finish.h"
 #include "ccsd_k_eval.h"
+#include "ccsd_k_orbit.h"
 #include "ccsd_k_eig.h"
 #include "ccsd_k_lg.h"

@@ -8,14 +8,17 @@ needs no external program:
   rank1_distrib_stats, rank2_distrib_stats, eval_CC_batch         (cc_utils.py:1208-1474, eval_CC_list)
   spectral_stats                                                  (stats.py:125-203)    -> SampleOps.spectral_hist (ccsd_spectral_hist)
   hodge_laplacian_spectrum_stats                                  (cc_utils.py:994-1098) -> SampleOps.hodge_spectrum (ccsd_hodge_spectrum)
+  orbit_stats_all                                                 (stats.py:343-435)    -> SampleOps.orbit_counts (ccsd_orbit_counts)
 
 The reference builds networkx graphs / toponetx complexes on the host and solves one pyemd linear program per pair of histograms.
 Here a sample set is a dict of per-sample integer DESCRIPTORS on the device -- `describe()`: the descriptor outputs of
 SampleOps.finish plus `cluster_hist` -- and every score is one ccsd_mmd call on them (ccsd_amd/samples.py: the plan-free calls; no
 network plan is built here).  The two spectral scores need an eigenvalue
 solver (ccsd_eigvalsh, a batched Jacobi iteration on the device) and cost O(N^3) per sample where the others cost O(N^2): they are
-opt-in, `spectra=True`.  There is no CPU fallback: methods that need an external program raise NotImplementedError (UNSUPPORTED);
-their histograms, computed elsewhere, can still be scored through compute_mmd.
+opt-in, `spectra=True`.  The orbit score counts 4-node graphlets per graph on the device where the reference starts the orca program
+once per graph; its cost grows with the triangles of a graph, so it is opt-in as well, `orbits=True`.  There is no CPU fallback:
+methods that need an external program raise NotImplementedError (UNSUPPORTED); their histograms, computed elsewhere, can still be
+scored through compute_mmd.
 """
 from __future__ import annotations
 
@@ -46,7 +49,7 @@ gaussian_tv = KernelSelector("gaussian_tv", "tv")
 gaussian = KernelSelector("gaussian", "l2")
 
 UNSUPPORTED = {
-    "orbit": "orbit counts come from the external orca program (evaluation/stats.py:343-379)",
+    "orbit": "counts the 4-node graphlet orbits of every graph (evaluation/stats.py:343-435) and is opt-in: pass orbits=True",
     "spectral": "runs a symmetric eigenvalue solver per graph (evaluation/stats.py:125-137) and is opt-in: pass spectra=True",
     "hodge_laplacian_spectrum": "runs a symmetric eigenvalue solver per complex (cc_utils.py:994-1060) and is opt-in: pass spectra=True",
     "nspdk": "needs the EDeN graph vectoriser (evaluation/eden.py, mmd.py:331-337)",
@@ -127,17 +130,20 @@ def compute_mmd(samples1, samples2, kernel: KernelSelector = gaussian_emd, is_hi
 # descriptors
 # ---------------------------------------------------------------------------------------------
 def describe(adj: torch.Tensor, x: Optional[torch.Tensor] = None, rank2: Optional[torch.Tensor] = None, *, mol: bool = False,
-             thr: float = 0.5, bins: int = 100, d_min: int = 0, d_max: int = 0, spectra: bool = False, device=None,
-             lib=None) -> Dict[str, torch.Tensor]:
+             thr: float = 0.5, bins: int = 100, d_min: int = 0, d_max: int = 0, spectra: bool = False, orbits: bool = False,
+             device=None, lib=None) -> Dict[str, torch.Tensor]:
     """The descriptor dict of a batch: SampleOps.finish's descriptors (degree, degree_hist, edge_hist; n_nodes, x_hist with x;
     rank2_cell_bits / _count / _hist, rank2_nnz with rank2) plus cluster_hist (B, bins) and tri2 (B, N).  adj: (B, N, N), raw samples,
     quantised samples or a 0/1 data set (any real or integer dtype).  spectra=True adds spectral_hist (B, 200) int32 and, with rank2,
-    hodge_spectrum (B, E) float32 (SampleOps.spectral_hist / hodge_spectrum: an eigenvalue solve per sample)."""
+    hodge_spectrum (B, E) float32 (SampleOps.spectral_hist / hodge_spectrum: an eigenvalue solve per sample).  orbits=True adds
+    orbit_counts (B, 15) int64 and orbit_nodes (B,) int32 (SampleOps.orbit_counts)."""
     eng = _ops(device if device is not None else (adj.device if adj.device.type == "cuda" else None), lib)
     mv = lambda t: None if t is None else t.to(device=eng.device, dtype=torch.float32).contiguous()
     adj, x, rank2 = mv(adj), mv(x), mv(rank2)
     out = eng.finish(x, adj, rank2, None, mol=mol, thr=thr, d_min=d_min, d_max=d_max, dense_rank2=False, dense_adj=False)
     out.update(eng.cluster_hist(adj, mol=mol, thr=thr, bins=bins))
+    if orbits:
+        out.update(eng.orbit_counts(adj, mol=mol, thr=thr))
     if spectra:
         out.update(eng.spectral_hist(adj, mol=mol, thr=thr))
         if rank2 is not None:
@@ -200,6 +206,28 @@ def spectral_stats(ref, pred, kernel: KernelSelector = gaussian_emd, **kw) -> fl
         if h.shape[1] != SPECTRAL_BINS:
             raise ValueError(f"spectral_stats: spectral_hist has {h.shape[1]} bins, not {SPECTRAL_BINS}")
     return compute_mmd(a, b, kernel, **_dev_kw(kw))
+
+
+def orbit_rows(obj, kw) -> torch.Tensor:
+    """The rows orbit_stats_all scores, (B, 15) float64: a graph's orbit counts divided by its node count -- the IEEE division the
+    reference performs on its int64 sums (stats.py:414).  Taken from a descriptor dict that holds orbit_counts and orbit_nodes,
+    computed from its `adj` (or from a raw batch) otherwise."""
+    if not (isinstance(obj, dict) and "orbit_counts" in obj and "orbit_nodes" in obj):
+        if isinstance(obj, dict) and "adj" not in obj:
+            raise KeyError("descriptor dict lacks orbit_counts / orbit_nodes and the adj to compute them from; describe(..., orbits=True) produces them")
+        adj = obj["adj"] if isinstance(obj, dict) else torch.as_tensor(obj)
+        eng = _ops(kw.get("device") if kw.get("device") is not None else (adj.device if adj.device.type == "cuda" else None), kw.get("lib"))
+        adj = adj.to(device=eng.device, dtype=torch.float32).contiguous()
+        obj = eng.orbit_counts(adj, mol=kw.get("mol", False), thr=kw.get("thr", 0.5))
+    return obj["orbit_counts"].double() / obj["orbit_nodes"].double()[:, None]
+
+
+def orbit_stats_all(ref, pred, kernel: KernelSelector = gaussian, **kw) -> float:
+    """orbit_stats_all (stats.py:382-435): MMD of the per-graph orbit counts over the node count, raw vectors (is_hist=False) with
+    sigma = 30.  ref / pred: adjacency batches or descriptor dicts (orbit_counts and orbit_nodes, or adj to compute them from).
+    gaussian_emd has no meaning on raw vectors: ccsd_mmd refuses it."""
+    a, b = orbit_rows(ref, kw), orbit_rows(pred, kw)
+    return compute_mmd(a, b, kernel, is_hist=False, sigma=30.0, **_dev_kw(kw))
 
 
 def _cc_keep(desc: Dict[str, torch.Tensor], n: Optional[int], drop_empty: bool) -> torch.Tensor:
@@ -270,6 +298,10 @@ CC_METHOD_NAME_TO_FUNC = {"rank1_distrib": rank1_distrib_stats, "rank2_distrib":
 # the methods that run the eigenvalue solver: accepted only with spectra=True
 SPECTRA_METHOD_NAME_TO_FUNC = {"spectral": spectral_stats}
 SPECTRA_CC_METHOD_NAME_TO_FUNC = {"hodge_laplacian_spectrum": hodge_laplacian_spectrum_stats}
+# the method that counts graphlet orbits: accepted only with orbits=True
+ORBIT_METHOD_NAME_TO_FUNC = {"orbit": orbit_stats_all}
+# the kernel a method gets when `kernels` does not name one: load_eval_settings' choice for "orbit" (utils/loader.py:660-684)
+DEFAULT_KERNEL = {"orbit": gaussian}
 
 
 def _check_methods(methods, table, spectra=False):
@@ -283,14 +315,19 @@ def _check_methods(methods, table, spectra=False):
 
 
 def eval_torch_batch(ref_batch, pred_batch, methods: Optional[Sequence[str]] = None, kernels: Optional[dict] = None, *,
-                     mol: bool = False, thr: float = 0.5, bins: int = 100, spectra: bool = False, **kw) -> Dict[str, float]:
+                     mol: bool = False, thr: float = 0.5, bins: int = 100, spectra: bool = False, orbits: bool = False,
+                     **kw) -> Dict[str, float]:
     """eval_torch_batch / eval_graph_list (stats.py:480-570): {method: round(score, 6)}.  ref_batch / pred_batch: adjacency batches
-    (B, N, N) or descriptor dicts.  Default methods: "degree", "cluster" -- the reference's third default, "orbit", needs the orca
-    program and has to be asked for by name to get its NotImplementedError.  Default kernel: gaussian_emd for both.
-    spectra=True also accepts "spectral" in `methods` (it is never a default) and computes spectral_hist for a side given as a raw
-    batch; without it the name raises NotImplementedError."""
-    methods = ["degree", "cluster"] if methods is None else list(methods)
-    table = dict(METHOD_NAME_TO_FUNC, **SPECTRA_METHOD_NAME_TO_FUNC) if spectra else METHOD_NAME_TO_FUNC
+    (B, N, N) or descriptor dicts.  Default methods: "degree", "cluster"; default kernel: gaussian_emd for both.
+    orbits=True also accepts "orbit" (default kernel: gaussian, as load_eval_settings sets it) and, with methods=None, scores the
+    reference's own default list "degree", "cluster", "orbit"; the counts of a side that does not hold them are computed from its
+    adjacency.  spectra=True also accepts "spectral" and computes spectral_hist for a side given as a raw batch; with methods=None
+    it is appended when orbits=True as well, which gives load_eval_settings' list "degree", "cluster", "orbit", "spectral", and is
+    left out otherwise.  Without its keyword either name raises NotImplementedError."""
+    if methods is None:
+        methods = ["degree", "cluster"] + (["orbit"] + (["spectral"] if spectra else []) if orbits else [])
+    methods = list(methods)
+    table = dict(METHOD_NAME_TO_FUNC, **(SPECTRA_METHOD_NAME_TO_FUNC if spectra else {}), **(ORBIT_METHOD_NAME_TO_FUNC if orbits else {}))
     _check_methods(methods, table, spectra)
     kernels = kernels or {}
     want_spec = "spectral" in methods
@@ -300,12 +337,14 @@ def eval_torch_batch(ref_batch, pred_batch, methods: Optional[Sequence[str]] = N
     for obj in (ref_batch, pred_batch):
         if isinstance(obj, dict) and want_spec and "spectral_hist" not in obj and "adj" in obj:
             obj = dict(obj, spectral_hist=_spectral_rows(obj, dict(mol=mol, thr=thr, **_dev_kw(kw))))
-        sides.append(_descriptors(obj, need, **dkw, **({"spectra": True} if want_spec else {})))
+        # (a raw batch is described once, with everything the methods read; a dict side that lacks the orbit counts has them computed
+        # from its adj inside orbit_stats_all)
+        sides.append(_descriptors(obj, need, **dkw, **({"spectra": True} if want_spec else {}), **({"orbits": True} if "orbit" in methods else {})))
     ref, pred = sides
     out = {}
     for m in methods:
-        extra = {"bins": bins} if m == "cluster" else {}
-        out[m] = round(table[m](ref, pred, kernels.get(m, gaussian_emd), **extra, **_dev_kw(kw)), 6)
+        extra = {"bins": bins} if m == "cluster" else dict(mol=mol, thr=thr) if m == "orbit" else {}
+        out[m] = round(table[m](ref, pred, kernels.get(m, DEFAULT_KERNEL.get(m, gaussian_emd)), **extra, **_dev_kw(kw)), 6)
     return out
 
 

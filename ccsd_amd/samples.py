@@ -152,6 +152,24 @@ class SampleOps:
                                                   _ptr(res["cluster_hist"]), self._stream()))
         return res
 
+    def orbit_counts(self, adj: torch.Tensor, *, mol: bool = False, thr: float = 0.5, per_node: bool = False) -> dict:
+        """4-node graphlet orbit counts per graph (ccsd_orbit_counts): what orbit_stats_all of the reference (evaluation/stats.py:382-435)
+        reads from the external orca program (`orca node 4`) for adjs_to_graphs of the quantised adjacency, with finish()'s quantiser
+        (`mol`, `thr`; in mol mode every bond order is a plain edge).  adj (B,N,N) float32, SYMMETRIC.
+          orbit_counts (B,15) int64     the column sums of orca's per-node rows (ORCA's orbit numbering, include/ccsd_hip.h)
+          orbit_nodes (B,) int32        G.number_of_nodes(): the nodes that have an edge, 1 for a graph without any
+          node_orbits (B,N,15) int64    the per-node rows, zeros for nodes without an edge                          [per_node]
+        Nothing is synchronised."""
+        adj = self._adj("orbit_counts", adj)
+        B, N = adj.shape[0], adj.shape[1]
+        res = {"orbit_counts": torch.empty((B, _lib.ORBITS), dtype=torch.int64, device=adj.device),
+               "orbit_nodes": torch.empty((B,), dtype=torch.int32, device=adj.device)}
+        if per_node:
+            res["node_orbits"] = torch.empty((B, N, _lib.ORBITS), dtype=torch.int64, device=adj.device)
+        self.lib.check(self.lib.ccsd_orbit_counts(_ptr(adj), B, N, _adj_mode(mol), float(thr), _ptr(res.get("node_orbits")),
+                                                  _ptr(res["orbit_counts"]), _ptr(res["orbit_nodes"]), self._stream()))
+        return res
+
     def mmd(self, s1: torch.Tensor, s2: torch.Tensor, kind: str = "emd", *, is_hist: bool = True, degree: bool = False,
             f32_pmf: bool = False, sigma: float = 1.0, distance_scaling: float = 1.0, lens1: Optional[torch.Tensor] = None,
             lens2: Optional[torch.Tensor] = None) -> torch.Tensor:

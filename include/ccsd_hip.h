@@ -36,6 +36,8 @@
  *                              rank2_distrib_worker, cc_utils.py:1208-1334)
  * ccsd_cluster_hist            clustering_worker on adjs_to_graphs(adj): np.histogram of nx.clustering per graph
  *                              (evaluation/stats.py:206-220; graph_utils.py:216-251)
+ * ccsd_orbit_counts            what orbit_stats_all reads from the external orca program (`orca node 4`): the 4-node graphlet orbit
+ *                              counts per node and per graph, and the node count it divides by (evaluation/stats.py:343-435)
  * ccsd_mmd                     compute_mmd with gaussian_emd / gaussian_tv / gaussian: the scores of degree_stats, clustering_stats,
  *                              rank1_distrib_stats, rank2_distrib_stats (evaluation/mmd.py:27-257; evaluation/stats.py:60-310;
  *                              cc_utils.py:1235-1406); ccsd_mmd_workspace_bytes sizes its workspace
@@ -332,6 +334,21 @@ int ccsd_finish(const ccsd_finish_dims_t* dims, const ccsd_state_t* in, const fl
 #define CCSD_CLUSTER_MAX_BINS 1024
 int ccsd_cluster_hist(const float* adj_dev, int32_t B, int32_t N, int32_t adj_mode, float thr, const double* edges_dev, int32_t bins,
                       int32_t* tri2_dev, int32_t* cluster_hist_dev, void* stream);
+
+/* The graphlet orbit counts of every graph of adj_dev (B,N,N), 2 <= N <= 512: the integers orbit_stats_all (evaluation/stats.py:382-435)
+ * gets from `orca node 4` on adjs_to_graphs (graph_utils.py:216-251), computed from the adjacency bit masks by a closed form -- no
+ * program is started.  Edges, the quantiser (adj_mode, thr) and the SYMMETRIC-adjacency contract are ccsd_cluster_hist's.
+ * The CCSD_ORBITS = 15 orbits are ORCA's: 0 edge; 1, 2 end and middle of the 3-path; 3 triangle; 4, 5 end and inner node of the 4-path;
+ * 6, 7 leaf and centre of the claw; 8 4-cycle; 9, 10, 11 the paw's pendant, its triangle nodes without and with the tail; 12, 13 the
+ * diamond's nodes of degree 2 and 3; 14 K4.
+ * node_orbits_dev (B,N,15) int64: node_orbits[b][v][k] = the induced connected subgraphs on 2, 3 or 4 nodes in which node v sits at orbit
+ * k; zeros for nodes without an edge.  The rows of the nodes that have an edge, in slot order, are orca's output rows.
+ * graph_orbits_dev (B,15) int64: the column sums over the nodes (above 2^32 for dense graphs of a few hundred nodes).
+ * orbit_nodes_dev (B,) int32: the nodes that have an edge, or 1 for a graph without any: G.number_of_nodes(), orbit_stats_all's divisor.
+ * All three nullable; with all three NULL nothing is launched.  No workspace.  CCSD_ERR_INVALID with a message for N outside 2..512. */
+#define CCSD_ORBITS 15
+int ccsd_orbit_counts(const float* adj_dev, int32_t B, int32_t N, int32_t adj_mode, float thr, int64_t* node_orbits_dev,
+                      int64_t* graph_orbits_dev, int32_t* orbit_nodes_dev, void* stream);
 
 /* compute_mmd (evaluation/mmd.py:230-257) of two sets of histograms, in fp64 and bit-reproducible from call to call:
  *   mmd = disc(1,1) + disc(2,2) - 2 disc(1,2),  disc = mean over all pairs of exp(-dist(x, y)^2 / (2 sigma^2)). */

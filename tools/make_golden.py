@@ -763,6 +763,101 @@ def e1_eval():
 
 
 # ---------------------------------------------------------------------------------------------
+# e3_orbit.npz: the reference's orbit counter and orbit_stats_all on the graph sets of e1_eval.npz (`python tools/make_golden.py orbit`)
+# ---------------------------------------------------------------------------------------------
+def e3_six4():
+    """six4 (6, 4, 4): the six connected graphs on 4 nodes -- K4, C4, claw (centre 0), paw (triangle 0 1 2, tail 2 -- 3), diamond
+    (0 and 1 of degree 3), P4 (0 - 1 - 2 - 3)."""
+    edges = [[(0, 1), (0, 2), (0, 3), (1, 2), (1, 3), (2, 3)], [(0, 1), (1, 2), (2, 3), (3, 0)], [(0, 1), (0, 2), (0, 3)],
+             [(0, 1), (1, 2), (0, 2), (2, 3)], [(0, 1), (0, 2), (0, 3), (1, 2), (1, 3)], [(0, 1), (1, 2), (2, 3)]]
+    a = np.zeros((6, 4, 4), np.int8)
+    for b, es in enumerate(edges):
+        for i, j in es:
+            a[b, i, j] = a[b, j, i] = 1
+    return a
+
+
+def e3_orbit():
+    """e3_orbit.npz: `orca node 4` of the reference's own counter on adjs_to_graphs of every graph set of e1_eval.npz and of six4, and
+    the reference's orbit_stats_all / eval_graph_list on eval_ref against eval_pred.  The counter is compiled, at generation time only,
+    into a temporary folder laid out as <tmp>/ccsd/src/evaluation/orca/ (orbit_stats_all writes its edge lists next to the binary and
+    takes the folder above as `folder`); nothing compiled or copied from the reference is kept."""
+    import tempfile
+    import threading
+    import time
+
+    record = {"tl": threading.local()}
+    sys.modules["pyemd"] = _pyemd_stand_in(record)
+    from ccsd.src.evaluation import mmd as ref_mmd
+    from ccsd.src.evaluation import stats as ref_stats
+
+    ref_mmd.pyemd = sys.modules["pyemd"]
+    e1 = np.load(os.path.join(GOLD, "e1_eval.npz"))
+    e1_meta = json.loads(str(e1["meta"]))
+    out, meta = {}, {"graph_sets": {}, "seconds": {}}
+    with tempfile.TemporaryDirectory() as tmp:
+        orca_dir = os.path.join(tmp, "ccsd", "src", "evaluation", "orca")
+        os.makedirs(orca_dir)
+        subprocess.check_call(["g++", "-O2", "-std=c++11", "-o", os.path.join(orca_dir, "orca"),
+                               os.path.join(refshim.REFERENCE_ROOT, "ccsd", "src", "evaluation", "orca", "orca.cpp")])
+        sets = {name: (e1[f"graphs/{name}/adj"], e1_meta["graph_sets"][name]["mol"]) for name in e1_meta["graph_sets"]}
+        sets["six4"] = (e3_six4(), False)
+        out["graphs/six4/adj"] = sets["six4"][0]
+        graphs = {}
+        for name, (adj, mol) in sets.items():
+            t0 = time.time()
+            q = ref_gu.quantize_mol(torch.as_tensor(adj, dtype=torch.float32)) if mol else ref_gu.quantize(torch.as_tensor(adj, dtype=torch.float32)).numpy()
+            q = np.asarray(q, np.float32)
+            G = graphs[name] = ref_gu.adjs_to_graphs(q)
+            B, N = adj.shape[:2]
+            rows, nodes = np.zeros((B, N, 15), np.int64), np.zeros(B, np.int32)
+            for b, g in enumerate(G):
+                nodes[b] = g.number_of_nodes()
+                if g.number_of_edges() == 0:
+                    continue                       # (the one-node stand-in of an edgeless graph: every count is 0)
+                cnt = ref_stats.orca(g, orca_dir)
+                # orca's row r belongs to the r-th node of G.nodes() (edge_list_reindexed); a node of G is a slot of the adjacency
+                slots = list(g.nodes())
+                assert cnt.shape == (len(slots), 15) and slots == sorted(slots), (name, b)
+                rows[b, slots] = cnt
+            small = np.abs(rows).max() < 2 ** 31
+            out[f"graphs/{name}/orca"] = rows.astype(np.int32) if small and rows.size > 100000 else rows
+            out[f"graphs/{name}/nodes"] = nodes
+            meta["graph_sets"][name] = {"mol": bool(mol), "N": int(N), "B": int(B)}
+            meta["seconds"][name] = round(time.time() - t0, 3)           # (this machine's CPU: the reference's program, one process per graph)
+            print("e3", name, meta["seconds"][name], "s")
+        gr, gp = graphs["eval_ref"], graphs["eval_pred"]
+        totals = {}
+        real_compute = ref_stats.compute_mmd
+
+        def spy(s1, s2, **kw):                     # orbit_stats_all's own rows, as it hands them to compute_mmd
+            if kw.get("is_hist") is False:
+                totals["ref"], totals["pred"] = np.array(s1, np.float64), np.array(s2, np.float64)
+            return real_compute(s1, s2, **kw)
+
+        ref_stats.compute_mmd = spy
+        try:
+            meta["orbit_stats_all"] = float(ref_stats.orbit_stats_all(gr, gp, ref_mmd.gaussian, folder=tmp))
+        finally:
+            ref_stats.compute_mmd = real_compute
+        out["total_counts_ref"], out["total_counts_pred"] = totals["ref"], totals["pred"]
+        meta["orbit_self"] = float(ref_stats.orbit_stats_all(gr, gr, ref_mmd.gaussian, folder=tmp))
+        _, kernels = ref_loader.load_eval_settings("")
+        assert kernels["orbit"] is ref_mmd.gaussian or kernels["orbit"].__name__ == "gaussian"
+        meta["eval_graph_list"] = ref_stats.eval_graph_list(gr, gp, methods=["degree", "cluster", "orbit"],
+                                                            kernels={"degree": ref_mmd.gaussian_emd, "cluster": ref_mmd.gaussian_emd,
+                                                                     "orbit": ref_mmd.gaussian}, folder=tmp)
+    meta["note"] = ("orca = the rows `orca node 4` prints for adjs_to_graphs of each graph, scattered to node slots (zeros for removed slots); "
+                    "nodes = G.number_of_nodes(); total_counts_* = the rows orbit_stats_all hands to compute_mmd; gaussian_emd ran on a stand-in "
+                    "pyemd (scipy.optimize.linprog), as in e1_eval.npz; seconds = the reference's counter per set on the generating machine's CPU")
+    out["meta"] = np.array(json.dumps(plain(meta)))
+    path = os.path.join(GOLD, "e3_orbit.npz")
+    np.savez_compressed(path, **out)
+    assert os.path.getsize(path) <= MAX_FIXTURE // 4, os.path.getsize(path)
+    print("wrote e3_orbit", os.path.getsize(path), "bytes; orbit_stats_all", meta["orbit_stats_all"], meta["eval_graph_list"])
+
+
+# ---------------------------------------------------------------------------------------------
 # e2_spectrum.npz: the reference's two spectral evaluators on small sets (`python tools/make_golden.py spectrum`)
 # ---------------------------------------------------------------------------------------------
 class _StandInComplex:
@@ -1774,6 +1869,9 @@ def main():
         return
     if only == {"spectrum"}:
         e2_spectrum()
+        return
+    if only == {"orbit"}:
+        e3_orbit()
         return
     if only == {"d1"}:
         # ~a quarter of an hour of reference CPU time was the estimate; the fixture's metadata holds what it took
