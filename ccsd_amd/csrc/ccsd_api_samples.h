@@ -1,5 +1,5 @@
 // ccsd_api_samples.h -- host side of the PLAN-FREE entry points of include/ccsd_hip.h: the operations on finished samples, which take
-// tensors and sizes and never a ccsd_plan_t (ccsd_quantize, ccsd_rank2_cells, ccsd_finish, ccsd_cluster_hist, ccsd_orbit_counts, ccsd_mmd, ccsd_eigvalsh,
+// tensors and sizes and never a ccsd_plan_t (ccsd_quantize, ccsd_rank2_cells, ccsd_finish, ccsd_cluster_hist, ccsd_orbit_counts, ccsd_nspdk_features, ccsd_nspdk_mmd, ccsd_mmd, ccsd_eigvalsh,
 // ccsd_spectral_hist, ccsd_hodge_spectrum and their *_workspace_bytes).  Included by ccsd_api.h as its last line; of what stands above it
 // there, this file uses set_err, grid_for, RT_CHECK and LAUNCH_CHECK only.
 //
@@ -144,6 +144,97 @@ extern "C" int ccsd_orbit_counts(const float* adj, int32_t B, int32_t N, int32_t
     if (!node_orbits && !graph_orbits && !orbit_nodes) return CCSD_OK;
     CCSD_LAUNCH(k_orbit_counts, dim3(B), dim3(CCSD_NTHREADS), 0, stream, adj, (int)N, quant_thr(adj_mode, thr), (long long*)node_orbits,
                 (long long*)graph_orbits, (int*)orbit_nodes);
+    LAUNCH_CHECK();
+    return CCSD_OK;
+}
+
+// ---------------- NSPDK feature vectors and their MMD (ccsd_k_nspdk.h) ----------------
+static_assert(CCSD_NSPDK_MAX_NODES == CCSD_NSPDK_MAXN && CCSD_NSPDK_FEATURES == CCSD_NSPDK_COLS + 1, "the header's limits are k_nspdk_features'");
+// the workgroups of k_nspdk_features: each owns one 2^16-entry table of the workspace, so their number is bounded and does not grow with B
+#define CCSD_NSPDK_MAX_GRID 512
+static int nspdk_grid(int B) { return B < CCSD_NSPDK_MAX_GRID ? B : CCSD_NSPDK_MAX_GRID; }
+static int nspdk_dims(const char* who, int B, int N) {
+    const std::string w = std::string(who) + ": ";
+    if (B < 1) return set_err(CCSD_ERR_INVALID, w + "B must be >= 1");
+    if (N < 1) return set_err(CCSD_ERR_INVALID, w + "N = " + std::to_string(N) + " must be >= 1");
+    if (N > CCSD_NSPDK_MAXN)
+        return set_err(CCSD_ERR_UNSUPPORTED, w + "N = " + std::to_string(N) + " is above CCSD_NSPDK_MAX_NODES = " + std::to_string(CCSD_NSPDK_MAXN) +
+                                                 ": a row of the adjacency is one 64-bit mask and the breadth-first layers are operations on such masks");
+    return CCSD_OK;
+}
+// two keys per (ordered pair of nodes within distance 4, radius 0..4): at most 10 N^2 non-zeros, and never more than the 2^16 indices
+extern "C" int32_t ccsd_nspdk_row_capacity(int32_t N) {
+    if (nspdk_dims("ccsd_nspdk_row_capacity", 1, N)) return 0;
+    const int c = 2 * CCSD_NSPDK_NL * N * N;
+    return c < CCSD_NSPDK_COLS ? c : CCSD_NSPDK_COLS;
+}
+extern "C" size_t ccsd_nspdk_workspace_bytes(int32_t B, int32_t N) {
+    if (nspdk_dims("ccsd_nspdk_workspace_bytes", B, N)) return 0;
+    return (size_t)nspdk_grid(B) * CCSD_NSPDK_COLS * 4;
+}
+
+// ccsd_nspdk_features: the NSPDK feature vector of every graph (k_nspdk_features; same quantiser arguments as ccsd_finish)
+extern "C" int ccsd_nspdk_features(const float* adj, const int32_t* labels, int32_t B, int32_t N, int32_t adj_mode, float thr, int32_t* nnz,
+                                   int32_t* indices, double* values, void* workspace, size_t ws_bytes, void* stream) {
+    if (!adj || !nnz || !indices || !values) return set_err(CCSD_ERR_INVALID, "ccsd_nspdk_features: NULL argument");
+    if (int st = nspdk_dims("ccsd_nspdk_features", B, N)) return st;
+    if (int st = check_batch("ccsd_nspdk_features", B, N, adj_mode, thr, /*fin_n=*/false)) return st;
+    const size_t need = (size_t)nspdk_grid(B) * CCSD_NSPDK_COLS * 4;
+    if (int st = check_scratch("ccsd_nspdk_features", workspace, ws_bytes, need)) return st;
+    RT_CHECK(rt_memset_async(workspace, 0, need, stream));          // (the tables start from zero; the kernel leaves them zero)
+    CCSD_LAUNCH(k_nspdk_features, dim3(nspdk_grid(B)), dim3(CCSD_NTHREADS), 0, stream, adj, (const int*)labels, (int)B, (int)N,
+                quant_thr(adj_mode, thr), (int)ccsd_nspdk_row_capacity(N), (unsigned*)workspace, (int*)nnz, (int*)indices, values);
+    LAUNCH_CHECK();
+    return CCSD_OK;
+}
+
+// Workspace of ccsd_nspdk_mmd: the chunk offsets of both sets (n x 257 int64 each), the 256 x 3 partial
+// products, the count of non-empty rows of the second set.
+struct NspdkMmdWs {
+    size_t cp[2], part, cnt, bytes;
+};
+static NspdkMmdWs carve_nspdk_mmd(int64_t n1, int64_t n2) {
+    NspdkMmdWs w;
+    size_t o = 0;
+    w.cp[0] = o; o += (size_t)n1 * (CCSD_NSPDK_CHUNKS + 1) * 8;
+    w.cp[1] = o; o += (size_t)n2 * (CCSD_NSPDK_CHUNKS + 1) * 8;
+    w.part = o; o += (size_t)CCSD_NSPDK_CHUNKS * 3 * 8;
+    w.cnt = o; o += 8;
+    w.bytes = o;
+    return w;
+}
+static bool nspdk_mmd_dims_ok(int64_t n1, int64_t n2) { return n1 >= 1 && n2 >= 1 && n1 <= CCSD_MMD_MAX_ROWS && n2 <= CCSD_MMD_MAX_ROWS; }
+extern "C" size_t ccsd_nspdk_mmd_workspace_bytes(int32_t n1, int32_t n2) {
+    if (!nspdk_mmd_dims_ok(n1, n2))
+        return no_bytes(CCSD_ERR_INVALID, "ccsd_nspdk_mmd_workspace_bytes: n1, n2 must be in 1.." + std::to_string(CCSD_MMD_MAX_ROWS));
+    return carve_nspdk_mmd(n1, n2).bytes;
+}
+
+// ccsd_nspdk_mmd: compute_nspdk_mmd (mmd.py:352-377) of two sets of feature rows: k_nspdk_chunks per set, k_nspdk_dots, k_nspdk_final
+extern "C" int ccsd_nspdk_mmd(const int64_t* indptr1, const int32_t* indices1, const double* values1, int32_t n1, const int64_t* indptr2,
+                              const int32_t* indices2, const double* values2, int32_t n2, void* workspace, size_t ws_bytes, double* out,
+                              void* stream) {
+    if (!nspdk_mmd_dims_ok(n1, n2))
+        return set_err(CCSD_ERR_INVALID, "ccsd_nspdk_mmd: n1 = " + std::to_string(n1) + ", n2 = " + std::to_string(n2) + " outside 1.." + std::to_string(CCSD_MMD_MAX_ROWS));
+    if (!indptr1 || !indices1 || !values1 || !indptr2 || !indices2 || !values2 || !out) return set_err(CCSD_ERR_INVALID, "ccsd_nspdk_mmd: NULL argument");
+    const NspdkMmdWs w = carve_nspdk_mmd(n1, n2);
+    if (int st = check_scratch("ccsd_nspdk_mmd", workspace, ws_bytes, w.bytes)) return st;
+    char* base = (char*)workspace;
+    int* cnt = (int*)(base + w.cnt);
+    RT_CHECK(rt_memset_async(cnt, 0, 8, stream));
+    for (int i = 0; i < 2; ++i) {
+        const int n = i ? n2 : n1;
+        CCSD_LAUNCH(k_nspdk_chunks, dim3(grid_for((int64_t)n * (CCSD_NSPDK_CHUNKS + 1), 256)), dim3(CCSD_NTHREADS), 0, stream,
+                    (const long long*)(i ? indptr2 : indptr1), (const int*)(i ? indices2 : indices1), n, (long long*)(base + w.cp[i]),
+                    i ? cnt : (int*)nullptr);
+        LAUNCH_CHECK();
+    }
+    double* part = (double*)(base + w.part);
+    CCSD_LAUNCH(k_nspdk_dots, dim3(CCSD_NSPDK_CHUNKS), dim3(CCSD_NTHREADS), 0, stream, (const int*)indices1, values1,
+                (const long long*)(base + w.cp[0]), (int)n1, (const int*)indices2, values2, (const long long*)(base + w.cp[1]), (int)n2,
+                (const int*)cnt, part);
+    LAUNCH_CHECK();
+    CCSD_LAUNCH(k_nspdk_final, dim3(1), dim3(CCSD_NTHREADS == 1 ? 1 : 64), 0, stream, (const double*)part, out);
     LAUNCH_CHECK();
     return CCSD_OK;
 }

@@ -22,6 +22,9 @@
 //                    sets of histograms (the evaluation of finished samples)
 //   ccsd_k_orbit.h   k_orbit_counts: the 4-node graphlet orbit counts per node and per graph from the same bit-mask rows, by a closed
 //                    form (what the reference's "orbit" score reads from the external orca program)
+//   ccsd_k_nspdk.h   k_nspdk_features, k_nspdk_chunks, k_nspdk_dots, k_nspdk_final: the NSPDK feature vector per graph (breadth-first
+//                    layers as mask operations, CPython's tuple hash in 64-bit integers, integer counting) and the linear-kernel MMD
+//                    of two sets of such rows (the reference's "nspdk" score of molecule runs)
 //   ccsd_k_eig.h     k_eigvalsh, k_norm_laplacian, k_hodge_laplacian: a batched symmetric eigenvalue solver (parallel Jacobi) and the
 //                    two matrices whose spectra the reference scores (normalised graph Laplacian, hodge Laplacian F F^T)
 //   ccsd_api.h       host side of the C ABI: plan, route, workspace, launchers, the sampler loop; its last line includes
@@ -39,5 +42,6 @@
 #include "ccsd_k_finish.h"
 #include "ccsd_k_eval.h"
 #include "ccsd_k_orbit.h"
+#include "ccsd_k_nspdk.h"
 #include "ccsd_k_eig.h"
 #include "ccsd_k_lg.h"

@@ -9,6 +9,8 @@ needs no external program:
   spectral_stats                                                  (stats.py:125-203)    -> SampleOps.spectral_hist (ccsd_spectral_hist)
   hodge_laplacian_spectrum_stats                                  (cc_utils.py:994-1098) -> SampleOps.hodge_spectrum (ccsd_hodge_spectrum)
   orbit_stats_all                                                 (stats.py:343-435)    -> SampleOps.orbit_counts (ccsd_orbit_counts)
+  nspdk_stats, compute_nspdk_mmd with eden.py's vectorize         (stats.py:438-467, mmd.py:309-377, eden.py)
+                                                                                        -> SampleOps.nspdk_features / nspdk_mmd
 
 The reference builds networkx graphs / toponetx complexes on the host and solves one pyemd linear program per pair of histograms.
 Here a sample set is a dict of per-sample integer DESCRIPTORS on the device -- `describe()`: the descriptor outputs of
@@ -16,7 +18,11 @@ SampleOps.finish plus `cluster_hist` -- and every score is one ccsd_mmd call on 
 network plan is built here).  The two spectral scores need an eigenvalue
 solver (ccsd_eigvalsh, a batched Jacobi iteration on the device) and cost O(N^3) per sample where the others cost O(N^2): they are
 opt-in, `spectra=True`.  The orbit score counts 4-node graphlets per graph on the device where the reference starts the orca program
-once per graph; its cost grows with the triangles of a graph, so it is opt-in as well, `orbits=True`.  There is no CPU fallback:
+once per graph; its cost grows with the triangles of a graph, so it is opt-in as well, `orbits=True`.  The NSPDK score -- the one
+graph score the reference prints for molecule runs -- hashes neighbourhood pairs per graph on the device and is opt-in, `nspdk=True`;
+it takes INTEGER node labels (mol_labels) and scores the quantised samples AS SAMPLED: the reference scores molecules after rdkit's
+valency correction and largest-fragment selection, which this build does not have (a user with rdkit can pass corrected adj / labels),
+and labels atoms with symbol strings, whose Python hash differs from process to process.  There is no CPU fallback:
 methods that need an external program raise NotImplementedError (UNSUPPORTED); their histograms, computed elsewhere, can still be
 scored through compute_mmd.
 """
@@ -52,7 +58,7 @@ UNSUPPORTED = {
     "orbit": "counts the 4-node graphlet orbits of every graph (evaluation/stats.py:343-435) and is opt-in: pass orbits=True",
     "spectral": "runs a symmetric eigenvalue solver per graph (evaluation/stats.py:125-137) and is opt-in: pass spectra=True",
     "hodge_laplacian_spectrum": "runs a symmetric eigenvalue solver per complex (cc_utils.py:994-1060) and is opt-in: pass spectra=True",
-    "nspdk": "needs the EDeN graph vectoriser (evaluation/eden.py, mmd.py:331-337)",
+    "nspdk": "hashes the neighbourhood pairs of every graph (evaluation/eden.py, mmd.py:331-377) and is opt-in: pass nspdk=True",
     "rank0_distrib": "the node label it histograms is data-set specific (cc_utils.py:1098-1205)",
 }
 
@@ -131,12 +137,14 @@ def compute_mmd(samples1, samples2, kernel: KernelSelector = gaussian_emd, is_hi
 # ---------------------------------------------------------------------------------------------
 def describe(adj: torch.Tensor, x: Optional[torch.Tensor] = None, rank2: Optional[torch.Tensor] = None, *, mol: bool = False,
              thr: float = 0.5, bins: int = 100, d_min: int = 0, d_max: int = 0, spectra: bool = False, orbits: bool = False,
-             device=None, lib=None) -> Dict[str, torch.Tensor]:
+             nspdk: bool = False, nspdk_labels: Optional[torch.Tensor] = None, device=None, lib=None) -> Dict[str, torch.Tensor]:
     """The descriptor dict of a batch: SampleOps.finish's descriptors (degree, degree_hist, edge_hist; n_nodes, x_hist with x;
     rank2_cell_bits / _count / _hist, rank2_nnz with rank2) plus cluster_hist (B, bins) and tri2 (B, N).  adj: (B, N, N), raw samples,
     quantised samples or a 0/1 data set (any real or integer dtype).  spectra=True adds spectral_hist (B, 200) int32 and, with rank2,
     hodge_spectrum (B, E) float32 (SampleOps.spectral_hist / hodge_spectrum: an eigenvalue solve per sample).  orbits=True adds
-    orbit_counts (B, 15) int64 and orbit_nodes (B,) int32 (SampleOps.orbit_counts)."""
+    orbit_counts (B, 15) int64 and orbit_nodes (B,) int32 (SampleOps.orbit_counts).  nspdk=True adds the NSPDK feature rows
+    nspdk_indptr, nspdk_indices, nspdk_values (SampleOps.nspdk_features, N <= 64) with the node labels nspdk_labels (B, N), or
+    mol_labels(x) when `mol` and x is given, or label 0 in every slot."""
     eng = _ops(device if device is not None else (adj.device if adj.device.type == "cuda" else None), lib)
     mv = lambda t: None if t is None else t.to(device=eng.device, dtype=torch.float32).contiguous()
     adj, x, rank2 = mv(adj), mv(x), mv(rank2)
@@ -144,6 +152,10 @@ def describe(adj: torch.Tensor, x: Optional[torch.Tensor] = None, rank2: Optiona
     out.update(eng.cluster_hist(adj, mol=mol, thr=thr, bins=bins))
     if orbits:
         out.update(eng.orbit_counts(adj, mol=mol, thr=thr))
+    if nspdk:
+        if nspdk_labels is None and mol and x is not None:
+            nspdk_labels = mol_labels(x)
+        out.update(eng.nspdk_features(adj, None if nspdk_labels is None else torch.as_tensor(nspdk_labels).to(eng.device), mol=mol, thr=thr))
     if spectra:
         out.update(eng.spectral_hist(adj, mol=mol, thr=thr))
         if rank2 is not None:
@@ -230,6 +242,46 @@ def orbit_stats_all(ref, pred, kernel: KernelSelector = gaussian, **kw) -> float
     return compute_mmd(a, b, kernel, is_hist=False, sigma=30.0, **_dev_kw(kw))
 
 
+NSPDK_KEYS = ("nspdk_indptr", "nspdk_indices", "nspdk_values")
+
+
+def mol_labels(x) -> torch.Tensor:
+    """Integer node labels of a molecule batch from its raw or one-hot node features x (B, N, F): the index of the first channel
+    above 0.5, or -1 where there is none (the "no atom" column of x_onehot, sampler.py:1222-1224) -- such a slot holds no node."""
+    x = torch.as_tensor(x)
+    on = x > 0.5
+    first = on.to(torch.int8).argmax(-1)
+    return torch.where(on.any(-1), first, torch.full_like(first, -1)).to(torch.int32)
+
+
+def nspdk_rows(obj, kw) -> Dict[str, torch.Tensor]:
+    """The NSPDK feature rows of a side (CSR: NSPDK_KEYS): taken from a dict that holds them, computed from its `adj` with the labels
+    `nspdk_labels`, or mol_labels(x) of its `x` in mol mode, or label 0 (a raw batch has label 0 in every slot)."""
+    if isinstance(obj, dict) and all(k in obj for k in NSPDK_KEYS):
+        return obj
+    if isinstance(obj, dict) and "adj" not in obj:
+        raise KeyError("descriptor dict lacks nspdk_indptr / nspdk_indices / nspdk_values and the adj to compute them from; describe(..., nspdk=True) produces them")
+    adj = obj["adj"] if isinstance(obj, dict) else torch.as_tensor(obj)
+    eng = _ops(kw.get("device") if kw.get("device") is not None else (adj.device if adj.device.type == "cuda" else None), kw.get("lib"))
+    adj = adj.to(device=eng.device, dtype=torch.float32).contiguous()
+    labels = None
+    if isinstance(obj, dict):
+        labels = obj.get("nspdk_labels")
+        if labels is None and kw.get("mol", False) and obj.get("x") is not None:
+            labels = mol_labels(obj["x"])
+    return eng.nspdk_features(adj, None if labels is None else torch.as_tensor(labels).to(eng.device), mol=kw.get("mol", False), thr=kw.get("thr", 0.5))
+
+
+def nspdk_stats(ref, pred, **kw) -> float:
+    """nspdk_stats (stats.py:438-467): the MMD of the two sets' NSPDK feature rows under the linear kernel -- it takes no kernel
+    argument.  ref / pred: adjacency batches (label 0 in every slot) or dicts (the three nspdk_* keys, or adj plus nspdk_labels or x).
+    Predicted graphs without a node are left out, as in the reference.  The score is of the quantised samples as sampled, with integer
+    labels: see the module docstring for what the reference does differently for molecules."""
+    a, b = nspdk_rows(ref, kw), nspdk_rows(pred, kw)
+    eng = _ops(kw.get("device") if kw.get("device") is not None else (a["nspdk_indptr"].device if a["nspdk_indptr"].device.type == "cuda" else None), kw.get("lib"))
+    return float(eng.nspdk_mmd(a, b)[3].item())
+
+
 def _cc_keep(desc: Dict[str, torch.Tensor], n: Optional[int], drop_empty: bool) -> torch.Tensor:
     """Row indices eval_CC_list scores: the first n complexes (cc_nb_eval slices first), minus -- predictions only -- the complexes
     with no node, edge or cell (is_empty_cc, cc_utils.py:982-991)."""
@@ -300,6 +352,8 @@ SPECTRA_METHOD_NAME_TO_FUNC = {"spectral": spectral_stats}
 SPECTRA_CC_METHOD_NAME_TO_FUNC = {"hodge_laplacian_spectrum": hodge_laplacian_spectrum_stats}
 # the method that counts graphlet orbits: accepted only with orbits=True
 ORBIT_METHOD_NAME_TO_FUNC = {"orbit": orbit_stats_all}
+# the method that hashes neighbourhood pairs: accepted only with nspdk=True, never a default, and without a kernel argument
+NSPDK_METHOD_NAME_TO_FUNC = {"nspdk": nspdk_stats}
 # the kernel a method gets when `kernels` does not name one: load_eval_settings' choice for "orbit" (utils/loader.py:660-684)
 DEFAULT_KERNEL = {"orbit": gaussian}
 
@@ -316,33 +370,41 @@ def _check_methods(methods, table, spectra=False):
 
 def eval_torch_batch(ref_batch, pred_batch, methods: Optional[Sequence[str]] = None, kernels: Optional[dict] = None, *,
                      mol: bool = False, thr: float = 0.5, bins: int = 100, spectra: bool = False, orbits: bool = False,
-                     **kw) -> Dict[str, float]:
+                     nspdk: bool = False, **kw) -> Dict[str, float]:
     """eval_torch_batch / eval_graph_list (stats.py:480-570): {method: round(score, 6)}.  ref_batch / pred_batch: adjacency batches
     (B, N, N) or descriptor dicts.  Default methods: "degree", "cluster"; default kernel: gaussian_emd for both.
     orbits=True also accepts "orbit" (default kernel: gaussian, as load_eval_settings sets it) and, with methods=None, scores the
     reference's own default list "degree", "cluster", "orbit"; the counts of a side that does not hold them are computed from its
     adjacency.  spectra=True also accepts "spectral" and computes spectral_hist for a side given as a raw batch; with methods=None
     it is appended when orbits=True as well, which gives load_eval_settings' list "degree", "cluster", "orbit", "spectral", and is
-    left out otherwise.  Without its keyword either name raises NotImplementedError."""
+    left out otherwise.  nspdk=True also accepts "nspdk" in `methods` (it is never a default; nspdk_stats: the linear-kernel MMD of
+    the NSPDK feature rows, no kernel argument; like the reference's, its result is not rounded).  Without its keyword each of the
+    three names raises NotImplementedError."""
     if methods is None:
         methods = ["degree", "cluster"] + (["orbit"] + (["spectral"] if spectra else []) if orbits else [])
     methods = list(methods)
-    table = dict(METHOD_NAME_TO_FUNC, **(SPECTRA_METHOD_NAME_TO_FUNC if spectra else {}), **(ORBIT_METHOD_NAME_TO_FUNC if orbits else {}))
+    table = dict(METHOD_NAME_TO_FUNC, **(SPECTRA_METHOD_NAME_TO_FUNC if spectra else {}), **(ORBIT_METHOD_NAME_TO_FUNC if orbits else {}),
+                 **(NSPDK_METHOD_NAME_TO_FUNC if nspdk else {}))
     _check_methods(methods, table, spectra)
     kernels = kernels or {}
     want_spec = "spectral" in methods
     dkw = dict(mol=mol, thr=thr, bins=bins, **_dev_kw(kw))
-    need = ["degree_hist", "cluster_hist"] + (["spectral_hist"] if want_spec else [])
+    # what a dict side must hold: the histograms of the methods asked for (orbit counts and NSPDK rows may be computed from its adj)
+    need = (["degree_hist"] if "degree" in methods else []) + (["cluster_hist"] if "cluster" in methods else []) + (["spectral_hist"] if want_spec else [])
     sides = []
     for obj in (ref_batch, pred_batch):
         if isinstance(obj, dict) and want_spec and "spectral_hist" not in obj and "adj" in obj:
             obj = dict(obj, spectral_hist=_spectral_rows(obj, dict(mol=mol, thr=thr, **_dev_kw(kw))))
         # (a raw batch is described once, with everything the methods read; a dict side that lacks the orbit counts has them computed
-        # from its adj inside orbit_stats_all)
-        sides.append(_descriptors(obj, need, **dkw, **({"spectra": True} if want_spec else {}), **({"orbits": True} if "orbit" in methods else {})))
+        # from its adj inside orbit_stats_all; likewise the NSPDK rows -- a raw batch has label 0 in every slot)
+        sides.append(_descriptors(obj, need, **dkw, **({"spectra": True} if want_spec else {}), **({"orbits": True} if "orbit" in methods else {}),
+                                  **({"nspdk": True} if "nspdk" in methods else {})))
     ref, pred = sides
     out = {}
     for m in methods:
+        if m == "nspdk":
+            out[m] = nspdk_stats(ref, pred, mol=mol, thr=thr, **_dev_kw(kw))
+            continue
         extra = {"bins": bins} if m == "cluster" else dict(mol=mol, thr=thr) if m == "orbit" else {}
         out[m] = round(table[m](ref, pred, kernels.get(m, DEFAULT_KERNEL.get(m, gaussian_emd)), **extra, **_dev_kw(kw)), 6)
     return out

@@ -353,7 +353,7 @@ class Sampler:
 
 
     def evaluate(self, result, ref, methods: Optional[List[str]] = None, cc_methods: Optional[List[str]] = None, bins: int = 100,
-                 cc_nb_eval: Optional[int] = 1000, spectra: bool = False, orbits: bool = False) -> Dict[str, float]:
+                 cc_nb_eval: Optional[int] = 1000, spectra: bool = False, orbits: bool = False, nspdk: bool = False) -> Dict[str, float]:
         """Score a finished run against a held-out set on the GPU (ccsd_amd/evaluation.py): what the reference prints after
         sampling from eval_graph_list and eval_CC_list (sampler.py:253-262, 565-583), for the methods this build computes.
         `result`: what sample() returned.  `ref`: an adjacency batch (B, N, N) of the held-out graphs, a descriptor dict
@@ -364,7 +364,12 @@ class Sampler:
         sample: "spectral" and, for combinatorial complexes, "hodge_laplacian_spectrum" -- both computed from `adj` and
         `rank2_cell_bits`, so results of sample(dense_rank2=False) and saved .npz files serve as well.  orbits=True adds "orbit", the
         reference's third default score for generic graphs (orbit_stats_all: 4-node graphlet orbit counts per graph, which the
-        reference gets from the external orca program), computed from `adj` of each side.  In a sharded run every rank holds the gathered samples and rank 0 alone
+        reference gets from the external orca program), computed from `adj` of each side.  nspdk=True adds "nspdk", the graph score the
+        reference prints for molecule runs (nspdk_stats; not rounded, as in the reference), computed from `adj` of each side (at most 64
+        nodes) and integer node labels: for molecule samplers evaluation.mol_labels of the side's `x`, or its `nspdk_labels`
+        (KeyError when a side has neither), label 0 otherwise.  It scores the quantised samples AS SAMPLED: the reference scores
+        molecules after rdkit's valency correction and largest-fragment selection, which this build does not have -- pass corrected
+        `adj` / `nspdk_labels` to score those.  In a sharded run every rank holds the gathered samples and rank 0 alone
         evaluates; the other ranks return {}."""
         from . import evaluation as ev
 
@@ -374,7 +379,8 @@ class Sampler:
         kw = dict(device=self.device0, lib=lib)
 
         keep = ("adj", "degree_hist", "edge_hist", "n_nodes", "rank2_cell_hist", "cluster_hist") + (
-            ("rank2_cell_bits", "spectral_hist", "hodge_spectrum") if spectra else ()) + (("orbit_counts", "orbit_nodes") if orbits else ())
+            ("rank2_cell_bits", "spectral_hist", "hodge_spectrum") if spectra else ()) + (("orbit_counts", "orbit_nodes") if orbits else ()) + (
+            ("x", "nspdk_labels") + ev.NSPDK_KEYS if nspdk else ())
 
         def side(obj):
             if isinstance(obj, (str, os.PathLike)):
@@ -386,13 +392,17 @@ class Sampler:
                     if "adj" not in desc:
                         raise KeyError("evaluate: a descriptor dict needs degree_hist, edge_hist and cluster_hist, or adj to compute them from")
                     desc.update(ev.describe(desc["adj"], mol=self.is_mol, bins=bins, **kw))
+                if nspdk and self.is_mol and not all(k in desc for k in ev.NSPDK_KEYS) and "x" not in desc and "nspdk_labels" not in desc:
+                    raise KeyError("evaluate: nspdk=True on a molecule run needs x or nspdk_labels (or the nspdk_* rows) on each side")
                 return desc
-            return ev.describe(torch.as_tensor(obj), mol=self.is_mol, bins=bins, orbits=orbits, **kw)
+            if nspdk and self.is_mol:
+                raise KeyError("evaluate: nspdk=True on a molecule run needs x or nspdk_labels beside the adjacency batch: pass a dict")
+            return ev.describe(torch.as_tensor(obj), mol=self.is_mol, bins=bins, orbits=orbits, nspdk=nspdk, **kw)
 
         pred, held = side(result), side(ref)
         if methods is None:
-            methods = ["degree", "cluster"] + (["orbit"] if orbits else []) + (["spectral"] if spectra else [])
-        out = ev.eval_torch_batch(held, pred, methods, bins=bins, mol=self.is_mol, spectra=spectra, orbits=orbits, **kw)
+            methods = ["degree", "cluster"] + (["orbit"] if orbits else []) + (["spectral"] if spectra else []) + (["nspdk"] if nspdk else [])
+        out = ev.eval_torch_batch(held, pred, methods, bins=bins, mol=self.is_mol, spectra=spectra, orbits=orbits, nspdk=nspdk, **kw)
         if self.is_cc:
             data = _get(self.config, "data")
             wk = {"min_edge_val": _get(data, "min_edge_val", 1), "max_edge_val": _get(data, "max_edge_val", 3 if self.is_mol else 1)}

@@ -170,6 +170,64 @@ class SampleOps:
                                                   _ptr(res["orbit_counts"]), _ptr(res["orbit_nodes"]), self._stream()))
         return res
 
+    def nspdk_features(self, adj: torch.Tensor, labels: Optional[torch.Tensor] = None, *, mol: bool = False, thr: float = 0.5) -> dict:
+        """NSPDK feature rows (ccsd_nspdk_features): what vectorize(graphs, complexity=4, discrete=True) of the reference
+        (evaluation/eden.py; mmd.py:331-337) gives for the graphs of the quantised adjacency, finish()'s quantiser (`mol`, `thr`; in
+        mol mode the bond order 1..3 is the edge label), when nodes carry INTEGER labels.  adj (B,N,N) float32, SYMMETRIC, N <= 64.
+        labels (B,N) integer: the label per node slot, negative = the slot holds no node (its edges are ignored); None = every slot is
+        a node with label 0.  -> the rows in CSR form, compacted on the device:
+          nspdk_indptr (B+1,) int64, nspdk_indices (nnz,) int32 ascending within a row in 1..65536, nspdk_values (nnz,) float64
+        Each row has unit L2 norm; a graph without a node has an empty row.  Two calls give identical bits.  The one host round trip
+        is the total size.  N > 64 raises NotImplementedError."""
+        adj = self._adj("nspdk_features", adj)
+        B, N = adj.shape[0], adj.shape[1]
+        if labels is not None:
+            if tuple(labels.shape) != (B, N) or labels.dtype.is_floating_point or labels.device.type != self.device.type:
+                raise ValueError(f"nspdk_features: labels must be integer of shape ({B}, {N}) on {self.device}, got {labels.dtype} {tuple(labels.shape)} {labels.device}")
+            labels = labels.to(torch.int32).contiguous()
+        cap = self.lib.ccsd_nspdk_row_capacity(N)
+        nbytes = self.lib.ccsd_nspdk_workspace_bytes(B, N)
+        if cap == 0 or nbytes == 0:
+            self.lib.check(_lib.ERR_UNSUPPORTED if N > _lib.NSPDK_MAX_NODES else _lib.ERR_INVALID)
+        nnz = torch.empty((B,), dtype=torch.int32, device=adj.device)
+        idx = torch.empty((B, cap), dtype=torch.int32, device=adj.device)
+        val = torch.empty((B, cap), dtype=torch.float64, device=adj.device)
+        ws = self._scratch(nbytes, adj.device)
+        self.lib.check(self.lib.ccsd_nspdk_features(_ptr(adj), _ptr(labels), B, N, _adj_mode(mol), float(thr), _ptr(nnz), _ptr(idx), _ptr(val),
+                                                    _ptr(ws), ws.numel() * 8, self._stream()))
+        indptr = torch.zeros((B + 1,), dtype=torch.int64, device=adj.device)
+        torch.cumsum(nnz, 0, out=indptr[1:])
+        keep = torch.arange(cap, device=adj.device)[None, :] < nnz[:, None]
+        return {"nspdk_indptr": indptr, "nspdk_indices": idx[keep], "nspdk_values": val[keep]}
+
+    def nspdk_mmd(self, a: dict, b: dict) -> torch.Tensor:
+        """compute_nspdk_mmd of the reference (evaluation/mmd.py:352-377) on two sets of nspdk_features rows (ccsd_nspdk_mmd) -> a
+        float64 device tensor [mean Kxx, mean Kyy, mean Kxy, mmd].  a: the reference set (empty rows count as zero vectors), b: the
+        predicted set (empty rows are left out, as nspdk_stats drops graphs without a node).  Nothing is synchronised."""
+        sets = []
+        for name, d in (("a", a), ("b", b)):
+            try:
+                ip, ix, vl = d["nspdk_indptr"], d["nspdk_indices"], d["nspdk_values"]
+            except KeyError as e:
+                raise KeyError(f"nspdk_mmd: set {name} lacks {e.args[0]}; nspdk_features produces it") from None
+            if ip.dtype != torch.int64 or ix.dtype != torch.int32 or vl.dtype != torch.float64 or ip.dim() != 1 or ip.numel() < 2 or ix.shape != vl.shape:
+                raise ValueError(f"nspdk_mmd: set {name} must hold nspdk_indptr (n+1,) int64, nspdk_indices int32 and nspdk_values float64 of one shape")
+            for t in (ip, ix, vl):
+                if t.device.type != self.device.type:
+                    raise ValueError(f"nspdk_mmd: set {name} must be on {self.device}, got {t.device}")
+            if ix.numel() == 0:                                   # (no non-zero at all: the C call still wants addresses)
+                ix, vl = ix.new_zeros(1), vl.new_zeros(1)
+            sets.append((ip.contiguous(), ix.contiguous(), vl.contiguous(), ip.numel() - 1))
+        (p1, i1, v1, n1), (p2, i2, v2, n2) = sets
+        out = torch.empty(4, dtype=torch.float64, device=p1.device)
+        nbytes = self.lib.ccsd_nspdk_mmd_workspace_bytes(n1, n2)
+        if nbytes == 0:
+            self.lib.check(_lib.ERR_INVALID)
+        ws = self._scratch(nbytes, p1.device)
+        self.lib.check(self.lib.ccsd_nspdk_mmd(_ptr(p1), _ptr(i1), _ptr(v1), n1, _ptr(p2), _ptr(i2), _ptr(v2), n2, _ptr(ws), ws.numel() * 8,
+                                               _ptr(out), self._stream()))
+        return out
+
     def mmd(self, s1: torch.Tensor, s2: torch.Tensor, kind: str = "emd", *, is_hist: bool = True, degree: bool = False,
             f32_pmf: bool = False, sigma: float = 1.0, distance_scaling: float = 1.0, lens1: Optional[torch.Tensor] = None,
             lens2: Optional[torch.Tensor] = None) -> torch.Tensor:

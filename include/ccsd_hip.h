@@ -38,6 +38,9 @@
  *                              (evaluation/stats.py:206-220; graph_utils.py:216-251)
  * ccsd_orbit_counts            what orbit_stats_all reads from the external orca program (`orca node 4`): the 4-node graphlet orbit
  *                              counts per node and per graph, and the node count it divides by (evaluation/stats.py:343-435)
+ * ccsd_nspdk_features          eden.py's vectorize(graphs, complexity=4, discrete=True) for graphs with INTEGER node labels: the NSPDK
+ *                              feature row of every graph (evaluation/eden.py; mmd.py:331-337)
+ * ccsd_nspdk_mmd               compute_nspdk_mmd on two sets of such rows (evaluation/mmd.py:352-377; nspdk_stats, stats.py:438-467)
  * ccsd_mmd                     compute_mmd with gaussian_emd / gaussian_tv / gaussian: the scores of degree_stats, clustering_stats,
  *                              rank1_distrib_stats, rank2_distrib_stats (evaluation/mmd.py:27-257; evaluation/stats.py:60-310;
  *                              cc_utils.py:1235-1406); ccsd_mmd_workspace_bytes sizes its workspace
@@ -349,6 +352,37 @@ int ccsd_cluster_hist(const float* adj_dev, int32_t B, int32_t N, int32_t adj_mo
 #define CCSD_ORBITS 15
 int ccsd_orbit_counts(const float* adj_dev, int32_t B, int32_t N, int32_t adj_mode, float thr, int64_t* node_orbits_dev,
                       int64_t* graph_orbits_dev, int32_t* orbit_nodes_dev, void* stream);
+
+/* The NSPDK feature vector of every graph of adj_dev (B,N,N), 1 <= N <= 64: the row eden.py's vectorize(graphs, complexity = 4,
+ * discrete = True) gives for the graph whose nodes carry INTEGER labels (Python's hash of an int is the int, so the row is deterministic;
+ * the reference's atom-symbol strings hash differently in every process).  labels_dev (B,N) int32: the label per node slot, negative = the
+ * slot holds no node; NULL = every slot is a node with label 0.  Edges, the quantiser (adj_mode, thr) and the SYMMETRIC-adjacency contract
+ * are ccsd_cluster_hist's; an edge with an absent endpoint is ignored; the edge label is the quantised bond order 1..3 with
+ * CCSD_FINISH_ADJ_MOL and 1 otherwise.  The vectoriser's steps are written out in ccsd_amd/csrc/ccsd_k_nspdk.h.
+ * Output, a row-capacity layout with cap = ccsd_nspdk_row_capacity(N) = min(65536, 10 N^2):
+ *   nnz_dev (B,) int32            non-zeros of the row; 0 for a graph without a node
+ *   indices_dev (B,cap) int32     the feature indices, ascending, 1 .. 65536 (the feature space is CCSD_NSPDK_FEATURES = 65537 wide)
+ *   values_dev (B,cap) fp64       the values (the row has unit L2 norm); entries at and past nnz are not written
+ * All counting is integer and every floating-point sum has a fixed order: two calls give identical bits.
+ * workspace: ccsd_nspdk_workspace_bytes(B, N) bytes, 8-byte aligned (it does not grow with B past 512 graphs).
+ * N > 64: CCSD_ERR_UNSUPPORTED; other bad sizes: CCSD_ERR_INVALID (the size functions then return 0). */
+#define CCSD_NSPDK_MAX_NODES 64
+#define CCSD_NSPDK_FEATURES 65537
+int32_t ccsd_nspdk_row_capacity(int32_t N);
+size_t ccsd_nspdk_workspace_bytes(int32_t B, int32_t N);
+int ccsd_nspdk_features(const float* adj_dev, const int32_t* labels_dev, int32_t B, int32_t N, int32_t adj_mode, float thr,
+                        int32_t* nnz_dev, int32_t* indices_dev, double* values_dev, void* workspace, size_t ws_bytes, void* stream);
+
+/* compute_nspdk_mmd (evaluation/mmd.py:352-377) of two sets of feature rows in CSR form on the device: indptr (n + 1) int64, indices
+ * int32 ascending within a row and in 1 .. 65536, values fp64.  Under the linear kernel the mean over all pairs of K(x, x') is the squared
+ * norm of the set's mean vector, so out_dev (4 doubles) = [mean Kxx, mean Kyy, mean Kxy, mmd = Kxx + Kyy - 2 Kxy] comes from the two
+ * mean vectors, every sum in a fixed order.  Rows of the FIRST set without a non-zero count as zero vectors; rows of the SECOND
+ * (predicted) set without a non-zero are left out, as nspdk_stats drops graphs without a node (stats.py:452-454) -- a second set with
+ * no row left gives NaN.  1 <= n1, n2 <= CCSD_MMD_MAX_ROWS.  workspace: ccsd_nspdk_mmd_workspace_bytes(n1, n2) bytes, 8-byte aligned. */
+size_t ccsd_nspdk_mmd_workspace_bytes(int32_t n1, int32_t n2);
+int ccsd_nspdk_mmd(const int64_t* indptr1_dev, const int32_t* indices1_dev, const double* values1_dev, int32_t n1,
+                   const int64_t* indptr2_dev, const int32_t* indices2_dev, const double* values2_dev, int32_t n2, void* workspace,
+                   size_t ws_bytes, double* out_dev, void* stream);
 
 /* compute_mmd (evaluation/mmd.py:230-257) of two sets of histograms, in fp64 and bit-reproducible from call to call:
  *   mmd = disc(1,1) + disc(2,2) - 2 disc(1,2),  disc = mean over all pairs of exp(-dist(x, y)^2 / (2 sigma^2)). */

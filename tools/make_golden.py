@@ -858,6 +858,72 @@ def e3_orbit():
 
 
 # ---------------------------------------------------------------------------------------------
+# e4_nspdk.npz: the reference's NSPDK vectoriser and compute_nspdk_mmd on the graph sets of tests/nspdk_cases.py
+# (`python tools/make_golden.py nspdk`)
+# ---------------------------------------------------------------------------------------------
+def e4_graphs(adj, labels):
+    """networkx graphs of a set: a slot with a non-negative label is a node carrying that INTEGER as its label (hash(int) is the int:
+    the vectoriser's rows do not depend on the process); an edge between two nodes carries the bond order as its label."""
+    import networkx as nx
+
+    graphs = []
+    for a, l in zip(adj, labels):
+        g = nx.Graph()
+        for i in np.nonzero(l >= 0)[0]:
+            g.add_node(int(i), label=int(l[i]))
+        for i, j in zip(*np.nonzero(np.triu(a, 1))):
+            if l[i] >= 0 and l[j] >= 0:
+                g.add_edge(int(i), int(j), label=int(a[i, j]))
+        graphs.append(g)
+    return graphs
+
+
+def e4_nspdk():
+    """e4_nspdk.npz: per graph set the adjacency and labels (as tests/nspdk_cases.py generates them), the CSR rows of the reference's
+    vectorize(graphs, complexity=4, discrete=True), its compute_nspdk_mmd for the first half of the set against the rest and for mol9
+    against itself, and the difference between that pairwise form and the float64 mean form of the reference's own rows."""
+    import time
+
+    sys.path.insert(0, ROOT)
+    from tests import nspdk_cases as nc
+    from tests import nspdk_ref
+
+    record = {"tl": __import__("threading").local()}
+    sys.modules.setdefault("pyemd", _pyemd_stand_in(record))
+    from ccsd.src.evaluation import eden as ref_eden
+    from ccsd.src.evaluation import mmd as ref_mmd
+
+    out, meta = {}, {"sets": {}}
+    graphs = {}
+    for name, (adj, lab) in nc.graph_sets().items():
+        G = graphs[name] = e4_graphs(adj, lab)
+        t0 = time.time()
+        X = ref_eden.vectorize(G, complexity=4, discrete=True).tocsr()
+        sec = time.time() - t0
+        X.sort_indices()
+        assert X.shape == (len(G), 65537) and (X.data > 0).all()
+        out[f"{name}/adj"], out[f"{name}/labels"] = adj.astype(np.int8), lab.astype(np.int32)
+        out[f"{name}/indptr"], out[f"{name}/indices"], out[f"{name}/values"] = X.indptr.astype(np.int64), X.indices.astype(np.int32), X.data.astype(np.float64)
+        s1, s2 = nc.split(name)
+        mmd = float(ref_mmd.compute_nspdk_mmd(G[s1], G[s2], metric="nspdk", is_hist=False, n_jobs=None))
+        rows = (out[f"{name}/indptr"], out[f"{name}/indices"], out[f"{name}/values"])
+        cut = lambda sl: (rows[0][sl.start:sl.stop + 1] - rows[0][sl.start], rows[1][rows[0][sl.start]:rows[0][sl.stop]], rows[2][rows[0][sl.start]:rows[0][sl.stop]])
+        mean_form = nspdk_ref.mmd_mean_form(cut(s1), cut(s2))[3]
+        meta["sets"][name] = {"B": int(adj.shape[0]), "N": int(adj.shape[1]), "nnz": int(X.nnz), "max_row_nnz": int(np.diff(X.indptr).max()), "mmd": mmd,
+                              "pairwise_minus_mean_form": mmd - mean_form, "vectorize_seconds": round(sec, 3)}
+        print("e4", name, meta["sets"][name])
+    meta["self"] = {"set": "mol9", "mmd": float(ref_mmd.compute_nspdk_mmd(graphs["mol9"], graphs["mol9"], metric="nspdk", is_hist=False, n_jobs=None))}
+    meta["note"] = ("indptr / indices / values = the CSR rows of the reference's vectorize(graphs, complexity=4, discrete=True) on networkx graphs whose "
+                    "node labels are the integers of `labels` (negative: no node) and whose edge labels are the bond orders of `adj`; mmd = "
+                    "compute_nspdk_mmd(first half, rest, metric='nspdk'); vectorize_seconds = the reference's vectoriser on the generating machine's CPU")
+    out["meta"] = np.array(json.dumps(plain(meta)))
+    path = os.path.join(GOLD, "e4_nspdk.npz")
+    np.savez_compressed(path, **out)
+    assert os.path.getsize(path) <= MAX_FIXTURE // 2, os.path.getsize(path)
+    print("wrote e4_nspdk", os.path.getsize(path), "bytes; self", meta["self"])
+
+
+# ---------------------------------------------------------------------------------------------
 # e2_spectrum.npz: the reference's two spectral evaluators on small sets (`python tools/make_golden.py spectrum`)
 # ---------------------------------------------------------------------------------------------
 class _StandInComplex:
@@ -1872,6 +1938,9 @@ def main():
         return
     if only == {"orbit"}:
         e3_orbit()
+        return
+    if only == {"nspdk"}:
+        e4_nspdk()
         return
     if only == {"d1"}:
         # ~a quarter of an hour of reference CPU time was the estimate; the fixture's metadata holds what it took
