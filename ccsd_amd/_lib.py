@@ -24,7 +24,7 @@ EXPORTS = [
     "ccsd_plan_create", "ccsd_plan_destroy", "ccsd_weight_count", "ccsd_rank2_dims", "ccsd_workspace_bytes",
     "ccsd_last_error", "ccsd_score", "ccsd_init_state", "ccsd_corrector_norms", "ccsd_corrector_apply",
     "ccsd_predictor", "ccsd_s4_apply", "ccsd_sampler_run", "ccsd_quantize", "ccsd_rank2_cells", "ccsd_profile_kernel", "ccsd_profile_stride", "ccsd_profile_read", "ccsd_profile_launches", "ccsd_debug_stamps",
-    "ccsd_noise_draws", "ccsd_plan_query", "ccsd_sampler_run_ex", "ccsd_finish",
+    "ccsd_noise_draws", "ccsd_noise_draws_at", "ccsd_plan_query", "ccsd_sampler_run_ex", "ccsd_finish",
     "ccsd_cluster_hist", "ccsd_orbit_counts", "ccsd_mmd_workspace_bytes", "ccsd_mmd",
     "ccsd_eig_workspace_bytes", "ccsd_eigvalsh", "ccsd_spectral_workspace_bytes", "ccsd_spectral_hist",
     "ccsd_hodge_workspace_bytes", "ccsd_hodge_spectrum",
@@ -166,6 +166,8 @@ class Library:
         L.ccsd_debug_stamps.restype = C.c_int
         L.ccsd_noise_draws.argtypes = [vp, i32, vp, u64, i64, i32, i32, P(State), vp]
         L.ccsd_noise_draws.restype = C.c_int
+        L.ccsd_noise_draws_at.argtypes = [vp, i32, vp, u64, i64, C.c_uint32, i32, P(State), vp]
+        L.ccsd_noise_draws_at.restype = C.c_int
         L.ccsd_plan_query.argtypes = [vp, i32, P(i64)]
         L.ccsd_plan_query.restype = C.c_int
         L.ccsd_finish.argtypes = [P(FinishDims), P(State), vp, P(FinishOut), vp]

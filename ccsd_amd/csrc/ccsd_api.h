@@ -1273,6 +1273,12 @@ extern "C" int ccsd_noise_draws(ccsd_plan_t* pl, int32_t B, const float* flags, 
                           corr ? pl->rt.corrector_flat : pl->rt.predictor_flat);
 }
 
+extern "C" int ccsd_noise_draws_at(ccsd_plan_t* pl, int32_t B, const float* flags, uint64_t seed, int64_t sample_offset, uint32_t draw,
+                                   int32_t flat_rank2, ccsd_state_t* out, void* stream) {
+    if (!pl) return set_err(CCSD_ERR_INVALID, "NULL plan");
+    return draws_to_state(pl, B, flags, nullptr, seed, sample_offset, draw, out, stream, flat_rank2 ? 1 : 0);
+}
+
 extern "C" int ccsd_plan_query(const ccsd_plan_t* pl, int32_t what, int64_t* value) {
     if (!pl || !value) return set_err(CCSD_ERR_INVALID, "NULL argument");
     const Route& r = pl->rt;

@@ -151,7 +151,54 @@ struct NoiseArgs {
     int flat_r;
 };
 
-// Philox4x32-10 (Salmon et al. 2011), counter = (group, sample, draw, 0), key = seed
+// How philox4 (below) avoids the s_nop behind its three-input sums on the GPU, per translation unit; both forms compute the same words.
+// v_mad_u64_u32 also writes a carry-out nobody reads.  Left alone the compiler gives it the free scalar pair in which it then forms the
+// next round key, and the sum that reads the key right behind -- a VALU read of an SGPR a VALU wrote -- waits an s_nop: 402 of them in
+// the baked qm9 k_r2.  Measured per kernel family, profiles/r18_rng_diet.md:
+//   1  the running keys are pinned in registers of their own, round by round.  The default: kernels with several independent
+//      generations in flight per thread (k_gemm_p0's fused modes, k_hf_score, k_hp_full, k_ew1, ...), k_xa, k_init_state.
+//   2  the multiply's carry-out goes to VCC (philox_mul, an asm statement).  The units of k_r2 (ccsd_r2*.hip define the macro ahead of
+//      this header), whose block load runs ONE dependent Philox chain per thread.  With several chains the asm statements, which all
+//      write VCC, stay in program order and the chains no longer interleave: there form 1 is the faster one.
+#ifndef CCSD_PHILOX_FORM
+#define CCSD_PHILOX_FORM 1
+#endif
+#if CCSD_PHILOX_FORM != 1 && CCSD_PHILOX_FORM != 2
+#error "CCSD_PHILOX_FORM must be 1 or 2"
+#endif
+
+// a ^ b ^ c.  gfx950 has a three-input bitwise instruction (v_bitop3_b32, truth table 0x96 = odd parity); the builtin rather than inline
+// asm, so the compiler still schedules it.  Host emulation, the host pass of hipcc and a compiler without the builtin take the two XORs.
+CCSD_DEV unsigned int xor3(unsigned int a, unsigned int b, unsigned int c) {
+#if !defined(CCSD_EMU) && defined(__HIP_DEVICE_COMPILE__) && defined(__has_builtin)
+#if __has_builtin(__builtin_amdgcn_bitop3_b32)
+    return __builtin_amdgcn_bitop3_b32(a, b, c, 0x96);
+#else
+    return a ^ b ^ c;
+#endif
+#else
+    return a ^ b ^ c;
+#endif
+}
+
+// m * c as 64 bits, c per-lane; form 2: v_mad_u64_u32 with its carry-out in VCC, so that the keys' registers are never VALU-written.
+// Plain asm, not volatile: still scheduled, merged and dropped like any other instruction.  The compiler's hazard recognizer does
+// NOT look inside an asm statement: it inserts no wait states between this multiply and an MFMA that reads or writes the same
+// VGPRs, nor behind a transcendental.  The operands here are integer Philox words, never an MFMA's or a transcendental's result, and in
+// every k_r2 instance built today the nearest MFMA whose accumulator overlaps the destination is 18 issue slots away; that rests on
+// register allocation and scheduling, not on construction -- after an edit of k_r2 that moves draws next to its MFMAs, look again.
+CCSD_DEV unsigned long long philox_mul(unsigned int m, unsigned int c) {
+#if CCSD_PHILOX_FORM == 2 && !defined(CCSD_EMU) && defined(__HIP_DEVICE_COMPILE__)
+    unsigned long long p;
+    asm("v_mad_u64_u32 %0, vcc, %1, %2, 0" : "=v"(p) : "v"(c), "s"(m) : "vcc");
+    return p;
+#else
+    return (unsigned long long)m * c;
+#endif
+}
+
+// Philox4x32-10 (Salmon et al. 2011), counter = (group, sample, draw, 0), key = seed.  On the GPU the key (k0, k1) must be wave-uniform
+// (it is the run's seed everywhere): the "+s" pins below keep it in scalar registers.
 CCSD_DEV void philox4(unsigned int c0, unsigned int c1, unsigned int c2, unsigned int c3, unsigned int k0,
                       unsigned int k1, unsigned int* out) {
 #ifndef CCSD_EMU
@@ -161,14 +208,24 @@ CCSD_DEV void philox4(unsigned int c0, unsigned int c1, unsigned int c2, unsigne
 #endif
 #pragma unroll
     for (int r = 0; r < 10; ++r) {
-        const unsigned long long p0 = (unsigned long long)0xD2511F53u * c0;
-        const unsigned long long p1 = (unsigned long long)0xCD9E8D57u * c2;
-        const unsigned int n0 = (unsigned int)(p1 >> 32) ^ c1 ^ k0;       // (gfx950 has no three-operand xor: two v_xor_b32)
-        const unsigned int n2 = (unsigned int)(p0 >> 32) ^ c3 ^ k1;
+        // (round 1's c2 and round 2's c0 are wave-uniform in the hot kernels: those two products stay plain C, on the scalar ALU)
+        const unsigned long long p0 = r != 1 ? philox_mul(0xD2511F53u, c0) : (unsigned long long)0xD2511F53u * c0;
+        const unsigned long long p1 = r != 0 ? philox_mul(0xCD9E8D57u, c2) : (unsigned long long)0xCD9E8D57u * c2;
+        // In the hot kernels only the group is per-lane: (c1, c2, c3) = (sample, draw, sample >> 32) are wave-uniform, so until the
+        // third round one or two terms of each sum are scalars.  Those stay plain C: the compiler folds the uniform terms on the scalar ALU
+        // and issues one v_xor_b32 (a three-input instruction takes one scalar operand only and would pull them onto the vector ALU).
+        // From where all three terms are per-lane (n0: round 3, n2: round 4) the sum is one v_bitop3_b32 instead of two v_xor_b32.
+        const unsigned int n0 = r >= 2 ? xor3((unsigned int)(p1 >> 32), c1, k0) : (unsigned int)(p1 >> 32) ^ c1 ^ k0;
+        const unsigned int n2 = r >= 3 ? xor3((unsigned int)(p0 >> 32), c3, k1) : (unsigned int)(p0 >> 32) ^ c3 ^ k1;
         const unsigned int n1 = (unsigned int)p1;
         const unsigned int n3 = (unsigned int)p0;
         c0 = n0; c1 = n1; c2 = n2; c3 = n3;
         k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
+#if CCSD_PHILOX_FORM == 1 && !defined(CCSD_EMU)
+        // the running keys stay in registers of their own: the compiler cannot fold round r's key to k + r W in a scratch register,
+        // which is the pair the multiply's dead carry-out went to
+        asm volatile("" : "+s"(k0), "+s"(k1));
+#endif
     }
     out[0] = c0; out[1] = c1; out[2] = c2; out[3] = c3;
 }
@@ -181,7 +238,9 @@ CCSD_DEV void philox_normal4(unsigned long long seed, unsigned int draw, long lo
     const float inv24 = 1.0f / 16777216.0f;
 #pragma unroll
     for (int h = 0; h < 2; ++h) {
-        const float u1 = (float)((r[2 * h] >> 8) + 1u) * inv24;    // (0, 1]
+        // (n + 1) 2^-24 in (0, 1], n = r >> 8 < 2^24, as one FMA: n and n + 1 <= 2^24 are exact in fp32 and the scaling is by a power
+        // of two with no denormal in range, so this is bit for bit (float)(n + 1) * 2^-24 (tests/test_u1_exact.py walks all 2^24 n)
+        const float u1 = fmaf((float)(r[2 * h] >> 8), inv24, inv24);
         const float u2 = (float)(r[2 * h + 1] >> 8) * inv24;       // [0, 1)
 #ifdef CCSD_EMU
         const float rad = sqrtf(-2.0f * logf(u1));

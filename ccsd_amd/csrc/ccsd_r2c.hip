@@ -1,4 +1,5 @@
 // ccsd_r2c.hip -- product translation unit: instantiations of the fused rank-2 kernel k_r2 -- the affine shapes with one row tile (E <= 15).
+#define CCSD_PHILOX_FORM 2      // k_r2 draws through one dependent Philox chain per thread (ccsd_dev.h)
 #include "ccsd_dev.h"
 #include "ccsd_k_r2.h"
 #define CCSD_INST template

@@ -131,6 +131,14 @@ class PCEngine(SampleOps):
         self.lib.check(self.lib.ccsd_noise_draws(self.handle, B, _ptr(flags), seed, sample_offset, int(step), int(phase),
                                                  C.byref(so), self._stream()))
 
+    def noise_draws_at(self, flags, draw: int, flat_rank2: bool, out, seed: int = 0, sample_offset: int = 0):
+        """The masked draws of draw indices `draw`, `draw` + 1, `draw` + 2 (mod 2^32) for x, adj, rank2 (ccsd_noise_draws_at): a test
+        hook for draw indices that no (step, phase) of the plan reaches."""
+        B = flags.shape[0]
+        so = self._state(*out, B, "out")
+        self.lib.check(self.lib.ccsd_noise_draws_at(self.handle, B, _ptr(flags), seed, sample_offset, int(draw) & 0xFFFFFFFF,
+                                                    int(bool(flat_rank2)), C.byref(so), self._stream()))
+
     def query(self, what: str) -> int:
         """Which kernels the plan selected (ccsd_plan_query): "fused_r2", "xa_variant", "r2_lds_bytes", "xa_lds_bytes", "fused_loop", "merged_r2", "ew1", "large_graph";
         the rest of the route: "r2_family", "r2_instance", "loop_form", "tiled_fuse", "ew1_fuse", "h_general", "geo_ek", "p0_narrow" and, for the

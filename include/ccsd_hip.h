@@ -177,6 +177,14 @@ int ccsd_init_state(ccsd_plan_t* plan, int32_t B, const float* flags_dev, const 
 int ccsd_noise_draws(ccsd_plan_t* plan, int32_t B, const float* flags_dev, uint64_t seed, int64_t sample_offset,
                      int32_t step, int32_t phase, ccsd_state_t* out, void* stream);
 
+/* The same masked draws at an explicit draw index: x, adj and rank2 take draws `draw`, `draw` + 1 and `draw` + 2 (mod 2^32);
+ * flat_rank2 selects the element -> group map of the rank-2 draw (0: four edge rows of a column, 1: four consecutive elements).
+ * Test hook for the ends of the counter range, which no (step, phase) of a plan reaches.  Arguments are checked as ccsd_init_state
+ * checks them.  (A library built before this entry point existed does not load under the Python binding, which resolves every
+ * declared symbol: to compare against such a build, run it from its own source tree.) */
+int ccsd_noise_draws_at(ccsd_plan_t* plan, int32_t B, const float* flags_dev, uint64_t seed, int64_t sample_offset,
+                        uint32_t draw, int32_t flat_rank2, ccsd_state_t* out, void* stream);
+
 /* Which kernels a plan selected (host-side facts, no device work). */
 enum {
     CCSD_QUERY_FUSED_R2 = 0,      /* 1: the LDS-resident fused rank-2 kernel k_r2 serves the rank-2 side; 0: the tiled kernels */

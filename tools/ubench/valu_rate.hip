@@ -45,6 +45,24 @@ __global__ void k_rate(int iters, float* out, long long* cyc) {
                 asm volatile("v_mad_u64_u32 %0, %4, %8, %9, 0\n\tv_mad_u64_u32 %1, %5, %9, %10, 0\n\tv_mad_u64_u32 %2, %6, %10, %11, 0\n\tv_mad_u64_u32 %3, %7, %11, %8, 0"
                              : "=&v"(q0), "=&v"(q1), "=&v"(q2), "=&v"(q3), "=&s"(k0), "=&s"(k1), "=&s"(k2), "=&s"(k3) : "v"(u4), "v"(u5), "v"(u6), "v"(u7));
                 u4 ^= (unsigned)q0; u5 ^= (unsigned)(q1 >> 32); u6 ^= (unsigned)q2; u7 ^= (unsigned)(q3 >> 32);
+            } else if (MODE == 8) {   // v_bitop3_b32, truth table 0x96 = a ^ b ^ c (VOP3), independent: beside MODE 3, which needs two instructions for it
+                asm volatile("v_bitop3_b32 %0, %0, %1, %2 bitop3:0x96\n\tv_bitop3_b32 %1, %1, %2, %3 bitop3:0x96\n\tv_bitop3_b32 %2, %2, %3, %4 bitop3:0x96\n\t"
+                             "v_bitop3_b32 %3, %3, %4, %5 bitop3:0x96\n\tv_bitop3_b32 %4, %4, %5, %6 bitop3:0x96\n\tv_bitop3_b32 %5, %5, %6, %7 bitop3:0x96\n\t"
+                             "v_bitop3_b32 %6, %6, %7, %0 bitop3:0x96\n\tv_bitop3_b32 %7, %7, %0, %1 bitop3:0x96"
+                             : "+v"(u0), "+v"(u1), "+v"(u2), "+v"(u3), "+v"(u4), "+v"(u5), "+v"(u6), "+v"(u7));
+            } else if (MODE == 9 || MODE == 10) {   // a Philox round pair per chain: 2 v_mad_u64_u32 + 2 three-input sums, as 2 v_bitop3_b32 (9) or 4 v_xor_b32 (10); four chains
+                unsigned long long q0, q1, q2, q3, k0, k1, k2, k3;
+                asm volatile("v_mad_u64_u32 %0, %4, %8, %9, 0\n\tv_mad_u64_u32 %1, %5, %9, %10, 0\n\tv_mad_u64_u32 %2, %6, %10, %11, 0\n\tv_mad_u64_u32 %3, %7, %11, %8, 0"
+                             : "=&v"(q0), "=&v"(q1), "=&v"(q2), "=&v"(q3), "=&s"(k0), "=&s"(k1), "=&s"(k2), "=&s"(k3) : "v"(u0), "v"(u1), "v"(u2), "v"(u3));
+                if (MODE == 9)
+                    asm volatile("v_bitop3_b32 %0, %4, %0, %1 bitop3:0x96\n\tv_bitop3_b32 %1, %5, %1, %2 bitop3:0x96\n\t"
+                                 "v_bitop3_b32 %2, %6, %2, %3 bitop3:0x96\n\tv_bitop3_b32 %3, %7, %3, %0 bitop3:0x96"
+                                 : "+v"(u4), "+v"(u5), "+v"(u6), "+v"(u7) : "v"((unsigned)(q0 >> 32)), "v"((unsigned)(q1 >> 32)), "v"((unsigned)(q2 >> 32)), "v"((unsigned)(q3 >> 32)));
+                else
+                    asm volatile("v_xor_b32 %0, %4, %0\n\tv_xor_b32 %1, %5, %1\n\tv_xor_b32 %2, %6, %2\n\tv_xor_b32 %3, %7, %3\n\t"
+                                 "v_xor_b32 %0, %0, %1\n\tv_xor_b32 %1, %1, %2\n\tv_xor_b32 %2, %2, %3\n\tv_xor_b32 %3, %3, %0"
+                                 : "+v"(u4), "+v"(u5), "+v"(u6), "+v"(u7) : "v"((unsigned)(q0 >> 32)), "v"((unsigned)(q1 >> 32)), "v"((unsigned)(q2 >> 32)), "v"((unsigned)(q3 >> 32)));
+                u0 ^= (unsigned)q0; u1 ^= (unsigned)q1; u2 ^= (unsigned)q2; u3 ^= (unsigned)q3;     // (keeps the low halves live: 4 more v_xor_b32 in both modes)
             } else {                  // v_mul_hi_u32
                 asm volatile("v_mul_hi_u32 %0, %0, %0\n\tv_mul_hi_u32 %1, %1, %1\n\tv_mul_hi_u32 %2, %2, %2\n\tv_mul_hi_u32 %3, %3, %3\n\t"
                              "v_mul_hi_u32 %4, %4, %4\n\tv_mul_hi_u32 %5, %5, %5\n\tv_mul_hi_u32 %6, %6, %6\n\tv_mul_hi_u32 %7, %7, %7"
@@ -84,9 +102,14 @@ int main() {
     run<4>("v_exp_f32 independent", dout, dc);
     run<5>("v_pk_fma_f32 independent", dout, dc);
     run<7>("v_mad_u64_u32 x8 + 8 v_xor (per 16 instr)", dout, dc);
+    run<8>("v_bitop3_b32 0x96 independent", dout, dc);
+    run<10>("round pair, xor: per 1 v_mad + 3 v_xor", dout, dc);
+    run<9>("round pair, bitop3: per 1 v_mad+1 bitop3+1 xor", dout, dc);
     return 0;
 }
 // Measured (profiles/r03_c_valu_rate.txt, cycles per wave64 instruction issued on a SIMD that holds 4 waves): v_fma_f32 2.65, v_xor_b32 2.47,
 // v_mul_lo/hi_u32 4.39, v_exp_f32 8.27, v_pk_fma_f32 8.42 (two FMAs: no gain over two v_fma_f32), v_mad_u64_u32 ~13 in this loop; ONE
 // wave alone issues a VALU instruction every 5.4-5.8 cycles whether dependent or not, two waves reach 3.4.  (Replacing Philox's
 // v_mad_u64_u32 by v_mul_hi_u32 + v_mul_lo_u32 in the kernels was nevertheless slower: k_r2 167.7 -> 172.5 us.)
+// profiles/r18_valu_rate.txt: v_bitop3_b32 bitop3:0x96 (a ^ b ^ c in one VOP3 instruction) 2.53 beside v_xor_b32 2.42; a Philox round pair
+// per chain 7.14 (1 v_mad_u64_u32 + 3 v_xor_b32 per quarter body) against 5.53 with the three-input sums (1 + 1 + 1).
