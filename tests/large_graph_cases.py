@@ -37,26 +37,35 @@ def engine(meta, parts, lib, device, **kw):
                     d_max=0, device=device, lib=lib, **kw)
 
 
-def case_forward_vs_oracle_src(meta, parts, lib, device, counts, what, seed=11, expect_lg=1):
-    """Both networks' forward (raw nets and the score scaling at t = 0.5) on masked random inputs against the oracle."""
+def case_forward_vs_oracle_src(meta, parts, lib, device, counts, what, seed=11, expect_lg=1, batch_hint=0, oracle=None):
+    """Both networks' forward (raw nets and the score scaling at t = 0.5) on masked random inputs against the oracle.  `expect_lg`
+    None leaves the route to the planner; `batch_hint` is the plan's (it picks k_xa's LDS budget); `oracle` is a dict that keeps
+    the oracle's outputs for a later call on the same networks, inputs and seed (another plan of theirs).  Returns the plan's
+    (large_graph, xa_variant, xa_lds_bytes)."""
     N, F = meta["params_adj"]["max_node_num"], meta["params_x"]["max_feat_num"]
-    eng = engine(meta, parts, lib, device)
-    assert eng.query("large_graph") == expect_lg
+    eng = engine(meta, parts, lib, device, batch_hint=batch_hint)
+    route = tuple(eng.query(q) for q in ("large_graph", "xa_variant", "xa_lds_bytes"))
+    assert expect_lg is None or route[0] == expect_lg
     flags = make_flags(len(counts), N, counts)
     dv = lambda t: t.to(device)
     for tag, scale in (("unit", 1.0), ("small", 0.3)):
         x, adj, _ = pc.masked_state(seed, len(counts), N, F, False, 0, 0, flags, scale)
         for t, p in enumerate(["x", "adj"]):
-            with torch.no_grad():
-                want = O.run_network(meta[f"params_{p}"], parts[p], x, adj, None, flags)
+            want = None if oracle is None else oracle.get((tag, p))
+            if want is None:
+                with torch.no_grad():
+                    want = O.run_network(meta[f"params_{p}"], parts[p], x, adj, None, flags)
+                if oracle is not None:
+                    oracle[(tag, p)] = want
             got = eng.score(t, dv(x), dv(adj), None, dv(flags))
             pc.assert_close(got, want, f"{what} {tag} net_{p}")
             got2 = eng.score(t, dv(x), dv(adj), None, dv(flags), 0.25)
             pc.assert_close(got2, 0.25 * want, f"{what} {tag} 0.25 * net_{p}")
-        # masks: zero outside the flags, zero diagonal
-        a = eng.score(1, dv(x), dv(adj), None, dv(flags)).cpu()
+        # masks of the adj score just computed: zero outside the flags, zero diagonal
+        a = got.cpu()
         fm = flags[:, :, None] * flags[:, None, :]
         assert torch.all(a[fm == 0] == 0) and torch.all(torch.diagonal(a, dim1=1, dim2=2) == 0)
+    return route
 
 
 def case_forced_vs_xa(name, lib, device, B, counts, seed=4, monkeypatch=None):
