@@ -8,12 +8,14 @@
 // The launchers read the plan's Route; nothing on a launch path compares plans or tests a geometry.  What also depends on the
 // batch of the CALL (threads per graph of k_xa, k_gemm_h_full / k_hp_full at >= 256 complexes, k_normsum's block) is a function of
 // (route, B) next to resolve_route.  ccsd_plan_query reports the Route, on the product and on the emulation alike.
+// What depends on the ARGUMENTS of a call is no Route field: corrector_norms / predictor name the form of their pass's rank-2 side (NR_* / PR_*) once.
 #pragma once
 #include "ccsd_kernels.h"
 #define CCSD_INST_TABLES
 #include "ccsd_instances.h"
 #include <stdio.h>
 #include <stdlib.h>
+#include <memory>
 #include <string>
 #include <vector>
 
@@ -138,20 +140,20 @@ struct ccsd_plan {
     size_t init_off_cap = 0;
     Knobs knobs;                // the environment, read ONCE at plan creation (read_knobs)
     Route rt;                   // which kernels serve the plan (resolve_route)
-    // optional per-kernel timing with HIP events on the launch stream (bench.py roofline leg)
-    unsigned prof_mask = 0;
-    size_t prof_used[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    // optional per-kernel timing with HIP events on the launch stream (bench.py roofline leg); mutable: the launchers hold the plan const
+    mutable unsigned prof_mask = 0;
+    mutable size_t prof_used[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     // every prof_stride-th launch of a selected kernel is bracketed by events (event records break back-to-back dispatch:
     // bracketing every launch costs ~6 % of the step)
-    int prof_stride = 1;
-    size_t prof_calls[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    mutable int prof_stride = 1;
+    mutable size_t prof_calls[8] = {0, 0, 0, 0, 0, 0, 0, 0};
 #ifndef CCSD_EMU
-    std::vector<hipEvent_t> prof_ev[8];
+    mutable std::vector<hipEvent_t> prof_ev[8];
 #endif
 };
 
 enum { KID_XA = 0, KID_GEMM_P = 1, KID_HF = 2, KID_GEMM_H = 3, KID_LANGEVIN = 4, KID_R2 = 5, KID_S4 = 6, KID_EW1 = 7 };
-static void prof_mark(ccsd_plan* pl, int kid, void* stream) {
+static void prof_mark(const ccsd_plan* pl, int kid, void* stream) {
 #ifndef CCSD_EMU
     if (!(pl->prof_mask & (1u << kid))) return;
     const size_t call = pl->prof_calls[kid]++;                 // two calls per launch: before and after
@@ -278,6 +280,7 @@ static int resolve_route(ccsd_plan* pl) {
     // ---- ccsd_sampler_run.  The Langevin apply fuses into the predictor launches of k_r2 plans, of k_ew1 plans whose hodge
     // projections do not depend on the adjacency (at most one hodge layer) and of tiled plans with one hodge layer
     const bool fused_apply = !r.lg && (fused || (ew1 && p.h_L <= 1) || r.tiled_fuse) && !k.no_fused_apply;
+    // (LOOP_LANGEVIN means n_corr_steps == 1: ccsd_sampler_run_ex runs it as the multi-iteration branch with its one iteration)
     r.loop = s4 ? LOOP_S4 : !langevin ? LOOP_PRED_ONLY : c.n_corr_steps != 1 ? LOOP_LANGEVIN_MULTI : fused_apply ? LOOP_LANGEVIN_FUSED : LOOP_LANGEVIN;
     // merged k_r2 launches (predictor of step i + rank-2 side of the norms pass of step i + 1): the row-strip instantiation of the
     // kernel (E = 33..36, affine ScoreNetworkF, linear mlp_value), pair-wise block load (K even, E K a multiple of 4)
@@ -293,6 +296,9 @@ static int resolve_route(ccsd_plan* pl) {
 static inline bool use_h_full(const Route& r, int B) { return r.h_full && B >= 256; }      // at least one complex per CU
 static inline bool use_hp_full(const Route& r, int B, int mode) { return B >= 256 && ((r.hp_full_modes >> mode) & 1u); }
 #define HP_FULL_LDS ((size_t)(2 * 192 * H_LD + 2 * 16 * H_LD) * 4)       /* dynamic LDS of k_hp_full */
+// k_hodge_value[_w]: columns of Rin one workgroup holds in LDS as its [E][cw] slab, and the slab's bytes (the rule of ccsd_k_rank2.h)
+static inline int hodge_value_cw(int E) { return E > 128 ? 32 : 64; }
+static inline size_t hodge_value_lds(int E) { return (size_t)E * hodge_value_cw(E) * 4; }
 // Threads per graph of k_xa, and the instance that takes them.  256 (four waves) is right when the batch fills the chip -- 1024 graphs =
 // four co-resident workgroups per CU -- and k_xa is bound by the latency of one graph's critical path either way; when the batch leaves
 // a CU with one or two workgroups (B <= 256 / <= 512) the same graph runs on sixteen / eight waves: every per-pair, per-tile and
@@ -383,27 +389,26 @@ extern "C" int ccsd_plan_create(const ccsd_config_t* cfg, const float* weights, 
                                 const ccsd_step_coef_t* step_coef, ccsd_plan_t** out) {
     if (!cfg || !weights || !step_coef || !out) return set_err(CCSD_ERR_INVALID, "NULL argument");
     *out = nullptr;
-    ccsd_plan* pl = new ccsd_plan();
+    std::unique_ptr<ccsd_plan, void (*)(ccsd_plan_t*)> guard(new ccsd_plan(), ccsd_plan_destroy);   // every failure leaves through it
+    ccsd_plan* pl = guard.get();
     pl->cfg = *cfg;
     const Knobs& k = pl->knobs = read_knobs();
     PlanBuilder pb;
     pb.lg_force = k.lg_force; pb.xa_pass = k.xa_pass; pb.xa_gch = k.xa_gch; pb.no_mlp_wt = k.no_mlp_wt; pb.verbose = k.verbose;
     pl->nweights = ccsd_build_plan(cfg, &pl->h, pb);
-    if (pb.status != CCSD_OK) { delete pl; return set_err(pb.status, pb.err); }
+    if (pb.status != CCSD_OK) return set_err(pb.status, pb.err);
     pl->rt.lg = pb.lg; pl->rt.h_wide = pb.h_wide;
     memcpy(pl->hbx, pb.hbx, sizeof(pl->hbx));
     memcpy(pl->hdm, pb.hdm, sizeof(pl->hdm));
     pl->afin_lg = pb.afin_lg;
     pl->h.geo_off = k.geo_off;
     pl->npacked = (size_t)pb.pcur;
-    if (pl->nweights != n_weights) {
-        delete pl;
+    if (pl->nweights != n_weights)
         return set_err(CCSD_ERR_WEIGHTS, "weight blob has " + std::to_string(n_weights) + " floats, config needs " +
                                              std::to_string(pl->nweights));
-    }
-    if (cfg->predictor != CCSD_PRED_EULER && cfg->predictor != CCSD_PRED_REVERSE && cfg->predictor != CCSD_PRED_S4) { delete pl; return set_err(CCSD_ERR_UNSUPPORTED, "unknown predictor"); }
-    if (cfg->corrector != CCSD_CORR_NONE && cfg->corrector != CCSD_CORR_LANGEVIN) { delete pl; return set_err(CCSD_ERR_UNSUPPORTED, "unknown corrector"); }
-    if (cfg->diff_steps < 1 || cfg->n_corr_steps < 0) { delete pl; return set_err(CCSD_ERR_INVALID, "bad step counts"); }
+    if (cfg->predictor != CCSD_PRED_EULER && cfg->predictor != CCSD_PRED_REVERSE && cfg->predictor != CCSD_PRED_S4) return set_err(CCSD_ERR_UNSUPPORTED, "unknown predictor");
+    if (cfg->corrector != CCSD_CORR_NONE && cfg->corrector != CCSD_CORR_LANGEVIN) return set_err(CCSD_ERR_UNSUPPORTED, "unknown corrector");
+    if (cfg->diff_steps < 1 || cfg->n_corr_steps < 0) return set_err(CCSD_ERR_INVALID, "bad step counts");
     ccsd_fold_fnet(&pl->h, weights);
     pl->coef.assign(step_coef, step_coef + (size_t)cfg->diff_steps * 3);
     // enumeration tables (get_cells, cc_utils.py:72-94): edges = combinations(range(N),2) row-major;
@@ -433,19 +438,18 @@ extern "C" int ccsd_plan_create(const ccsd_config_t* cfg, const float* weights, 
                 for (int j = i + 1; j < k; ++j) idx[j] = idx[j - 1] + 1;
             }
         }
-        if ((int)c != K) { delete pl; return set_err(CCSD_ERR_INVALID, "cell enumeration mismatch"); }
+        if ((int)c != K) return set_err(CCSD_ERR_INVALID, "cell enumeration mismatch");
     }
-#define PC(expr) do { rtError_t _e = (expr); if (_e != RT_OK) { ccsd_plan_destroy(pl); return set_err(CCSD_ERR_RUNTIME, std::string(#expr) + ": " + rt_error_string(_e)); } } while (0)
-    PC(rt_malloc((void**)&pl->d, sizeof(PlanD)));
-    PC(rt_h2d(pl->d, &pl->h, sizeof(PlanD)));
+    RT_CHECK(rt_malloc((void**)&pl->d, sizeof(PlanD)));
+    RT_CHECK(rt_h2d(pl->d, &pl->h, sizeof(PlanD)));
     {
         const size_t wtotal = pl->h.f_blk >= 0 ? (size_t)pl->h.f_blk + CCSD_FBLK_FLOATS : n_weights;
-        PC(rt_malloc((void**)&pl->w, wtotal * sizeof(float)));
-        PC(rt_h2d(pl->w, weights, n_weights * sizeof(float)));
+        RT_CHECK(rt_malloc((void**)&pl->w, wtotal * sizeof(float)));
+        RT_CHECK(rt_h2d(pl->w, weights, n_weights * sizeof(float)));
         if (pl->h.f_blk >= 0) {
             std::vector<float> blk(CCSD_FBLK_FLOATS);
             ccsd_pack_fnet_blocks(&pl->h, weights, blk.data());
-            PC(rt_h2d(pl->w + pl->h.f_blk, blk.data(), blk.size() * sizeof(float)));
+            RT_CHECK(rt_h2d(pl->w + pl->h.f_blk, blk.data(), blk.size() * sizeof(float)));
         }
     }
     {
@@ -483,47 +487,46 @@ extern "C" int ccsd_plan_create(const ccsd_config_t* cfg, const float* weights, 
             for (int k = 0; k < K; ++k)
                 for (int n = 0; n < h.wc; ++n) packed[(size_t)h.wcatT + (size_t)n * Kp + k] = weights[(size_t)h.wcat + (size_t)k * h.wc + n];
         }
-        PC(rt_malloc((void**)&pl->wp, packed.size() * sizeof(float)));
-        PC(rt_h2d(pl->wp, packed.data(), packed.size() * sizeof(float)));
+        RT_CHECK(rt_malloc((void**)&pl->wp, packed.size() * sizeof(float)));
+        RT_CHECK(rt_h2d(pl->wp, packed.data(), packed.size() * sizeof(float)));
     }
     if (pl->h.h_L > 1 && !pl->rt.lg) {     // (k_xa's pair table; the tiled route walks tiles)
-        if (E > 255) { ccsd_plan_destroy(pl); return set_err(CCSD_ERR_UNSUPPORTED, "dense hodge layer needs E <= 255"); }
+        if (E > 255) return set_err(CCSD_ERR_UNSUPPORTED, "dense hodge layer needs E <= 255");
         std::vector<unsigned char> hp;
         for (int e = 0; e < E; ++e)
             for (int e2 = e; e2 < E; ++e2) { hp.push_back((unsigned char)e); hp.push_back((unsigned char)e2); }
-        PC(rt_malloc((void**)&pl->hpairs, hp.size()));
-        PC(rt_h2d(pl->hpairs, hp.data(), hp.size()));
+        RT_CHECK(rt_malloc((void**)&pl->hpairs, hp.size()));
+        RT_CHECK(rt_h2d(pl->hpairs, hp.data(), hp.size()));
     }
-    PC(rt_malloc((void**)&pl->edges, edges.size()));
-    PC(rt_h2d(pl->edges, edges.data(), edges.size()));
-    PC(rt_malloc((void**)&pl->cells, cells.size() * sizeof(unsigned long long)));
-    PC(rt_h2d(pl->cells, cells.data(), cells.size() * sizeof(unsigned long long)));
-    if (int st = resolve_route(pl)) { ccsd_plan_destroy(pl); return st; }
+    RT_CHECK(rt_malloc((void**)&pl->edges, edges.size()));
+    RT_CHECK(rt_h2d(pl->edges, edges.data(), edges.size()));
+    RT_CHECK(rt_malloc((void**)&pl->cells, cells.size() * sizeof(unsigned long long)));
+    RT_CHECK(rt_h2d(pl->cells, cells.data(), cells.size() * sizeof(unsigned long long)));
+    if (int st = resolve_route(pl)) return st;
     {
         const Route& r = pl->rt;
         const size_t xlds = (size_t)pl->h.xa_lds_floats * 4;
         if (xlds > 64 * 1024) {
-            PC(rt_set_max_dyn_smem((const void*)r.xa->fn, xlds));
-            if (r.xa_twin) PC(rt_set_max_dyn_smem((const void*)r.xa_twin->fn, xlds));
+            RT_CHECK(rt_set_max_dyn_smem((const void*)r.xa->fn, xlds));
+            if (r.xa_twin) RT_CHECK(rt_set_max_dyn_smem((const void*)r.xa_twin->fn, xlds));
         }
-        if (r.r2 && r.r2_lds > 64 * 1024) PC(rt_set_max_dyn_smem((const void*)r.r2->fn, r.r2_lds));
-        if (r.lg && lg_nmlp_lds(pl->h) > 64 * 1024) PC(rt_set_max_dyn_smem((const void*)k_lg_nmlp, lg_nmlp_lds(pl->h)));
+        if (r.r2 && r.r2_lds > 64 * 1024) RT_CHECK(rt_set_max_dyn_smem((const void*)r.r2->fn, r.r2_lds));
+        if (r.lg && lg_nmlp_lds(pl->h) > 64 * 1024) RT_CHECK(rt_set_max_dyn_smem((const void*)k_lg_nmlp, lg_nmlp_lds(pl->h)));
         if (r.lg && pl->h.hb_L > 1) {
             size_t v = 0;
             for (int l = 0; l + 1 < pl->h.hb_L; ++l) if (lg_hb_dense_lds(pl->hbx[l]) > v) v = lg_hb_dense_lds(pl->hbx[l]);
-            if (v > 64 * 1024) PC(rt_set_max_dyn_smem((const void*)k_lg_hb_dense, v));
+            if (v > 64 * 1024) RT_CHECK(rt_set_max_dyn_smem((const void*)k_lg_hb_dense, v));
         }
         // (k_lg_hd_dense stays below 64 KB: at most 8 channels of 2 x 16 rows of 33 floats + 256 pairs)
-        if (r.lg && r.h_general && (size_t)E * (E > 128 ? 32 : 64) * 4 > 64 * 1024)
-            PC(rt_set_max_dyn_smem(r.h_wide ? (const void*)k_hodge_value_w : (const void*)k_hodge_value, (size_t)E * (E > 128 ? 32 : 64) * 4));
+        if (r.lg && r.h_general && hodge_value_lds(E) > 64 * 1024)
+            RT_CHECK(rt_set_max_dyn_smem(r.h_wide ? (const void*)k_hodge_value_w : (const void*)k_hodge_value, hodge_value_lds(E)));
 #ifndef CCSD_EMU
         if (r.hp_full_modes) {      // k_hp_full: 66.6 KB of dynamic LDS
-            PC(rt_set_max_dyn_smem((const void*)k_hp_full<CCSD_FULL_E, CCSD_FULL_K, 1>, HP_FULL_LDS));
-            PC(rt_set_max_dyn_smem((const void*)k_hp_full<CCSD_FULL_E, CCSD_FULL_K, 2>, HP_FULL_LDS));
+            RT_CHECK(rt_set_max_dyn_smem((const void*)k_hp_full<CCSD_FULL_E, CCSD_FULL_K, 1>, HP_FULL_LDS));
+            RT_CHECK(rt_set_max_dyn_smem((const void*)k_hp_full<CCSD_FULL_E, CCSD_FULL_K, 2>, HP_FULL_LDS));
         }
 #endif
     }
-#undef PC
     if (const char* path = k.dump_plan) {     // tools/bake_plan.py: the plan's architecture bytes as a C header
         const char* nm = k.dump_plan_name ? k.dump_plan_name : "QM9";
         std::vector<unsigned char> bytes(sizeof(PlanD));
@@ -539,10 +542,9 @@ extern "C" int ccsd_plan_create(const ccsd_config_t* cfg, const float* weights, 
             fclose(f);
         }
     }
-    *out = pl;
+    *out = guard.release();
     return CCSD_OK;
 }
-
 
 #define CCSD_P_SPLITS 8     /* most K slices k_gemm_p is split into when its row tiles cannot fill the chip */
 
@@ -692,11 +694,12 @@ static int grid_for(long long n, int block) {
     return (int)g;
 }
 
-static int check_common(const ccsd_plan* pl, int B, const void* flags, const void* ws, size_t ws_bytes) {
+static int check_common(const ccsd_plan* pl, int B, const void* flags, void* ws, size_t ws_bytes, Workspace& w) {
     if (!pl) return set_err(CCSD_ERR_INVALID, "NULL plan");
     if (B < 1) return set_err(CCSD_ERR_INVALID, "B must be >= 1");
     if (!flags) return set_err(CCSD_ERR_INVALID, "NULL flags");
-    if (!ws || ws_bytes < carve_ws(pl, B, nullptr).bytes) return set_err(CCSD_ERR_WORKSPACE, "workspace too small");
+    if (ws) w = carve_ws(pl, B, ws);       // the one carve of the call
+    if (!ws || ws_bytes < w.bytes) return set_err(CCSD_ERR_WORKSPACE, "workspace too small");
     return CCSD_OK;
 }
 static int check_state(const ccsd_plan* pl, const ccsd_state_t* s, const char* what) {
@@ -725,7 +728,7 @@ static int launch_h(const ccsd_plan* pl, int B, const float* rank2, Pass& ps, Wo
     const bool full = use_h_full(pl->rt, B);        // (a GPU-only kernel: the emulation launches k_gemm_h)
     const int nth_ = (p.E + T_BM - 1) / T_BM;
     dim3 g(xcd_grid(B, nth_ * (nth_ + 1) / 2));
-    prof_mark(const_cast<ccsd_plan*>(pl), KID_GEMM_H, stream);
+    prof_mark(pl, KID_GEMM_H, stream);
 #ifndef CCSD_EMU
     if (full && pl->knobs.split_bf16 == 3) hipLaunchKernelGGL((k_gemm_h_full<CCSD_FULL_E, CCSD_FULL_K, 2>), dim3(B), dim3(256), 0, (hipStream_t)stream, rank2, w.H, p.f_hmask);
     else if (full) hipLaunchKernelGGL((k_gemm_h_full<CCSD_FULL_E, CCSD_FULL_K>), dim3(B), dim3(256), 0, (hipStream_t)stream, rank2, w.H, p.f_hmask);
@@ -737,7 +740,7 @@ static int launch_h(const ccsd_plan* pl, int B, const float* rank2, Pass& ps, Wo
         GEO_EK(pl->rt.geo, H_GO);
 #undef H_GO
     }
-    prof_mark(const_cast<ccsd_plan*>(pl), KID_GEMM_H, stream);
+    prof_mark(pl, KID_GEMM_H, stream);
     LAUNCH_CHECK();
     for (int j = 2; j < p.f_cnum; ++j) {       // H^j = H^(j-1) . H  (pow_tensor_cc, cc_utils.py:972-977)
         const size_t slab = (size_t)B * p.E * h_ld(p.E);
@@ -748,7 +751,33 @@ static int launch_h(const ccsd_plan* pl, int B, const float* rank2, Pass& ps, Wo
     }
     return CCSD_OK;
 }
-struct RankEpi;
+// out = R Wcat of hodge layer `h` for a materialised R: plain k_gemm_p (on wide plans too), whole K, no acoef.  The caller checks the launch
+static void launch_gemm_p_whole(const ccsd_plan* pl, int B, const float* R, const HodgeLayerD& h, float* out, const Workspace& w, void* stream) {
+    const PlanD& p = pl->h;
+    const int rows = B * p.E;
+    CCSD_LAUNCH(k_gemm_p, dim3((h.wc + T_BN - 1) / T_BN, (rows + T_BM - 1) / T_BM, 1), dim3(CCSD_NTHREADS), 0, stream, R, (const float*)pl->w, out,
+                rows, p.E, p.K, h.wc, h.wcat, 0, h.mval, h.cin, (const float*)nullptr, (const unsigned long long*)w.offbits,
+                (const unsigned char*)pl->edges, (const unsigned long long*)pl->cells, p.K);
+}
+// Rout = fl fr mlp_value_h(cat_c H_c Rin) (k_hodge_value[_w]): H [cin][E][E] per sample, h_stride floats apart; nullptr: layer 0's diagonal form, a_c o Rin with `acoef`
+static void launch_hodge_value(const ccsd_plan* pl, int B, const float* Rin, const float* H, size_t h_stride, const float* acoef,
+                              const HodgeLayerD& h, float* Rout, const Workspace& w, void* stream) {
+    const PlanD& p = pl->h;
+    const int cw = hodge_value_cw(p.E);
+    CCSD_LAUNCH(pl->rt.h_wide ? k_hodge_value_w : k_hodge_value, dim3((p.K + cw - 1) / cw, B), dim3(CCSD_NTHREADS), hodge_value_lds(p.E), stream, Rin, H,
+                (int)h_stride, acoef, (const float*)pl->w, h.mval, h.cin, Rout, p.E, p.K, cw,
+                (const unsigned long long*)w.offbits, (const unsigned char*)pl->edges, (const unsigned long long*)pl->cells);
+}
+// Layer l >= 2 of the general hodge stack, with H^(l-1) (the dense output of layer l - 2) in w.hgH:
+// R_l = fl fr mlp_value_(l-1)(cat_c H^(l-1)_c R_(l-1)) into the other of the two R buffers, then P_l = R_l Wcat_l.  launch_p left R_1.
+static int hodge_stack_layer(const ccsd_plan* pl, int B, int l, Workspace& w, void* stream) {
+    float* Rl = w.hgR[(l - 1) & 1];
+    launch_hodge_value(pl, B, w.hgR[(l - 2) & 1], w.hgH, w.hg_hstride, nullptr, ccsd_hl(pl->h, l - 1), Rl, w, stream);
+    LAUNCH_CHECK();
+    launch_gemm_p_whole(pl, B, Rl, ccsd_hl(pl->h, l), w.hgP[l - 1], w, stream);
+    LAUNCH_CHECK();
+    return CCSD_OK;
+}
 static int launch_r2(const ccsd_plan* pl, int B, const float* rank2, const float* adj, const float* flags, int want_p,
                      RankEpi& ep, NoiseArgs& na, Pass& ps, Workspace& w, void* stream, const CorrFuse* cf, int merge_draw);
 // hodge projections for ScoreNetworkA_CC from (adj, rank2)
@@ -778,12 +807,12 @@ static int launch_p(const ccsd_plan* pl, int B, const float* adj, const float* r
     if (hp_full) {
         const HodgeLayerD& h = p.hl[0];
         const float* WT = (const float*)pl->wp + h.wcatT;
-        prof_mark(const_cast<ccsd_plan*>(pl), KID_GEMM_H, stream);
+        prof_mark(pl, KID_GEMM_H, stream);
         if (fuse->mode == 1)
             hipLaunchKernelGGL((k_hp_full<CCSD_FULL_E, CCSD_FULL_K, 1>), dim3(B), dim3(512), HP_FULL_LDS, (hipStream_t)stream, rank2, WT, w.H, w.P0, h.wc, p.f_hmask, *fuse);
         else
             hipLaunchKernelGGL((k_hp_full<CCSD_FULL_E, CCSD_FULL_K, 2>), dim3(B), dim3(512), HP_FULL_LDS, (hipStream_t)stream, rank2, WT, w.H, w.P0, h.wc, p.f_hmask, *fuse);
-        prof_mark(const_cast<ccsd_plan*>(pl), KID_GEMM_H, stream);
+        prof_mark(pl, KID_GEMM_H, stream);
         LAUNCH_CHECK();
         ps.h_src = fuse->mode == 2 ? fuse->f1 : rank2;
         return CCSD_OK;
@@ -792,8 +821,7 @@ static int launch_p(const ccsd_plan* pl, int B, const float* adj, const float* r
     (void)hp_full;
     {
         const HodgeLayerD& h = p.hl[0];
-        dim3 g((h.wc + T_BN - 1) / T_BN, (rows + T_BM - 1) / T_BM, 1);
-        prof_mark(const_cast<ccsd_plan*>(pl), KID_GEMM_P, stream);
+        prof_mark(pl, KID_GEMM_P, stream);
         P0Fuse pf{};
         if (fuse) pf = *fuse;
 #ifndef CCSD_EMU
@@ -809,11 +837,9 @@ static int launch_p(const ccsd_plan* pl, int B, const float* adj, const float* r
                 LAUNCH_CHECK();
                 if (pf.mode == 2 || pf.mode == 4) src = pf.f1;
             }
-            CCSD_LAUNCH(k_gemm_p, g, dim3(CCSD_NTHREADS), 0, stream, src, (const float*)pl->w, w.P0, rows, p.E, p.K, h.wc,
-                        h.wcat, 0, h.mval, h.cin, (const float*)nullptr, (const unsigned long long*)w.offbits,
-                        (const unsigned char*)pl->edges, (const unsigned long long*)pl->cells, p.K);
+            launch_gemm_p_whole(pl, B, src, h, w.P0, w, stream);
         }
-        prof_mark(const_cast<ccsd_plan*>(pl), KID_GEMM_P, stream);
+        prof_mark(pl, KID_GEMM_P, stream);
         LAUNCH_CHECK();
     }
     if (p.h_L > 1) {
@@ -844,11 +870,8 @@ static int launch_p(const ccsd_plan* pl, int B, const float* adj, const float* r
             LAUNCH_CHECK();
         }
         if (rt.h_general) {
-            // R_1 = fl fr mlp_value_0(a_c o rank2), materialised for the layers behind it (launch_xa goes on from here)
-            const int cw = p.E > 128 ? 32 : 64;
-            CCSD_LAUNCH(rt.h_wide ? k_hodge_value_w : k_hodge_value, dim3((p.K + cw - 1) / cw, B), dim3(CCSD_NTHREADS), (size_t)p.E * cw * 4, stream, rank2, (const float*)nullptr, 0,
-                        (const float*)w.acoef, (const float*)pl->w, h0.mval, h0.cin, w.hgR[0], p.E, p.K, cw,
-                        (const unsigned long long*)w.offbits, (const unsigned char*)pl->edges, (const unsigned long long*)pl->cells);
+            // R_1 = fl fr mlp_value_0(a_c o rank2), materialised for the layers behind it (launch_xa / launch_lg go on from here)
+            launch_hodge_value(pl, B, rank2, nullptr, 0, w.acoef, h0, w.hgR[0], w, stream);
             LAUNCH_CHECK();
         }
     }
@@ -864,7 +887,7 @@ static int launch_xa(const ccsd_plan* pl, int B, XaArgs& xa, NoiseArgs& na, cons
     xa.dbg = pl->dbg ? pl->dbg + 32 : nullptr;
     int xa_threads;
     const XaEntry* inst = xa_launch(rt, B, &xa_threads);
-    prof_mark(const_cast<ccsd_plan*>(pl), KID_XA, stream);
+    prof_mark(pl, KID_XA, stream);
     xa.wp = pl->wp; xa.hpairs = pl->hpairs;
     xa.prio_mode = pl->knobs.xa_prio;
     const dim3 xblk(CCSD_NTHREADS == 1 ? 1 : xa_threads);
@@ -872,35 +895,23 @@ static int launch_xa(const ccsd_plan* pl, int B, XaArgs& xa, NoiseArgs& na, cons
 #define XA_LAUNCH(XA_) CCSD_LAUNCH(inst->fn, dim3(B), xblk, xlds, stream, (const PlanD*)pl->d, (const float*)pl->w, (const unsigned char*)pl->edges, XA_, na)
     if (rt.h_general) {
         // general hodge stack: layer l >= 2 projects R_l = fl fr mlp_value_(l-1)(cat_c H^(l-1)_c R_(l-1)).  H^(l-1) is the dense output of
-        // layer l - 2 inside k_xa: a launch that stops behind it dumps it, k_hodge_value forms R_l, k_gemm_p projects it -- then the next
+        // layer l - 2 inside k_xa: a launch that stops behind it dumps it, hodge_stack_layer forms R_l and projects it -- then the next
         // layer, and at last the full launch with every P_l delivered.  (launch_p left P_0, P_1 and R_1.)
         const PlanD& p = pl->h;
         if (rt.xa_variant != XA_GEN) return set_err(CCSD_ERR_RUNTIME, "general hodge stack needs k_xa<., XA_GEN>");
         xa.pdirect = 1;
         for (int l = 1; l < p.h_L; ++l) xa.Pd[l - 1] = w.hgP[l - 1];
-        const int rows = B * p.E;
         for (int l = 2; l < p.h_L; ++l) {
             XaArgs pre = xa;
             pre.hdump_layer = l - 1; pre.hdump = w.hgH; pre.hdump_stride = (int)w.hg_hstride;
             XA_LAUNCH(pre);
             LAUNCH_CHECK();
-            const HodgeLayerD& hp = ccsd_hl(p, l - 1);
-            const HodgeLayerD& h = ccsd_hl(p, l);
-            float* Rl = w.hgR[(l - 1) & 1];
-            const int cw = p.E > 128 ? 32 : 64;
-            CCSD_LAUNCH(k_hodge_value, dim3((p.K + cw - 1) / cw, B), dim3(CCSD_NTHREADS), (size_t)p.E * cw * 4, stream, (const float*)w.hgR[(l - 2) & 1],
-                        (const float*)w.hgH, (int)w.hg_hstride, (const float*)nullptr, (const float*)pl->w, hp.mval, hp.cin, Rl, p.E, p.K, cw,
-                        (const unsigned long long*)w.offbits, (const unsigned char*)pl->edges, (const unsigned long long*)pl->cells);
-            LAUNCH_CHECK();
-            CCSD_LAUNCH(k_gemm_p, dim3((h.wc + T_BN - 1) / T_BN, (rows + T_BM - 1) / T_BM, 1), dim3(CCSD_NTHREADS), 0, stream, (const float*)Rl,
-                        (const float*)pl->w, w.hgP[l - 1], rows, p.E, p.K, h.wc, h.wcat, 0, h.mval, h.cin, (const float*)nullptr,
-                        (const unsigned long long*)w.offbits, (const unsigned char*)pl->edges, (const unsigned long long*)pl->cells, p.K);
-            LAUNCH_CHECK();
+            if (int st = hodge_stack_layer(pl, B, l, w, stream)) return st;
         }
     }
     XA_LAUNCH(xa);
 #undef XA_LAUNCH
-    prof_mark(const_cast<ccsd_plan*>(pl), KID_XA, stream);
+    prof_mark(pl, KID_XA, stream);
     LAUNCH_CHECK();
     return CCSD_OK;
 }
@@ -917,7 +928,7 @@ static int launch_lg(const ccsd_plan* pl, int B, XaArgs& xa, NoiseArgs& na, Work
     const int rt = (N + 15) / 16, gt = (N + CCSD_LG_GT - 1) / CCSD_LG_GT, at = (N + CCSD_LG_AT - 1) / CCSD_LG_AT;
     const dim3 blk(CCSD_NTHREADS);
     auto cdiv = [](int a, int b_) { return (a + b_ - 1) / b_; };
-    prof_mark(const_cast<ccsd_plan*>(pl), KID_XA, stream);
+    prof_mark(pl, KID_XA, stream);
     if (xa.do_x) {
         // ScoreNetworkX (ScoreNetwork_X.py:102-132): depth x tanh(DenseGCNConv) on adjX, concatenated behind x, final MLP per node
         CCSD_LAUNCH(k_lg_dis, dim3(grid_for(N, 256), B), blk, 0, stream, xa.adjX, (long long)NN, 0, 1, N, w.lg_dis);
@@ -958,7 +969,7 @@ static int launch_lg(const ccsd_plan* pl, int B, XaArgs& xa, NoiseArgs& na, Work
             const Route& rtp = pl->rt;
             if (!xa.P0 || (!rtp.h_general && !xa.P1)) return set_err(CCSD_ERR_RUNTIME, "tiled graph-network route: no hodge projections");
             if (p.h_L > 2 && !rtp.h_general) return set_err(CCSD_ERR_RUNTIME, "tiled graph-network route: more than two hodge layers need the general hodge stack");
-            const int E = p.E, et = (E + 15) / 16, rows = B * E;
+            const int E = p.E, et = (E + 15) / 16;
             const unsigned char* edges = (const unsigned char*)pl->edges;
             const float* wts = (const float*)pl->w;
             const float rks = 1.0f / (float)sqrt((double)p.K);
@@ -973,19 +984,8 @@ static int launch_lg(const ccsd_plan* pl, int B, XaArgs& xa, NoiseArgs& na, Work
                             (const float*)w.lg_hdq, qs, w.lg_hdH, hs, w.lg_S, ss, ch, N, E, xa.flags);
                 ch += hp.cout;
                 LAUNCH_CHECK();
-                if (rtp.h_general && j + 1 < p.h_L) {
-                    const HodgeLayerD& hn = ccsd_hl(p, j + 1);
-                    float* Rn = w.hgR[j & 1];
-                    const int cw = E > 128 ? 32 : 64;
-                    CCSD_LAUNCH(rtp.h_wide ? k_hodge_value_w : k_hodge_value, dim3((p.K + cw - 1) / cw, B), dim3(CCSD_NTHREADS), (size_t)E * cw * 4, stream, (const float*)w.hgR[(j - 1) & 1],
-                                (const float*)w.lg_hdH, (int)hs, (const float*)nullptr, wts, h.mval, h.cin, Rn, E, p.K, cw,
-                                (const unsigned long long*)w.offbits, edges, (const unsigned long long*)pl->cells);
-                    LAUNCH_CHECK();
-                    CCSD_LAUNCH(k_gemm_p, dim3((hn.wc + T_BN - 1) / T_BN, (rows + T_BM - 1) / T_BM, 1), dim3(CCSD_NTHREADS), 0, stream, (const float*)Rn,
-                                wts, w.hgP[j], rows, E, p.K, hn.wc, hn.wcat, 0, hn.mval, hn.cin, (const float*)nullptr,
-                                (const unsigned long long*)w.offbits, edges, (const unsigned long long*)pl->cells, p.K);
-                    LAUNCH_CHECK();
-                }
+                if (rtp.h_general && j + 1 < p.h_L)
+                    if (int st = hodge_stack_layer(pl, B, j + 1, w, stream)) return st;
                 const bool raw = j == 1 && !rtp.h_general && xa.p1_raw;
                 LgHdRaw rw{};
                 if (raw) {
@@ -1062,7 +1062,7 @@ static int launch_lg(const ccsd_plan* pl, int B, XaArgs& xa, NoiseArgs& na, Work
         LAUNCH_CHECK();
     }
     CCSD_LAUNCH(k_lg_epi, dim3(B), blk, 0, stream, (const float*)w.lg_xnet, xa.xX, xa.flags, xa, na, (const float*)w.lg_part, w.lg_tiles, N, F);
-    prof_mark(const_cast<ccsd_plan*>(pl), KID_XA, stream);
+    prof_mark(pl, KID_XA, stream);
     LAUNCH_CHECK();
     return CCSD_OK;
 }
@@ -1070,7 +1070,7 @@ static int launch_lg(const ccsd_plan* pl, int B, XaArgs& xa, NoiseArgs& na, Work
 static int launch_hf(const ccsd_plan* pl, int B, const float* rank2, RankEpi& ep, NoiseArgs& na, Workspace& w, void* stream) {
     const PlanD& p = pl->h;
     dim3 g(xcd_grid(B, ((p.K + T_BN - 1) / T_BN) * ((p.E + T_BM - 1) / T_BM)));
-    prof_mark(const_cast<ccsd_plan*>(pl), KID_HF, stream);
+    prof_mark(pl, KID_HF, stream);
 #define HF_ARGS (const PlanD*)pl->d, (const float*)pl->w, rank2, (const float*)w.H, (const unsigned long long*)w.offbits, \
                 (const unsigned char*)pl->edges, (const unsigned long long*)pl->cells, ep, na, B, w.masks()
     const int fw = fnet_width(p);
@@ -1090,7 +1090,7 @@ static int launch_hf(const ccsd_plan* pl, int B, const float* rank2, RankEpi& ep
 #undef HF_AFF1
 #undef HF_GEN1
 #undef HF_ARGS
-    prof_mark(const_cast<ccsd_plan*>(pl), KID_HF, stream);
+    prof_mark(pl, KID_HF, stream);
     LAUNCH_CHECK();
     return CCSD_OK;
 }
@@ -1109,11 +1109,11 @@ static int launch_ew1(const ccsd_plan* pl, int B, const float* rank2, RankEpi& e
         a.sums = lc.sums; a.ss = lc.ss[2]; a.sde_alpha = lc.alpha[2]; a.snr = lc.snr; a.seps = lc.seps; a.draw_corr = cf->draw_r;
     }
     a.E = p.E; a.K = p.K; a.mt = w.masks();
-    prof_mark(const_cast<ccsd_plan*>(pl), KID_EW1, stream);
+    prof_mark(pl, KID_EW1, stream);
 #define EW1_GO(EC_, KC_) CCSD_LAUNCH((k_ew1<EC_, KC_>), dim3(w.nchunk, B), dim3(CCSD_NTHREADS), 0, stream, a, na)
     GEO_EK(pl->rt.geo, EW1_GO);
 #undef EW1_GO
-    prof_mark(const_cast<ccsd_plan*>(pl), KID_EW1, stream);
+    prof_mark(pl, KID_EW1, stream);
     LAUNCH_CHECK();
     return CCSD_OK;
 }
@@ -1134,17 +1134,20 @@ static int launch_r2(const ccsd_plan* pl, int B, const float* rank2, const float
     ra.rank2 = rank2; ra.adj = adj; ra.flags = flags; ra.offbits = w.offbits; ra.P0 = w.P0; ra.P1 = w.P1; ra.U1 = w.U1; ra.want_p = want_p;
     ra.ldk = rt.r2_ldk; ra.ldh = rt.r2_ldh; ra.dbg = pl->dbg; ra.wp = pl->wp;
     if (want_p && pl->h.h_L > 1) ps.p1_raw = r2_p1_raw(pl->h);
-    prof_mark(const_cast<ccsd_plan*>(pl), KID_R2, stream);
+    prof_mark(pl, KID_R2, stream);
     CCSD_LAUNCH(rt.r2->fn, dim3(B), dim3(CCSD_NTHREADS == 1 ? 1 : 512), rt.r2_lds, stream, (const PlanD*)pl->d, (const float*)pl->w,
                 (const unsigned char*)pl->edges, (const unsigned long long*)pl->cells, ra, ep, na);
-    prof_mark(const_cast<ccsd_plan*>(pl), KID_R2, stream);
+    prof_mark(pl, KID_R2, stream);
     LAUNCH_CHECK();
     return CCSD_OK;
 }
 
-static unsigned int draw_base(const ccsd_plan* pl, int step, int phase) {
-    const int per_step = pl->cfg.predictor == CCSD_PRED_S4 ? 3 : pl->cfg.n_corr_steps + 1;   // S4: three draws per target per step
-    return 3u + (unsigned)((step * per_step + phase) * 3);
+static inline int draws_per_step(const ccsd_config_t& cfg) { return cfg.predictor == CCSD_PRED_S4 ? 3 : cfg.n_corr_steps + 1; }   // (per target; S4: three)
+static unsigned int draw_base(const ccsd_plan* pl, int step, int phase) { return 3u + (unsigned)((step * draws_per_step(pl->cfg) + phase) * 3); }
+// work items of an element-wise pass over a state: the elements of x and adj + rank2's Philox groups of four (Route::corrector_flat)
+static inline long long state_items(const PlanD& p, int B, int flat_r) {
+    const long long r4 = flat_r ? ((long long)p.E * p.K + 3) / 4 : (long long)((p.E + 3) / 4) * p.K;
+    return (long long)B * (p.N * p.F + p.N * p.N) + (p.is_cc ? (long long)B * r4 : 0);
 }
 static NoiseArgs make_noise(const ccsd_noise_t* n, uint64_t seed, int64_t off, unsigned int base, int flat_r = 0) {
     NoiseArgs na{};
@@ -1193,15 +1196,27 @@ static RankEpi pred_epi(const ccsd_plan* pl, int step, ccsd_state_t* out, ccsd_s
     ep.out = out->rank2; ep.mean = mean ? mean->rank2 : nullptr;
     return ep;
 }
+static RankEpi norms_epi(const Workspace& w) {
+    RankEpi ep{};
+    ep.mode = MODE_NORMS; ep.out = w.net_r; ep.part = w.part;
+    return ep;
+}
+// dst <- src: the first `n` samples of the three tensors of a state, asynchronously on `stream`
+static int copy_state(const ccsd_state_t& dst, const ccsd_state_t& src, const PlanD& p, size_t n, void* stream) {
+    RT_CHECK(rt_d2d_async(dst.x, src.x, n * p.N * p.F * 4, stream));
+    RT_CHECK(rt_d2d_async(dst.adj, src.adj, n * p.N * p.N * 4, stream));
+    if (p.is_cc && p.E && p.K) RT_CHECK(rt_d2d_async(dst.rank2, src.rank2, n * p.E * p.K * 4, stream));
+    return CCSD_OK;
+}
 
 // ---------------- API ----------------
 extern "C" int ccsd_score(ccsd_plan_t* pl, int32_t target, int32_t B, const ccsd_state_t* in, const float* flags,
                           float sscale, float* out, void* workspace, size_t ws_bytes, void* stream) {
-    int st = check_common(pl, B, flags, workspace, ws_bytes);
+    Workspace w{};
+    int st = check_common(pl, B, flags, workspace, ws_bytes, w);
     if (st) return st;
     if ((st = check_state(pl, in, "in"))) return st;
     if (!out) return set_err(CCSD_ERR_INVALID, "NULL out");
-    Workspace w = carve_ws(pl, B, workspace);
     if ((st = launch_flagbits(pl, B, flags, w, stream))) return st;
     NoiseArgs na{};
     Pass ps;
@@ -1249,9 +1264,7 @@ static int draws_to_state(ccsd_plan* pl, int32_t B, const float* flags, const cc
     unsigned long long* offbits = pl->init_off;
     if (!pl->rt.lg || p.is_cc) CCSD_LAUNCH(k_flagbits, dim3(grid_for(B, 256)), dim3(CCSD_NTHREADS), 0, stream, flags, offbits, B, p.N);   // (graph-only plans of the tiled route: no rank-2 draws read it)
     NoiseArgs na = make_noise(raw, seed, sample_offset, base, flat_r);
-    const long long total = (long long)B * (p.N * p.F + p.N * p.N) +
-                            (p.is_cc ? (flat_r ? (long long)B * (((long long)p.E * p.K + 3) / 4) : (long long)B * ((p.E + 3) / 4) * p.K) : 0);
-    CCSD_LAUNCH(k_init_state, dim3(grid_for(total, 256)), dim3(CCSD_NTHREADS), 0, stream, state->x, state->adj, state->rank2,
+    CCSD_LAUNCH(k_init_state, dim3(grid_for(state_items(p, B, flat_r), 256)), dim3(CCSD_NTHREADS), 0, stream, state->x, state->adj, state->rank2,
                 flags, na, (const unsigned long long*)offbits, (const unsigned char*)pl->edges,
                 (const unsigned long long*)pl->cells, B, p.N, p.F, p.E, p.K, p.is_cc);
     LAUNCH_CHECK();
@@ -1266,8 +1279,7 @@ extern "C" int ccsd_init_state(ccsd_plan_t* pl, int32_t B, const float* flags, c
 extern "C" int ccsd_noise_draws(ccsd_plan_t* pl, int32_t B, const float* flags, uint64_t seed, int64_t sample_offset, int32_t step,
                                 int32_t phase, ccsd_state_t* out, void* stream) {
     if (!pl) return set_err(CCSD_ERR_INVALID, "NULL plan");
-    const int per_step = pl->cfg.predictor == CCSD_PRED_S4 ? 3 : pl->cfg.n_corr_steps + 1;
-    if (step < 0 || step >= pl->cfg.diff_steps || phase < 0 || phase >= per_step) return set_err(CCSD_ERR_INVALID, "step / phase out of range");
+    if (step < 0 || step >= pl->cfg.diff_steps || phase < 0 || phase >= draws_per_step(pl->cfg)) return set_err(CCSD_ERR_INVALID, "step / phase out of range");
     const bool corr = pl->cfg.predictor != CCSD_PRED_S4 && phase < pl->cfg.n_corr_steps && pl->cfg.corrector == CCSD_CORR_LANGEVIN;
     return draws_to_state(pl, B, flags, nullptr, seed, sample_offset, draw_base(pl, step, phase), out, stream,
                           corr ? pl->rt.corrector_flat : pl->rt.predictor_flat);
@@ -1316,63 +1328,63 @@ static int corrector_norms(ccsd_plan* pl, int B, int step, int it, const ccsd_st
                            const float* flags, const ccsd_noise_t* noise, uint64_t seed, int64_t off, float* sums,
                            Workspace& w, void* stream, bool keep_net = true, bool r2_done = false) {
     const PlanD& p = pl->h;
-    int st;
+    int st = CCSD_OK;
     NoiseArgs na = make_noise(noise, seed, off, draw_base(pl, step, it), pl->rt.corrector_flat);
     // A-net sees (x_0, adj_cur, rank2_0): hodge projections from the base rank2, edge coefficients from adj_cur.
     // When the rank2 iterate is still the base state the fused kernel serves both the A-net's projections
     // and ScoreNetworkF in one pass over rank2.
     const Route& rt = pl->rt;
     Pass ps;
-    const bool fused = rt.r2_family == R2_FUSED && cur->rank2 == base->rank2;
-    // tiled path, one hodge layer: the noise norm of the corrector's (flat-keyed, in-kernel) rank2 draw rides on the projection pass
-    const bool zfuse = !fused && rt.tiled_fuse && na.flat_r && !na.zr;
-    // element-wise ScoreNetworkF plans: raw score + both norms per row ride on it too (no k_ew1 launch in this pass)
-    const bool e1fuse = !fused && rt.ew1_fuse && na.flat_r && !na.zr;
-    int ntiles = w.ntiles;
-    if (fused) {
-        RankEpi ep{};
-        ep.mode = MODE_NORMS; ep.out = w.net_r; ep.part = w.part;
+    // The rank-2 side of THIS pass, named once (same_r2: the rank2 iterate is still the base state; own_draw: the corrector's flat-keyed
+    // draw is made in the kernels).  Rests on resolve_route: tiled_fuse only with R2_TILED, ew1_fuse only with R2_EW1, R2_NONE iff !is_cc
+    enum { NR_NONE, NR_R2, NR_EW1_RIDE, NR_EW1, NR_TILED };     // NR_TILED: a k_r2 plan too, once its rank2 iterate has left the base state
+    const bool same_r2 = cur->rank2 == base->rank2, own_draw = na.flat_r && !na.zr;
+    const int form = !p.is_cc ? NR_NONE : rt.r2_family == R2_FUSED && same_r2 ? NR_R2 : rt.r2_family != R2_EW1 ? NR_TILED
+                   : rt.ew1_fuse && own_draw && same_r2 ? NR_EW1_RIDE : NR_EW1;
+    // ... NR_TILED with one hodge layer: the noise norm of the corrector's draw rides on the projection pass (P0Fuse mode 1), no k_noise_norm
+    const bool z_rides = form == NR_TILED && rt.tiled_fuse && own_draw;
+    RankEpi ep = norms_epi(w);
+    P0Fuse pf{};
+    int ntiles = w.ntiles;       // partials per sample in w.part
+    switch (form) {
+    case NR_R2:             // k_r2, launched here or left by the merged launch of the previous predictor
         if (r2_done) ps.p1_raw = r2_p1_raw(p);          // (as the merged launch left the second buffer set)
         else if ((st = launch_r2(pl, B, cur->rank2, cur->adj, flags, 1, ep, na, ps, w, stream))) return st;
         ntiles = 1;
-    } else {
-        P0Fuse pf{};
-        if (zfuse) { pf = p0_fuse(pl, 1, na, na.draw_r, w); pf.zrow = w.zpart; }
-        if (e1fuse && cur->rank2 == base->rank2) {
-            pf = p0_fuse(pl, 3, na, na.draw_r, w);
-            pf.zrow = w.part; pf.alpha = p.f_alpha; pf.gamma = p.f_gamma;
-            pf.net_out = keep_net ? w.net_r : nullptr;
-        }
-        if ((st = launch_p(pl, B, cur->adj, base->rank2, ps, w, stream, pf.mode ? &pf : nullptr))) return st;
+        break;
+    case NR_EW1_RIDE:       // k_ew1 plans, one hodge layer: raw score + both norms per row ride on the projection pass, no k_ew1 launch
+        pf = p0_fuse(pl, 3, na, na.draw_r, w);
+        pf.zrow = w.part; pf.alpha = p.f_alpha; pf.gamma = p.f_gamma;
+        pf.net_out = keep_net ? w.net_r : nullptr;
+        ntiles = p.E;                            // (per-row partials written by the projection pass)
+        break;
+    case NR_TILED:
+        if (z_rides) { pf = p0_fuse(pl, 1, na, na.draw_r, w); pf.zrow = w.zpart; }
+        break;
     }
+    if (form != NR_R2) st = launch_p(pl, B, cur->adj, base->rank2, ps, w, stream, pf.mode ? &pf : nullptr);
+    if (st) return st;
     XaArgs xa{};
     xa.xX = cur->x; xa.adjX = base->adj;      // score_x(x_cur, adj_0)      solver.py:761
     xa.xA = base->x; xa.adjA = cur->adj;      // score_adj(x_0, adj_cur)    solver.py:775
     xa.flags = flags; xa.do_x = xa.do_a = 1; xa.mode = MODE_NORMS;
     xa.out_x = w.net_x; xa.out_a = w.net_adj; xa.norm2 = w.norm2;
-    if ((st = launch_xa(pl, B, xa, na, ps, w, stream, fused && r2_done))) return st;
-    const bool ew1 = rt.r2_family == R2_EW1;
-    if (p.is_cc && !fused && ew1 && e1fuse && cur->rank2 == base->rank2) {
-        ntiles = p.E;                            // (per-row partials written by the projection pass above)
-    } else if (p.is_cc && !fused && ew1) {
+    if ((st = launch_xa(pl, B, xa, na, ps, w, stream, form == NR_R2 && r2_done))) return st;
+    if (form == NR_EW1) {
         // element-wise ScoreNetworkF: one streaming pass gives both norm partials per (sample, chunk); the raw score is kept only
         // for a separate ccsd_corrector_apply (the fused loop recomputes it)
-        RankEpi ep{};
-        ep.mode = MODE_NORMS; ep.out = w.net_r; ep.part = w.part;
         if ((st = launch_ew1(pl, B, cur->rank2, ep, na, w, stream, keep_net ? w.net_r : nullptr))) return st;
         ntiles = w.nchunk;
-    } else if (p.is_cc && !fused) {
+    } else if (form == NR_TILED) {
         if ((st = launch_h(pl, B, cur->rank2, ps, w, stream))) return st;
-        RankEpi ep{};
-        ep.mode = MODE_NORMS; ep.out = w.net_r; ep.part = w.part;
         if ((st = launch_hf(pl, B, cur->rank2, ep, na, w, stream))) return st;
     }
     const float* part = w.part;
-    if (p.is_cc && !fused) {
+    if (form != NR_NONE && form != NR_R2) {
         // tiled path: the noise norm of a flat-keyed Philox draw comes from its own (traffic-free) kernel; the per-tile partials of
         // k_hf_score and its chunk partials are reduced per sample first (one workgroup per sample), then over the batch
-        const bool zk = na.flat_r && !na.zr && !ew1;
-        if (zk && !zfuse) {
+        const bool zk = form == NR_TILED && own_draw;
+        if (zk && !z_rides) {
 #define NN_GO(EC_, KC_) CCSD_LAUNCH((k_noise_norm<EC_, KC_>), dim3(w.nchunk, B), dim3(CCSD_NTHREADS), 0, stream, na, w.masks(), p.E, p.K, w.zpart)
             GEO_EK(pl->rt.geo, NN_GO);
 #undef NN_GO
@@ -1381,7 +1393,7 @@ static int corrector_norms(ccsd_plan* pl, int B, int step, int it, const ccsd_st
         if (zk || ntiles > 8) {
             // (zpart: the chunk partials of k_noise_norm, or the E row partials of the fused projection pass)
             CCSD_LAUNCH(k_normpart, dim3(B), dim3(CCSD_NTHREADS), 0, stream, (const float*)w.part, ntiles, zk ? (const float*)w.zpart : (const float*)nullptr,
-                        zfuse ? p.E : w.nchunk, w.part2);
+                        z_rides ? p.E : w.nchunk, w.part2);
             LAUNCH_CHECK();
             part = w.part2; ntiles = 1;
         }
@@ -1397,7 +1409,7 @@ static int corrector_apply(ccsd_plan* pl, int B, int step, int it, const ccsd_st
     const PlanD& p = pl->h;
     NoiseArgs na = make_noise(noise, seed, off, draw_base(pl, step, it), pl->rt.corrector_flat);
     LangArgs a = lang_args(pl, B, step, cur, flags, sums, out, w);
-    const long long total = (long long)B * (p.N * p.F + p.N * p.N) + (p.is_cc ? (long long)B * (((long long)p.E * p.K + 3) / 4) : 0);
+    const long long total = state_items(p, B, 1);
     prof_mark(pl, KID_LANGEVIN, stream);
 #define LA_GO(EC_, KC_) CCSD_LAUNCH((k_langevin_apply<EC_, KC_>), dim3(grid_for(total, 256)), dim3(CCSD_NTHREADS), 0, stream, a, na, w.masks())
     GEO_EK(pl->rt.geo, LA_GO);
@@ -1410,47 +1422,56 @@ static int predictor(ccsd_plan* pl, int B, int step, const ccsd_state_t* in, con
                      uint64_t seed, int64_t off, ccsd_state_t* out, ccsd_state_t* mean, Workspace& w, void* stream,
                      const float* fuse_sums = nullptr, bool merge_next = false) {
     const PlanD& p = pl->h;
-    int st;
+    int st = CCSD_OK;
     NoiseArgs na = make_noise(noise, seed, off, draw_base(pl, step, pl->cfg.n_corr_steps), pl->rt.predictor_flat);
     const ccsd_step_coef_t* c = &pl->coef[(size_t)step * 3];
     const Route& rt = pl->rt;
     Pass ps;
-    const bool fused = rt.r2_family == R2_FUSED, ew1 = rt.r2_family == R2_EW1;
-    const float* r2_in = in->rank2;           // what the rank-2 kernels of the tiled path read (the corrected state when the apply is fused)
+    // The rank-2 side of THIS pass, named once as in corrector_norms (fuse_sums: the Langevin apply is fused in; na.zr: the host's rank2 draw)
+    enum { PR_NONE, PR_R2, PR_EW1_ONEPASS, PR_EW1, PR_TILED_APPLY, PR_TILED };
+    const int form = !p.is_cc ? PR_NONE : rt.r2_family == R2_FUSED ? PR_R2
+                   : rt.r2_family == R2_EW1 ? (fuse_sums && rt.ew1_fuse && !na.zr ? PR_EW1_ONEPASS : PR_EW1)
+                   : fuse_sums && rt.tiled_fuse ? PR_TILED_APPLY : PR_TILED;
     CorrFuse cf{};
     if (fuse_sums) {   // the Langevin corrector's apply pass runs in the prologues of this half-step's kernels
         cf.on = 1; cf.net_x = w.net_x; cf.net_adj = w.net_adj; cf.net_r = w.net_r; cf.lc = lang_coef(pl, step, fuse_sums);
         const unsigned int cb = draw_base(pl, step, 0);
         cf.draw_x = cb; cf.draw_adj = cb + 1; cf.draw_r = cb + 2;
     }
-    if (fused) {
-        RankEpi ep = pred_epi(pl, step, out, mean);
-        // merged launch: the rank-2 side of the NEXT step's norms pass follows in the same launch (its corrector draw: rank2 slot of
-        // draw_base(step + 1, 0))
-        const int md = merge_next ? (int)draw_base(pl, step + 1, 0) + 2 : -1;
+    RankEpi ep = pred_epi(pl, step, out, mean);
+    P0Fuse pf{};
+    const float* p_in = in->rank2;            // what the hodge projections are taken of
+    const float* r2_in = in->rank2;           // what the rank-2 kernels of the tiled path read (the corrected state when the apply is fused)
+    // merged launch: the rank-2 side of the NEXT step's norms pass follows in the same launch (its corrector draw: rank2 slot of
+    // draw_base(step + 1, 0))
+    const int md = merge_next ? (int)draw_base(pl, step + 1, 0) + 2 : -1;
+    switch (form) {
+    case PR_R2:
         if ((st = launch_r2(pl, B, in->rank2, in->adj, flags, 1, ep, na, ps, w, stream, &cf, md))) return st;
-    } else if (ew1 && cf.on && rt.ew1_fuse && !na.zr) {
-        // element-wise ScoreNetworkF, one hodge layer: corrector apply + projection + predictor update in ONE pass over rank2
-        P0Fuse pf = p0_fuse(pl, 4, na, cf.draw_r, w);
+        break;
+    case PR_EW1_ONEPASS:    // k_ew1 plans, one hodge layer: corrector apply + projection + predictor update in ONE pass over rank2
+        pf = p0_fuse(pl, 4, na, cf.draw_r, w);
         pf.draw_pred = na.draw_r; pf.cf = cf;
         pf.alpha = p.f_alpha; pf.gamma = p.f_gamma; pf.pa = c[2].pa; pf.pb = c[2].pb; pf.pc = c[2].pc;
         pf.out = out->rank2; pf.mean = mean ? mean->rank2 : nullptr;
         pf.f1 = w.net_r;                         // (host emulation only: its projection runs as a pass of its own over the corrected state)
-        if ((st = launch_p(pl, B, in->adj, in->rank2, ps, w, stream, &pf))) return st;
-    } else if (ew1) {
+        break;
+    case PR_EW1:
         // element-wise ScoreNetworkF first: with the fused apply it produces the corrected rank2 (in the raw-score scratch, which
         // the fused loop does not fill) that the hodge projections of the A-network must see
-        RankEpi ep = pred_epi(pl, step, out, mean);
         if ((st = launch_ew1(pl, B, in->rank2, ep, na, w, stream, nullptr, &cf, w.net_r))) return st;
-        if ((st = launch_p(pl, B, in->adj, cf.on ? (const float*)w.net_r : in->rank2, ps, w, stream))) return st;
-    } else if (cf.on && rt.tiled_fuse) {
-        // tiled path: the corrector apply rides on the projection pass -- corrected rank2 written in place over the raw scores it
-        // consumes (w.net_r), P_0 taken of it; k_gemm_h / k_hf_score below read the corrected state from there
-        P0Fuse pf = p0_fuse(pl, 2, na, cf.draw_r, w);
+        if (cf.on) p_in = w.net_r;
+        break;
+    case PR_TILED_APPLY:
+        // tiled path, one hodge layer: the corrector apply rides on the projection pass -- corrected rank2 written in place over the raw
+        // scores it consumes (w.net_r), P_0 taken of it; k_gemm_h / k_hf_score below read the corrected state from there
+        pf = p0_fuse(pl, 2, na, cf.draw_r, w);
         pf.net = w.net_r; pf.f1 = w.net_r; pf.cf = cf;
-        if ((st = launch_p(pl, B, in->adj, in->rank2, ps, w, stream, &pf))) return st;
         r2_in = w.net_r;
-    } else if ((st = launch_p(pl, B, in->adj, in->rank2, ps, w, stream))) return st;
+        break;
+    }
+    if (form != PR_R2) st = launch_p(pl, B, in->adj, p_in, ps, w, stream, pf.mode ? &pf : nullptr);
+    if (st) return st;
     XaArgs xa{};
     xa.xX = xa.xA = in->x; xa.adjX = xa.adjA = in->adj; xa.flags = flags;
     xa.do_x = xa.do_a = 1; xa.mode = MODE_PRED;
@@ -1460,9 +1481,8 @@ static int predictor(ccsd_plan* pl, int B, int step, const ccsd_state_t* in, con
     xa.mean_x = mean ? mean->x : nullptr; xa.mean_a = mean ? mean->adj : nullptr;
     xa.cf = cf;
     if ((st = launch_xa(pl, B, xa, na, ps, w, stream))) return st;
-    if (p.is_cc && !fused && !ew1) {
+    if (form == PR_TILED_APPLY || form == PR_TILED) {
         if ((st = launch_h(pl, B, r2_in, ps, w, stream))) return st;
-        RankEpi ep = pred_epi(pl, step, out, mean);
         if ((st = launch_hf(pl, B, r2_in, ep, na, w, stream))) return st;
     }
     return CCSD_OK;
@@ -1483,9 +1503,8 @@ static int s4_apply(ccsd_plan* pl, int B, int step, const ccsd_state_t* cur, con
     NoiseArgs na1 = make_noise(n1, seed, off, draw_base(pl, step, 0));
     NoiseArgs na2 = make_noise(n2, seed, off, draw_base(pl, step, 1));
     NoiseArgs na3 = make_noise(n3, seed, off, draw_base(pl, step, 2));
-    const long long total = (long long)B * (p.N * p.F + p.N * p.N) + (p.is_cc ? (long long)B * ((p.E + 3) / 4) * p.K : 0);
     prof_mark(pl, KID_S4, stream);
-    CCSD_LAUNCH(k_s4_apply, dim3(grid_for(total, 256)), dim3(CCSD_NTHREADS), 0, stream, q, na1, na2, na3,
+    CCSD_LAUNCH(k_s4_apply, dim3(grid_for(state_items(p, B, 0), 256)), dim3(CCSD_NTHREADS), 0, stream, q, na1, na2, na3,
                 (const unsigned long long*)w.offbits, (const unsigned char*)pl->edges, (const unsigned long long*)pl->cells);
     prof_mark(pl, KID_S4, stream);
     LAUNCH_CHECK();
@@ -1500,33 +1519,33 @@ static int check_step(const ccsd_plan* pl, int step) {
 extern "C" int ccsd_corrector_norms(ccsd_plan_t* pl, int32_t B, int32_t step, int32_t corr_iter, const ccsd_state_t* base,
                                     const ccsd_state_t* cur, const float* flags, const ccsd_noise_t* noise, uint64_t seed,
                                     int64_t sample_offset, float* norm_sums, void* workspace, size_t ws_bytes, void* stream) {
-    int st = check_common(pl, B, flags, workspace, ws_bytes);
+    Workspace w{};
+    int st = check_common(pl, B, flags, workspace, ws_bytes, w);
     if (st || (st = check_step(pl, step)) || (st = check_state(pl, base, "base")) || (st = check_state(pl, cur, "cur"))) return st;
     if (!norm_sums) return set_err(CCSD_ERR_INVALID, "NULL norm_sums");
-    Workspace w = carve_ws(pl, B, workspace);
     if ((st = launch_flagbits(pl, B, flags, w, stream))) return st;
     return corrector_norms(pl, B, step, corr_iter, base, cur, flags, noise, seed, sample_offset, norm_sums, w, stream);
 }
 extern "C" int ccsd_corrector_apply(ccsd_plan_t* pl, int32_t B, int32_t step, int32_t corr_iter, const ccsd_state_t* cur,
                                     const float* flags, const ccsd_noise_t* noise, uint64_t seed, int64_t sample_offset,
                                     const float* norm_sums, ccsd_state_t* out, void* workspace, size_t ws_bytes, void* stream) {
-    int st = check_common(pl, B, flags, workspace, ws_bytes);
+    Workspace w{};
+    int st = check_common(pl, B, flags, workspace, ws_bytes, w);
     if (st || (st = check_step(pl, step)) || (st = check_state(pl, cur, "cur")) || (st = check_state(pl, out, "out"))) return st;
     if (!norm_sums) return set_err(CCSD_ERR_INVALID, "NULL norm_sums");
-    Workspace w = carve_ws(pl, B, workspace);
     if ((st = launch_flagbits(pl, B, flags, w, stream))) return st;
     return corrector_apply(pl, B, step, corr_iter, cur, flags, noise, seed, sample_offset, norm_sums, out, w, stream);
 }
 extern "C" int ccsd_predictor(ccsd_plan_t* pl, int32_t B, int32_t step, const ccsd_state_t* in, const float* flags,
                               const ccsd_noise_t* noise, uint64_t seed, int64_t sample_offset, ccsd_state_t* out,
                               ccsd_state_t* mean, void* workspace, size_t ws_bytes, void* stream) {
-    int st = check_common(pl, B, flags, workspace, ws_bytes);
+    Workspace w{};
+    int st = check_common(pl, B, flags, workspace, ws_bytes, w);
     if (!st && pl->cfg.predictor == CCSD_PRED_S4) return set_err(CCSD_ERR_INVALID, "S4 plans step with ccsd_corrector_norms + ccsd_s4_apply");
     if (st || (st = check_step(pl, step)) || (st = check_state(pl, in, "in")) || (st = check_state(pl, out, "out"))) return st;
     if (mean && (st = check_state(pl, mean, "mean"))) return st;
     if (in->x == out->x || in->adj == out->adj || (pl->h.is_cc && in->rank2 == out->rank2))
         return set_err(CCSD_ERR_INVALID, "predictor cannot run in place");
-    Workspace w = carve_ws(pl, B, workspace);
     if ((st = launch_flagbits(pl, B, flags, w, stream))) return st;
     return predictor(pl, B, step, in, flags, noise, seed, sample_offset, out, mean, w, stream);
 }
@@ -1535,34 +1554,35 @@ extern "C" int ccsd_s4_apply(ccsd_plan_t* pl, int32_t B, int32_t step, const ccs
                              const ccsd_noise_t* noise1, const ccsd_noise_t* noise2, const ccsd_noise_t* noise3, uint64_t seed,
                              int64_t sample_offset, const float* norm_sums, ccsd_state_t* out, ccsd_state_t* mean,
                              void* workspace, size_t ws_bytes, void* stream) {
-    int st = check_common(pl, B, flags, workspace, ws_bytes);
+    Workspace w{};
+    int st = check_common(pl, B, flags, workspace, ws_bytes, w);
     if (st || (st = check_step(pl, step)) || (st = check_state(pl, cur, "cur")) || (st = check_state(pl, out, "out"))) return st;
     if (mean && (st = check_state(pl, mean, "mean"))) return st;
     if (pl->cfg.predictor != CCSD_PRED_S4) return set_err(CCSD_ERR_INVALID, "ccsd_s4_apply needs a plan created with CCSD_PRED_S4");
     if (!norm_sums) return set_err(CCSD_ERR_INVALID, "NULL norm_sums");
-    Workspace w = carve_ws(pl, B, workspace);
     if ((st = launch_flagbits(pl, B, flags, w, stream))) return st;
     return s4_apply(pl, B, step, cur, flags, noise1, noise2, noise3, seed, sample_offset, norm_sums, out, mean, w, stream);
 }
 
-// The loop behind ccsd_sampler_run (no hook) and ccsd_sampler_run_ex.  `reduce` is called once per norms pass, after its k_normsum
+// The library loop; ccsd_sampler_run is this call without options.  The reduce hook is called once per norms pass, after its k_normsum
 // has been enqueued and before any reader of w.sums is: the launches are the same with and without it.
-static int sampler_run(ccsd_plan_t* pl, int32_t B, const float* flags, uint64_t seed, int64_t sample_offset,
-                       int32_t first_step, int32_t last_step, ccsd_state_t* state, ccsd_state_t* scratch,
-                       ccsd_state_t* result, float* traj, void* workspace, size_t ws_bytes, void* stream,
-                       ccsd_reduce_fn reduce, void* user) {
-    int st = check_common(pl, B, flags, workspace, ws_bytes);
+extern "C" int ccsd_sampler_run_ex(ccsd_plan_t* pl, int32_t B, const float* flags, uint64_t seed, int64_t sample_offset,
+                                   int32_t first_step, int32_t last_step, ccsd_state_t* state, ccsd_state_t* scratch,
+                                   ccsd_state_t* result, float* traj, void* workspace, size_t ws_bytes, void* stream,
+                                   const ccsd_run_options_t* options) {
+    Workspace w{};
+    int st = check_common(pl, B, flags, workspace, ws_bytes, w);
     if (st || (st = check_state(pl, state, "state")) || (st = check_state(pl, scratch, "scratch")) ||
         (st = check_state(pl, result, "result"))) return st;
     if (first_step < 0 || last_step > pl->cfg.diff_steps || first_step >= last_step) return set_err(CCSD_ERR_INVALID, "bad step range");
     const Route& rt = pl->rt;
     const PlanD& p = pl->h;
-    Workspace w = carve_ws(pl, B, workspace);
     if ((st = launch_flagbits(pl, B, flags, w, stream))) return st;
     const size_t nx = (size_t)p.N * p.F, na = (size_t)p.N * p.N, nr = p.is_cc ? (size_t)p.E * p.K : 0;
     ccsd_state_t a = *state, b = *scratch;   // a = live buffer
     // exact multi-GPU mode: the caller all-reduces the six sums in place, ordered on `stream`
-#define REDUCE_SUMS() do { if (reduce && reduce(w.sums, 6, stream, user)) return set_err(CCSD_ERR_CALLBACK, "the reduce hook of ccsd_sampler_run_ex failed"); } while (0)
+#define REDUCE_SUMS() do { if (options && options->reduce && options->reduce(w.sums, 6, stream, options->user)) \
+                               return set_err(CCSD_ERR_CALLBACK, "the reduce hook of ccsd_sampler_run_ex failed"); } while (0)
     for (int step = first_step; step < last_step; ++step) {
         const bool lastone = step == last_step - 1;
         const bool want_mean = pl->cfg.denoise && (lastone || traj);
@@ -1585,14 +1605,9 @@ static int sampler_run(ccsd_plan_t* pl, int32_t B, const float* flags, uint64_t 
                 RT_CHECK(rt_d2d_async(w.U1b, w.U1, (size_t)B * p.h_pw * 4, stream));
             if ((st = predictor(pl, B, step, &a, flags, nullptr, seed, sample_offset, &b, want_mean ? result : nullptr, w, stream, w.sums, merge_next))) return st;
             ccsd_state_t t = a; a = b; b = t;
-        } else if (rt.loop == LOOP_LANGEVIN) {   // a -> (corrector) -> b -> (predictor) -> a
-            if ((st = corrector_norms(pl, B, step, 0, &a, &a, flags, nullptr, seed, sample_offset, w.sums, w, stream))) return st;
-            REDUCE_SUMS();
-            if ((st = corrector_apply(pl, B, step, 0, &a, flags, nullptr, seed, sample_offset, w.sums, &b, w, stream))) return st;
-            if ((st = predictor(pl, B, step, &b, flags, nullptr, seed, sample_offset, &a, want_mean ? result : nullptr, w, stream))) return st;
-        } else if (rt.loop == LOOP_LANGEVIN_MULTI && pl->cfg.n_corr_steps > 0) {
+        } else if (rt.loop == LOOP_LANGEVIN || (rt.loop == LOOP_LANGEVIN_MULTI && pl->cfg.n_corr_steps > 0)) {
             // a = base -> (corrector 0) -> b -> (corrector 1) -> third -> (corrector 2) -> b ... -> (predictor) -> a.  Every inner
-            // iteration scores against the base state with its own target's tensor taken from the current iterate (corrector_norms)
+            // iteration scores against the base state with its own target's tensor taken from the current iterate (corrector_norms).
             const ccsd_state_t* cur = &a;
             for (int it = 0; it < pl->cfg.n_corr_steps; ++it) {
                 ccsd_state_t* out = (it & 1) ? &w.third : &b;
@@ -1608,37 +1623,19 @@ static int sampler_run(ccsd_plan_t* pl, int32_t B, const float* flags, uint64_t 
         }
         if (traj) {
             const ccsd_state_t* src = pl->cfg.denoise ? result : &a;
-            float* slot = traj + (size_t)step * (nx + na + nr);
-            RT_CHECK(rt_d2d_async(slot, src->x, nx * 4, stream));
-            RT_CHECK(rt_d2d_async(slot + nx, src->adj, na * 4, stream));
-            if (nr) RT_CHECK(rt_d2d_async(slot + nx + na, src->rank2, nr * 4, stream));
+            float* slot = traj + (size_t)step * (nx + na + nr);      // (a slot holds the first sample's tensors back to back)
+            if ((st = copy_state(ccsd_state_t{slot, slot + nx, slot + nx + na}, *src, p, 1, stream))) return st;
         }
     }
-    if (a.x != state->x) {   // the live buffer ended up in `scratch`: bring the state home
-        RT_CHECK(rt_d2d_async(state->x, a.x, (size_t)B * nx * 4, stream));
-        RT_CHECK(rt_d2d_async(state->adj, a.adj, (size_t)B * na * 4, stream));
-        if (nr) RT_CHECK(rt_d2d_async(state->rank2, a.rank2, (size_t)B * nr * 4, stream));
-    }
-    if (!pl->cfg.denoise) {
-        RT_CHECK(rt_d2d_async(result->x, a.x, (size_t)B * nx * 4, stream));
-        RT_CHECK(rt_d2d_async(result->adj, a.adj, (size_t)B * na * 4, stream));
-        if (nr) RT_CHECK(rt_d2d_async(result->rank2, a.rank2, (size_t)B * nr * 4, stream));
-    }
 #undef REDUCE_SUMS
-    return CCSD_OK;
+    if (a.x != state->x) st = copy_state(*state, a, p, B, stream);      // the live buffer ended up in `scratch`: bring the state home
+    if (!st && !pl->cfg.denoise) st = copy_state(*result, a, p, B, stream);
+    return st;
 }
 extern "C" int ccsd_sampler_run(ccsd_plan_t* pl, int32_t B, const float* flags, uint64_t seed, int64_t sample_offset,
                                 int32_t first_step, int32_t last_step, ccsd_state_t* state, ccsd_state_t* scratch,
                                 ccsd_state_t* result, float* traj, void* workspace, size_t ws_bytes, void* stream) {
-    return sampler_run(pl, B, flags, seed, sample_offset, first_step, last_step, state, scratch, result, traj, workspace, ws_bytes,
-                       stream, nullptr, nullptr);
-}
-extern "C" int ccsd_sampler_run_ex(ccsd_plan_t* pl, int32_t B, const float* flags, uint64_t seed, int64_t sample_offset,
-                                   int32_t first_step, int32_t last_step, ccsd_state_t* state, ccsd_state_t* scratch,
-                                   ccsd_state_t* result, float* traj, void* workspace, size_t ws_bytes, void* stream,
-                                   const ccsd_run_options_t* options) {
-    return sampler_run(pl, B, flags, seed, sample_offset, first_step, last_step, state, scratch, result, traj, workspace, ws_bytes,
-                       stream, options ? options->reduce : nullptr, options ? options->user : nullptr);
+    return ccsd_sampler_run_ex(pl, B, flags, seed, sample_offset, first_step, last_step, state, scratch, result, traj, workspace, ws_bytes, stream, nullptr);
 }
 
 // the plan-free entry points (operations on finished samples): a file of their own, sharing set_err, grid_for and the check macros

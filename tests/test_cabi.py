@@ -163,3 +163,88 @@ def test_emu_workspace_bytes_are_the_recorded_ones(fn):
         assert getattr(emu, fn)(*args) == want, (fn, args)
         if err is not None:
             assert emu.ccsd_last_error().decode() == err, (fn, args)
+
+
+def _ckpt_engine(name, **kw):
+    from tests import parity_cases as pc
+
+    return lambda lib: pc.engine_from_ckpt(name, lib, "cpu", **kw)[0]
+
+
+def _zinc5b_engine(lib):
+    """The N = 38 substitute of test_zinc5b_substitute (tests/parity_cases.py::zinc5b_setup), without its inputs."""
+    import json
+
+    import torch
+
+    from ccsd_amd.engine import PCEngine
+    from tests.helpers import load_golden
+
+    g = load_golden("kat_zinc250k_CC_5b.npz")
+    meta = json.loads(str(g["meta"]))
+    sd = {tag: {k[len(tag) + 3:]: torch.from_numpy(g[k]) for k in g.files if k.startswith(f"{tag}/w/")} for tag in ("x", "adj", "rank2")}
+    N, Fd, d_min, d_max, _, _ = meta["dims"]
+    pm = meta["params"]
+    return PCEngine(pm["x"], sd["x"], pm["adj"], sd["adj"], pm["rank2"], sd["rank2"], N=N, F=Fd, is_cc=True, d_min=d_min, d_max=d_max,
+                    device="cpu", lib=lib)
+
+
+def _kat_general_engine(tag):
+    def make(lib):
+        import json
+
+        import torch
+
+        from tests import hodge_wide_cases as hw
+        from tests.helpers import load_golden
+
+        g = load_golden("kat_hodge_general.npz")
+        sd = {k[len(tag) + 3:]: torch.from_numpy(g[k]) for k in g.files if k.startswith(f"{tag}/w/")}
+        return hw.kat_engine(json.loads(str(g["meta"]))[tag], sd, lib, "cpu")
+    return make
+
+
+def _kat_wide_engine(tag):
+    def make(lib):
+        from tests import hodge_wide_cases as hw
+
+        return hw.kat_engine(*hw.kat_tag(tag)[:2], lib, "cpu")
+    return make
+
+
+# ccsd_workspace_bytes(plan, B) at B = 1 and B = 5, one plan per branch of the workspace carve-up (carve_ws, ccsd_amd/csrc/ccsd_api.h):
+# name -> (engine maker, environment at plan creation, the route queries that name the branch, (bytes at B = 1, bytes at B = 5)).  The
+# literals were RECORDED from the emulation library of the commit before every entry point's prologue began to carve once per call -- not
+# computed by the code under test: the layout must stay byte for byte.  The queries are asserted first, so that a route switch left in the
+# caller's environment fails by naming the branch the plan took, not by a bare byte count.
+PLAN_WORKSPACE_BYTES = {
+    "ccsd_qm9_CC": (_ckpt_engine("ccsd_qm9_CC"), {}, dict(r2_family=1, large_graph=0), (127744, 626944)),                                   # fused family: second projection set
+    "ccsd_enzymes_small_CC": (_ckpt_engine("ccsd_enzymes_small_CC"), {}, dict(r2_family=3, large_graph=0), (293120, 1453824)),              # tiled family, K slices of P_1
+    "ccsd_community_small_CC": (_ckpt_engine("ccsd_community_small_CC"), {}, dict(r2_family=3, large_graph=0), (1099776, 5490944)),
+    "zinc5b substitute": (_zinc5b_engine, {}, dict(r2_family=2, ew1=1), (25814528, 129064960)),                                     # k_ew1
+    "ccsd_qm9_Base_CC": (_ckpt_engine("ccsd_qm9_Base_CC"), {}, dict(r2_family=1, large_graph=0), (76032, 370432)),
+    "gdss_community_small": (_ckpt_engine("gdss_community_small"), {}, dict(r2_family=0, large_graph=0), (67072, 328960)),
+    "kat_hodge_general G3_n5": (_kat_general_engine("G3_n5"), {}, dict(h_general=1, large_graph=0), (17152, 69376)),                        # general hodge stack on k_xa
+    "kat_hodge_general G3_n5 on the route": (_kat_general_engine("G3_n5"), {"CCSD_LARGE_GRAPH": "2"}, dict(h_general=1, large_graph=1), (23296, 92160)),
+    "kat_hodge_wide W3_n12": (_kat_wide_engine("W3_n12"), {}, dict(h_wide=1, h_general=1, large_graph=1), (996608, 4960512)),                         # wide hodge MLPs (route, general stack)
+    "gdss_enzymes": (_ckpt_engine("gdss_enzymes"), {}, dict(r2_family=0, large_graph=1), (4950528, 24739840)),                              # N = 125: graph-only route
+    # the third state buffer of a Langevin corrector with two inner iterations
+    "ccsd_qm9_CC, n_steps = 2": (_ckpt_engine("ccsd_qm9_CC", predictor="Reverse", corrector="Langevin", snr=0.2, scale_eps=0.7, n_steps=2), {},
+                                 dict(r2_family=1, loop_form=4),
+                                 (195840, 965120)),
+}
+
+
+@pytest.mark.parametrize("name", list(PLAN_WORKSPACE_BYTES))
+def test_emu_plan_workspace_bytes_are_the_recorded_ones(name, monkeypatch):
+    from tests.emu_util import emu_library
+
+    emu = emu_library()
+    make, env, route, want = PLAN_WORKSPACE_BYTES[name]
+    monkeypatch.delenv("CCSD_LARGE_GRAPH", raising=False)
+    for k, v in env.items():
+        monkeypatch.setenv(k, v)
+    eng = make(emu)
+    assert {q: eng.query(q) for q in route} == route, name
+    assert (emu.ccsd_workspace_bytes(eng.handle, 1), emu.ccsd_workspace_bytes(eng.handle, 5)) == want, name
+
