@@ -1315,6 +1315,13 @@ extern "C" int ccsd_plan_query(const ccsd_plan_t* pl, int32_t what, int64_t* val
         case CCSD_QUERY_H_GENERAL: *value = r.h_general; break;
         case CCSD_QUERY_GEO_EK: *value = r.geo; break;
         case CCSD_QUERY_H_WIDE: *value = r.h_wide; break;
+        case CCSD_QUERY_MLP_FORMS: {
+            int64_t edge = 0;
+            for (int l = 0; l < pl->h.a_L; ++l) edge |= (int64_t)(pl->h.al[l].mlp.chain != 0) << l;
+            const int afin = r.lg && pl->afin_lg.chain ? pl->afin_lg.chain : pl->h.a_fin.chain;
+            *value = pl->h.x_fin.chain + 16 * afin + 256 * edge;
+            break;
+        }
         default: return set_err(CCSD_ERR_INVALID, "unknown query");
     }
     return CCSD_OK;

@@ -337,7 +337,8 @@ static inline const char* ccsd_lg_ineligible(const ccsd_config_t* c, const PlanD
         if (a.adim > 64) return "attention dimensions above 64";
     }
     // (57 to 64 channels: the route's own shape, for the plans that have no other kernel -- wide hodge MLPs; any other such plan stays with k_xa)
-    if (!p->a_fin.chain && !(h_wide && p->a_fdim <= 64)) return "final MLPs wider than 64 input channels";
+    if (!p->a_fin.chain && p->a_fdim > 64) return "final MLPs wider than 64 input channels";
+    if (!p->a_fin.chain && !h_wide) return "final MLPs of 57 to 64 input channels without hodge MLPs wider than 8";
     if (lg_nmlp_lds(*p) > 160 * 1024) return "per-node MLPs whose 16-row activations exceed the 160 KB LDS of a CU";
     return nullptr;
 }

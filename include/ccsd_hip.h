@@ -214,7 +214,11 @@ enum {
     CCSD_QUERY_EW1_FUSE = 15,     /* 1: k_ew1 plans, the whole rank-2 side of a half-step rides on the layer-0 projection pass */
     CCSD_QUERY_H_GENERAL = 16,    /* 1: general hodge stack (R_l materialised layer by layer) */
     CCSD_QUERY_GEO_EK = 17,       /* general-path kernels: 0 run-time (E, K); 1 community_small, 2 zinc250k, 3 ENZYMES_small compiled in */
-    CCSD_QUERY_H_WIDE = 18        /* 1: ScoreNetworkA_CC hodge MLPs wider than 8 (16-wide kernels of the tiled route and the tiled rank-2 family) */
+    CCSD_QUERY_H_WIDE = 18,       /* 1: ScoreNetworkA_CC hodge MLPs wider than 8 (16-wide kernels of the tiled route and the tiled rank-2 family) */
+    CCSD_QUERY_MLP_FORMS = 19     /* the form of the graph networks' MLPs: x_fin + 16 * a_fin + 256 * edge_mask.  x_fin / a_fin: the register-resident chain
+                                     shape of ScoreNetworkX's / ScoreNetworkA's final MLP (1 .. 7; 0: un-chained, the block-wise Linear form) on the route the
+                                     plan takes -- on the tiled route the shape of k_lg_fin_w (7) where that kernel runs the final MLP; bit l of edge_mask: the
+                                     edge MLP of AttentionLayer l of ScoreNetworkA is chained */
 };
 int ccsd_plan_query(const ccsd_plan_t* plan, int32_t what, int64_t* value);
 

@@ -37,7 +37,8 @@ def engine(meta, parts, lib, device, **kw):
                     d_max=0, device=device, lib=lib, **kw)
 
 
-def case_forward_vs_oracle_src(meta, parts, lib, device, counts, what, seed=11, expect_lg=1, batch_hint=0, oracle=None):
+def case_forward_vs_oracle_src(meta, parts, lib, device, counts, what, seed=11, expect_lg=1, batch_hint=0, oracle=None,
+                                scales=(("unit", 1.0), ("small", 0.3))):
     """Both networks' forward (raw nets and the score scaling at t = 0.5) on masked random inputs against the oracle.  `expect_lg`
     None leaves the route to the planner; `batch_hint` is the plan's (it picks k_xa's LDS budget); `oracle` is a dict that keeps
     the oracle's outputs for a later call on the same networks, inputs and seed (another plan of theirs).  Returns the plan's
@@ -48,7 +49,7 @@ def case_forward_vs_oracle_src(meta, parts, lib, device, counts, what, seed=11, 
     assert expect_lg is None or route[0] == expect_lg
     flags = make_flags(len(counts), N, counts)
     dv = lambda t: t.to(device)
-    for tag, scale in (("unit", 1.0), ("small", 0.3)):
+    for tag, scale in scales:
         x, adj, _ = pc.masked_state(seed, len(counts), N, F, False, 0, 0, flags, scale)
         for t, p in enumerate(["x", "adj"]):
             want = None if oracle is None else oracle.get((tag, p))

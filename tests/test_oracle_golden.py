@@ -265,6 +265,21 @@ def test_kat_cnum_more_hodge_powers():
         _close(out.numpy(), g[f"{tag}/out"], tag)
 
 
+def test_kat_arch_sweep():
+    """Six architectures of the architecture sweep (tests/arch_sweep_cases.py) built by the reference's constructors: an un-chained
+    edge MLP with five adjacency powers, one and three heads, four Linears per edge MLP, one AttentionLayer; ScoreNetworkF 12 wide
+    with four Linears."""
+    g = load_golden("kat_arch_sweep.npz")
+    meta = json.loads(str(g["meta"]))
+    assert len(meta) == 6
+    for tag, params in meta.items():
+        t = {k: torch.from_numpy(g[f"{tag}/{k}"]) if f"{tag}/{k}" in g.files else None for k in ("flags", "x", "adj", "rank2")}
+        w = {k[len(tag) + 3:]: torch.from_numpy(g[k]).requires_grad_(True) for k in g.files if k.startswith(f"{tag}/w/")}
+        with torch.no_grad():
+            out = O.run_network(params, w, t["x"], t["adj"], t["rank2"], t["flags"])
+        _close(out.numpy(), g[f"{tag}/out"], tag)
+
+
 def test_kat_hodge_layers_three_and_four():
     g = load_golden("kat_hodge_layers.npz")
     meta = json.loads(str(g["meta"]))

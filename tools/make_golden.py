@@ -1472,6 +1472,60 @@ def kat_cnum():
     print("kat_cnum", {k: (v.shape, float(np.abs(v).max())) for k, v in out.items() if k.endswith("/out")})
 
 
+def kat_arch_sweep():
+    """Six architectures of the architecture sweep (tests/arch_sweep_cases.py: KAT) built by the reference's constructors, biases
+    perturbed, B = 4 with node counts [N, N // 2 + 1, 1 or 2, 0]: ScoreNetworkA with an un-chained edge MLP and five adjacency powers,
+    one head, three heads on an attention dimension of 12, four Linears per edge MLP, a single AttentionLayer; ScoreNetworkF 12 wide
+    with four Linears per HodgeNetworkLayer (N = 6, d = 3..4).  Weights, inputs, flags and outputs only."""
+    from ccsd.src.models.ScoreNetwork_A import ScoreNetworkA
+    from ccsd.src.models.ScoreNetwork_F import ScoreNetworkF
+
+    base = dict(nhid=16, num_layers=3, num_linears=2, c_init=2, c_hid=8, c_final=4, adim=16, num_heads=4, conv="GCN")
+    graph = {"chid12_cinit5": (dict(c_hid=12, c_init=5), 0.5), "heads1": (dict(num_heads=1), 1.0),
+             "heads3": (dict(num_heads=3, adim=12, nhid=12), 1.0), "lin4": (dict(num_linears=4), 1.0),
+             "layers1": (dict(num_layers=1, c_hid=4, c_final=4), 1.0)}
+    out, meta = {}, {}
+    torch.manual_seed(1212)
+    for tag, (over, scale) in graph.items():
+        N, Fd = 9, 4
+        prm = dict(base, **over, max_feat_num=Fd, max_node_num=N, use_bn=False, is_cc=False)
+        m = ScoreNetworkA(**prm)
+        for k, p_ in m.named_parameters():
+            if k.endswith("bias"):
+                p_.data.normal_(0, 0.2)
+        m.eval()
+        flags = make_flags(4, N, [N, N // 2 + 1, 1, 0])
+        x, adj, _ = masked_state(53, 4, N, Fd, False, None, None, flags, scale)
+        out[f"{tag}/flags"], out[f"{tag}/x"], out[f"{tag}/adj"] = flags.numpy(), x.numpy(), adj.numpy()
+        with torch.no_grad():
+            for k, v in m.state_dict().items():
+                out[f"{tag}/w/{k}"] = v.numpy()
+            out[f"{tag}/out"] = m(x, adj, flags).numpy()
+        meta[tag] = dict(prm, model_type="ScoreNetworkA")
+    N, dmin, dmax = 6, 3, 4
+    prm = dict(num_layers_mlp=1, num_layers=2, num_linears=4, nhid=12, c_hid=12, c_final=12, cnum=2, max_node_num=N, d_min=dmin,
+               d_max=dmax, use_hodge_mask=True, use_bn=False, is_cc=True)
+    ref_cc.default_mask.cache_clear()
+    m = ScoreNetworkF(**prm)
+    for k, p_ in m.named_parameters():
+        if k.endswith("bias"):
+            p_.data.normal_(0, 0.2)
+    m.eval()
+    flags = make_flags(4, N, [N, N // 2 + 1, 2, 0])
+    x, adj, rank2 = masked_state(53, 4, N, 2, True, dmin, dmax, flags, 0.5)
+    tag = "f_w12_lin4"
+    out[f"{tag}/flags"], out[f"{tag}/rank2"] = flags.numpy(), rank2.numpy()
+    with torch.no_grad():
+        for k, v in m.state_dict().items():
+            out[f"{tag}/w/{k}"] = v.numpy()
+        out[f"{tag}/out"] = m(x, adj, rank2, flags).numpy()
+    meta[tag] = dict(prm, model_type="ScoreNetworkF")
+    out["meta"] = json.dumps(meta)
+    path = os.path.join(GOLD, "kat_arch_sweep.npz")
+    np.savez_compressed(path, **out)
+    print("kat_arch_sweep", os.path.getsize(path), "bytes", {k: (v.shape, float(np.abs(v).max())) for k, v in out.items() if k.endswith("/out")})
+
+
 def kat_hodge_layers():
     """ScoreNetworkA_CC with three and four HodgeAdjAttentionLayers (num_layers_h = 3, 4; num_linears_h = 1), built by the
     reference's constructor: no shipped checkpoint has more than two.  N = 5 (E = 10, K = 15; the geometry of kat_small_models, whose
@@ -1951,6 +2005,9 @@ def main():
         return
     if only == {"kat_hodge_wide"}:
         kat_hodge_wide()
+        return
+    if only == {"kat_arch_sweep"}:
+        kat_arch_sweep()
         return
     if only == {"grid_small_cc"}:
         grid_small_cc()
