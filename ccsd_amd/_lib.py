@@ -32,7 +32,7 @@ EXPORTS = [
 ]
 QUERIES = {"fused_r2": 0, "xa_variant": 1, "r2_lds_bytes": 2, "xa_lds_bytes": 3, "fused_loop": 4, "merged_r2": 5, "ew1": 6, "large_graph": 7,
            "r2_family": 8, "r2_instance": 9, "loop_form": 10, "h_full": 11, "hp_full": 12, "p0_narrow": 13, "tiled_fuse": 14, "ew1_fuse": 15,
-           "h_general": 16, "geo_ek": 17, "h_wide": 18, "mlp_forms": 19}
+           "h_general": 16, "geo_ek": 17, "h_wide": 18, "mlp_forms": 19, "fold_sums": 20, "fold_last_run": 21}
 KERNEL_IDS = {"k_xa": 0, "k_gemm_p": 1, "k_hf_score": 2, "k_gemm_h": 3, "k_langevin_apply": 4, "k_r2": 5, "k_s4_apply": 6, "k_ew1": 7}
 
 

@@ -41,6 +41,7 @@ static inline int fnet_width(const PlanD& p) {
 //   CCSD_NO_GEO          geo_off = 1           no instance with a geometry or plan compiled in                 tests (emu + gpu)
 //   CCSD_NO_BAKE         geo_off = 2           geometry instances yes, baked-plan instances no                 tests (gpu), tools/dev
 //   CCSD_NO_FUSED_APPLY  no_fused_apply        Langevin apply as a launch of its own in ccsd_sampler_run       tests (emu + gpu)
+//   CCSD_NO_SUM_FOLD     no_sum_fold           k_normsum as a launch of its own in the fused loop of k_r2 plans tests (emu + gpu), A/B
 //   CCSD_NO_H_FULL       no_h_full             k_gemm_h's 64 x 64 tiles instead of k_gemm_h_full / k_hp_full   tests (gpu)
 //   CCSD_NO_HP_FULL      no_hp_full            k_gemm_p0 + k_gemm_h_full instead of the one k_hp_full pass     tests (gpu)
 //   CCSD_HP_FULL_NORMS   hp_full_norms         k_hp_full in the norms pass too (slower: A/B only)              tests (gpu)
@@ -57,7 +58,7 @@ static inline int fnet_width(const PlanD& p) {
 //   CCSD_VERBOSE         verbose               print the k_xa LDS layout                        (PlanBuilder)  by hand
 //   CCSD_DUMP_PLAN[_NAME] dump_plan[_name]     write the plan's architecture bytes as a C header               tools/bake_plan.py
 struct Knobs {
-    int no_fused_r2 = 0, hodge_general = 0, geo_off = 0, no_fused_apply = 0, no_h_full = 0, no_hp_full = 0, hp_full_norms = 0, split_bf16 = 0;
+    int no_fused_r2 = 0, hodge_general = 0, geo_off = 0, no_fused_apply = 0, no_h_full = 0, no_hp_full = 0, hp_full_norms = 0, split_bf16 = 0, no_sum_fold = 0;
     int xa_threads = 0, xa_prio = 0, lg_force = 0, xa_pass = -1, xa_gch = 0, no_mlp_wt = 0, verbose = 0;
     const char *dump_plan = nullptr, *dump_plan_name = nullptr;
 };
@@ -67,7 +68,7 @@ static Knobs read_knobs() {
     k.no_fused_r2 = on("CCSD_NO_FUSED_R2"); k.hodge_general = on("CCSD_HODGE_GENERAL");
     k.geo_off = on("CCSD_NO_GEO") ? 1 : on("CCSD_NO_BAKE") ? 2 : 0;
     k.no_fused_apply = on("CCSD_NO_FUSED_APPLY"); k.no_h_full = on("CCSD_NO_H_FULL"); k.no_hp_full = on("CCSD_NO_HP_FULL");
-    k.hp_full_norms = on("CCSD_HP_FULL_NORMS");
+    k.hp_full_norms = on("CCSD_HP_FULL_NORMS"); k.no_sum_fold = on("CCSD_NO_SUM_FOLD");
     if (const char* v = getenv("CCSD_SPLIT_BF16")) k.split_bf16 = atoi(v) == 3 ? 3 : 0;
     if (const char* v = getenv("CCSD_XA_THREADS")) { const int t = atoi(v); if (t >= 64 && t <= 1024 && t % 64 == 0) k.xa_threads = t; }
     if (const char* v = getenv("CCSD_XA_PRIO")) k.xa_prio = atoi(v);
@@ -111,6 +112,8 @@ struct Route {
     // ccsd_sampler_run
     int loop = LOOP_PRED_ONLY;
     int merged = 0;                 // LOOP_LANGEVIN_FUSED: k_r2 runs predictor i and the rank-2 side of norms pass i + 1 in one launch
+    int fold_sums = 0;              // LOOP_LANGEVIN_FUSED, k_r2 plans: the predictor's k_r2 launch reduces the batch norm sums itself (R2Args::fold), no
+                                    // k_normsum launch in the loop -- unless the call has a reduce hook, which needs the sums between two launches
     int tiled_fuse = 0;             // tiled rank-2 path, ONE hodge layer: the corrector's rank2 work rides on the layer-0 projection pass
     int ew1_fuse = 0;               // k_ew1 plans, ONE hodge layer: the whole rank-2 side of a half-step rides on it (P0Fuse modes 3 / 4)
     // The Langevin corrector's rank2 draws are keyed by flat groups of four consecutive elements (NoiseArgs::flat_r): they are
@@ -140,6 +143,7 @@ struct ccsd_plan {
     size_t init_off_cap = 0;
     Knobs knobs;                // the environment, read ONCE at plan creation (read_knobs)
     Route rt;                   // which kernels serve the plan (resolve_route)
+    int last_run_folded = 0;    // the plan's latest ccsd_sampler_run[_ex] call took the folded norm sums (CCSD_QUERY_FOLD_LAST_RUN)
     // optional per-kernel timing with HIP events on the launch stream (bench.py roofline leg); mutable: the launchers hold the plan const
     mutable unsigned prof_mask = 0;
     mutable size_t prof_used[8] = {0, 0, 0, 0, 0, 0, 0, 0};
@@ -288,6 +292,9 @@ static int resolve_route(ccsd_plan* pl) {
     if (full_geo && r.tiled_fuse && p.hl[0].wc <= 16 && p.f_cnum == 2 && !k.no_hp_full)
         r.hp_full_modes = (r.loop == LOOP_LANGEVIN_FUSED ? 1u << 2 : 0u) | (k.hp_full_norms ? 1u << 1 : 0u);
     r.merged = r.loop == LOOP_LANGEVIN_FUSED && fused && mt == 3 && rs == 1 && aff && !gen1 && (K & 1) == 0 && ((E * K) & 3) == 0;
+    // folded norm sums: every k_r2 plan of the fused loop whose k_r2 reads no adjacency coefficient (the adjpow path of a non-linear
+    // mlp_value takes sums[1] / sums[4] inside the kernel, and those are complete only one launch later)
+    r.fold_sums = r.loop == LOOP_LANGEVIN_FUSED && fused && !gen1 && !k.no_sum_fold;
     r.corrector_flat = !s4;
     r.predictor_flat = ew1;
     return CCSD_OK;
@@ -314,7 +321,6 @@ static inline const XaEntry* xa_launch(const Route& r, int B, int* threads) {
     *threads = t > e->max_threads ? e->max_threads : t;
     return e;
 }
-static inline int normsum_threads(int B) { return B > 512 ? 1024 : B > 256 ? 512 : 256; }
 
 extern "C" const char* ccsd_last_error(void) { return g_last_error.c_str(); }
 
@@ -554,6 +560,8 @@ struct Workspace {
     unsigned char *mfr, *mfl;       // flag masks of every complex as byte tables (k_masktab): [B][Kp], [B][Ep]
     int Kp, Ep;
     float *H, *P0, *P1, *U1, *acoef, *net_x, *net_adj, *net_r, *norm2, *part, *sums, *chan, *zpart, *part2;
+    float* partb;                   // folded norm sums (Route::fold_sums): the second [B][2] buffer of k_r2's partials -- step parity picks w.part or this
+                                    // one; it is part2, which the folding loop does not use otherwise (the workspace does not grow)
     float* psplit; size_t psplit_floats;   // K slices of the layer-1 projection (k_gemm_p with few row tiles)
     float *P0b, *P1b, *U1b;         // second set of hodge projections (merged k_r2 launch: the next norms pass's)
     int ntiles, nchunk;
@@ -625,6 +633,7 @@ static Workspace carve_ws(const ccsd_plan* pl, int B, void* base) {
       w.part = (float*)take((size_t)B * (np ? np : 1) * 2 * 4); }
     w.zpart = (float*)take((size_t)B * ((size_t)w.nchunk > E ? (size_t)w.nchunk : E ? E : 1) * 4);   // chunk partials of k_noise_norm, or the row partials of P0Fuse mode 1
     w.part2 = (float*)take((size_t)B * 2 * 4);
+    w.partb = w.part2;          // (k_normpart's output: never launched on a pass k_r2 serves, and a folding loop has no other)
     w.sums = (float*)take(64);
     w.chan = (float*)take(p.chan_global ? (size_t)B * p.chan_rows * p.N * p.N * 4 : 0);
     if (pl->rt.lg) {
@@ -778,8 +787,12 @@ static int hodge_stack_layer(const ccsd_plan* pl, int B, int l, Workspace& w, vo
     LAUNCH_CHECK();
     return CCSD_OK;
 }
+// The partial buffers of a loop step with folded norm sums (Route::fold_sums; part_in == nullptr: no fold, w.part throughout):
+// part_in holds this step's rank-2 partials, part_next takes the next step's.
+struct SumFold { const float* part_in = nullptr; float* part_next = nullptr; };
 static int launch_r2(const ccsd_plan* pl, int B, const float* rank2, const float* adj, const float* flags, int want_p,
-                     RankEpi& ep, NoiseArgs& na, Pass& ps, Workspace& w, void* stream, const CorrFuse* cf, int merge_draw);
+                     RankEpi& ep, NoiseArgs& na, Pass& ps, Workspace& w, void* stream, const CorrFuse* cf, int merge_draw,
+                     const SumFold* fold = nullptr);
 // hodge projections for ScoreNetworkA_CC from (adj, rank2)
 // fuse (tiled path, h_L == 1; Route::tiled_fuse): the Langevin corrector's element-wise work on rank2 rides on the layer-0 projection
 // pass -- mode 1: the noise norm of the corrector's draw per row (-> fuse->zrow), mode 2: the corrector apply (corrected rank2 -> fuse->f1,
@@ -1119,18 +1132,22 @@ static int launch_ew1(const ccsd_plan* pl, int B, const float* rank2, RankEpi& e
 }
 
 // merge_draw >= 0: merged launch -- after this (predictor) pass the kernel runs the NEXT corrector's norms pass on the new block
-// (draw index merge_draw; raw score -> w.net_r, partials -> w.part, projections -> the second buffer set)
+// (draw index merge_draw; raw score -> w.net_r, partials -> w.part or fold->part_next, projections -> the second buffer set)
+// fold: the step's partial buffers when the launch reduces the batch norm sums itself (SumFold; launches with the fused apply only)
 static int launch_r2(const ccsd_plan* pl, int B, const float* rank2, const float* adj, const float* flags, int want_p,
-                     RankEpi& ep, NoiseArgs& na, Pass& ps, Workspace& w, void* stream, const CorrFuse* cf = nullptr, int merge_draw = -1) {
+                     RankEpi& ep, NoiseArgs& na, Pass& ps, Workspace& w, void* stream, const CorrFuse* cf = nullptr, int merge_draw = -1,
+                     const SumFold* fold) {
     const Route& rt = pl->rt;
     R2Args ra{};
     if (cf) ra.cf = *cf;
     // launches of the sampler loop that carry the fused corrector apply work on states this library produced: masked (R2Args::masked)
     ra.masked = (cf && cf->on) ? 1 : 0;
+    const bool folded = fold && fold->part_in && cf && cf->on;
     if (merge_draw >= 0) {
         ra.merge = 1; ra.draw_r2 = (unsigned)merge_draw;
-        ra.P0b = w.P0b; ra.P1b = w.P1b; ra.U1b = w.U1b; ra.net2 = w.net_r; ra.part2 = w.part;
+        ra.P0b = w.P0b; ra.P1b = w.P1b; ra.U1b = w.U1b; ra.net2 = w.net_r; ra.part2 = folded ? fold->part_next : w.part;
     }
+    if (folded) { ra.fold = 1; ra.part_in = fold->part_in; ra.norm2 = w.norm2; ra.sums_out = w.sums; }
     ra.rank2 = rank2; ra.adj = adj; ra.flags = flags; ra.offbits = w.offbits; ra.P0 = w.P0; ra.P1 = w.P1; ra.U1 = w.U1; ra.want_p = want_p;
     ra.ldk = rt.r2_ldk; ra.ldh = rt.r2_ldh; ra.dbg = pl->dbg; ra.wp = pl->wp;
     if (want_p && pl->h.h_L > 1) ps.p1_raw = r2_p1_raw(pl->h);
@@ -1302,6 +1319,8 @@ extern "C" int ccsd_plan_query(const ccsd_plan_t* pl, int32_t what, int64_t* val
         case CCSD_QUERY_XA_LDS_BYTES: *value = (int64_t)pl->h.xa_lds_floats * 4; break;
         case CCSD_QUERY_FUSED_LOOP: *value = r.loop == LOOP_LANGEVIN_FUSED; break;
         case CCSD_QUERY_MERGED_R2: *value = r.merged; break;
+        case CCSD_QUERY_FOLD_SUMS: *value = r.fold_sums; break;
+        case CCSD_QUERY_FOLD_LAST_RUN: *value = pl->last_run_folded; break;
         case CCSD_QUERY_EW1: *value = r.r2_family == R2_EW1; break;
         case CCSD_QUERY_LARGE_GRAPH: *value = r.lg; break;
         case CCSD_QUERY_R2_FAMILY: *value = r.r2_family; break;
@@ -1333,7 +1352,7 @@ extern "C" int ccsd_plan_query(const ccsd_plan_t* pl, int32_t what, int64_t* val
 // produced by the merged k_r2 launch of the previous predictor half-step
 static int corrector_norms(ccsd_plan* pl, int B, int step, int it, const ccsd_state_t* base, const ccsd_state_t* cur,
                            const float* flags, const ccsd_noise_t* noise, uint64_t seed, int64_t off, float* sums,
-                           Workspace& w, void* stream, bool keep_net = true, bool r2_done = false) {
+                           Workspace& w, void* stream, bool keep_net = true, bool r2_done = false, const SumFold* fold = nullptr) {
     const PlanD& p = pl->h;
     int st = CCSD_OK;
     NoiseArgs na = make_noise(noise, seed, off, draw_base(pl, step, it), pl->rt.corrector_flat);
@@ -1351,6 +1370,10 @@ static int corrector_norms(ccsd_plan* pl, int B, int step, int it, const ccsd_st
     // ... NR_TILED with one hodge layer: the noise norm of the corrector's draw rides on the projection pass (P0Fuse mode 1), no k_noise_norm
     const bool z_rides = form == NR_TILED && rt.tiled_fuse && own_draw;
     RankEpi ep = norms_epi(w);
+    // folded norm sums (the fused loop of k_r2 plans, form NR_R2 always): k_r2's partials go to the step's buffer and the predictor's k_r2
+    // launch reduces them, with norm2, itself -- no k_normsum below, `sums` is written by that launch
+    const bool folded = fold && fold->part_in;
+    if (folded) ep.part = const_cast<float*>(fold->part_in);
     P0Fuse pf{};
     int ntiles = w.ntiles;       // partials per sample in w.part
     switch (form) {
@@ -1405,6 +1428,7 @@ static int corrector_norms(ccsd_plan* pl, int B, int step, int it, const ccsd_st
             part = w.part2; ntiles = 1;
         }
     }
+    if (folded) return form == NR_R2 ? CCSD_OK : set_err(CCSD_ERR_RUNTIME, "folded norm sums on a pass k_r2 does not serve");
     CCSD_LAUNCH(k_normsum, dim3(1), dim3(CCSD_NTHREADS == 1 ? 1 : normsum_threads(B)), 0, stream, (const float*)w.norm2, part, B, ntiles,
                 p.is_cc, sums);
     LAUNCH_CHECK();
@@ -1427,7 +1451,7 @@ static int corrector_apply(ccsd_plan* pl, int B, int step, int it, const ccsd_st
 }
 static int predictor(ccsd_plan* pl, int B, int step, const ccsd_state_t* in, const float* flags, const ccsd_noise_t* noise,
                      uint64_t seed, int64_t off, ccsd_state_t* out, ccsd_state_t* mean, Workspace& w, void* stream,
-                     const float* fuse_sums = nullptr, bool merge_next = false) {
+                     const float* fuse_sums = nullptr, bool merge_next = false, const SumFold* fold = nullptr) {
     const PlanD& p = pl->h;
     int st = CCSD_OK;
     NoiseArgs na = make_noise(noise, seed, off, draw_base(pl, step, pl->cfg.n_corr_steps), pl->rt.predictor_flat);
@@ -1454,7 +1478,7 @@ static int predictor(ccsd_plan* pl, int B, int step, const ccsd_state_t* in, con
     const int md = merge_next ? (int)draw_base(pl, step + 1, 0) + 2 : -1;
     switch (form) {
     case PR_R2:
-        if ((st = launch_r2(pl, B, in->rank2, in->adj, flags, 1, ep, na, ps, w, stream, &cf, md))) return st;
+        if ((st = launch_r2(pl, B, in->rank2, in->adj, flags, 1, ep, na, ps, w, stream, &cf, md, fold))) return st;
         break;
     case PR_EW1_ONEPASS:    // k_ew1 plans, one hodge layer: corrector apply + projection + predictor update in ONE pass over rank2
         pf = p0_fuse(pl, 4, na, cf.draw_r, w);
@@ -1572,7 +1596,8 @@ extern "C" int ccsd_s4_apply(ccsd_plan_t* pl, int32_t B, int32_t step, const ccs
 }
 
 // The library loop; ccsd_sampler_run is this call without options.  The reduce hook is called once per norms pass, after its k_normsum
-// has been enqueued and before any reader of w.sums is: the launches are the same with and without it.
+// has been enqueued and before any reader of w.sums is: the launches are the same with and without it -- except on plans with folded
+// norm sums (Route::fold_sums), which drop the k_normsum launches only when there is no hook.
 extern "C" int ccsd_sampler_run_ex(ccsd_plan_t* pl, int32_t B, const float* flags, uint64_t seed, int64_t sample_offset,
                                    int32_t first_step, int32_t last_step, ccsd_state_t* state, ccsd_state_t* scratch,
                                    ccsd_state_t* result, float* traj, void* workspace, size_t ws_bytes, void* stream,
@@ -1586,6 +1611,8 @@ extern "C" int ccsd_sampler_run_ex(ccsd_plan_t* pl, int32_t B, const float* flag
     const PlanD& p = pl->h;
     if ((st = launch_flagbits(pl, B, flags, w, stream))) return st;
     const size_t nx = (size_t)p.N * p.F, na = (size_t)p.N * p.N, nr = p.is_cc ? (size_t)p.E * p.K : 0;
+    const bool folded = rt.fold_sums && !(options && options->reduce);
+    pl->last_run_folded = folded;
     ccsd_state_t a = *state, b = *scratch;   // a = live buffer
     // exact multi-GPU mode: the caller all-reduces the six sums in place, ordered on `stream`
 #define REDUCE_SUMS() do { if (options && options->reduce && options->reduce(w.sums, 6, stream, options->user)) \
@@ -1604,13 +1631,18 @@ extern "C" int ccsd_sampler_run_ex(ccsd_plan_t* pl, int32_t B, const float* flag
             // k_r2 also runs the rank-2 side of the next step's norms pass on the block it has just produced (r2_done below)
             const bool r2_done = rt.merged && step > first_step;
             const bool merge_next = rt.merged && !lastone;
-            if ((st = corrector_norms(pl, B, step, 0, &a, &a, flags, nullptr, seed, sample_offset, w.sums, w, stream, /*keep_net=*/rt.r2_family == R2_FUSED, r2_done))) return st;
+            // folded norm sums: no k_normsum launch -- the predictor's k_r2 reduces this step's partials (one of two buffers, by the
+            // parity of the step within the call: its merged pass writes the next step's into the other) and norm2, and leaves w.sums
+            // for the k_xa launch behind it.  A reduce hook needs the sums between two launches: today's launches then
+            SumFold sf;
+            if (folded) { const int par = (step - first_step) & 1; sf.part_in = par ? w.partb : w.part; sf.part_next = par ? w.part : w.partb; }
+            if ((st = corrector_norms(pl, B, step, 0, &a, &a, flags, nullptr, seed, sample_offset, w.sums, w, stream, /*keep_net=*/rt.r2_family == R2_FUSED, r2_done, &sf))) return st;
             REDUCE_SUMS();
             // u_1 = fr . Wcat_1 depends on the flags alone: the run's first (general) k_r2 launch has just written it; the masked launches
             // of the loop leave both copies alone (R2Args::masked), so the second buffer set gets its copy once
             if (rt.merged && !r2_done && r2_p1_raw(p))
                 RT_CHECK(rt_d2d_async(w.U1b, w.U1, (size_t)B * p.h_pw * 4, stream));
-            if ((st = predictor(pl, B, step, &a, flags, nullptr, seed, sample_offset, &b, want_mean ? result : nullptr, w, stream, w.sums, merge_next))) return st;
+            if ((st = predictor(pl, B, step, &a, flags, nullptr, seed, sample_offset, &b, want_mean ? result : nullptr, w, stream, w.sums, merge_next, &sf))) return st;
             ccsd_state_t t = a; a = b; b = t;
         } else if (rt.loop == LOOP_LANGEVIN || (rt.loop == LOOP_LANGEVIN_MULTI && pl->cfg.n_corr_steps > 0)) {
             // a = base -> (corrector 0) -> b -> (corrector 1) -> third -> (corrector 2) -> b ... -> (predictor) -> a.  Every inner

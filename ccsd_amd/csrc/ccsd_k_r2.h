@@ -25,6 +25,14 @@ struct R2Args {
     unsigned int draw_r2;  // the next step's corrector draw (flat groups)
     float* P0b; float* P1b; float* U1b;
     float* net2; float* part2;
+    // Folded batch norm sums (ccsd_sampler_run's fused loop, launches with cf.on; Route::fold_sums): no k_normsum launch ahead of this
+    // one.  EVERY workgroup reduces the rank-2 partial pairs part_in[B][2] of the previous k_r2 launch (normsum_waves: k_normsum's
+    // order, so its bits) and takes its rank-2 Langevin coefficients from its own two sums; workgroup 0 also reduces norm2[B][4] of the
+    // k_xa norms launch in between and stores all six to sums_out, where the k_xa launch after this one reads them.  part_in is never
+    // the buffer pass 1 of this launch writes (part2): the host alternates two by step parity, because with more complexes than
+    // resident workgroups a late workgroup would otherwise reduce partials an early one has already replaced.
+    int fold;
+    const float* part_in; const float* norm2; float* sums_out;
     int ldk, ldh;
     long long* dbg;
     const float* wp;       // packed buffer (Wcat^T of the hodge projections)
@@ -95,13 +103,22 @@ __global__ __launch_bounds__(512, 4) void k_r2(const PlanD* __restrict__ plan, c
     // mask tables, zero padding of the K tail, adjacency of the general mlp_value path; ends with the barrier that publishes them
     // (`between`: called after the tables' own global loads are requested and before they are used -- the block load puts its first
     // batch there, so that the in-order return of vector loads delivers the few table bytes first)
+    // folded batch norm sums (R2Args::fold).  Every workgroup: the rank-2 partial pairs are requested first of all, reduced once the
+    // other requests are out, and handed over in sRed (free until the kernel's last block_sums) by the tables' barrier.  Workgroup 0's
+    // four x / adj sums are off every other workgroup's path and wait until the block is loaded (below, in sRow, which nothing else uses)
+    const bool fold = ra.cf.on && ra.fold, fold_xa = fold && b == 0;
+    const int fB = (int)gridDim.x, fnv = normsum_threads(fB);
+    float c1f = 0.f, c2f = 0.f;                               // the rank-2 Langevin coefficients of the fused corrector apply
     auto build_tables = [&](auto&& between) {
         unsigned long long cw[2];
         unsigned int ew = 0;
+        NormsumPre fpre[2];                                   // (512 threads: the 16 virtual waves of B > 512 are two per wave)
+        if (fold) normsum_request<2>(fpre, nullptr, ra.part_in, fB, 1, false, true);
 #pragma unroll
         for (int u = 0; u < 2; ++u) { const int k = tid + u * nth; cw[u] = cells[k < K ? k : K - 1]; }
         if (tid < 64) ew = *reinterpret_cast<const unsigned short*>(edges + 2 * (tid < E ? tid : E - 1));
         between();
+        if (fold) normsum_waves<2>(fpre, nullptr, ra.part_in, fB, 1, fnv, false, true, nullptr, sRed);
 #pragma unroll
         for (int u = 0; u < 2; ++u) { const int k = tid + u * nth; if (k < Kp4) sFrb[k] = (k < K && !(cw[u] & off)) ? 1 : 0; }
         for (int k = tid + 2 * nth; k < Kp4; k += nth) sFrb[k] = (k < K && !(cells[k] & off)) ? 1 : 0;
@@ -124,6 +141,12 @@ __global__ __launch_bounds__(512, 4) void k_r2(const PlanD* __restrict__ plan, c
             }
         }
         __syncthreads();
+        if (fold) {   // langevin_coef over the workgroup's own two sums
+            const float fs[6] = {0.f, 0.f, normsum_total(sRed, fnv), 0.f, 0.f, normsum_total(sRed + 16, fnv)};
+            LangCoef lf = ra.cf.lc;
+            lf.sums = fs;
+            langevin_coef(lf, 2, &c1f, &c2f);
+        }
         stamp(ra.dbg, 8);
     };
     // The block load.  The Langevin corrector's rank2 draw is keyed by FLAT groups of four consecutive elements (NoiseArgs::flat_r)
@@ -137,8 +160,7 @@ __global__ __launch_bounds__(512, 4) void k_r2(const PlanD* __restrict__ plan, c
     // multiple of 4) a group is two aligned pairs (e, k..k+1), (e', k'..k'+1): masks and LDS stores go pair-wise.
     float s_net = 0.f, s_z = 0.f;
     {
-        float c1f = 0.f, c2f = 0.f;
-        if (ra.cf.on) langevin_coef(ra.cf.lc, 2, &c1f, &c2f);
+        if (ra.cf.on && !fold) langevin_coef(ra.cf.lc, 2, &c1f, &c2f);     // (fold: build_tables sets them, behind its barrier)
         NoiseArgs nc = na;                                   // the corrector draw of this launch
         if (ra.cf.on) { nc.zr = nullptr; nc.draw_r = ra.cf.draw_r; }
         const bool znorm = ep.mode == MODE_NORMS && na.flat_r, zuse = znorm || ra.cf.on;
@@ -263,7 +285,10 @@ __global__ __launch_bounds__(512, 4) void k_r2(const PlanD* __restrict__ plan, c
             __syncthreads();
         }
     }
+    if (fold_xa) normsum_waves<0>(nullptr, ra.norm2, nullptr, fB, 1, fnv, true, false, sRow, nullptr);
     __syncthreads();
+    if (fold_xa)      // all six sums to where the k_xa launch behind this one reads them
+        for (int i = tid; i < 6; i += nth) ra.sums_out[i] = normsum_sum_of(sRow, sRed, i, fnv, true);
     // ---- one pass = phase 1 + phase 2 over the LDS-resident block.  A merged launch (ra.merge) makes two: pass 0 the predictor
     // half-step (its epilogue writes the new rank2 to HBM AND back into the block), pass 1 the next corrector's norms pass on it.
     const int npass = ra.merge ? 2 : 1;

@@ -12,43 +12,12 @@ __global__ void k_normsum(const float* __restrict__ norm2, const float* __restri
     // up to 1024 threads: one sample per thread and one L2 round trip for B <= 1024; the six sums are reduced together (wave
     // butterflies, one barrier, a fixed-order pass over the waves) -- the launch sits between the norms pass and the predictor
     // kernels of every PC step, so its latency is on the step's critical path.  (Many tiles per sample: k_normpart first.)
-    __shared__ float red[16 * 6];
-    float acc[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-    for (int b = threadIdx.x; b < B; b += blockDim.x) {
-        const float4 n4 = *reinterpret_cast<const float4*>(norm2 + (size_t)b * 4);
-        acc[0] += sqrtf(n4.x);
-        acc[1] += sqrtf(n4.y);
-        acc[3] += sqrtf(n4.z);
-        acc[4] += sqrtf(n4.w);
-        if (is_cc) {
-            float sn = 0.f, sz = 0.f;
-            for (int t = 0; t < ntiles; ++t) {
-                const float* p2 = part + ((size_t)b * ntiles + t) * 2;
-                sn += p2[0];
-                sz += p2[1];
-            }
-            acc[2] += sqrtf(sn);
-            acc[5] += sqrtf(sz);
-        }
-    }
-#ifdef CCSD_EMU
-    for (int i = 0; i < 6; ++i) sums[i] = acc[i];
-#else
-    const int wave = wave_index(), lane = threadIdx.x & 63, nw = (blockDim.x + 63) >> 6;
-#pragma unroll
-    for (int i = 0; i < 6; ++i) {
-        float v = acc[i];
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-        if (lane == 0) red[wave * 6 + i] = v;
-    }
+    // The order itself is stated once, in normsum_waves (ccsd_rank2_common.h): here the virtual threads are the real ones.
+    __shared__ float red[6 * 16];            // rows 0..3: the x / adj quantities (sums 0, 1, 3, 4); rows 4, 5: the rank-2 ones (sums 2, 5)
+    const int nv = blockDim.x;
+    normsum_waves<0>(nullptr, norm2, part, B, ntiles, nv, true, is_cc != 0, red, red + 64);
     __syncthreads();
-    if (threadIdx.x < 6) {
-        float t = 0.f;
-        for (int w = 0; w < nw; ++w) t += red[w * 6 + threadIdx.x];
-        sums[threadIdx.x] = t;
-    }
-#endif
+    for (int i = threadIdx.x; i < 6; i += blockDim.x) sums[i] = normsum_sum_of(red, red + 64, i, nv, is_cc != 0);
 }
 
 // k_normpart: first level of the norm reduction when a sample has many partials (tiled rank-2 path: one pair per 64 x 64 tile of

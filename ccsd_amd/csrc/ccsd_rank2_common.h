@@ -256,6 +256,120 @@ CCSD_DEV void langevin_coef(const LangCoef& lc, int t, float* c1, float* c2) {
     *c1 = step * lc.ss[t];
     *c2 = sqrtf(step * 2.f) * lc.seps;
 }
+
+// ---------------------------------------------------------------------------------------------
+// The batch norm reduction: the ONLY statement of k_normsum's summation order (k_normsum runs it as a launch; k_r2 folds it into the
+// predictor launches of the fused loop, R2Args::fold).  The order is that of a workgroup of nv = normsum_threads(B) VIRTUAL threads,
+// whatever the size (a multiple of 64) of the workgroup that runs it:
+//   virtual thread v adds sqrt(.) of samples v, v + nv, ... to 0, one after the other;
+//   virtual wave v >> 6 sums its 64 threads with the six-step xor butterfly (32, 16, .., 1);
+//   the wave results go to LDS in virtual-wave order (red[quantity][16]) and, behind ONE barrier of the caller's, normsum_total adds
+//   them to 0 from wave 0 up.
+// A real wave takes the virtual waves wave, wave + nw, ... in turn.  xa: the four x / adj quantities of norm2[b][4] (sums 0, 1, 3, 4 ->
+// red_xa rows 0..3); r2: the two rank-2 quantities of part[b][ntiles][2] (sums 2, 5 -> red_r2 rows 0, 1); both wave-uniform.
+// NPRE: the first sample of the first NPRE virtual waves of a real wave comes from `pre`, which normsum_request filled -- a caller
+// with other loads to issue puts them between the two calls, and the in-order return of vector loads delivers these few bytes first.
+// Host emulation (one thread): the plain loop over the samples, red[quantity][0] the sum.
+// ---------------------------------------------------------------------------------------------
+static inline __host__ __device__ int normsum_threads(int B) { return B > 512 ? 1024 : B > 256 ? 512 : 256; }
+struct NormsumPre { float4 n4; float2 p2; };
+template <int NPRE>
+CCSD_DEV void normsum_request(NormsumPre* pre, const float* __restrict__ norm2, const float* __restrict__ part, int B, int ntiles,
+                              bool xa, bool r2) {
+#ifdef CCSD_EMU
+    (void)pre; (void)norm2; (void)part; (void)B; (void)ntiles; (void)xa; (void)r2;
+#else
+    const int wave = wave_index(), lane = threadIdx.x & 63, nw = blockDim.x >> 6;
+#pragma unroll
+    for (int u = 0; u < NPRE; ++u) {
+        const int v = (wave + u * nw) * 64 + lane, b = v < B ? v : B - 1;       // (clamped: a valid address, used only for v < B)
+        pre[u].n4 = make_float4(0.f, 0.f, 0.f, 0.f);
+        pre[u].p2 = make_float2(0.f, 0.f);
+        if (xa) pre[u].n4 = *reinterpret_cast<const float4*>(norm2 + (size_t)b * 4);
+        if (r2) pre[u].p2 = *reinterpret_cast<const float2*>(part + (size_t)b * ntiles * 2);
+    }
+#endif
+}
+template <int NPRE>
+CCSD_DEV void normsum_waves(const NormsumPre* pre, const float* __restrict__ norm2, const float* __restrict__ part, int B, int ntiles,
+                            int nv, bool xa, bool r2, float* red_xa, float* red_r2) {
+    float acc[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+    auto add = [&](const float4& n4, const float2& p2, int b) {
+        if (xa) {
+            acc[0] += sqrtf(n4.x);
+            acc[1] += sqrtf(n4.y);
+            acc[3] += sqrtf(n4.z);
+            acc[4] += sqrtf(n4.w);
+        }
+        if (r2) {
+            float sn = 0.f, sz = 0.f;
+            sn += p2.x;
+            sz += p2.y;
+            for (int t = 1; t < ntiles; ++t) {
+                const float* q2 = part + ((size_t)b * ntiles + t) * 2;
+                sn += q2[0];
+                sz += q2[1];
+            }
+            acc[2] += sqrtf(sn);
+            acc[5] += sqrtf(sz);
+        }
+    };
+    auto fetch = [&](int b) {
+        NormsumPre s;
+        s.n4 = make_float4(0.f, 0.f, 0.f, 0.f);
+        s.p2 = make_float2(0.f, 0.f);
+        if (xa) s.n4 = *reinterpret_cast<const float4*>(norm2 + (size_t)b * 4);
+        if (r2) s.p2 = *reinterpret_cast<const float2*>(part + (size_t)b * ntiles * 2);
+        return s;
+    };
+#ifdef CCSD_EMU
+    (void)pre; (void)nv;
+    for (int b = 0; b < B; ++b) { const NormsumPre s = fetch(b); add(s.n4, s.p2, b); }
+    if (xa) { red_xa[0] = acc[0]; red_xa[16] = acc[1]; red_xa[32] = acc[3]; red_xa[48] = acc[4]; }
+    if (r2) { red_r2[0] = acc[2]; red_r2[16] = acc[5]; }
+#else
+    const int wave = wave_index(), lane = threadIdx.x & 63, nw = blockDim.x >> 6, nvw = nv >> 6;
+    auto one_wave = [&](int vw, const NormsumPre* first) {
+#pragma unroll
+        for (int i = 0; i < 6; ++i) acc[i] = 0.f;
+        // (one `add` in the text of the loop: the sample of the next turn is loaded at the end of this one)
+        int b = vw * 64 + lane;
+        NormsumPre s = first ? *first : fetch(b < B ? b : B - 1);
+        while (b < B) {
+            add(s.n4, s.p2, b);
+            b += nv;
+            if (b < B) s = fetch(b);
+        }
+        auto wave_sum = [&](float v, float* dst) {
+#pragma unroll
+            for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+            if (lane == 0) dst[vw] = v;
+        };
+        if (xa) { wave_sum(acc[0], red_xa); wave_sum(acc[1], red_xa + 16); wave_sum(acc[3], red_xa + 32); wave_sum(acc[4], red_xa + 48); }
+        if (r2) { wave_sum(acc[2], red_r2); wave_sum(acc[5], red_r2 + 16); }
+    };
+#pragma unroll
+    for (int u = 0; u < NPRE; ++u)
+        if (wave + u * nw < nvw) one_wave(wave + u * nw, pre + u);
+    for (int vw = wave + NPRE * nw; vw < nvw; vw += nw) one_wave(vw, nullptr);
+#endif
+}
+// one quantity's sum from its row of 16 wave results (behind the barrier that follows normsum_waves); the same value in every thread
+CCSD_DEV float normsum_total(const float* red16, int nv) {
+#ifdef CCSD_EMU
+    (void)nv;
+    return red16[0];
+#else
+    float t = 0.f;
+    for (int w = 0; w < (nv >> 6); ++w) t += red16[w];
+    return t;
+#endif
+}
+// sums[i], i = 0..5, from the two row sets (r2 false: the rank-2 sums are zero, as sums of nothing)
+CCSD_DEV float normsum_sum_of(const float* red_xa, const float* red_r2, int i, int nv, bool r2) {
+    if (i == 2 || i == 5) return r2 ? normsum_total(red_r2 + (i == 5 ? 16 : 0), nv) : 0.f;
+    return normsum_total(red_xa + 16 * (i - (i > 2 ? 1 : 0)), nv);
+}
 // corrector apply: v_mean = v + step*score; v = v_mean + sqrt(2 step) * z * scale_eps, zz = the masked draw (solver.py:781-783, 797-801)
 CCSD_DEV float corr_apply(float c1, float c2, float net, float v, float zz) { return fmaf(c2, zz, fmaf(c1, net, v)); }
 // predictor update: v_mean = pa*v + pb*net; v = v_mean + pc * z, zz = the masked draw (solver.py:429-457)

@@ -143,7 +143,8 @@ class PCEngine(SampleOps):
         """Which kernels the plan selected (ccsd_plan_query): "fused_r2", "xa_variant", "r2_lds_bytes", "xa_lds_bytes", "fused_loop", "merged_r2", "ew1", "large_graph";
         the rest of the route: "r2_family", "r2_instance", "loop_form", "tiled_fuse", "ew1_fuse", "h_general", "geo_ek", "p0_narrow" and, for the
         plan's batch_hint, "h_full", "hp_full"; "h_wide"; "mlp_forms": x_fin chain + 16 * a_fin chain + 256 * (bit l: AttentionLayer l's edge
-        MLP is chained), 0 meaning the un-chained block-wise Linear form (include/ccsd_hip.h: CCSD_QUERY_*)."""
+        MLP is chained), 0 meaning the un-chained block-wise Linear form; "fold_sums": the fused loop's k_r2 reduces the batch norm sums itself
+        (no k_normsum launch), "fold_last_run": the latest run call did so (not with a reduce hook) (include/ccsd_hip.h: CCSD_QUERY_*)."""
         v = C.c_int64(0)
         self.lib.check(self.lib.ccsd_plan_query(self.handle, _lib.QUERIES[what], C.byref(v)))
         return v.value

@@ -215,6 +215,10 @@ enum {
     CCSD_QUERY_H_GENERAL = 16,    /* 1: general hodge stack (R_l materialised layer by layer) */
     CCSD_QUERY_GEO_EK = 17,       /* general-path kernels: 0 run-time (E, K); 1 community_small, 2 zinc250k, 3 ENZYMES_small compiled in */
     CCSD_QUERY_H_WIDE = 18,       /* 1: ScoreNetworkA_CC hodge MLPs wider than 8 (16-wide kernels of the tiled route and the tiled rank-2 family) */
+    CCSD_QUERY_FOLD_SUMS = 20,    /* 1: fused loop of a k_r2 plan, and the predictor's k_r2 launch reduces the batch norm sums itself: ccsd_sampler_run
+                                     launches no k_normsum (three launches per PC step with merged k_r2).  A call of ccsd_sampler_run_ex with a reduce
+                                     hook keeps the k_normsum launches; CCSD_NO_SUM_FOLD at plan creation turns the fold off */
+    CCSD_QUERY_FOLD_LAST_RUN = 21, /* 1: the plan's latest ccsd_sampler_run[_ex] call ran with the folded sums (0: with k_normsum launches, or no call yet) */
     CCSD_QUERY_MLP_FORMS = 19     /* the form of the graph networks' MLPs: x_fin + 16 * a_fin + 256 * edge_mask.  x_fin / a_fin: the register-resident chain
                                      shape of ScoreNetworkX's / ScoreNetworkA's final MLP (1 .. 7; 0: un-chained, the block-wise Linear form) on the route the
                                      plan takes -- on the tiled route the shape of k_lg_fin_w (7) where that kernel runs the final MLP; bit l of edge_mask: the
@@ -285,8 +289,9 @@ typedef struct {
     ccsd_reduce_fn reduce;   /* NULL: no hook */
     void* user;              /* handed to the hook */
 } ccsd_run_options_t;
-/* ccsd_sampler_run with options (NULL options or a NULL hook: exactly ccsd_sampler_run -- the same launches in number, order and
- * arguments, with and without a hook). */
+/* ccsd_sampler_run with options (NULL options or a NULL hook: exactly ccsd_sampler_run).  With a hook the launches are the same in
+ * number, order and arguments too, except on plans that fold the norm sums into k_r2 (CCSD_QUERY_FOLD_SUMS): there a hooked call
+ * launches k_normsum ahead of the hook, as CCSD_NO_SUM_FOLD would; the results are bit-identical either way. */
 int ccsd_sampler_run_ex(ccsd_plan_t* plan, int32_t B, const float* flags_dev, uint64_t seed, int64_t sample_offset,
                         int32_t first_step, int32_t last_step, ccsd_state_t* state, ccsd_state_t* scratch,
                         ccsd_state_t* result, float* traj_dev, void* workspace, size_t workspace_bytes, void* stream,
