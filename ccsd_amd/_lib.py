@@ -29,6 +29,7 @@ EXPORTS = [
     "ccsd_eig_workspace_bytes", "ccsd_eigvalsh", "ccsd_spectral_workspace_bytes", "ccsd_spectral_hist",
     "ccsd_hodge_workspace_bytes", "ccsd_hodge_spectrum",
     "ccsd_nspdk_row_capacity", "ccsd_nspdk_workspace_bytes", "ccsd_nspdk_features", "ccsd_nspdk_mmd_workspace_bytes", "ccsd_nspdk_mmd",
+    "ccsd_lift",
 ]
 QUERIES = {"fused_r2": 0, "xa_variant": 1, "r2_lds_bytes": 2, "xa_lds_bytes": 3, "fused_loop": 4, "merged_r2": 5, "ew1": 6, "large_graph": 7,
            "r2_family": 8, "r2_instance": 9, "loop_form": 10, "h_full": 11, "hp_full": 12, "p0_narrow": 13, "tiled_fuse": 14, "ew1_fuse": 15,
@@ -71,6 +72,7 @@ MMD_IS_HIST, MMD_DEGREE, MMD_F32_PMF = 1, 2, 4
 CLUSTER_MAX_BINS, MMD_MAX_ROWS, MMD_MAX_BINS = 1024, 1 << 20, 1 << 16      # CCSD_CLUSTER_MAX_BINS, CCSD_MMD_MAX_ROWS, CCSD_MMD_MAX_BINS
 ORBITS = 15                                                               # CCSD_ORBITS: ORCA's orbits of the graphlets on 2..4 nodes
 NSPDK_MAX_NODES, NSPDK_FEATURES = 64, 65537                               # CCSD_NSPDK_MAX_NODES, CCSD_NSPDK_FEATURES
+LIFT_PATHS, LIFT_CYCLES, LIFT_MAX_NODES = 0, 1, 64                         # CCSD_LIFT_PATHS, CCSD_LIFT_CYCLES; the node limit of ccsd_lift
 EIG_MAXN, EIG_MAX_SWEEPS = 512, 30                                        # CCSD_EIG_MAXN; the sweep cap of k_eigvalsh
 
 
@@ -202,6 +204,8 @@ class Library:
         L.ccsd_nspdk_mmd_workspace_bytes.restype = sz
         L.ccsd_nspdk_mmd.argtypes = [vp, vp, vp, i32, vp, vp, vp, i32, vp, sz, vp, vp]
         L.ccsd_nspdk_mmd.restype = C.c_int
+        L.ccsd_lift.argtypes = [vp, i32, i32, i32, f32, i32, i32, u64, i32, i32, vp, vp, vp, vp, vp, vp, vp]
+        L.ccsd_lift.restype = C.c_int
 
     def __getattr__(self, name):
         return getattr(self.c, name)

@@ -1,6 +1,6 @@
 // ccsd_api_samples.h -- host side of the PLAN-FREE entry points of include/ccsd_hip.h: the operations on finished samples, which take
 // tensors and sizes and never a ccsd_plan_t (ccsd_quantize, ccsd_rank2_cells, ccsd_finish, ccsd_cluster_hist, ccsd_orbit_counts, ccsd_nspdk_features, ccsd_nspdk_mmd, ccsd_mmd, ccsd_eigvalsh,
-// ccsd_spectral_hist, ccsd_hodge_spectrum and their *_workspace_bytes).  Included by ccsd_api.h as its last line; of what stands above it
+// ccsd_spectral_hist, ccsd_hodge_spectrum, ccsd_lift and their *_workspace_bytes).  Included by ccsd_api.h as its last line; of what stands above it
 // there, this file uses set_err, grid_for, RT_CHECK and LAUNCH_CHECK only.
 //
 // One definition per rule: check_batch (B, N, the quantiser), check_hist (bins, edges), check_scratch (workspace), no_bytes, quant_thr,
@@ -452,4 +452,62 @@ extern "C" int ccsd_hodge_spectrum(const float* adj, const uint64_t* cell_bits, 
                 (int)d_max, (int)K, quant_thr(adj_mode, thr), H);
     LAUNCH_CHECK();
     return eig_launch(H, B, E, (long long)E * E, E, nullptr, (char*)workspace + hbytes, nullptr, spectrum, (int*)sweeps, nullptr, 0, nullptr, stream);
+}
+
+// ---------------- graphs lifted to combinatorial complexes (ccsd_k_lift.h) ----------------
+static_assert(CCSD_LIFT_MAXN == CCSD_NSPDK_MAX_NODES && CCSD_LIFT_MAXN <= CCSD_FIN_MAXBINS, "a row of the adjacency is one 64-bit mask; FinishTab holds every size");
+// ccsd_lift: convert_graphs_to_CCs (cc_utils.py:816-880) of every graph: k_lift_paths or k_lift_cycles, then k_lift_dense on request
+extern "C" int ccsd_lift(const float* adj, int32_t B, int32_t N, int32_t adj_mode, float thr, int32_t procedure, int32_t path_length,
+                         uint64_t sources_mask, int32_t d_min, int32_t d_max, uint64_t* cell_bits, int32_t* count, int32_t* cell_hist,
+                         int32_t* nnz, int32_t* dropped, float* rank2, void* stream) {
+    if (B == 0) return CCSD_OK;
+    if (int st = check_batch("ccsd_lift", B, N, adj_mode, thr, /*fin_n=*/false)) return st;
+    if (N < 2) return set_err(CCSD_ERR_INVALID, "ccsd_lift: N = " + std::to_string(N) + " must be >= 2");
+    if (N > CCSD_LIFT_MAXN)
+        return set_err(CCSD_ERR_UNSUPPORTED, "ccsd_lift: N = " + std::to_string(N) + " is above " + std::to_string(CCSD_LIFT_MAXN) +
+                                                 ": a row of the adjacency is one 64-bit mask and both liftings are operations on such masks");
+    if (procedure != CCSD_LIFT_PATHS && procedure != CCSD_LIFT_CYCLES)
+        return set_err(CCSD_ERR_INVALID, "ccsd_lift: unknown procedure " + std::to_string(procedure));
+    if (d_min < 1 || d_max < d_min || d_max > N)
+        return set_err(CCSD_ERR_INVALID, "ccsd_lift: bad cell sizes d_min = " + std::to_string(d_min) + ", d_max = " + std::to_string(d_max));
+    FinishTab tab;
+    memset(&tab, 0, sizeof tab);
+    const int64_t K64 = cell_count(N, d_min, d_max, tab.end);
+    if (K64 < 0) return set_err(CCSD_ERR_INVALID, "ccsd_lift: sum C(N, d) for d = d_min..d_max exceeds 2^24");
+    tab.nb = d_max - d_min + 1;
+    if (procedure == CCSD_LIFT_PATHS) {
+        if (path_length < 1) return set_err(CCSD_ERR_INVALID, "ccsd_lift: path_length = " + std::to_string(path_length) + " must be >= 1");
+        if (path_length != 3)
+            return set_err(CCSD_ERR_UNSUPPORTED, "ccsd_lift: path_length = " + std::to_string(path_length) +
+                                                     " is not built: the path rule is a closed form for paths of 3 nodes, the length every shipped config uses");
+        if (path_length < d_min || path_length > d_max)
+            return set_err(CCSD_ERR_INVALID, "ccsd_lift: path_length = " + std::to_string(path_length) + " outside d_min..d_max = " +
+                                                 std::to_string(d_min) + ".." + std::to_string(d_max) + ": its cells have no column");
+    }
+    if (!adj || !cell_bits || !count) return set_err(CCSD_ERR_INVALID, "ccsd_lift: NULL argument");
+    if ((uintptr_t)cell_bits & 7) return set_err(CCSD_ERR_INVALID, "ccsd_lift: cell_bits must be 8-byte aligned");
+    const int K = (int)K64, W = (K + 63) / 64, nb = tab.nb;
+    // the counters start from zero (one atomicAdd per workgroup of k_lift_paths; the walking lane of k_lift_cycles adds per cell)
+    RT_CHECK(rt_memset_async(count, 0, (size_t)B * 4, stream));
+    if (cell_hist) RT_CHECK(rt_memset_async(cell_hist, 0, (size_t)B * nb * 4, stream));
+    if (nnz) RT_CHECK(rt_memset_async(nnz, 0, (size_t)B * 4, stream));
+    if (dropped) RT_CHECK(rt_memset_async(dropped, 0, (size_t)B * 4, stream));
+    if (procedure == CCSD_LIFT_PATHS) {
+        const int bin3 = 3 - d_min, off3 = bin3 ? tab.end[bin3 - 1] : 0, C3 = tab.end[bin3] - off3;
+        CCSD_LAUNCH(k_lift_paths, dim3(B, (W + CCSD_LIFT_WPG - 1) / CCSD_LIFT_WPG), dim3(CCSD_NTHREADS), 0, stream, adj, (int)N,
+                    quant_thr(adj_mode, thr), (unsigned long long)sources_mask, W, off3, C3, nb, bin3, (unsigned long long*)cell_bits,
+                    (int*)count, (int*)cell_hist, (int*)nnz);
+    } else {
+        RT_CHECK(rt_memset_async(cell_bits, 0, (size_t)B * W * 8, stream));      // (the walk sets bits)
+        CCSD_LAUNCH(k_lift_cycles, dim3(B), dim3(CCSD_NTHREADS == 1 ? 1 : 64), 0, stream, adj, (int)N, quant_thr(adj_mode, thr), tab, (int)d_min,
+                    (int)d_max, W, (unsigned long long*)cell_bits, (int*)count, (int*)cell_hist, (int*)nnz, (int*)dropped);
+    }
+    LAUNCH_CHECK();
+    if (rank2) {
+        RT_CHECK(rt_memset_async(rank2, 0, (size_t)B * (N * (N - 1) / 2) * K * 4, stream));      // the zero fill: the ones are scattered onto it
+        CCSD_LAUNCH(k_lift_dense, dim3(B, (W + CCSD_LIFT_DENSE_WPG - 1) / CCSD_LIFT_DENSE_WPG), dim3(CCSD_NTHREADS), 0, stream, adj, (int)N,
+                    quant_thr(adj_mode, thr), tab, (int)d_min, K, W, (const unsigned long long*)cell_bits, rank2);
+        LAUNCH_CHECK();
+    }
+    return CCSD_OK;
 }

@@ -27,8 +27,10 @@
 //                    of two sets of such rows (the reference's "nspdk" score of molecule runs)
 //   ccsd_k_eig.h     k_eigvalsh, k_norm_laplacian, k_hodge_laplacian: a batched symmetric eigenvalue solver (parallel Jacobi) and the
 //                    two matrices whose spectra the reference scores (normalised graph Laplacian, hodge Laplacian F F^T)
+//   ccsd_k_lift.h    k_lift_paths, k_lift_cycles, k_lift_dense: graphs lifted to combinatorial complexes (rank-2 cells from the paths of
+//                    three nodes or from networkx's cycle basis) as ccsd_finish's cell bitmask and descriptors, and the dense incidence tensor
 //   ccsd_api.h       host side of the C ABI: plan, route, workspace, launchers, the sampler loop; its last line includes
-//   ccsd_api_samples.h   the host side of the plan-free entry points (ccsd_quantize .. ccsd_hodge_spectrum: operations on finished samples)
+//   ccsd_api_samples.h   the host side of the plan-free entry points (ccsd_quantize .. ccsd_lift: operations on finished samples)
 // The product library is built from several translation units compiled in parallel (ccsd_hip.hip: C ABI + the small kernels;
 // ccsd_r2*.hip / ccsd_xa.hip: the explicit instantiations of the two big kernel templates); the host emulation used by the
 // CPU tests includes everything in one unit.  Reference file:line citations sit next to each restated formula.
@@ -44,4 +46,5 @@
 #include "ccsd_k_orbit.h"
 #include "ccsd_k_nspdk.h"
 #include "ccsd_k_eig.h"
+#include "ccsd_k_lift.h"
 #include "ccsd_k_lg.h"

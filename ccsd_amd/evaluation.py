@@ -11,6 +11,8 @@ needs no external program:
   orbit_stats_all                                                 (stats.py:343-435)    -> SampleOps.orbit_counts (ccsd_orbit_counts)
   nspdk_stats, compute_nspdk_mmd with eden.py's vectorize         (stats.py:438-467, mmd.py:309-377, eden.py)
                                                                                         -> SampleOps.nspdk_features / nspdk_mmd
+  convert_graphs_to_CCs with path_based (path_length 3) / cycles  (cc_utils.py:816-880, 1644-1754) -> SampleOps.lift (ccsd_lift); opt-in:
+                                                                  describe(lift=), eval_CC_batch(lift=), lift_settings
 
 The reference builds networkx graphs / toponetx complexes on the host and solves one pyemd linear program per pair of histograms.
 Here a sample set is a dict of per-sample integer DESCRIPTORS on the device -- `describe()`: the descriptor outputs of
@@ -137,19 +139,28 @@ def compute_mmd(samples1, samples2, kernel: KernelSelector = gaussian_emd, is_hi
 # ---------------------------------------------------------------------------------------------
 def describe(adj: torch.Tensor, x: Optional[torch.Tensor] = None, rank2: Optional[torch.Tensor] = None, *, mol: bool = False,
              thr: float = 0.5, bins: int = 100, d_min: int = 0, d_max: int = 0, spectra: bool = False, orbits: bool = False,
-             nspdk: bool = False, nspdk_labels: Optional[torch.Tensor] = None, device=None, lib=None) -> Dict[str, torch.Tensor]:
+             nspdk: bool = False, nspdk_labels: Optional[torch.Tensor] = None, lift: Optional[dict] = None, device=None,
+             lib=None) -> Dict[str, torch.Tensor]:
     """The descriptor dict of a batch: SampleOps.finish's descriptors (degree, degree_hist, edge_hist; n_nodes, x_hist with x;
     rank2_cell_bits / _count / _hist, rank2_nnz with rank2) plus cluster_hist (B, bins) and tri2 (B, N).  adj: (B, N, N), raw samples,
     quantised samples or a 0/1 data set (any real or integer dtype).  spectra=True adds spectral_hist (B, 200) int32 and, with rank2,
     hodge_spectrum (B, E) float32 (SampleOps.spectral_hist / hodge_spectrum: an eigenvalue solve per sample).  orbits=True adds
     orbit_counts (B, 15) int64 and orbit_nodes (B,) int32 (SampleOps.orbit_counts).  nspdk=True adds the NSPDK feature rows
     nspdk_indptr, nspdk_indices, nspdk_values (SampleOps.nspdk_features, N <= 64) with the node labels nspdk_labels (B, N), or
-    mol_labels(x) when `mol` and x is given, or label 0 in every slot."""
+    mol_labels(x) when `mol` and x is given, or label 0 in every slot.  lift=dict(procedure=..., d_min=..., d_max=..., and optionally
+    path_length, sources: the keywords of SampleOps.lift; lift_settings reads them from a config) without rank2 LIFTS the graphs to
+    complexes (N <= 64): it adds rank2_cell_bits / _count / _hist, rank2_nnz and lift_dropped, and with spectra=True hodge_spectrum from
+    them.  The cycles rule is networkx's cycle basis of the adjacency, not the reference's set-order-dependent one (SampleOps.lift)."""
+    if lift is not None and rank2 is not None:
+        raise ValueError("describe: lift= builds the rank-2 cells of a graph; a batch that brings its own rank2 is not lifted")
     eng = _ops(device if device is not None else (adj.device if adj.device.type == "cuda" else None), lib)
     mv = lambda t: None if t is None else t.to(device=eng.device, dtype=torch.float32).contiguous()
     adj, x, rank2 = mv(adj), mv(x), mv(rank2)
     out = eng.finish(x, adj, rank2, None, mol=mol, thr=thr, d_min=d_min, d_max=d_max, dense_rank2=False, dense_adj=False)
     out.update(eng.cluster_hist(adj, mol=mol, thr=thr, bins=bins))
+    if lift is not None:
+        out.update(eng.lift(adj, mol=mol, thr=thr, **lift))
+        d_min, d_max = int(lift["d_min"]), int(lift["d_max"])
     if orbits:
         out.update(eng.orbit_counts(adj, mol=mol, thr=thr))
     if nspdk:
@@ -158,9 +169,35 @@ def describe(adj: torch.Tensor, x: Optional[torch.Tensor] = None, rank2: Optiona
         out.update(eng.nspdk_features(adj, None if nspdk_labels is None else torch.as_tensor(nspdk_labels).to(eng.device), mol=mol, thr=thr))
     if spectra:
         out.update(eng.spectral_hist(adj, mol=mol, thr=thr))
-        if rank2 is not None:
+        if rank2 is not None or lift is not None:
             out["hodge_spectrum"] = eng.hodge_spectrum(adj, out["rank2_cell_bits"], d_min=d_min, d_max=d_max, mol=mol, thr=thr)
     return out
+
+
+def lift_settings(data_cfg, N: Optional[int] = None) -> Optional[dict]:
+    """The lifting rule of a config's `data` section as keywords of SampleOps.lift (procedure, and for path_based path_length and
+    sources), read as convert_graphs_to_CCs reads lifting_procedure / lifting_procedure_kwargs (cc_utils.py:851-878); None when the
+    config names no procedure.  "basic" means every one of the N = max_node_num node slots is a source and path_length 3; a dict
+    passes sources_nodes / path_length through, its sources at or past N dropped (they are no node of any graph of the batch).  A string other than "basic", a string for cycles and an unknown procedure raise
+    NotImplementedError with the reference's message."""
+    get = lambda k: data_cfg.get(k) if isinstance(data_cfg, dict) else getattr(data_cfg, k, None)
+    proc, kwargs = get("lifting_procedure"), get("lifting_procedure_kwargs")
+    if proc is None:
+        return None
+    if kwargs is None:
+        kwargs = {}
+    if proc == "path_based":
+        if isinstance(kwargs, str):
+            if kwargs != "basic":
+                raise NotImplementedError(f"Lifting procedure kwargs {kwargs} not implemented")
+            kwargs = {"sources_nodes": None, "path_length": 3}        # (range(max_node_num): every slot, which SampleOps.lift spells None)
+        src = kwargs.get("sources_nodes")
+        return {"procedure": "path_based", "path_length": int(kwargs.get("path_length", 3)), "sources": None if src is None else [int(n) for n in src if N is None or int(n) < N]}
+    if proc == "cycles":
+        if isinstance(kwargs, str):
+            raise NotImplementedError(f"Lifting procedure kwargs {kwargs} not implemented")
+        return {"procedure": "cycles"}
+    raise NotImplementedError(f"Lifting procedure {proc} not implemented")
 
 
 def _descriptors(obj, need: Sequence[str], **kw) -> Dict[str, torch.Tensor]:
@@ -411,12 +448,25 @@ def eval_torch_batch(ref_batch, pred_batch, methods: Optional[Sequence[str]] = N
 
 
 def eval_CC_batch(ref_desc, pred_desc, worker_kwargs, methods: Optional[Sequence[str]] = None, kernels: Optional[dict] = None,
-                  cc_nb_eval: Optional[int] = 1000, *, spectra: bool = False, mol: bool = False, thr: float = 0.5, **kw) -> Dict[str, float]:
+                  cc_nb_eval: Optional[int] = 1000, *, spectra: bool = False, mol: bool = False, thr: float = 0.5, lift: Optional[dict] = None,
+                  **kw) -> Dict[str, float]:
     """eval_CC_list (cc_utils.py:1418-1474) on descriptor dicts: {method: round(score, 6)}.  Default methods: "rank1_distrib",
     "rank2_distrib" (the reference's other two defaults raise NotImplementedError when asked for, see UNSUPPORTED).
     spectra=True also accepts "hodge_laplacian_spectrum" in `methods` (it is never a default): a side without hodge_spectrum has it
     computed from its adj and rank2_cell_bits with the quantiser `mol`, `thr` and worker_kwargs' d_min, d_max.  Without spectra=True
-    the name raises NotImplementedError."""
+    the name raises NotImplementedError.  lift=dict(procedure=..., d_min=..., d_max=..., ...) (describe's keyword) lifts a side that
+    holds `adj` and edge_hist but no rank2_cell_hist -- a set of graphs -- to complexes first; the dicts passed in are not written to."""
+    if lift is not None:
+        sides = []
+        for desc in (ref_desc, pred_desc):
+            if "rank2_cell_hist" not in desc:
+                if "adj" not in desc:
+                    raise KeyError("eval_CC_batch: lift= needs adj on a side without rank2_cell_hist")
+                adj = desc["adj"]
+                eng = _ops(kw.get("device") if kw.get("device") is not None else (adj.device if adj.device.type == "cuda" else None), kw.get("lib"))
+                desc = dict(desc, **eng.lift(adj.to(device=eng.device, dtype=torch.float32), mol=mol, thr=thr, **lift))
+            sides.append(desc)
+        ref_desc, pred_desc = sides
     methods = ["rank1_distrib", "rank2_distrib"] if methods is None else list(methods)
     table = dict(CC_METHOD_NAME_TO_FUNC, **SPECTRA_CC_METHOD_NAME_TO_FUNC) if spectra else CC_METHOD_NAME_TO_FUNC
     _check_methods(methods, table, spectra)

@@ -353,7 +353,8 @@ class Sampler:
 
 
     def evaluate(self, result, ref, methods: Optional[List[str]] = None, cc_methods: Optional[List[str]] = None, bins: int = 100,
-                 cc_nb_eval: Optional[int] = 1000, spectra: bool = False, orbits: bool = False, nspdk: bool = False) -> Dict[str, float]:
+                 cc_nb_eval: Optional[int] = 1000, spectra: bool = False, orbits: bool = False, nspdk: bool = False,
+                 lift: bool = False) -> Dict[str, float]:
         """Score a finished run against a held-out set on the GPU (ccsd_amd/evaluation.py): what the reference prints after
         sampling from eval_graph_list and eval_CC_list (sampler.py:253-262, 565-583), for the methods this build computes.
         `result`: what sample() returned.  `ref`: an adjacency batch (B, N, N) of the held-out graphs, a descriptor dict
@@ -369,14 +370,34 @@ class Sampler:
         nodes) and integer node labels: for molecule samplers evaluation.mol_labels of the side's `x`, or its `nspdk_labels`
         (KeyError when a side has neither), label 0 otherwise.  It scores the quantised samples AS SAMPLED: the reference scores
         molecules after rdkit's valency correction and largest-fragment selection, which this build does not have -- pass corrected
-        `adj` / `nspdk_labels` to score those.  In a sharded run every rank holds the gathered samples and rank 0 alone
-        evaluates; the other ranks return {}."""
+        `adj` / `nspdk_labels` to score those.  lift=True LIFTS graphs to complexes by the config's rule (data.lifting_procedure /
+        lifting_procedure_kwargs with data.d_min / d_max; evaluation.lift_settings, SampleOps.lift, at most 64 nodes), as the reference's
+        data generators and Sampler_Graph do (sampler.py:259-287): on a sampler of complexes a side that has `adj` but no rank-2
+        descriptors -- normally the held-out graphs -- is lifted, so that "rank2_distrib" and, with spectra=True,
+        "hodge_laplacian_spectrum" are scored; on a graph sampler both sides are lifted and the eval_CC_batch scores are added (the
+        reference's "CCs eval" line).  The cycles rule is networkx's cycle basis of the adjacency, not the reference's
+        set-order-dependent one; both sides go through the same rule.  A config without lifting_procedure raises ValueError, a
+        molecule sampler NotImplementedError (its cells are rdkit's rings, which this build does not have).  In a sharded run every
+        rank holds the gathered samples and rank 0 alone evaluates; the other ranks return {}."""
         from . import evaluation as ev
 
         if self.rank != 0:
             return {}
         lib = self.extra.get("lib")
         kw = dict(device=self.device0, lib=lib)
+        data = _get(self.config, "data")
+        datat = _get(getattr(self, "configt", None), "data")     # (the cell sizes sample() hands to finish(); no checkpoint loaded yet: none)
+        cell_sizes = dict(d_min=_get(data, "d_min") or _get(datat, "d_min") or 0, d_max=_get(data, "d_max") or _get(datat, "d_max") or 0)
+        lift_kw = None
+        if lift:
+            if self.is_mol:
+                raise NotImplementedError("evaluate: lift=True on a molecule sampler: the reference's cells of a molecule are rdkit's rings, which this build does not have")
+            lift_kw = ev.lift_settings(data, _get(data, "max_node_num") or _get(datat, "max_node_num"))
+            if lift_kw is None:
+                raise ValueError("evaluate: lift=True needs data.lifting_procedure in the config")
+            if not cell_sizes["d_min"] or not cell_sizes["d_max"]:
+                raise ValueError("evaluate: lift=True needs data.d_min and data.d_max in the config")
+            lift_kw.update(cell_sizes)
 
         keep = ("adj", "degree_hist", "edge_hist", "n_nodes", "rank2_cell_hist", "cluster_hist") + (
             ("rank2_cell_bits", "spectral_hist", "hodge_spectrum") if spectra else ()) + (("orbit_counts", "orbit_nodes") if orbits else ()) + (
@@ -394,22 +415,27 @@ class Sampler:
                     desc.update(ev.describe(desc["adj"], mol=self.is_mol, bins=bins, **kw))
                 if nspdk and self.is_mol and not all(k in desc for k in ev.NSPDK_KEYS) and "x" not in desc and "nspdk_labels" not in desc:
                     raise KeyError("evaluate: nspdk=True on a molecule run needs x or nspdk_labels (or the nspdk_* rows) on each side")
+                if lift_kw is not None and "rank2_cell_hist" not in desc:
+                    if "adj" not in desc:
+                        raise KeyError("evaluate: lift=True needs adj on a side without rank-2 descriptors")
+                    desc.update(SampleOps(self.device0, lib).lift(desc["adj"].to(torch.float32), mol=self.is_mol, **lift_kw))
                 return desc
             if nspdk and self.is_mol:
                 raise KeyError("evaluate: nspdk=True on a molecule run needs x or nspdk_labels beside the adjacency batch: pass a dict")
-            return ev.describe(torch.as_tensor(obj), mol=self.is_mol, bins=bins, orbits=orbits, nspdk=nspdk, **kw)
+            desc = ev.describe(torch.as_tensor(obj), mol=self.is_mol, bins=bins, orbits=orbits, nspdk=nspdk, lift=lift_kw, **kw)
+            if lift_kw is not None:
+                desc["adj"] = torch.as_tensor(obj).to(self.device0)          # (what hodge_laplacian_spectrum reads beside the lifted cells)
+            return desc
 
         pred, held = side(result), side(ref)
         if methods is None:
             methods = ["degree", "cluster"] + (["orbit"] if orbits else []) + (["spectral"] if spectra else []) + (["nspdk"] if nspdk else [])
         out = ev.eval_torch_batch(held, pred, methods, bins=bins, mol=self.is_mol, spectra=spectra, orbits=orbits, nspdk=nspdk, **kw)
-        if self.is_cc:
-            data = _get(self.config, "data")
+        if self.is_cc or lift_kw is not None:
             wk = {"min_edge_val": _get(data, "min_edge_val", 1), "max_edge_val": _get(data, "max_edge_val", 3 if self.is_mol else 1)}
             have = ["rank1_distrib"] + (["rank2_distrib"] if "rank2_cell_hist" in pred and "rank2_cell_hist" in held else [])
             if spectra:
-                datat = _get(self.configt, "data")                   # (the cell sizes sample() hands to finish())
-                wk.update(d_min=_get(data, "d_min") or _get(datat, "d_min") or 0, d_max=_get(data, "d_max") or _get(datat, "d_max") or 0)
+                wk.update(cell_sizes)
                 if all("hodge_spectrum" in d or ("adj" in d and "rank2_cell_bits" in d) for d in (pred, held)):
                     have.append("hodge_laplacian_spectrum")
             out.update(ev.eval_CC_batch(held, pred, wk, have if cc_methods is None else cc_methods, cc_nb_eval=cc_nb_eval, spectra=spectra,

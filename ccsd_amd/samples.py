@@ -338,6 +338,58 @@ class SampleOps:
                                                     _ptr(sw), _ptr(ws), ws.numel() * 8, self._stream()))
         return (out, sw) if sweeps else out
 
+    def lift(self, adj: torch.Tensor, procedure: str, *, d_min: int, d_max: int, path_length: int = 3, sources=None, mol: bool = False,
+             thr: float = 0.5, dense: bool = False) -> dict:
+        """Graphs lifted to combinatorial complexes (ccsd_lift): the rank-2 cells convert_graphs_to_CCs of the reference (cc_utils.py:
+        816-880) adds to the graphs of the quantised adjacency, finish()'s quantiser (`mol`, `thr`; in mol mode every bond order is a
+        plain edge), in the form finish() writes.  adj (B,N,N) float32, N <= 64; pair (i, j), i < j, is read from row i, as
+        hodge_spectrum reads it, and the diagonal is ignored.
+          procedure "path_based"   path_based_lift_CC with path_length 3: {a, b, c} is a cell iff one of the three nodes is adjacent to
+                                   the other two and one of those two is in `sources` (an iterable of node indices; None = every node,
+                                   the reference's "basic" setting; empty = no cell).  Another path_length raises NotImplementedError.
+          procedure "cycles"       cycles_lift_CC: the node sets of networkx.cycle_basis(networkx.from_numpy_array(A)).  The reference
+                                   rebuilds the graph from frozenset edges first, so its walk follows CPython's set-slot order and finds
+                                   another basis for about half of all random graphs; the number of cycles, E - V + C, is the same, and
+                                   both sides of a score are lifted by the one rule here.
+        -> rank2_cell_bits (B, ceil(K/64)) int64, rank2_cell_count (B,), rank2_cell_hist (B, d_max-d_min+1), rank2_nnz (B,) int32 as
+        finish() gives them for the lifted complex's incidence tensor; lift_dropped (B,) int32: the basis cycles whose size lies outside
+        d_min..d_max, which have no column (0 for paths); and rank2 (B, E, K) float32, the incidence tensor of create_incidence_1_2
+        (chords of a cycle count), when `dense`.  Every output is written in full.  Nothing is synchronised.  N > 64 raises
+        NotImplementedError."""
+        adj = self._adj("lift", adj)
+        B, N = adj.shape[0], adj.shape[1]
+        procs = {"path_based": _lib.LIFT_PATHS, "cycles": _lib.LIFT_CYCLES}
+        if procedure not in procs:
+            raise ValueError(f"lift: procedure must be one of {sorted(procs)}, got {procedure!r}")
+        d_min, d_max = int(d_min), int(d_max)
+        mask = (1 << 64) - 1
+        if sources is not None:
+            mask = 0
+            for n in sources:                                     # (a source that is no node of the graph starts no path, as in the reference)
+                if not 0 <= int(n) < _lib.LIFT_MAX_NODES:
+                    raise ValueError(f"lift: source node {n} outside 0..{_lib.LIFT_MAX_NODES - 1}")
+                mask |= 1 << int(n)
+        if B and not 2 <= N <= _lib.LIFT_MAX_NODES:               # (the C call names the limit; it launches nothing)
+            self.lib.check(self.lib.ccsd_lift(_ptr(adj), B, N, _adj_mode(mol), float(thr), procs[procedure], int(path_length), mask, d_min, d_max,
+                                              None, None, None, None, None, None, self._stream()))
+        if not 1 <= d_min <= d_max <= N:
+            raise ValueError(f"lift: bad cell sizes d_min = {d_min}, d_max = {d_max} for N = {N}")
+        K = sum(math.comb(N, d) for d in range(d_min, d_max + 1))
+        if K > 1 << 24:
+            raise ValueError(f"lift: sum C(N, d) for d = {d_min}..{d_max} exceeds 2^24")
+        dev = adj.device
+        res = {"rank2_cell_bits": torch.empty((B, (K + 63) // 64), dtype=torch.int64, device=dev),
+               "rank2_cell_count": torch.empty((B,), dtype=torch.int32, device=dev),
+               "rank2_cell_hist": torch.empty((B, d_max - d_min + 1), dtype=torch.int32, device=dev),
+               "rank2_nnz": torch.empty((B,), dtype=torch.int32, device=dev),
+               "lift_dropped": torch.empty((B,), dtype=torch.int32, device=dev)}
+        if dense:
+            res["rank2"] = torch.empty((B, N * (N - 1) // 2, K), dtype=torch.float32, device=dev)
+        self.lib.check(self.lib.ccsd_lift(_ptr(adj), B, N, _adj_mode(mol), float(thr), procs[procedure], int(path_length), mask, d_min, d_max,
+                                          _ptr(res["rank2_cell_bits"]), _ptr(res["rank2_cell_count"]), _ptr(res["rank2_cell_hist"]),
+                                          _ptr(res["rank2_nnz"]), _ptr(res["lift_dropped"]), _ptr(res.get("rank2")), self._stream()))
+        return res
+
 
 def cells_from_bits(bits_row, N: int, d_min: int, d_max: int):
     """Cell tuples of one complex from its bitmask row, in the reference's enumeration order (get_cells,

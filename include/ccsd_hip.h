@@ -50,6 +50,9 @@
  *                              (evaluation/stats.py:125-137); ccsd_spectral_workspace_bytes sizes its workspace
  * ccsd_hodge_spectrum          hodge_laplacian_spectrum_worker: the eigenvalues of F F^T of the complex's rank-1 / rank-2 incidence
  *                              matrix (cc_utils.py:994-1060); ccsd_hodge_workspace_bytes sizes its workspace
+ * ccsd_lift                    convert_graphs_to_CCs + CC_to_incidence_matrices for the two lifting rules the configs ship:
+ *                              path_based_lift_CC with path_length 3 and cycles_lift_CC (cc_utils.py:816-880, 1644-1754, 265-330), as the
+ *                              cell bitmask and descriptors ccsd_finish writes, and on request the dense rank-2 incidence tensor
  */
 #ifndef CCSD_HIP_H
 #define CCSD_HIP_H
@@ -476,6 +479,37 @@ size_t ccsd_hodge_workspace_bytes(int32_t B, int32_t N);
 int ccsd_hodge_spectrum(const float* adj_dev, const uint64_t* cell_bits_dev, int32_t B, int32_t N, int32_t d_min, int32_t d_max,
                         int32_t adj_mode, float thr, float* spectrum_dev, int32_t* sweeps_dev, void* workspace_dev, size_t ws_bytes,
                         void* stream);
+
+/* Graphs lifted to combinatorial complexes: the rank-2 cells convert_graphs_to_CCs (cc_utils.py:816-880) adds to every graph of
+ * adj_dev (B,N,N), 2 <= N <= 64, in the sparse form ccsd_finish writes and ccsd_hodge_spectrum reads.  The graph is the quantised
+ * adjacency (adj_mode, thr as in ccsd_finish; in mol mode every bond order is a plain edge); the diagonal is ignored and pair (i, j),
+ * i < j, is read from row i, exactly as ccsd_hodge_spectrum reads it.  Column k names its nodes as get_cells does: sizes d_min..d_max,
+ * itertools.combinations(range(N), d) order within a size; K = sum of C(N, d).
+ * procedure CCSD_LIFT_PATHS (path_based_lift_CC, cc_utils.py:1692-1724) with path_length 3: {a, b, c} is a cell iff one of the three nodes
+ *   is adjacent to the other two and at least one of those two is a source (bit n of sources_mask: node n starts paths; the reference's
+ *   "basic" setting is all ones; the empty mask gives no cell).  Any other path_length: CCSD_ERR_UNSUPPORTED; path_length outside
+ *   d_min..d_max: CCSD_ERR_INVALID.
+ * procedure CCSD_LIFT_CYCLES (cycles_lift_CC, cc_utils.py:1727-1754): the node sets of networkx.cycle_basis(networkx.from_numpy_array(A))
+ *   -- components in descending order of their highest node, which is the root; a LIFO stack walk that visits neighbours in ascending
+ *   order.  path_length and sources_mask are ignored.  DIFFERENCE from the reference: it rebuilds the graph from frozenset edges first, so its
+ *   root and neighbour order follow CPython's set-slot order and its basis is another one for about half of all random graphs; the
+ *   NUMBER of cycles, E - V + C, is the same.  A cycle whose size lies outside d_min..d_max has no column (the reference raises KeyError
+ *   there): it is counted in dropped_dev and not represented.
+ * Outputs, every one fully written by the call (the caller need not clear anything):
+ *   cell_bits_dev (B, ceil(K/64)) uint64   bit k % 64 of word k / 64 = column k is a cell; the tail bits of the last word are 0
+ *   cell_count_dev (B,) int32              the set bits (a node set two cycles share counts once)
+ *   cell_hist_dev (B, d_max-d_min+1) int32 the set bits per cell size                                         (nullable)
+ *   nnz_dev (B,) int32                     the ones of the incidence matrix                                   (nullable)
+ *   dropped_dev (B,) int32                 cycles without a column; 0 for paths                               (nullable)
+ *   rank2_dev (B,E,K) fp32                 the incidence matrix of create_incidence_1_2 (cc_utils.py:265-330): F[e][k] = 1 iff column k
+ *                                          is a cell and edge e of the graph lies inside it (chords of a cycle count), E = N (N - 1) / 2;
+ *                                          zero-filled, then only the ones are stored                        (nullable)
+ * B = 0 is a no-op.  N > 64: CCSD_ERR_UNSUPPORTED (a row of the adjacency is one 64-bit mask); 1 <= d_min <= d_max <= N and K <= 2^24, else
+ * CCSD_ERR_INVALID. */
+enum { CCSD_LIFT_PATHS = 0, CCSD_LIFT_CYCLES = 1 };
+int ccsd_lift(const float* adj_dev, int32_t B, int32_t N, int32_t adj_mode, float thr, int32_t procedure, int32_t path_length,
+              uint64_t sources_mask, int32_t d_min, int32_t d_max, uint64_t* cell_bits_dev, int32_t* cell_count_dev,
+              int32_t* cell_hist_dev, int32_t* nnz_dev, int32_t* dropped_dev, float* rank2_dev, void* stream);
 
 /* Measurement hooks (bench.py): time every launch of selected kernels with HIP events on the launch stream.
  * kernel_id: 0 k_xa, 1 k_gemm_p, 2 k_hf_score, 3 k_gemm_h, 4 k_langevin_apply, 5 k_r2, 6 k_s4_apply, 7 k_ew1; each call adds one kernel to the

@@ -1979,8 +1979,137 @@ def base_cc_route():
     print("base_cc_route done")
 
 
+# ---------------------------------------------------------------------------------------------
+# e5_lift.npz: the reference's path_based lifting of graphs and what its evaluators make of the lifted complexes
+# (`python tools/make_golden.py lift`)
+# ---------------------------------------------------------------------------------------------
+def e5_lift():
+    """e5_lift.npz: convert_graphs_to_CCs(graphs, False, "path_based", "basic", max_nb_nodes=N) of the reference on two sets of 24 graphs
+    at N = 12 and at N = 20 (d_min = d_max = 3), then its own CC_to_incidence_matrices, rank2_distrib_worker,
+    hodge_laplacian_spectrum_worker and eval_CC_list on the lifted complexes.  Stored per graph: the cell bits of the padded incidence
+    matrix, the size histogram, its number of ones and the float32 spectrum -- no dense tensor.  gaussian_emd ran on the stand-in pyemd,
+    the complexes on _StandInComplex; lp_vs_closed / f32_vs_f64 as in e2_spectrum.npz.  The hodge score costs one linear program of
+    E^2 variables per pair, so it is recorded on the first `hodge_nb` complexes of each side."""
+    import threading
+    import time
+
+    import networkx as nx
+
+    record = {"tl": threading.local()}
+    stand_in = _pyemd_stand_in(record)
+    sys.modules["pyemd"] = stand_in
+    from ccsd.src.evaluation import mmd as ref_mmd
+
+    ref_mmd.pyemd = stand_in
+    ref_cc.CombinatorialComplex = _StandInComplex
+    t0 = time.time()
+    out, meta = {}, {"sets": {}, "lp_vs_closed": {}, "f32_vs_f64": {}}
+    worst = {"v": 0.0}
+
+    def k_emd(x, y, **kw):
+        record["tl"].mode = "closed"
+        try:
+            kc = ref_mmd.gaussian_emd(x, y, **kw)
+        finally:
+            record["tl"].mode = "lp"
+        kl = ref_mmd.gaussian_emd(x, y, **kw)
+        worst["v"] = max(worst["v"], abs(float(kl) - float(kc)))
+        return kl
+
+    def graphs_of(rng, N, B, p, d_min, d_max):
+        """B graphs with their lifted complexes.  A graph whose hodge Laplacian the reference's LAPACK call gives up on (the worker then
+        returns zeros of the UNPADDED length, cc_utils.py:1013-1019) is drawn again: that path is the solver's, not the lifting's."""
+        adj = np.zeros((B, N, N), np.int8)
+        ccs, b = [], 0
+        while b < B:
+            n = N - int(rng.integers(0, 5)) if b else N              # (masked slots at the end, as finished samples have them)
+            u = np.triu(rng.random((n, n)) < p[b % len(p)], 1)
+            u[0, 1] |= not u.any()                                   # (path_based_lift_CC reads the rank-1 cells of its input: a graph has an edge)
+            g = nx.Graph()
+            g.add_nodes_from(range(n))
+            for i, j in zip(*np.nonzero(u)):
+                g.add_edge(int(i), int(j), label=1)
+            (cc,) = ref_cc.convert_graphs_to_CCs([g], False, "path_based", "basic", max_nb_nodes=N)
+            spec = ref_cc.hodge_laplacian_spectrum_worker(cc, d_min, d_max, N)
+            F = ref_cc.CC_to_incidence_matrices(cc, d_min, d_max)[2]
+            f64 = np.zeros(N * (N - 1) // 2)
+            if F.size:
+                F = np.asarray(ref_cc.pad_rank2(F, node_number=N, d_min=d_min, d_max=d_max), np.float64)
+                f64 = np.linalg.eigvalsh(F @ F.T)
+            # (... or returns without an exception what is no spectrum: NaNs, or values off by more than float32 can explain)
+            if len(spec) != len(f64) or not np.isfinite(spec).all() or np.abs(spec - f64).max() > 1e-4 * max(1.0, f64.max()):
+                meta["redrawn"] = meta.get("redrawn", 0) + 1
+                continue
+            adj[b] = 0
+            adj[b, :n, :n] = u + u.T
+            ccs.append(cc)
+            b += 1
+        return adj, ccs
+
+    for N, hodge_nb in ((12, 6), (20, 3)):
+        d_min = d_max = 3
+        E, K = N * (N - 1) // 2, ref_cc.get_rank2_dim(N, d_min, d_max)[1]
+        rng = np.random.default_rng(20261020 + N)
+        wk = {"min_edge_val": 1, "max_edge_val": 1, "edge_label": "label", "d_min": d_min, "d_max": d_max, "N": N}
+        ccs, f32 = {}, 0.0
+        for side, p in (("ref", (0.15, 0.3, 0.5)), ("pred", (0.2, 0.4, 0.1))):
+            adj, ccs[side] = graphs_of(rng, N, 24, p, d_min, d_max)
+            bits = np.zeros((24, (K + 63) // 64), np.uint64)
+            hist, nnz, spec = np.zeros((24, 1), np.int32), np.zeros(24, np.int32), np.zeros((24, E), np.float32)
+            for b, cc in enumerate(ccs[side]):
+                F = ref_cc.CC_to_incidence_matrices(cc, d_min, d_max)[2]
+                if F.size:
+                    F = np.asarray(ref_cc.pad_rank2(F, node_number=N, d_min=d_min, d_max=d_max))
+                    assert F.shape == (E, K) and set(np.unique(F).tolist()) <= {0.0, 1.0}
+                    for k in np.nonzero(F.any(0))[0]:
+                        bits[b, k >> 6] |= np.uint64(1 << int(k & 63))
+                    nnz[b] = int(F.sum())
+                    f32 = max(f32, float(np.abs(np.linalg.eigvalsh(F.astype(np.float64) @ F.T.astype(np.float64)) -
+                                                ref_cc.hodge_laplacian_spectrum_worker(cc, d_min, d_max, N).astype(np.float64)).max()))
+                hist[b] = ref_cc.rank2_distrib_worker(cc, d_min, d_max)
+                spec[b] = ref_cc.hodge_laplacian_spectrum_worker(cc, d_min, d_max, N)
+                assert int(hist[b].sum()) == len(cc.cells.hyperedge_dict.get(2, {}))
+            out[f"n{N}/{side}/adj"], out[f"n{N}/{side}/bits"], out[f"n{N}/{side}/hist"] = adj, bits, hist
+            out[f"n{N}/{side}/nnz"], out[f"n{N}/{side}/spectrum"] = nnz, spec
+        meta["f32_vs_f64"][f"n{N}/eig"] = f32
+        kern = {m: k_emd for m in ("hodge_laplacian_spectrum", "rank1_distrib", "rank2_distrib")}
+        worst["v"] = 0.0
+        meta[f"eval_CC_list/n{N}"] = ref_cc.eval_CC_list(ccs["ref"], ccs["pred"], wk, methods=["rank1_distrib", "rank2_distrib"], kernels=kern, cc_nb_eval=1000)
+        meta["lp_vs_closed"][f"eval_CC_list/n{N}"] = worst["v"]
+        worst["v"] = 0.0
+        meta[f"eval_CC_list/n{N}/first{hodge_nb}"] = ref_cc.eval_CC_list(ccs["ref"], ccs["pred"], wk, methods=list(kern), kernels=kern, cc_nb_eval=hodge_nb)
+        meta["lp_vs_closed"][f"eval_CC_list/n{N}/first{hodge_nb}"] = worst["v"]
+        # the hodge score again from float64 eigenvalues rounded to float32 once: what the solver's precision is worth in the score
+        rows = []
+        for side in ("ref", "pred"):
+            r = []
+            for cc in ccs[side][:hodge_nb]:
+                if side == "pred" and ref_cc.is_empty_cc(cc):
+                    continue
+                F = ref_cc.CC_to_incidence_matrices(cc, d_min, d_max)[2]
+                if F.size:
+                    F = np.asarray(ref_cc.pad_rank2(F, node_number=N, d_min=d_min, d_max=d_max), np.float64)
+                    r.append(np.linalg.eigvalsh(F @ F.T).astype(np.float32))
+                else:
+                    r.append(np.zeros(E, np.float32))
+            rows.append(r)
+        unrounded = float(ref_cc.hodge_laplacian_spectrum_stats(ccs["ref"][:hodge_nb], ccs["pred"][:hodge_nb], wk, k_emd, is_parallel=False))
+        meta["f32_vs_f64"][f"eval_CC_list/n{N}/first{hodge_nb}"] = abs(float(ref_mmd.compute_mmd(rows[0], rows[1], kernel=k_emd)) - unrounded)
+        meta["sets"][f"n{N}"] = {"N": N, "d_min": d_min, "d_max": d_max, "E": E, "K": K, "hodge_nb": hodge_nb, "worker_kwargs": wk}
+        print("e5 lift n", N, round(time.time() - t0, 1), "s", record.get("programs", 0), "programs")
+    meta["programs"], meta["seconds"] = record.get("programs", 0), round(time.time() - t0, 1)
+    out["meta"] = np.array(json.dumps(plain(meta)))
+    path = os.path.join(GOLD, "e5_lift.npz")
+    np.savez_compressed(path, **out)
+    assert os.path.getsize(path) <= MAX_FIXTURE, os.path.getsize(path)
+    print("wrote e5_lift", os.path.getsize(path), "bytes;", meta["programs"], "programs,", meta["seconds"], "s")
+
+
 def main():
     only = set(sys.argv[1:])
+    if only == {"lift"}:
+        e5_lift()
+        return
     if only == {"f1"}:
         f1_finish()
         return
