@@ -108,6 +108,10 @@ class PCEngine(SampleOps):
 
     # -- API
     def score(self, target: int, x, adj, rank2, flags, sscale: float = 1.0) -> torch.Tensor:
+        """sscale * net_target(x, adj, rank2, flags) (ccsd_score).  `flags` is any 0 / 1 node mask, the live nodes need not be a
+        prefix; the state need not be masked by it and the adjacency may carry a diagonal.  The adjacency must be SYMMETRIC: for an
+        asymmetric one the result depends on the route the planner picks (k_xa reads the unordered pairs, the tiled graph-network
+        route the whole matrix; include/ccsd_hip.h)."""
         B = x.shape[0]
         st = self._state(x, adj, rank2, B)
         self._check(flags, (B, self.N), "flags")

@@ -103,6 +103,9 @@ class _ScoreNetwork:
         return self._engine[1]
 
     def forward(self, x, adj, *rest, lib=None):
+        """model(x, adj[, rank2], flags) through the HIP kernels (PCEngine.score).  `flags` is any 0 / 1 node mask -- the reference's
+        node_flags(adj) puts a hole wherever a node is isolated -- and the inputs need not be masked by it; the adjacency may carry a
+        diagonal but must be SYMMETRIC: for an asymmetric one the result depends on the route the planner picks (include/ccsd_hip.h)."""
         rank2, flags = (rest + (None, None))[:2] if len(rest) != 1 else (None, rest[0])
         if flags is None:
             flags = torch.ones(x.shape[0], adj.shape[-1], device=x.device)
@@ -133,6 +136,7 @@ class ScoreNetworkX(_ScoreNetwork):
         return self._engine[1]
 
     def forward(self, x, adj, *rest, lib=None):
+        """model(x, adj[, rank2], flags): any 0 / 1 node mask, inputs masked or not, adjacency SYMMETRIC (see _ScoreNetwork.forward)."""
         flags = rest[-1] if rest else None
         if flags is None:
             flags = torch.ones(x.shape[0], adj.shape[-1], device=x.device)
@@ -173,6 +177,7 @@ class ScoreNetworkA(_ScoreNetwork):
         return self._engine[1]
 
     def forward(self, x, adj, *rest, lib=None):
+        """model(x, adj[, rank2], flags): any 0 / 1 node mask, inputs masked or not, adjacency SYMMETRIC (see _ScoreNetwork.forward)."""
         flags = rest[-1] if rest else None
         if flags is None:
             flags = torch.ones(x.shape[0], adj.shape[-1], device=x.device)

@@ -269,8 +269,17 @@ int ccsd_s4_apply(ccsd_plan_t* plan, int32_t B, int32_t step, const ccsd_state_t
  * `scratch` is a second state used for ping-pong.  PRECONDITION: `state` is MASKED by `flags_dev` -- x rows, adj rows / columns
  * and rank2 rows / columns of switched-off nodes hold zeros, as in every state the reference's loop ever sees (its prior is masked,
  * solver.py:1111-1118, and every update preserves the masks) and in everything ccsd_init_state or an earlier ccsd_sampler_run
- * wrote.  The loop's rank-2 kernels rely on it (they skip re-masking rank2 in the hodge-projection loader); the step calls above
- * (ccsd_score, ccsd_corrector_norms, ccsd_predictor, ...) accept arbitrary states.  traj_dev (nullable): [diff_steps][N*F+N*N+E*K]
+ * wrote.  The loop's rank-2 kernels rely on it (they skip re-masking rank2 in the hodge-projection loader).
+ * EVERY call -- this one and the step calls above (ccsd_score, ccsd_corrector_norms, ccsd_corrector_apply, ccsd_predictor,
+ * ccsd_s4_apply, ccsd_init_state, ccsd_noise_draws) -- accepts ANY node mask: flags_dev is 0 / 1 per node, the live nodes need not
+ * be a prefix (the reference's node_flags(adj) switches an isolated node off wherever it sits).  The step calls also accept states
+ * that are NOT masked -- values in the rows / columns of switched-off nodes -- and an adjacency with a NON-ZERO DIAGONAL: the
+ * networks see them as the reference's modules do.  What the update calls write for switched-off nodes is what the reference's update
+ * carries there, whose score and noise are masked: pa * in for ccsd_predictor, the input for ccsd_corrector_apply, the two
+ * transition factors times the input for ccsd_s4_apply (zero on a masked state).
+ * The adjacency must be SYMMETRIC.  For an asymmetric one the result is undefined and depends on the route the planner picks: k_xa
+ * reads the E unordered pairs (i < j) and takes adj[j][i] = adj[i][j], the tiled graph-network route (CCSD_QUERY_LARGE_GRAPH) reads
+ * the whole matrix as the reference does.  traj_dev (nullable): [diff_steps][N*F+N*N+E*K]
  * receives sample 0 of every step (diff_traj, solver.py:1150-1165).  first_step/last_step allow
  * running a sub-range [first_step, last_step) of the diff_steps steps.  Every sampler.n_steps runs here: with n_steps != 1 the
  * Langevin inner iterations (solver.py:1131-1137) go through a third state buffer that ccsd_workspace_bytes includes. */

@@ -107,15 +107,18 @@ def slot_id(hs):
     return "prior" if hs is None else "s%dp%d" % hs
 
 
-def case_stream(plan, lib, device, seed, sample_offset, hs, bound):
+def case_stream(plan, lib, device, seed, sample_offset, hs, bound, flags=None):
     """One call -- the prior (hs None) or half-step hs = (step, phase) -- at one (seed, sample_offset), B = 5 with node counts
-    [N, 0, 1, 2, N - 3]: every element against the reference.  Returns the largest distance."""
+    [N, 0, 1, 2, N - 3]: every element against the reference.  `flags`: a (B, N) node mask of the caller's (default: those counts,
+    the live nodes a prefix).  Returns the largest distance."""
     eng, meta = engine_for(plan, lib, device)
     _, predictor, _, n_steps, _ = PLANS[plan]
     N, F, is_cc = eng.N, eng.F, eng.is_cc
     d = meta["config"]["data"]
     d_min, d_max = (d["d_min"], d["d_max"]) if is_cc else (0, 0)
-    flags = make_flags(B, N, counts_for(N))
+    if flags is None:
+        flags = make_flags(B, N, counts_for(N))
+    assert tuple(flags.shape) == (B, N)
     dflags = flags.to(device)
     buf = eng.alloc_state(B)
     for t in buf:

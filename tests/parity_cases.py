@@ -484,13 +484,16 @@ def case_philox_prior_statistics(lib, device):
     assert torch.equal(st2[2].cpu()[0], r[1]), "sample_offset must shift the global sample index"
 
 
-def case_one_step_vs_oracle_large(name, lib, device, B, counts, predictor, corrector, snr, seps, seed=3):
-    """One full PC step with host-supplied noise on a bigger batch, against the oracle (not the goldens)."""
+def case_one_step_vs_oracle_large(name, lib, device, B, counts, predictor, corrector, snr, seps, seed=3, flags=None):
+    """One full PC step with host-supplied noise on a bigger batch, against the oracle (not the goldens).  `flags`: a (B, N) node mask
+    of the caller's (default: make_flags(B, N, counts), the live nodes a prefix)."""
     meta, parts = load_ckpt_np(name)
     cfg, is_cc = meta["config"], meta["is_cc"]
     N, Fd = cfg["data"]["max_node_num"], cfg["data"]["max_feat_num"]
     names = ["x", "adj"] + (["rank2"] if is_cc else [])
-    flags = make_flags(B, N, counts)
+    if flags is None:
+        flags = make_flags(B, N, counts)
+    assert tuple(flags.shape) == (B, N)
     kw = dict(shape_x=(B, N, Fd), shape_adj=(B, N, N), predictor=predictor, corrector=corrector, snr=snr, scale_eps=seps,
               n_steps=1, probability_flow=False, continuous=True, denoise=True, eps=1e-4)
     if is_cc:
@@ -531,7 +534,7 @@ def loop_phases(predictor, corrector, n_steps=1):
 
 
 def case_production_loop_vs_oracle(name, lib, device, B, counts, steps, predictor, corrector, snr, seps, seed=5, expect_fused=None,
-                                   source=None, keep_traj=False, subset=None, expect_route=None, stepwise=True):
+                                   source=None, keep_traj=False, subset=None, expect_route=None, stepwise=True, flags=None):
     """The PRODUCTION loop -- one ccsd_sampler_run call: in-kernel Philox noise, the Langevin apply fused into the predictor
     kernels' prologues where the plan supports it -- against the oracle, value for value, in each of its four step forms (S4,
     Langevin fused, Langevin unfused, predictor only).  ccsd_noise_draws exports the masked draws the kernels consume for every
@@ -543,7 +546,8 @@ def case_production_loop_vs_oracle(name, lib, device, B, counts, steps, predicto
     `subset`: batch rows the oracle replays (draws and prior are sliced on the device before the copy to the host).  Only for the
     corrector-free predictor loop: with corrector None every update of a complex reads that complex's state, score and draws alone
     -- no batch-mean norm couples the complexes, as the Langevin corrector's and S4's step sizes do -- so the rows of a subset
-    evolve exactly as they do inside the full batch.  `expect_route`: {plan query: value} the plan must have selected."""
+    evolve exactly as they do inside the full batch.  `expect_route`: {plan query: value} the plan must have selected.  `flags`: a
+    (B, N) node mask of the caller's (default: make_flags(B, N, counts), the live nodes a prefix)."""
     s4 = predictor == "S4"
     if subset is not None:
         assert corrector == "None" and not s4, "a subset replay needs complexes that do not couple through batch-mean norms"
@@ -555,7 +559,9 @@ def case_production_loop_vs_oracle(name, lib, device, B, counts, steps, predicto
     N, Fd = cfg["data"]["max_node_num"], cfg["data"]["max_feat_num"]
     names = ["x", "adj"] + (["rank2"] if is_cc else [])
     nt = len(names)
-    flags = make_flags(B, N, counts)
+    if flags is None:
+        flags = make_flags(B, N, counts)
+    assert tuple(flags.shape) == (B, N)
     rows = list(range(B)) if subset is None else list(subset)
     Bo = len(rows)
 
@@ -1063,16 +1069,18 @@ def case_kat_hodge_layers(lib, device):
 
 
 def case_env_switches_bitwise(lib, device, switches, B=512, steps=2, name="ccsd_community_small_CC", counts=(20, 12, 16, 18, 14, 20),
-                              predictor="Euler", corrector="Langevin", snr=0.05, scale_eps=0.7):
+                              predictor="Euler", corrector="Langevin", snr=0.05, scale_eps=0.7, flags=None, expect=None):
     """Instances of the SAME arithmetic selected by plan switches (read from the environment at plan creation) must agree BIT FOR
     BIT: the production loop and the three scores with no switch set against every entry of `switches` (dicts of environment
     variables).  Used for the one-workgroup-per-complex rank-2 kernels of the community_small geometry (k_gemm_h_full, k_hp_full)
-    against the tile kernels they replace."""
+    against the tile kernels they replace.  `flags`: a (B, N) node mask of the caller's (default: make_flags(B, N, counts)); `expect`:
+    one {plan query: value} per plan, the default plan first, that the plan must answer."""
     meta, parts = load_ckpt_np(name)
     cfg, is_cc = meta["config"], meta["is_cc"]
     N, Fd = cfg["data"]["max_node_num"], cfg["data"]["max_feat_num"]
     names = ["x", "adj"] + (["rank2"] if is_cc else [])
-    flags = make_flags(B, N, list(counts)).to(device)
+    flags = (make_flags(B, N, list(counts)) if flags is None else flags).to(device)
+    assert tuple(flags.shape) == (B, N)
     kw = dict(shape_x=(B, N, Fd), shape_adj=(B, N, N), predictor=predictor, corrector=corrector, snr=snr, scale_eps=scale_eps, n_steps=1,
               probability_flow=False, continuous=True, denoise=True, eps=1e-4)
     if is_cc:
@@ -1091,6 +1099,8 @@ def case_env_switches_bitwise(lib, device, switches, B=512, steps=2, name="ccsd_
             fn = solver.get_pc_sampler(device=device, rng="philox", seed=11, max_steps=steps, lib=lib, **skw, **kw)
             res = fn(*ms, flags)
             eng = fn.engine()
+            for what, v in (expect[len(outs)] if expect else {}).items():
+                assert eng.query(what) == v, f"{name} B={B} under {env}: plan query {what} = {eng.query(what)}, expected {v}"
             st = eng.alloc_state(B)
             eng.init_state(flags, st, None, 3, 0)
             scores = [eng.score(t, st[0], st[1], st[2] if is_cc else None, flags).clone() for t in range(len(names))]
