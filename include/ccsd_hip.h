@@ -137,7 +137,30 @@ void ccsd_plan_destroy(ccsd_plan_t* plan);
 size_t ccsd_weight_count(const ccsd_config_t* cfg);
 /* E and K for the config */
 void ccsd_rank2_dims(const ccsd_config_t* cfg, int32_t* E, int64_t* K);
-/* bytes of device scratch the step/run calls need for batch B */
+/* bytes of device scratch the step/run calls need for batch B
+ *
+ * THE WORKSPACE CONTRACT (every call that takes `workspace`, `workspace_bytes`; pinned by tests/purity_cases.py):
+ *   - Contents on entry are ARBITRARY: stale bytes of another call, another batch size or another plan, NaN patterns, anything.  No
+ *     call clears the workspace as a whole; whatever a kernel reads it either wrote earlier in the same call (or in the first call of
+ *     a pair, below) or discards with a select.  So one workspace may serve several plans in turn.
+ *   - Nothing outside [workspace, workspace + ccsd_workspace_bytes(plan, B)) is touched, whatever `workspace_bytes` says beyond that;
+ *     a smaller `workspace_bytes` returns CCSD_ERR_WORKSPACE and launches nothing.
+ *   - A call is self-contained, with these exceptions, which carry state through the workspace (the raw network outputs and the
+ *     noise norms of the norms pass): ccsd_corrector_norms -> ccsd_corrector_apply and ccsd_corrector_norms -> ccsd_s4_apply.  The
+ *     second call must receive the same workspace, plan, B and stream, with no other call on that workspace in between.
+ *     ccsd_sampler_run(_ex) is one call: everything it carries from step to step, the third state buffer of n_steps > 1 included,
+ *     it writes itself.  The reduce hook sees the six sums INSIDE the workspace.
+ *   - Alignment: the base must be a multiple of 256 bytes.  The buffers are carved from the base at multiples of 256 bytes, and the
+ *     kernels read them with 16-byte loads (float4 rows of H at stride h_ld(E), the Kp / Ep byte tables in words), so a base that is
+ *     not 16-byte aligned is undefined behaviour; 256 is what the carve assumes and what every hipMalloc / torch allocation gives.
+ *   The plan-free operations (ccsd_mmd, ccsd_eigvalsh, ...) state the size and the 8-byte alignment of their scratch with their
+ *   declarations; the same holds for it: arbitrary contents on entry, nothing touched outside the stated size.
+ *
+ * HOST SYNCHRONISATION.  Every call only enqueues work on `stream` and returns, except: ccsd_plan_create and ccsd_plan_destroy
+ * (uploads, frees); ccsd_init_state, ccsd_noise_draws and ccsd_noise_draws_at when B exceeds every B these three have seen on the
+ * plan (the plan-owned off-bit buffer grows: the DEVICE is synchronised, then the buffer is reallocated); ccsd_profile_read (waits
+ * for its events).  No other call waits for the device, allocates or frees.  (ccsd_amd's Python wrapper of ccsd_nspdk_features
+ * reads the row counts back to compact the rows: that round trip is the wrapper's, not the C call's.) */
 size_t ccsd_workspace_bytes(const ccsd_plan_t* plan, int32_t B);
 
 const char* ccsd_last_error(void);
