@@ -123,17 +123,13 @@ struct Route {
     int corrector_flat = 0, predictor_flat = 0;
 };
 
-struct ccsd_plan {
+struct ccsd_plan : PlanRouteOut {   // (hbx, hdm, afin_lg, npacked: the planner's outputs beside PlanD, ccsd_plan.h)
     ccsd_config_t cfg;
     PlanD h;                    // host copy
-    HodgeBaseD hbx[CCSD_LG_MAXHB];   // every HodgeBaselineLayer of ScoreNetworkA_Base_CC (h.hb holds the first two): arguments of the k_lg_hb_* launches
-    MlpD hdm[CCSD_MAXHL + CCSD_MAXHLX];   // route plans with two or more HodgeAdjAttentionLayers: the chained mlp_attention of k_lg_hd_dense (PlanBuilder::hdm)
-    MlpD afin_lg;               // route plans whose final MLP has 57 to 64 channels: its chained form (PlanBuilder::afin_lg; chain == 0: h.a_fin is chained)
     PlanD* d = nullptr;         // device copy
     float* w = nullptr;         // device weights
     float* wp = nullptr;        // device: zero-padded copies of the chain MLPs' linears (mlp_chain_tile)
     unsigned char* hpairs = nullptr;   // device: (e, e2), e <= e2, row-major: unordered pairs of the dense hodge layer
-    size_t npacked = 0;
     unsigned char* edges = nullptr;
     unsigned long long* cells = nullptr;
     std::vector<ccsd_step_coef_t> coef;  // [diff_steps][3]
@@ -391,6 +387,48 @@ extern "C" void ccsd_plan_destroy(ccsd_plan_t* plan) {
     delete plan;
 }
 
+// the weight blob on the device, ScoreNetworkF's zero-padded blocks behind it (PlanD::f_blk)
+static int upload_weights(ccsd_plan* pl, const float* weights, size_t n_weights) {
+    const size_t wtotal = pl->h.f_blk >= 0 ? (size_t)pl->h.f_blk + CCSD_FBLK_FLOATS : n_weights;
+    RT_CHECK(rt_malloc((void**)&pl->w, wtotal * sizeof(float)));
+    RT_CHECK(rt_h2d(pl->w, weights, n_weights * sizeof(float)));
+    if (pl->h.f_blk >= 0) {
+        std::vector<float> blk(CCSD_FBLK_FLOATS);
+        ccsd_pack_fnet_blocks(&pl->h, weights, blk.data());
+        RT_CHECK(rt_h2d(pl->w + pl->h.f_blk, blk.data(), blk.size() * sizeof(float)));
+    }
+    return CCSD_OK;
+}
+// the max-dynamic-LDS attribute of every kernel of the plan's route that may ask for more than 64 KB
+static int set_lds_attributes(const ccsd_plan* pl) {
+    const Route& r = pl->rt;
+    const int E = pl->h.E;
+    const size_t xlds = (size_t)pl->h.xa_lds_floats * 4;
+    if (xlds > 64 * 1024) {
+        RT_CHECK(rt_set_max_dyn_smem((const void*)r.xa->fn, xlds));
+        if (r.xa_twin) RT_CHECK(rt_set_max_dyn_smem((const void*)r.xa_twin->fn, xlds));
+    }
+    if (r.r2 && r.r2_lds > 64 * 1024) RT_CHECK(rt_set_max_dyn_smem((const void*)r.r2->fn, r.r2_lds));
+    if (r.lg && lg_nmlp_lds(pl->h) > 64 * 1024) RT_CHECK(rt_set_max_dyn_smem((const void*)k_lg_nmlp, lg_nmlp_lds(pl->h)));
+    if (r.lg && pl->h.hb_L > 1) {
+        size_t v = 0;
+        for (int l = 0; l + 1 < pl->h.hb_L; ++l) if (lg_hb_dense_lds(pl->hbx[l]) > v) v = lg_hb_dense_lds(pl->hbx[l]);
+        if (v > 64 * 1024) RT_CHECK(rt_set_max_dyn_smem((const void*)k_lg_hb_dense, v));
+    }
+    // (k_lg_hd_dense stays below 64 KB: at most 8 channels of 2 x 16 rows of 33 floats + 256 pairs)
+    if (r.lg && r.h_general && hodge_value_lds(E) > 64 * 1024)
+        RT_CHECK(rt_set_max_dyn_smem(r.h_wide ? (const void*)k_hodge_value_w : (const void*)k_hodge_value, hodge_value_lds(E)));
+#ifndef CCSD_EMU
+    if (r.hp_full_modes) {      // k_hp_full: 66.6 KB of dynamic LDS
+        RT_CHECK(rt_set_max_dyn_smem((const void*)k_hp_full<CCSD_FULL_E, CCSD_FULL_K, 1>, HP_FULL_LDS));
+        RT_CHECK(rt_set_max_dyn_smem((const void*)k_hp_full<CCSD_FULL_E, CCSD_FULL_K, 2>, HP_FULL_LDS));
+    }
+#endif
+    return CCSD_OK;
+}
+
+// Plans the networks (ccsd_build_plan), uploads the plan, the weights and their packed copies and the enumeration tables (the builders and
+// packers of ccsd_plan.h), resolves the route.  Every failure leaves through the one guard.
 extern "C" int ccsd_plan_create(const ccsd_config_t* cfg, const float* weights, size_t n_weights,
                                 const ccsd_step_coef_t* step_coef, ccsd_plan_t** out) {
     if (!cfg || !weights || !step_coef || !out) return set_err(CCSD_ERR_INVALID, "NULL argument");
@@ -403,12 +441,9 @@ extern "C" int ccsd_plan_create(const ccsd_config_t* cfg, const float* weights, 
     pb.lg_force = k.lg_force; pb.xa_pass = k.xa_pass; pb.xa_gch = k.xa_gch; pb.no_mlp_wt = k.no_mlp_wt; pb.verbose = k.verbose;
     pl->nweights = ccsd_build_plan(cfg, &pl->h, pb);
     if (pb.status != CCSD_OK) return set_err(pb.status, pb.err);
+    static_cast<PlanRouteOut&>(*pl) = pb;
     pl->rt.lg = pb.lg; pl->rt.h_wide = pb.h_wide;
-    memcpy(pl->hbx, pb.hbx, sizeof(pl->hbx));
-    memcpy(pl->hdm, pb.hdm, sizeof(pl->hdm));
-    pl->afin_lg = pb.afin_lg;
     pl->h.geo_off = k.geo_off;
-    pl->npacked = (size_t)pb.pcur;
     if (pl->nweights != n_weights)
         return set_err(CCSD_ERR_WEIGHTS, "weight blob has " + std::to_string(n_weights) + " floats, config needs " +
                                              std::to_string(pl->nweights));
@@ -417,90 +452,21 @@ extern "C" int ccsd_plan_create(const ccsd_config_t* cfg, const float* weights, 
     if (cfg->diff_steps < 1 || cfg->n_corr_steps < 0) return set_err(CCSD_ERR_INVALID, "bad step counts");
     ccsd_fold_fnet(&pl->h, weights);
     pl->coef.assign(step_coef, step_coef + (size_t)cfg->diff_steps * 3);
-    // enumeration tables (get_cells, cc_utils.py:72-94): edges = combinations(range(N),2) row-major;
-    // cells = combinations(range(N),k) for k = d_min..d_max, lexicographic, as node bitmasks
-    const int N = cfg->N, E = pl->h.E, K = pl->h.K;
-    std::vector<unsigned char> edges((size_t)2 * E + 2);
-    {
-        int e = 0;
-        for (int i = 0; i < N; ++i)
-            for (int j = i + 1; j < N; ++j) { edges[2 * e] = (unsigned char)i; edges[2 * e + 1] = (unsigned char)j; ++e; }
-    }
-    std::vector<unsigned long long> cells((size_t)K + 1);
-    if (cfg->is_cc) {
-        size_t c = 0;
-        std::vector<int> idx;
-        for (int k = cfg->d_min; k <= cfg->d_max; ++k) {
-            idx.resize(k);
-            for (int i = 0; i < k; ++i) idx[i] = i;
-            while (true) {
-                unsigned long long m = 0;
-                for (int i = 0; i < k; ++i) m |= 1ull << idx[i];
-                cells[c++] = m;
-                int i = k - 1;
-                while (i >= 0 && idx[i] == N - k + i) --i;
-                if (i < 0) break;
-                ++idx[i];
-                for (int j = i + 1; j < k; ++j) idx[j] = idx[j - 1] + 1;
-            }
-        }
-        if ((int)c != K) return set_err(CCSD_ERR_INVALID, "cell enumeration mismatch");
-    }
+    const int E = pl->h.E;
+    const std::vector<unsigned char> edges = ccsd_edge_table(cfg->N, E);
+    std::vector<unsigned long long> cells;
+    if (!ccsd_cell_table(cfg, pl->h.K, &cells)) return set_err(CCSD_ERR_INVALID, "cell enumeration mismatch");
     RT_CHECK(rt_malloc((void**)&pl->d, sizeof(PlanD)));
     RT_CHECK(rt_h2d(pl->d, &pl->h, sizeof(PlanD)));
+    if (int st = upload_weights(pl, weights, n_weights)) return st;
     {
-        const size_t wtotal = pl->h.f_blk >= 0 ? (size_t)pl->h.f_blk + CCSD_FBLK_FLOATS : n_weights;
-        RT_CHECK(rt_malloc((void**)&pl->w, wtotal * sizeof(float)));
-        RT_CHECK(rt_h2d(pl->w, weights, n_weights * sizeof(float)));
-        if (pl->h.f_blk >= 0) {
-            std::vector<float> blk(CCSD_FBLK_FLOATS);
-            ccsd_pack_fnet_blocks(&pl->h, weights, blk.data());
-            RT_CHECK(rt_h2d(pl->w + pl->h.f_blk, blk.data(), blk.size() * sizeof(float)));
-        }
-    }
-    {
-        std::vector<float> packed(pl->npacked + 4, 0.f);
-        ccsd_pack_mlp(pl->h.x_fin, weights, packed.data());
-        for (int l = 0; l < pl->h.a_L; ++l) {
-            ccsd_pack_mlp(pl->h.al[l].mlp, weights, packed.data()); ccsd_pack_mlp(pl->h.al[l].mc, weights, packed.data());
-            ccsd_pack_qkv(pl->h.al[l], weights, packed.data()); ccsd_pack_mc(pl->h.al[l], weights, packed.data());
-        }
-        if (pl->h.x_gmh) for (int l = 0; l < pl->h.x_depth; ++l) {
-            ccsd_pack_mlp(pl->h.gl[l].mlp, weights, packed.data()); ccsd_pack_mlp(pl->h.gl[l].mc, weights, packed.data());
-            ccsd_pack_qkv(pl->h.gl[l], weights, packed.data()); ccsd_pack_mc(pl->h.gl[l], weights, packed.data());
-        }
-        for (int l = 0; l < pl->h.hb_L; ++l) {   // mlp_hodge of the dense layers; transposed copies of the BaselineBlocks' weights
-            const HodgeBaseD& h = pl->hbx[l];
-            ccsd_pack_mlp(h.mh, weights, packed.data());
-            for (int c = 0; c < h.cin; ++c) {
-                const float* blk = weights + h.blk_base + (size_t)c * h.blk_stride;    // W1[hid][E] b1[hid] W2[E][hid] b2[E]
-                const float* w2 = blk + h.hid * E + h.hid;
-                for (int e = 0; e < E; ++e)
-                    for (int hh = 0; hh < h.hid; ++hh) {
-                        packed[(size_t)h.w2t + ((size_t)c * h.hid + hh) * E + e] = w2[e * h.hid + hh];
-                        packed[(size_t)h.w1t + ((size_t)c * E + e) * h.hid + hh] = blk[hh * E + e];
-                    }
-            }
-        }
-        ccsd_pack_mlp(pl->h.a_fin, weights, packed.data());
-        if (pl->rt.lg) {
-            for (int l = 0; l < pl->h.h_L; ++l) ccsd_pack_mlp(pl->hdm[l], weights, packed.data());     // (the last layer's: wide plans only)
-            if (pl->afin_lg.chain) ccsd_pack_mlp(pl->afin_lg, weights, packed.data());
-        }
-        for (int l = 0; l < pl->h.h_L; ++l) {   // Wcat^T of the hodge projections for k_r2
-            const HodgeLayerD& h = ccsd_hl(pl->h, l);
-            const int Kp = (K + 31) & ~31;
-            for (int k = 0; k < K; ++k)
-                for (int n = 0; n < h.wc; ++n) packed[(size_t)h.wcatT + (size_t)n * Kp + k] = weights[(size_t)h.wcat + (size_t)k * h.wc + n];
-        }
+        const std::vector<float> packed = ccsd_pack_weights(pl->h, *pl, pl->rt.lg, weights);
         RT_CHECK(rt_malloc((void**)&pl->wp, packed.size() * sizeof(float)));
         RT_CHECK(rt_h2d(pl->wp, packed.data(), packed.size() * sizeof(float)));
     }
     if (pl->h.h_L > 1 && !pl->rt.lg) {     // (k_xa's pair table; the tiled route walks tiles)
         if (E > 255) return set_err(CCSD_ERR_UNSUPPORTED, "dense hodge layer needs E <= 255");
-        std::vector<unsigned char> hp;
-        for (int e = 0; e < E; ++e)
-            for (int e2 = e; e2 < E; ++e2) { hp.push_back((unsigned char)e); hp.push_back((unsigned char)e2); }
+        const std::vector<unsigned char> hp = ccsd_hodge_pairs(E);
         RT_CHECK(rt_malloc((void**)&pl->hpairs, hp.size()));
         RT_CHECK(rt_h2d(pl->hpairs, hp.data(), hp.size()));
     }
@@ -509,45 +475,8 @@ extern "C" int ccsd_plan_create(const ccsd_config_t* cfg, const float* weights, 
     RT_CHECK(rt_malloc((void**)&pl->cells, cells.size() * sizeof(unsigned long long)));
     RT_CHECK(rt_h2d(pl->cells, cells.data(), cells.size() * sizeof(unsigned long long)));
     if (int st = resolve_route(pl)) return st;
-    {
-        const Route& r = pl->rt;
-        const size_t xlds = (size_t)pl->h.xa_lds_floats * 4;
-        if (xlds > 64 * 1024) {
-            RT_CHECK(rt_set_max_dyn_smem((const void*)r.xa->fn, xlds));
-            if (r.xa_twin) RT_CHECK(rt_set_max_dyn_smem((const void*)r.xa_twin->fn, xlds));
-        }
-        if (r.r2 && r.r2_lds > 64 * 1024) RT_CHECK(rt_set_max_dyn_smem((const void*)r.r2->fn, r.r2_lds));
-        if (r.lg && lg_nmlp_lds(pl->h) > 64 * 1024) RT_CHECK(rt_set_max_dyn_smem((const void*)k_lg_nmlp, lg_nmlp_lds(pl->h)));
-        if (r.lg && pl->h.hb_L > 1) {
-            size_t v = 0;
-            for (int l = 0; l + 1 < pl->h.hb_L; ++l) if (lg_hb_dense_lds(pl->hbx[l]) > v) v = lg_hb_dense_lds(pl->hbx[l]);
-            if (v > 64 * 1024) RT_CHECK(rt_set_max_dyn_smem((const void*)k_lg_hb_dense, v));
-        }
-        // (k_lg_hd_dense stays below 64 KB: at most 8 channels of 2 x 16 rows of 33 floats + 256 pairs)
-        if (r.lg && r.h_general && hodge_value_lds(E) > 64 * 1024)
-            RT_CHECK(rt_set_max_dyn_smem(r.h_wide ? (const void*)k_hodge_value_w : (const void*)k_hodge_value, hodge_value_lds(E)));
-#ifndef CCSD_EMU
-        if (r.hp_full_modes) {      // k_hp_full: 66.6 KB of dynamic LDS
-            RT_CHECK(rt_set_max_dyn_smem((const void*)k_hp_full<CCSD_FULL_E, CCSD_FULL_K, 1>, HP_FULL_LDS));
-            RT_CHECK(rt_set_max_dyn_smem((const void*)k_hp_full<CCSD_FULL_E, CCSD_FULL_K, 2>, HP_FULL_LDS));
-        }
-#endif
-    }
-    if (const char* path = k.dump_plan) {     // tools/bake_plan.py: the plan's architecture bytes as a C header
-        const char* nm = k.dump_plan_name ? k.dump_plan_name : "QM9";
-        std::vector<unsigned char> bytes(sizeof(PlanD));
-        ccsd_plan_arch_bytes(pl->h, bytes.data());
-        if (FILE* f = fopen(path, "w")) {
-            fprintf(f, "// GENERATED by tools/bake_plan.py (do not edit): the PlanD of a shipped configuration at its bench batch as a compile-time\n"
-                       "// constant (architecture bytes: ccsd_plan_arch_bytes, the weight-derived affine fold zeroed).  The baked kernel instances read\n"
-                       "// their plan from it instead of from memory; the host selects them only for plans whose architecture bytes are equal.\n"
-                       "#pragma once\n#define CCSD_BAKED_%s_SIZE %zu\n#define CCSD_BAKED_%s_A_L %d      /* AttentionLayers of ScoreNetworkA: unroll count */\n"
-                       "alignas(16) static constexpr unsigned char CCSD_BAKED_%s_PLAN[CCSD_BAKED_%s_SIZE] = {", nm, sizeof(PlanD), nm, pl->h.a_L, nm, nm);
-            for (size_t i = 0; i < bytes.size(); ++i) fprintf(f, "%s%u,", (i % 40) ? "" : "\n    ", (unsigned)bytes[i]);
-            fprintf(f, "\n};\n");
-            fclose(f);
-        }
-    }
+    if (int st = set_lds_attributes(pl)) return st;
+    if (k.dump_plan) ccsd_dump_plan(pl->h, k.dump_plan, k.dump_plan_name ? k.dump_plan_name : "QM9");
     *out = guard.release();
     return CCSD_OK;
 }

@@ -29,6 +29,9 @@
 //                    two matrices whose spectra the reference scores (normalised graph Laplacian, hodge Laplacian F F^T)
 //   ccsd_k_lift.h    k_lift_paths, k_lift_cycles, k_lift_dense: graphs lifted to combinatorial complexes (rank-2 cells from the paths of
 //                    three nodes or from networkx's cycle basis) as ccsd_finish's cell bitmask and descriptors, and the dense incidence tensor
+//   ccsd_plan.h      PlanD (what the kernels read of a plan) and the planner: ccsd_build_plan = plan_geometry, plan_xnet, plan_anet_graph,
+//                    plan_anet_hodge, plan_fnet, plan_route (k_xa's LDS layout: xa_layout per candidate, plan_xa_layout the search);
+//                    the packers and table builders of plan creation (ccsd_pack_*, ccsd_edge_table, ccsd_cell_table, ccsd_hodge_pairs)
 //   ccsd_api.h       host side of the C ABI: plan, route, workspace, launchers, the sampler loop; its last line includes
 //   ccsd_api_samples.h   the host side of the plan-free entry points (ccsd_quantize .. ccsd_lift: operations on finished samples)
 // The product library is built from several translation units compiled in parallel (ccsd_hip.hip: C ABI + the small kernels;

@@ -53,7 +53,6 @@ struct AttnLayerD {
     int ci0, co0;             // first input / output channel inside the channel stack
     int attn_base, attn_stride;  // per-channel block: Wq[fin][ad] bq Wk bk Wv[fin][fo] bv
     int conv_mlp;                // conv="MLP": Q / K blocks are W1[2ad][fin] b1[2ad] W2[ad][2ad] b2[ad] (attention.py:168-178)
-    int w_lo, w_hi;              // blob range of this layer's weights (attention blocks, mlp, multi_channel)
     MlpD mlp, mc;
     // packed buffer (conv = "GCN"): per input channel [fin][cp] weights + [cp] biases with the Q | K | V columns side by side,
     // zero padded to cp = pad16(2 adim + fout) -- the B operand / bias of gcn_tile_multi without column-part arithmetic
@@ -84,7 +83,7 @@ struct PlanD {
     int N, F, E, K, is_cc;
     float snr, seps;
     // ScoreNetworkX
-    int x_depth, x_nhid, x_fdim, x_wlo, x_whi;
+    int x_depth, x_nhid, x_fdim;
     int x_gw[CCSD_MAXL], x_gb[CCSD_MAXL];
     MlpD x_fin;
     // ScoreNetworkA(_CC)
@@ -101,10 +100,8 @@ struct PlanD {
     // k_xa LDS carve-up (float offsets) and strides
     int ldn, ldp, pch;          // node-row stride; final-MLP chunk: stride, pairs per chunk
     int cg, pchp, ldpp, pw_pair; // attention channels per group; edge-MLP chunk: pairs, stride, widest hidden layer
-    int o_flags, o_x, o_adj, o_an, o_xw, o_qkv, o_tmp, o_xcat, o_h1, o_h2, o_chan, o_att, o_xcur, o_xnext,
-        o_vcat, o_c0, o_c1, o_acoef, o_hq, o_hatt, o_h1m, o_hd, o_red;
+    int o_flags, o_x, o_adj, o_an, o_xcat, o_h1, o_h2, o_chan, o_att, o_xcur, o_xnext, o_vcat, o_c0, o_hq, o_hd, o_red;
     int xa_lds_floats;
-    int o_wst, wst_floats;      // weight staging buffer (0 floats: weights are read in place)
     int o_hw, hw_stride;        // zero-padded hodge mlp_attention weight blocks (stride between the two layers)
     int o_deg;                  // degree scratch of the dense hodge layer
     int o_edge;                 // LDS copy of the edge table (E ints)
@@ -153,6 +150,21 @@ static inline void ccsd_plan_arch_bytes(const PlanD& p, unsigned char* out) {
     for (int j = 0; j < CCSD_MAXCN; ++j) q.f_betas[j] = 0.f;
     memcpy(out, &q, sizeof(PlanD));
 }
+// ... written as a C header (CCSD_DUMP_PLAN; tools/bake_plan.py).  nm: the macro infix, CCSD_BAKED_<nm>_PLAN
+static inline void ccsd_dump_plan(const PlanD& p, const char* path, const char* nm) {
+    unsigned char bytes[sizeof(PlanD)];
+    ccsd_plan_arch_bytes(p, bytes);
+    FILE* f = fopen(path, "w");
+    if (!f) return;
+    fprintf(f, "// GENERATED by tools/bake_plan.py (do not edit): the PlanD of a shipped configuration at its bench batch as a compile-time\n"
+               "// constant (architecture bytes: ccsd_plan_arch_bytes, the weight-derived affine fold zeroed).  The baked kernel instances read\n"
+               "// their plan from it instead of from memory; the host selects them only for plans whose architecture bytes are equal.\n"
+               "#pragma once\n#define CCSD_BAKED_%s_SIZE %zu\n#define CCSD_BAKED_%s_A_L %d      /* AttentionLayers of ScoreNetworkA: unroll count */\n"
+               "alignas(16) static constexpr unsigned char CCSD_BAKED_%s_PLAN[CCSD_BAKED_%s_SIZE] = {", nm, sizeof(PlanD), nm, p.a_L, nm, nm);
+    for (size_t i = 0; i < sizeof(PlanD); ++i) fprintf(f, "%s%u,", (i % 40) ? "" : "\n    ", (unsigned)bytes[i]);
+    fprintf(f, "\n};\n");
+    fclose(f);
+}
 
 static inline int64_t ccsd_comb(int n, int k) {
     if (k < 0 || k > n) return 0;
@@ -168,7 +180,20 @@ static inline void ccsd_dims(const ccsd_config_t* c, int* E, int64_t* K) {
     *K = k;
 }
 
-struct PlanBuilder {
+// What the planner decides beside PlanD, for the tiled route's launches and the packed buffer: ccsd_plan keeps a copy (one assignment).
+// Its verdicts lg and h_wide are not in here: they are fields of the plan's Route (ccsd_api.h), which resolve_route completes
+struct PlanRouteOut {
+    HodgeBaseD hbx[CCSD_LG_MAXHB] = {};   // every HodgeBaselineLayer of ScoreNetworkA_Base_CC (PlanD::hb holds the first two): arguments of the k_lg_hb_* launches
+    // route plans with two or more HodgeAdjAttentionLayers: mlp_attention of every layer but the last with packed copies for
+    // mlp_chain_tile (k_lg_hd_dense).  Kept out of PlanD, and reserved behind everything else in the packed buffer: no plan k_xa serves moves.
+    // Plans with hodge MLPs wider than 8 (h_wide): EVERY layer's -- the last layer's diagonal runs the chain too (k_lg_hd_diag_w, k_lg_hodge1_w)
+    MlpD hdm[CCSD_MAXHL + CCSD_MAXHLX] = {};
+    // wide plans whose PlanD::a_fin has no chained shape, 57 to 64 channels (k_xa runs those through block_linear, and narrow plans with such
+    // a final MLP stay with it): the final MLP with packed copies in the route's own shape (CCSD_CHAIN_AFIN_LG, k_lg_fin_w); chain == 0: none
+    MlpD afin_lg = {};
+    size_t npacked = 0;                   // floats of the packed buffer
+};
+struct PlanBuilder : PlanRouteOut {
     int cur = 0;
     int pcur = 0;     // packed (chain) weight buffer
     // reserve padded copies of an MLP's linears for mlp_chain_tile
@@ -187,18 +212,10 @@ struct PlanBuilder {
     int xa_gch = 0;     // CCSD_XA_GCH: the channel stack in the HBM workspace first
     int verbose = 0;    // CCSD_VERBOSE
     int lg = 0;         // out: the plan takes the tiled graph-network route (ccsd_k_lg.h) instead of k_xa
-    HodgeBaseD hbx[CCSD_LG_MAXHB] = {};   // out: every HodgeBaselineLayer of ScoreNetworkA_Base_CC (the route's k_lg_hb_* launches)
-    // out (route plans with two or more HodgeAdjAttentionLayers): mlp_attention of every layer but the last with packed copies for
-    // mlp_chain_tile (k_lg_hd_dense).  Kept out of PlanD, and reserved behind everything else in the packed buffer: no plan k_xa serves moves
-    MlpD hdm[CCSD_MAXHL + CCSD_MAXHLX] = {};
     // out: some Linear of the hodge branch's MLPs is wider than CCSD_SMALLW (num_linears_h >= 2, hid = 9 .. 16).  Such a plan takes the route
-    // at any N, never k_xa or k_r2 (their per-thread small_mlp stays 8 wide), and hdm holds EVERY layer's mlp_attention: the last layer's
-    // diagonal runs the chain too (k_lg_hd_diag_w, k_lg_hodge1_w)
+    // at any N, never k_xa or k_r2 (their per-thread small_mlp stays 8 wide)
     int h_wide = 0;
-    // out (wide plans whose PlanD::a_fin has no chained shape, 57 to 64 channels -- k_xa runs those through block_linear, and narrow plans
-    // with such a final MLP stay with it): the final MLP with packed copies in the route's own shape (CCSD_CHAIN_AFIN_LG, k_lg_fin_w)
-    MlpD afin_lg = {};
-    // the packed copies only route plans read, reserved behind everything else in the packed buffer (no plan k_xa serves moves)
+    // the packed copies only route plans read (hdm, afin_lg), reserved behind everything else in the packed buffer (no plan k_xa serves moves)
     void route_copies(const PlanD& p) {
         if (h_wide && !p.a_fin.chain) {
             afin_lg = p.a_fin; chainify(afin_lg, CCSD_CHAIN_AFIN_LG);
@@ -218,6 +235,7 @@ struct PlanBuilder {
     void fail(int st, const std::string& m) {
         if (status == CCSD_OK) { status = st; err = m; }
     }
+    bool reject(int st, const std::string& m) { fail(st, m); return false; }   // (for the planning steps, which return whether to go on)
     MlpD mlp(int n, int in, int hid, int out) {
         MlpD m{};
         m.n = n; m.in = in; m.hid = hid; m.out = out;
@@ -300,19 +318,90 @@ static inline void ccsd_pack_qkv(const AttnLayerD& a, const float* w, float* pac
     }
 }
 
+// transposed copies of a HodgeBaselineLayer's BaselineBlocks (HodgeBaseD::w2t, w1t)
+static inline void ccsd_pack_hb_blocks(const HodgeBaseD& h, int E, const float* w, float* packed) {
+    for (int c = 0; c < h.cin; ++c) {
+        const float* blk = w + h.blk_base + (size_t)c * h.blk_stride;    // W1[hid][E] b1[hid] W2[E][hid] b2[E]
+        const float* w2 = blk + h.hid * E + h.hid;
+        for (int e = 0; e < E; ++e)
+            for (int hh = 0; hh < h.hid; ++hh) {
+                packed[(size_t)h.w2t + ((size_t)c * h.hid + hh) * E + e] = w2[e * h.hid + hh];
+                packed[(size_t)h.w1t + ((size_t)c * E + e) * h.hid + hh] = blk[hh * E + e];
+            }
+    }
+}
+// The packed weight buffer (ccsd_plan::wp; 4 floats of slack behind it): every copy the planner reserved, zero padded.  lg: the plan takes
+// the tiled route, whose own copies (x.hdm, x.afin_lg) are packed too
+static inline std::vector<float> ccsd_pack_weights(const PlanD& p, const PlanRouteOut& x, int lg, const float* w) {
+    std::vector<float> packed(x.npacked + 4, 0.f);
+    float* out = packed.data();
+    auto attn = [&](const AttnLayerD& a) { ccsd_pack_mlp(a.mlp, w, out); ccsd_pack_mlp(a.mc, w, out); ccsd_pack_qkv(a, w, out); ccsd_pack_mc(a, w, out); };
+    ccsd_pack_mlp(p.x_fin, w, out);
+    for (int l = 0; l < p.a_L; ++l) attn(p.al[l]);
+    if (p.x_gmh) for (int l = 0; l < p.x_depth; ++l) attn(p.gl[l]);
+    for (int l = 0; l < p.hb_L; ++l) {      // mlp_hodge of the dense layers; the BaselineBlocks' weights
+        ccsd_pack_mlp(x.hbx[l].mh, w, out);
+        ccsd_pack_hb_blocks(x.hbx[l], p.E, w, out);
+    }
+    ccsd_pack_mlp(p.a_fin, w, out);
+    if (lg) {
+        for (int l = 0; l < p.h_L; ++l) ccsd_pack_mlp(x.hdm[l], w, out);     // (the last layer's: wide plans only)
+        if (x.afin_lg.chain) ccsd_pack_mlp(x.afin_lg, w, out);
+    }
+    const int Kp = (p.K + 31) & ~31;
+    for (int l = 0; l < p.h_L; ++l) {       // Wcat^T of the hodge projections for k_r2
+        const HodgeLayerD& h = ccsd_hl(p, l);
+        for (int k = 0; k < p.K; ++k)
+            for (int n = 0; n < h.wc; ++n) out[(size_t)h.wcatT + (size_t)n * Kp + k] = w[(size_t)h.wcat + (size_t)k * h.wc + n];
+    }
+    return packed;
+}
+
+// Enumeration tables (get_cells, cc_utils.py:72-94).  Edges: combinations(range(N), 2) row-major, (i, j) in bytes (2 bytes of slack)
+static inline std::vector<unsigned char> ccsd_edge_table(int N, int E) {
+    std::vector<unsigned char> edges((size_t)2 * E + 2);
+    int e = 0;
+    for (int i = 0; i < N; ++i)
+        for (int j = i + 1; j < N; ++j) { edges[2 * e] = (unsigned char)i; edges[2 * e + 1] = (unsigned char)j; ++e; }
+    return edges;
+}
+// Cells: combinations(range(N), k) for k = d_min .. d_max, lexicographic, as node bitmasks (one word of slack).  false: not K of them
+static inline bool ccsd_cell_table(const ccsd_config_t* cfg, int K, std::vector<unsigned long long>* cells) {
+    cells->assign((size_t)K + 1, 0ull);
+    if (!cfg->is_cc) return true;
+    const int N = cfg->N;
+    size_t c = 0;
+    std::vector<int> idx;
+    for (int k = cfg->d_min; k <= cfg->d_max; ++k) {
+        idx.resize(k);
+        for (int i = 0; i < k; ++i) idx[i] = i;
+        while (true) {
+            unsigned long long m = 0;
+            for (int i = 0; i < k; ++i) m |= 1ull << idx[i];
+            (*cells)[c++] = m;
+            int i = k - 1;
+            while (i >= 0 && idx[i] == N - k + i) --i;
+            if (i < 0) break;
+            ++idx[i];
+            for (int j = i + 1; j < k; ++j) idx[j] = idx[j - 1] + 1;
+        }
+    }
+    return (int)c == K;
+}
+// k_xa's pair table of the dense hodge layer: (e, e2), e <= e2, row-major, in bytes (E <= 255)
+static inline std::vector<unsigned char> ccsd_hodge_pairs(int E) {
+    std::vector<unsigned char> hp;
+    for (int e = 0; e < E; ++e)
+        for (int e2 = e; e2 < E; ++e2) { hp.push_back((unsigned char)e); hp.push_back((unsigned char)e2); }
+    return hp;
+}
+
 static inline int round_ld(int rows) {  // node-row stride of the feature-major LDS arrays: multiple of 8, never a multiple of 32
     int r = (rows + 7) / 8 * 8;          // (== 16 mod 32 is conflict-free for the MFMA A-fragment reads, 8 / 24 mod 32 two-way)
     if (r % 32 == 0) r += 8;
     return r;
 }
 
-// Why the tiled graph-network route (ccsd_k_lg.h) cannot serve a plan whose networks `p` holds (nullptr: it can).  It covers plans
-// with the plain ScoreNetworkX and a GCN-conv ScoreNetworkA whose edge MLPs are the 16-wide MFMA chains and whose final MLP is a
-// chained shape (fdim <= 64): graph-only ones, and combinatorial complexes (N <= 64) with ScoreNetworkA_CC -- ONE
-// HodgeAdjAttentionLayer, whose hodge adjacency is diagonal (k_lg_hodge1), or 2 to 8 of them up to E = CCSD_LG_HD_MAXE (k_lg_hd_*),
-// attention dimensions at most CCSD_LG_HAD -- or with ScoreNetworkA_Base_CC, 1 to CCSD_LG_MAXHB HodgeBaselineLayers and BaselineBlocks
-// at most CCSD_LG_HBW wide (k_lg_hb_*); the dense E x E layers of both are tiled through the workspace.
-// ScoreNetworkX_GMH, conv = "MLP", wider BaselineBlocks and ScoreNetworkA_CC stacks of two or more layers beyond E = 703 stay with k_xa.
 // dynamic LDS of the route's per-node MLP kernel k_lg_nmlp for one MLP: 16 rows of its input and of two activations (bytes)
 static inline size_t lg_nmlp_lds_of(const MlpD& m) {
     const int wmax = m.hid > m.out ? m.hid : m.out;
@@ -323,6 +412,13 @@ static inline size_t lg_nmlp_lds(const PlanD& p) {
     for (int l = 0; l < p.a_L; ++l) if (lg_nmlp_lds_of(p.al[l].mc) > v) v = lg_nmlp_lds_of(p.al[l].mc);
     return v;
 }
+// Why the tiled graph-network route (ccsd_k_lg.h) cannot serve a plan whose networks `p` holds (nullptr: it can).  It covers plans
+// with the plain ScoreNetworkX and a GCN-conv ScoreNetworkA whose edge MLPs are the 16-wide MFMA chains and whose final MLP is a
+// chained shape (fdim <= 64): graph-only ones, and combinatorial complexes (N <= 64) with ScoreNetworkA_CC -- ONE
+// HodgeAdjAttentionLayer, whose hodge adjacency is diagonal (k_lg_hodge1), or 2 to 8 of them up to E = CCSD_LG_HD_MAXE (k_lg_hd_*),
+// attention dimensions at most CCSD_LG_HAD -- or with ScoreNetworkA_Base_CC, 1 to CCSD_LG_MAXHB HodgeBaselineLayers and BaselineBlocks
+// at most CCSD_LG_HBW wide (k_lg_hb_*); the dense E x E layers of both are tiled through the workspace.
+// ScoreNetworkX_GMH, conv = "MLP", wider BaselineBlocks and ScoreNetworkA_CC stacks of two or more layers beyond E = 703 stay with k_xa.
 static inline const char* ccsd_lg_ineligible(const ccsd_config_t* c, const PlanD* p, int h_wide) {
     if (p->a_is_cc == 2 && (c->h_nhid > CCSD_LG_HBW || (c->h_num_layers > 1 && c->h_adim > CCSD_LG_HBW)))
         return "ScoreNetworkA_Base_CC with BaselineBlocks wider than 16";
@@ -343,159 +439,176 @@ static inline const char* ccsd_lg_ineligible(const ccsd_config_t* c, const PlanD
     return nullptr;
 }
 
-// Fills `p` (except the affine fold, which needs the weights) and returns the blob size.
-static inline size_t ccsd_build_plan(const ccsd_config_t* c, PlanD* p, PlanBuilder& pb) {
-    memset(p, 0, sizeof(*p));
-    if (!c || c->abi_version != CCSD_ABI_VERSION) { pb.fail(CCSD_ERR_INVALID, "abi_version mismatch"); return 0; }
-    if (c->N < 2 || c->F < 1) { pb.fail(CCSD_ERR_UNSUPPORTED, "need 2 <= N <= 512 and F >= 1"); return 0; }
-    if (c->N > CCSD_LG_MAXN) { pb.fail(CCSD_ERR_UNSUPPORTED, "N = " + std::to_string(c->N) + " exceeds the ceiling of the tiled graph-network route (N <= 512)"); return 0; }
-    // above 64 nodes only the tiled route serves (checked once the networks are known: lg_reason below)
-    const bool big = c->N > CCSD_XA_MAXN;
-    if (big && c->is_cc) { pb.fail(CCSD_ERR_UNSUPPORTED, "combinatorial-complex plans need N <= 64 (the tiled route above 64 nodes is graph-only)"); return 0; }
+// ---- ccsd_build_plan, step by step.  Each step returns whether to go on (false: pb holds the failure).  The ORDER of the pb.take /
+// pb.mlp calls is the blob order shared with ccsd_amd/plan.py; the order of the pb.pcur reservations fixes the packed offsets the plan stores.
+
+// Channels into and out of layer l of a stack of L: c_init into the first, c_hid between the layers, c_final out of the last -- a single
+// layer counts as a first one and puts out c_hid (the channel-count checks then demand c_hid == c_final).  plan.py: stack_io
+static inline void ccsd_stack_io(int l, int L, int c_init, int c_hid, int c_final, int* cin, int* cout) {
+    *cin = l == 0 ? c_init : c_hid;
+    *cout = (l == L - 1 && l != 0) ? c_final : c_hid;
+}
+
+// geometry and range checks
+static inline bool plan_geometry(const ccsd_config_t* c, PlanD* p, PlanBuilder& pb) {
+    if (!c || c->abi_version != CCSD_ABI_VERSION) return pb.reject(CCSD_ERR_INVALID, "abi_version mismatch");
+    if (c->N < 2 || c->F < 1) return pb.reject(CCSD_ERR_UNSUPPORTED, "need 2 <= N <= 512 and F >= 1");
+    if (c->N > CCSD_LG_MAXN)
+        return pb.reject(CCSD_ERR_UNSUPPORTED, "N = " + std::to_string(c->N) + " exceeds the ceiling of the tiled graph-network route (N <= 512)");
+    // (above 64 nodes only the tiled route serves: checked once the networks are known, plan_route)
+    if (c->N > CCSD_XA_MAXN && c->is_cc)
+        return pb.reject(CCSD_ERR_UNSUPPORTED, "combinatorial-complex plans need N <= 64 (the tiled route above 64 nodes is graph-only)");
     int E; int64_t K64;
     ccsd_dims(c, &E, &K64);
-    if (c->is_cc && (c->d_min < 1 || c->d_max < c->d_min || c->d_max > c->N)) { pb.fail(CCSD_ERR_INVALID, "bad d_min/d_max"); return 0; }
-    if (K64 > (1 << 24)) { pb.fail(CCSD_ERR_UNSUPPORTED, "rank-2 width K too large"); return 0; }
+    if (c->is_cc && (c->d_min < 1 || c->d_max < c->d_min || c->d_max > c->N)) return pb.reject(CCSD_ERR_INVALID, "bad d_min/d_max");
+    if (K64 > (1 << 24)) return pb.reject(CCSD_ERR_UNSUPPORTED, "rank-2 width K too large");
     p->N = c->N; p->F = c->F; p->E = E; p->K = (int)K64; p->is_cc = c->is_cc;
     p->snr = c->snr; p->seps = c->scale_eps;
-    const int N = c->N, F = c->F, K = (int)K64;
-    // ---- ScoreNetworkX
-    if (c->x_depth < 1 || c->x_depth > CCSD_MAXL) { pb.fail(CCSD_ERR_UNSUPPORTED, "x_depth out of range"); return 0; }
-    p->x_depth = c->x_depth; p->x_nhid = c->x_nhid; p->x_fdim = F + c->x_depth * c->x_nhid;
-    // one AttentionLayer (attention.py:203-304) of a stack: dims, blob ranges, chained edge MLP
-    auto attn_layer = [&](AttnLayerD& a, bool first, bool last, int c_init, int c_hid, int c_final, int nhid, int adim,
-                          int heads, int num_linears, int conv_mlp, int& ch) -> bool {
-        a.cin = first ? c_init : c_hid;
-        a.cout = last ? c_final : c_hid;
-        a.fin = first ? F : nhid;
-        a.adim = first ? nhid : adim;
-        a.fout = nhid;
-        a.dsplit = a.adim / heads;
-        if (a.dsplit < 1 || a.adim % a.dsplit) { pb.fail(CCSD_ERR_INVALID, "attn_dim not divisible into head chunks"); return false; }
-        a.nchunk = a.adim / a.dsplit;
-        a.ci0 = ch - a.cin; a.co0 = ch; ch += a.cout;
-        a.conv_mlp = conv_mlp ? 1 : 0;
-        a.attn_stride = (a.conv_mlp ? 2 * (2 * a.adim * a.fin + 2 * a.adim + a.adim * 2 * a.adim + a.adim) : 2 * (a.fin * a.adim + a.adim)) +
-                        a.fin * a.fout + a.fout;
-        a.attn_base = pb.take((int64_t)a.cin * a.attn_stride);
-        a.w_lo = a.attn_base;
-        a.cp = pad16(2 * a.adim + a.fout);
-        a.qkvp = pb.pcur;
-        if (!a.conv_mlp) pb.pcur += a.cin * (a.fin * a.cp + a.cp);
-        const int hid = 2 * (a.cin > a.cout ? a.cin : a.cout);
-        a.mlp = pb.mlp(num_linears, 2 * a.cin, hid, a.cout);
-        pb.chainify(a.mlp, CCSD_CHAIN_EDGE);
-        pb.transposed(a.mlp);
-        a.mc = pb.mlp(2, a.cin * a.fout, hid, a.fout);
-        pb.transposed(a.mc);
-        a.w_hi = pb.cur;
-        a.mcs = (a.fout + 3) >> 2;
-        a.mcp = pb.pcur;
-        pb.pcur += (pad16(hid) >> 4) * a.cin * a.mcs * 64;
-        return true;
-    };
-    p->x_gmh = c->x_gmh ? 1 : 0; p->g_cinit = 0; p->g_nch = 0;
+    return true;
+}
+
+// hyper-parameters of a stack of AttentionLayers (ScoreNetworkA's graph branch, ScoreNetworkX_GMH)
+struct AttnStackCfg { int L, c_init, c_hid, c_final, nhid, adim, heads, num_linears, conv_mlp; };
+// one AttentionLayer (attention.py:203-304) of a stack: dims, blob ranges, chained edge MLP.  ch: the stack's channels so far
+static inline bool plan_attn_layer(PlanBuilder& pb, AttnLayerD& a, int l, const AttnStackCfg& s, int F, int& ch) {
+    const bool first = l == 0;
+    ccsd_stack_io(l, s.L, s.c_init, s.c_hid, s.c_final, &a.cin, &a.cout);
+    a.fin = first ? F : s.nhid;
+    a.adim = first ? s.nhid : s.adim;
+    a.fout = s.nhid;
+    a.dsplit = a.adim / s.heads;
+    if (a.dsplit < 1 || a.adim % a.dsplit) return pb.reject(CCSD_ERR_INVALID, "attn_dim not divisible into head chunks");
+    a.nchunk = a.adim / a.dsplit;
+    a.ci0 = ch - a.cin; a.co0 = ch; ch += a.cout;
+    a.conv_mlp = s.conv_mlp ? 1 : 0;
+    a.attn_stride = (a.conv_mlp ? 2 * (2 * a.adim * a.fin + 2 * a.adim + a.adim * 2 * a.adim + a.adim) : 2 * (a.fin * a.adim + a.adim)) +
+                    a.fin * a.fout + a.fout;
+    a.attn_base = pb.take((int64_t)a.cin * a.attn_stride);
+    a.cp = pad16(2 * a.adim + a.fout);
+    a.qkvp = pb.pcur;
+    if (!a.conv_mlp) pb.pcur += a.cin * (a.fin * a.cp + a.cp);
+    const int hid = 2 * (a.cin > a.cout ? a.cin : a.cout);
+    a.mlp = pb.mlp(s.num_linears, 2 * a.cin, hid, a.cout);
+    pb.chainify(a.mlp, CCSD_CHAIN_EDGE);
+    pb.transposed(a.mlp);
+    a.mc = pb.mlp(2, a.cin * a.fout, hid, a.fout);
+    pb.transposed(a.mc);
+    a.mcs = (a.fout + 3) >> 2;
+    a.mcp = pb.pcur;
+    pb.pcur += (pad16(hid) >> 4) * a.cin * a.mcs * 64;
+    return true;
+}
+// ... and the whole stack; *nch: its channels, the c_init inputs included
+static inline bool plan_attn_stack(PlanBuilder& pb, AttnLayerD* layers, const AttnStackCfg& s, int F, int* nch) {
+    int ch = s.c_init;
+    for (int l = 0; l < s.L; ++l)
+        if (!plan_attn_layer(pb, layers[l], l, s, F, ch)) return false;
+    *nch = ch;
+    return true;
+}
+
+// ScoreNetworkX, plain (GCN layers) or GMH (AttentionLayers on g_cinit adjacency powers)
+static inline bool plan_xnet(const ccsd_config_t* c, PlanD* p, PlanBuilder& pb) {
+    if (c->x_depth < 1 || c->x_depth > CCSD_MAXL) return pb.reject(CCSD_ERR_UNSUPPORTED, "x_depth out of range");
+    p->x_depth = c->x_depth; p->x_nhid = c->x_nhid; p->x_fdim = c->F + c->x_depth * c->x_nhid;
+    p->x_gmh = c->x_gmh ? 1 : 0;
     if (p->x_gmh) {
-        if (c->x_num_heads < 1 || c->x_c_init < 1) { pb.fail(CCSD_ERR_INVALID, "bad heads/c_init (ScoreNetworkX_GMH)"); return 0; }
+        if (c->x_num_heads < 1 || c->x_c_init < 1) return pb.reject(CCSD_ERR_INVALID, "bad heads/c_init (ScoreNetworkX_GMH)");
         p->g_cinit = c->x_c_init;
-        int gch = c->x_c_init;
-        for (int l = 0; l < c->x_depth; ++l)
-            if (!attn_layer(p->gl[l], l == 0, l == c->x_depth - 1 && l != 0, c->x_c_init, c->x_c_hid, c->x_c_final, c->x_nhid,
-                            c->x_adim, c->x_num_heads, c->x_num_linears, c->x_conv_mlp, gch)) return 0;
-        p->g_nch = gch;
+        const AttnStackCfg s = {c->x_depth, c->x_c_init, c->x_c_hid, c->x_c_final, c->x_nhid, c->x_adim, c->x_num_heads, c->x_num_linears, c->x_conv_mlp};
+        if (!plan_attn_stack(pb, p->gl, s, c->F, &p->g_nch)) return false;
         p->x_gw[0] = p->gl[0].attn_base;
-    } else
-    for (int l = 0; l < c->x_depth; ++l) {
-        p->x_gw[l] = pb.take((int64_t)(l ? c->x_nhid : F) * c->x_nhid);
-        p->x_gb[l] = pb.take(c->x_nhid);
+    } else {
+        for (int l = 0; l < c->x_depth; ++l) {
+            p->x_gw[l] = pb.take((int64_t)(l ? c->x_nhid : c->F) * c->x_nhid);
+            p->x_gb[l] = pb.take(c->x_nhid);
+        }
     }
-    p->x_wlo = p->x_gw[0];
-    p->x_fin = pb.mlp(3, p->x_fdim, 2 * p->x_fdim, F);
+    p->x_fin = pb.mlp(3, p->x_fdim, 2 * p->x_fdim, c->F);
     pb.chainify(p->x_fin, CCSD_CHAIN_XFIN);
     pb.transposed(p->x_fin);
-    p->x_whi = pb.cur;
-    // ---- ScoreNetworkA graph branch
-    if (c->a_num_layers < 1 || c->a_num_layers > CCSD_MAXL) { pb.fail(CCSD_ERR_UNSUPPORTED, "a_num_layers out of range"); return 0; }
-    if (c->a_num_heads < 1 || c->a_c_init < 1) { pb.fail(CCSD_ERR_INVALID, "bad heads/c_init"); return 0; }
+    return true;
+}
+
+// ScoreNetworkA, graph branch
+static inline bool plan_anet_graph(const ccsd_config_t* c, PlanD* p, PlanBuilder& pb) {
+    if (c->a_num_layers < 1 || c->a_num_layers > CCSD_MAXL) return pb.reject(CCSD_ERR_UNSUPPORTED, "a_num_layers out of range");
+    if (c->a_num_heads < 1 || c->a_c_init < 1) return pb.reject(CCSD_ERR_INVALID, "bad heads/c_init");
     p->a_L = c->a_num_layers; p->a_cinit = c->a_c_init; p->a_is_cc = c->a_is_cc_net;
-    int ch = c->a_c_init;
-    for (int l = 0; l < p->a_L; ++l) {
-        if (!attn_layer(p->al[l], l == 0, l == p->a_L - 1 && l != 0, c->a_c_init, c->a_c_hid, c->a_c_final, c->a_nhid, c->a_adim,
-                        c->a_num_heads, c->a_num_linears, c->a_conv_mlp, ch)) return 0;
+    const AttnStackCfg s = {c->a_num_layers, c->a_c_init, c->a_c_hid, c->a_c_final, c->a_nhid, c->a_adim, c->a_num_heads, c->a_num_linears, c->a_conv_mlp};
+    if (!plan_attn_stack(pb, p->al, s, c->F, &p->a_nch_graph)) return false;
+    if (c->a_c_hid * (p->a_L - 1) + c->a_c_final + c->a_c_init != p->a_nch_graph)
+        return pb.reject(CCSD_ERR_INVALID, "ScoreNetworkA channel count inconsistent (num_layers==1 needs c_hid==c_final)");
+    return true;
+}
+
+// ScoreNetworkA_Base_CC's hodge branch: every HodgeBaselineLayer into pb.hbx, the first CCSD_MAXHL into p->hb as well
+static inline bool plan_hodge_base(const ccsd_config_t* c, PlanD* p, PlanBuilder& pb) {
+    if (!c->is_cc) return pb.reject(CCSD_ERR_INVALID, "ScoreNetworkA_Base_CC is only for combinatorial complexes");
+    if (c->h_num_layers < 1 || c->h_num_layers > CCSD_LG_MAXHB) return pb.reject(CCSD_ERR_UNSUPPORTED, "HIP path supports 1 to 8 HodgeBaselineLayers");
+    p->hb_L = c->h_num_layers;
+    const int E = p->E;
+    for (int l = 0; l < p->hb_L; ++l) {
+        HodgeBaseD& h = pb.hbx[l];
+        ccsd_stack_io(l, p->hb_L, c->a_c_init, c->h_c_hid, c->h_c_final, &h.cin, &h.cout);
+        h.hid = l == 0 ? c->h_nhid : c->h_adim;
+        if (h.hid < 1) return pb.reject(CCSD_ERR_INVALID, "HodgeBaselineLayer hidden width < 1");
+        h.blk_stride = 2 * h.hid * E + h.hid + E;
+        h.blk_base = pb.take((int64_t)h.cin * h.blk_stride);
+        h.w2t = pb.pcur; pb.pcur += h.cin * h.hid * E;
+        h.w1t = pb.pcur; pb.pcur += h.cin * h.hid * E;
+        const int hid = 2 * (h.cin > h.cout ? h.cin : h.cout);
+        h.mh = pb.mlp(c->h_num_linears, h.cin, hid, h.cout);
+        // a dense layer evaluates it per (e, e') pair on MFMA: the first one (k_xa, k_lg_hb_dense) and, on the tiled route, every other
+        // layer but the last (only stacks of more than two have such a layer: no plan k_xa serves moves)
+        if (l == 0 || l < p->hb_L - 1) pb.chainify(h.mh, CCSD_CHAIN_EDGE);
+        if (h.cin > CCSD_FW || (c->h_num_linears > 1 && hid > CCSD_FW) || h.cout > CCSD_FW)
+            return pb.reject(CCSD_ERR_UNSUPPORTED, "HodgeBaselineLayer mlp_hodge wider than 16");
+        if (l < CCSD_MAXHL) p->hb[l] = h;
+        p->a_nch_hodge += h.cout;
     }
-    p->a_nch_graph = ch;
-    int fdim = c->a_c_hid * (p->a_L - 1) + c->a_c_final + c->a_c_init;
-    if (fdim != ch) { pb.fail(CCSD_ERR_INVALID, "ScoreNetworkA channel count inconsistent (num_layers==1 needs c_hid==c_final)"); return 0; }
-    // ---- hodge branch
-    p->h_L = 0; p->a_nch_hodge = 0; p->hb_L = 0;
-    if (c->a_is_cc_net == 2) {
-        if (!c->is_cc) { pb.fail(CCSD_ERR_INVALID, "ScoreNetworkA_Base_CC is only for combinatorial complexes"); return 0; }
-        if (c->h_num_layers < 1 || c->h_num_layers > CCSD_LG_MAXHB) {
-            pb.fail(CCSD_ERR_UNSUPPORTED, "HIP path supports 1 to 8 HodgeBaselineLayers"); return 0; }
-        p->hb_L = c->h_num_layers;
-        int hch = c->a_c_init;
-        for (int l = 0; l < p->hb_L; ++l) {
-            HodgeBaseD& h = pb.hbx[l];
-            const bool first = (l == 0), last = (l == p->hb_L - 1) && !first;
-            h.cin = first ? c->a_c_init : c->h_c_hid;
-            h.cout = last ? c->h_c_final : c->h_c_hid;
-            h.hid = first ? c->h_nhid : c->h_adim;
-            if (h.hid < 1) { pb.fail(CCSD_ERR_INVALID, "HodgeBaselineLayer hidden width < 1"); return 0; }
-            h.blk_stride = 2 * h.hid * E + h.hid + E;
-            h.blk_base = pb.take((int64_t)h.cin * h.blk_stride);
-            h.w2t = pb.pcur; pb.pcur += h.cin * h.hid * E;
-            h.w1t = pb.pcur; pb.pcur += h.cin * h.hid * E;
-            const int hid = 2 * (h.cin > h.cout ? h.cin : h.cout);
-            h.mh = pb.mlp(c->h_num_linears, h.cin, hid, h.cout);
-            // a dense layer evaluates it per (e, e') pair on MFMA: the first one (k_xa, k_lg_hb_dense) and, on the tiled route, every other
-            // layer but the last (only stacks of more than two have such a layer: no plan k_xa serves moves)
-            if (first || l < p->hb_L - 1) pb.chainify(h.mh, CCSD_CHAIN_EDGE);
-            if (h.cin > CCSD_FW || (c->h_num_linears > 1 && hid > CCSD_FW) || h.cout > CCSD_FW) {
-                pb.fail(CCSD_ERR_UNSUPPORTED, "HodgeBaselineLayer mlp_hodge wider than 16"); return 0; }
-            if (l < CCSD_MAXHL) p->hb[l] = h;
-            hch += h.cout;
-        }
-        p->a_nch_hodge = hch;
-        int hf = c->h_c_hid * (p->hb_L - 1) + c->h_c_final + c->a_c_init;
-        if (hf != hch) { pb.fail(CCSD_ERR_INVALID, "hodge channel count inconsistent (num_layers_h==1 needs c_hid_h==c_final_h)"); return 0; }
-    } else if (c->a_is_cc_net) {
-        if (!c->is_cc) { pb.fail(CCSD_ERR_INVALID, "ScoreNetworkA_CC is only for combinatorial complexes"); return 0; }
-        if (c->h_num_layers < 1 || c->h_num_layers > CCSD_MAXHL + CCSD_MAXHLX) {
-            pb.fail(CCSD_ERR_UNSUPPORTED, "HIP path supports 1 to 8 HodgeAdjAttentionLayers"); return 0; }
-        p->h_L = c->h_num_layers;
-        int hch = c->a_c_init;
-        for (int l = 0; l < p->h_L; ++l) {
-            HodgeLayerD& h = ccsd_hl_mut(*p, l);
-            const bool first = (l == 0), last = (l == p->h_L - 1) && !first;
-            h.cin = first ? c->a_c_init : c->h_c_hid;
-            h.cout = last ? c->h_c_final : c->h_c_hid;
-            h.adim = first ? c->h_nhid : c->h_adim;
-            h.dsplit = h.adim / c->h_num_heads;
-            if (h.dsplit < 1 || h.adim % h.dsplit) { pb.fail(CCSD_ERR_INVALID, "hodge attn_dim not divisible into head chunks"); return 0; }
-            h.nchunk = h.adim / h.dsplit;
-            h.wc = h.cin * 2 * h.adim;
-            h.wcat = pb.take((int64_t)K * h.wc);
-            h.bcat = pb.take(h.wc);
-            h.wcatT = pb.pcur; pb.pcur += pad16(h.wc) * ((K + 31) & ~31);
-            const int hid = 2 * (h.cin > h.cout ? h.cin : h.cout);
-            h.mval = pb.mlp(c->h_num_linears, h.cin, hid, 1);
-            h.matt = pb.mlp(c->h_num_linears, h.cin, hid, h.cout);
-            // (a single-Linear MLP has no Linear of width hid)
-            const int hidw = c->h_num_linears > 1 ? hid : 0;
-            if (h.cin > CCSD_SMALLW || hidw > CCSD_HWIDE || h.cout > CCSD_SMALLW) {
-                pb.fail(CCSD_ERR_UNSUPPORTED, "hodge MLP wider than 16"); return 0; }
-            if (hidw > CCSD_SMALLW) pb.h_wide = 1;
-            hch += h.cout;
-        }
-        p->a_nch_hodge = hch;
-        int hf = c->h_c_hid * (p->h_L - 1) + c->h_c_final + c->a_c_init;
-        if (hf != hch) { pb.fail(CCSD_ERR_INVALID, "hodge channel count inconsistent (num_layers_h==1 needs c_hid_h==c_final_h)"); return 0; }
+    return true;
+}
+// ScoreNetworkA_CC's hodge branch: HodgeAdjAttentionLayers
+static inline bool plan_hodge_attn(const ccsd_config_t* c, PlanD* p, PlanBuilder& pb) {
+    if (!c->is_cc) return pb.reject(CCSD_ERR_INVALID, "ScoreNetworkA_CC is only for combinatorial complexes");
+    if (c->h_num_layers < 1 || c->h_num_layers > CCSD_MAXHL + CCSD_MAXHLX)
+        return pb.reject(CCSD_ERR_UNSUPPORTED, "HIP path supports 1 to 8 HodgeAdjAttentionLayers");
+    p->h_L = c->h_num_layers;
+    const int K = p->K;
+    for (int l = 0; l < p->h_L; ++l) {
+        HodgeLayerD& h = ccsd_hl_mut(*p, l);
+        ccsd_stack_io(l, p->h_L, c->a_c_init, c->h_c_hid, c->h_c_final, &h.cin, &h.cout);
+        h.adim = l == 0 ? c->h_nhid : c->h_adim;
+        h.dsplit = h.adim / c->h_num_heads;
+        if (h.dsplit < 1 || h.adim % h.dsplit) return pb.reject(CCSD_ERR_INVALID, "hodge attn_dim not divisible into head chunks");
+        h.nchunk = h.adim / h.dsplit;
+        h.wc = h.cin * 2 * h.adim;
+        h.wcat = pb.take((int64_t)K * h.wc);
+        h.bcat = pb.take(h.wc);
+        h.wcatT = pb.pcur; pb.pcur += pad16(h.wc) * ((K + 31) & ~31);
+        const int hid = 2 * (h.cin > h.cout ? h.cin : h.cout);
+        h.mval = pb.mlp(c->h_num_linears, h.cin, hid, 1);
+        h.matt = pb.mlp(c->h_num_linears, h.cin, hid, h.cout);
+        const int hidw = c->h_num_linears > 1 ? hid : 0;        // (a single-Linear MLP has no Linear of width hid)
+        if (h.cin > CCSD_SMALLW || hidw > CCSD_HWIDE || h.cout > CCSD_SMALLW) return pb.reject(CCSD_ERR_UNSUPPORTED, "hodge MLP wider than 16");
+        if (hidw > CCSD_SMALLW) pb.h_wide = 1;
+        p->a_nch_hodge += h.cout;
+    }
+    return true;
+}
+// ScoreNetworkA's hodge branch (none for the graph-only network) and its final MLP over the channels of both branches
+static inline bool plan_anet_hodge(const ccsd_config_t* c, PlanD* p, PlanBuilder& pb) {
+    if (c->a_is_cc_net) {
+        p->a_nch_hodge = c->a_c_init;
+        if (!(c->a_is_cc_net == 2 ? plan_hodge_base(c, p, pb) : plan_hodge_attn(c, p, pb))) return false;
+        if (c->h_c_hid * (p->hb_L + p->h_L - 1) + c->h_c_final + c->a_c_init != p->a_nch_hodge)
+            return pb.reject(CCSD_ERR_INVALID, "hodge channel count inconsistent (num_layers_h==1 needs c_hid_h==c_final_h)");
         // the transposed copies Wcat_l^T of layers >= 1 are consecutive [pad16(wc_l)][Kp] blocks: k_r2 treats them as ONE
         // projection of h_pw columns
-        p->h_pw = 0;
         for (int l = 1; l < p->h_L; ++l) {
             p->h_poff[l] = p->h_pw;
-            if (ccsd_hl(*p, l).wcatT != ccsd_hl(*p, 1).wcatT + p->h_pw * ((K + 31) & ~31)) { pb.fail(CCSD_ERR_RUNTIME, "Wcat^T blocks not consecutive"); return 0; }
+            if (ccsd_hl(*p, l).wcatT != ccsd_hl(*p, 1).wcatT + p->h_pw * ((p->K + 31) & ~31)) return pb.reject(CCSD_ERR_RUNTIME, "Wcat^T blocks not consecutive");
             p->h_pw += l == p->h_L - 1 ? ccsd_hl(*p, l).wc : pad16(ccsd_hl(*p, l).wc);
         }
     }
@@ -503,241 +616,262 @@ static inline size_t ccsd_build_plan(const ccsd_config_t* c, PlanD* p, PlanBuild
     p->a_fin = pb.mlp(3, p->a_fdim, 2 * p->a_fdim, 1);
     pb.chainify(p->a_fin, CCSD_CHAIN_AFIN);
     pb.transposed(p->a_fin);
-    // ---- ScoreNetworkF
-    if (c->is_cc) {
-        if (c->f_num_layers < 1 || c->f_num_layers > CCSD_MAXFL) { pb.fail(CCSD_ERR_UNSUPPORTED, "f_num_layers out of range"); return 0; }
-        if (c->f_cnum < 1 || c->f_cnum > CCSD_MAXCN) { pb.fail(CCSD_ERR_UNSUPPORTED, "HIP path supports cnum in 1..4"); return 0; }
-        p->f_L = c->f_num_layers; p->f_cnum = c->f_cnum; p->f_hmask = c->f_use_hodge_mask;
-        int fch = c->f_cnum;
-        for (int l = 0; l < p->f_L; ++l) {
-            const bool first = (l == 0), last = (l == p->f_L - 1) && !first;
-            const int cin = first ? c->f_cnum : c->f_c_hid, cout = last ? c->f_c_final : c->f_c_hid;
-            p->fl[l] = pb.mlp(c->f_num_linears, cin, c->f_nhid, cout);
-            if (cin > CCSD_FWMAX || cout > CCSD_FWMAX || c->f_nhid > CCSD_FWMAX) { pb.fail(CCSD_ERR_UNSUPPORTED, "ScoreNetworkF layer wider than 32"); return 0; }
-            fch += cout;
-        }
-        p->f_fdim = c->f_c_hid * (p->f_L - 1) + c->f_c_final + c->f_cnum;
-        if (p->f_fdim != fch) { pb.fail(CCSD_ERR_INVALID, "ScoreNetworkF channel count inconsistent"); return 0; }
-        p->f_fin = pb.mlp(c->f_num_layers_mlp, p->f_fdim, 2 * p->f_fdim, 1);
-        if (p->f_fdim > CCSD_FWMAX || (c->f_num_layers_mlp > 1 && 2 * p->f_fdim > CCSD_FWMAX)) {
-            pb.fail(CCSD_ERR_UNSUPPORTED, "ScoreNetworkF final MLP wider than 32"); return 0; }
-        p->f_affine = (c->f_num_linears == 1 && c->f_num_layers_mlp == 1) ? 1 : 0;
-    }
-    const size_t nweights = (size_t)pb.cur;
-    // ScoreNetworkF, general (non-affine) path with every layer width <= 8 and a single-Linear head: zero-padded [8][8] + [8]
-    // blocks (CCSD_HWBLK floats per Linear) and the head's weights in 8-wide segments, appended to the device copy of the blob
+    return true;
+}
+
+// ScoreNetworkF (combinatorial complexes), and whether its general path reads zero-padded blocks behind the blob (f_blk)
+static inline bool plan_fnet(const ccsd_config_t* c, PlanD* p, PlanBuilder& pb) {
     p->f_blk = -1;
-    if (c->is_cc && !p->f_affine && p->f_fin.n == 1 && p->f_cnum <= 8) {
-        bool ok = true;
-        for (int l = 0; l < p->f_L; ++l) ok = ok && p->fl[l].in <= 8 && p->fl[l].out <= 8 && (p->fl[l].n == 1 || p->fl[l].hid <= 8);
-        if (ok) p->f_blk = (int)((nweights + 15) & ~(size_t)15);
+    if (!c->is_cc) return true;
+    if (c->f_num_layers < 1 || c->f_num_layers > CCSD_MAXFL) return pb.reject(CCSD_ERR_UNSUPPORTED, "f_num_layers out of range");
+    if (c->f_cnum < 1 || c->f_cnum > CCSD_MAXCN) return pb.reject(CCSD_ERR_UNSUPPORTED, "HIP path supports cnum in 1..4");
+    p->f_L = c->f_num_layers; p->f_cnum = c->f_cnum; p->f_hmask = c->f_use_hodge_mask;
+    int fch = c->f_cnum;
+    bool narrow = true;        // every layer width <= 8
+    for (int l = 0; l < p->f_L; ++l) {
+        int cin, cout;
+        ccsd_stack_io(l, p->f_L, c->f_cnum, c->f_c_hid, c->f_c_final, &cin, &cout);
+        const MlpD& m = p->fl[l] = pb.mlp(c->f_num_linears, cin, c->f_nhid, cout);
+        if (cin > CCSD_FWMAX || cout > CCSD_FWMAX || c->f_nhid > CCSD_FWMAX) return pb.reject(CCSD_ERR_UNSUPPORTED, "ScoreNetworkF layer wider than 32");
+        narrow = narrow && m.in <= 8 && m.out <= 8 && (m.n == 1 || m.hid <= 8);
+        fch += cout;
     }
+    p->f_fdim = c->f_c_hid * (p->f_L - 1) + c->f_c_final + c->f_cnum;
+    if (p->f_fdim != fch) return pb.reject(CCSD_ERR_INVALID, "ScoreNetworkF channel count inconsistent");
+    p->f_fin = pb.mlp(c->f_num_layers_mlp, p->f_fdim, 2 * p->f_fdim, 1);
+    if (p->f_fdim > CCSD_FWMAX || (c->f_num_layers_mlp > 1 && 2 * p->f_fdim > CCSD_FWMAX))
+        return pb.reject(CCSD_ERR_UNSUPPORTED, "ScoreNetworkF final MLP wider than 32");
+    p->f_affine = (c->f_num_linears == 1 && c->f_num_layers_mlp == 1) ? 1 : 0;
+    // the general (non-affine) path with every layer width <= 8 and a single-Linear head: zero-padded [8][8] + [8] blocks (CCSD_HWBLK
+    // floats per Linear) and the head's weights in 8-wide segments, appended to the device copy of the blob (ccsd_pack_fnet_blocks)
+    if (!p->f_affine && p->f_fin.n == 1 && p->f_cnum <= 8 && narrow) p->f_blk = (pb.cur + 15) & ~15;
+    return true;
+}
 
-    // ---- route: tiled graph-network kernels (ccsd_k_lg.h) when k_xa cannot place the plan (N > 64, or no LDS layout below) or when forced
-    const char* lg_reason = ccsd_lg_ineligible(c, p, pb.h_wide);
-    if (big) {
-        if (lg_reason) { pb.fail(CCSD_ERR_UNSUPPORTED, std::string("N > 64 needs the tiled graph-network route, which does not serve ") + lg_reason); return 0; }
-        pb.lg = 1;
-        pb.route_copies(*p);
-        p->ldn = round_ld(N);
-        p->chan_rows = p->a_fdim;
-        return nweights;            // (no k_xa layout: its LDS fields stay zero)
-    }
-    // ScoreNetworkA_Base_CC with more than two HodgeBaselineLayers: k_xa's hodge branch is written for one or two, only the route serves
-    if (p->hb_L > CCSD_MAXHL) {
-        if (lg_reason) { pb.fail(CCSD_ERR_UNSUPPORTED, std::string("more than 2 HodgeBaselineLayers need the tiled graph-network route, which does not serve ") + lg_reason); return 0; }
-        pb.lg = 1;
-        pb.route_copies(*p);
-        p->ldn = round_ld(N);
-        p->chan_rows = p->a_fdim;
-        return nweights;
-    }
-    // ScoreNetworkA_CC with hodge MLPs wider than 8: k_xa's (and k_r2's) per-thread small_mlp is 8 wide, only the route evaluates them
-    if (pb.h_wide) {
-        if (lg_reason) { pb.fail(CCSD_ERR_UNSUPPORTED, std::string("hodge MLPs wider than 8 need the tiled graph-network route, which does not serve ") + lg_reason); return 0; }
-        pb.lg = 1;
-        pb.route_copies(*p);
-        p->ldn = round_ld(N);
-        p->chan_rows = p->a_fdim;
-        return nweights;
-    }
-    // ... and a dense HodgeBaselineLayer beyond E = 255 -- the envelope k_xa's dense hodge layers are built and tested in (ccsd_plan_create
-    // holds ScoreNetworkA_CC stacks to it; every shipped Base_CC geometry lies inside: E = 36 .. 190) -- takes the route where it is
-    // eligible: one workgroup per complex would walk the E^2 pairs alone (grid_small_Base_CC: E = 1176, a 148 KB k_xa layout)
-    if (p->hb_L > 1 && E > 255 && !lg_reason) pb.lg = 1;
-    // ... and so does a ScoreNetworkA_CC stack of two or more layers there: k_xa's pair table of the dense layer holds edge indices in bytes
-    if (p->h_L > 1 && E > 255 && !lg_reason) pb.lg = 1;
-    // (1 leaves combinatorial complexes on k_xa, as before the route served any of them: tests/golden/route_plans.json pins those plans)
-    if (pb.lg_force && !lg_reason && (!c->is_cc || pb.lg_force >= 2)) pb.lg = 1;
+// A plan k_xa has no code for (`need`: why) takes the tiled route, or fails with the reason the route does not serve it either.
+// No k_xa layout: the plan's LDS fields stay zero.
+static inline void plan_route_only(PlanD* p, PlanBuilder& pb, const char* lg_reason, const char* need) {
+    if (lg_reason) { pb.fail(CCSD_ERR_UNSUPPORTED, std::string(need) + " the tiled graph-network route, which does not serve " + lg_reason); return; }
+    pb.lg = 1;
+    pb.route_copies(*p);
+    p->ldn = round_ld(p->N);
+    p->chan_rows = p->a_fdim;
+}
 
-    // ---- k_xa LDS carve-up
-    const int NN = N * N;
-    p->ldn = round_ld(N);
-    int fmaxA = F > c->a_nhid ? F : c->a_nhid;
-    int colmax = 0, mchid = 0, cinmax = 0;
-    int pw_pair = 1;   // widest hidden activation of the per-layer edge MLPs
-    bool pair_chained_all = true;
+// ---- k_xa's LDS layout.  What it needs to know of the networks: maxima over the AttentionLayers of both stacks, the hodge branch's scratch
+struct XaNeeds {
+    int fmaxA;                    // widest node-feature row
+    int colmax, mchid, cinmax;    // Q | K | V columns, multi_channel's hidden width, input channels of a layer
+    int pw_pair, pw_fin;          // widest hidden activation of the per-layer edge MLPs / of the final MLP
+    bool pair_chained, fin_chained;   // ... which stay in registers when every such MLP is chained
+    int hq_floats, h1m_floats;    // hodge branch: Q | K scratch, dense buffer of a layer that feeds another
+    int hw_n;                     // ... most Linears of a mlp_attention
+};
+static inline XaNeeds xa_needs(const ccsd_config_t* c, const PlanD& p) {
+    XaNeeds n = {};
+    n.fmaxA = p.F > c->a_nhid ? p.F : c->a_nhid;
+    n.pw_pair = 1; n.pair_chained = true;
     auto layer_max = [&](const AttnLayerD& a) {
-        int cols = 2 * a.adim + a.fout; if (cols > colmax) colmax = cols;
-        if (a.mc.hid > mchid) mchid = a.mc.hid;
-        if (a.cin > cinmax) cinmax = a.cin;
-        if (a.mlp.n > 1 && a.mlp.hid > pw_pair) pw_pair = a.mlp.hid;
-        pair_chained_all = pair_chained_all && a.mlp.chain != 0;
+        const int cols = 2 * a.adim + a.fout;
+        if (cols > n.colmax) n.colmax = cols;
+        if (a.mc.hid > n.mchid) n.mchid = a.mc.hid;
+        if (a.cin > n.cinmax) n.cinmax = a.cin;
+        if (a.mlp.n > 1 && a.mlp.hid > n.pw_pair) n.pw_pair = a.mlp.hid;
+        n.pair_chained = n.pair_chained && a.mlp.chain != 0;
     };
-    for (int l = 0; l < p->a_L; ++l) layer_max(p->al[l]);
-    if (p->x_gmh) {
-        for (int l = 0; l < p->x_depth; ++l) layer_max(p->gl[l]);
-        if (c->x_nhid > fmaxA) fmaxA = c->x_nhid;
+    for (int l = 0; l < p.a_L; ++l) layer_max(p.al[l]);
+    if (p.x_gmh) {
+        for (int l = 0; l < p.x_depth; ++l) layer_max(p.gl[l]);
+        if (c->x_nhid > n.fmaxA) n.fmaxA = c->x_nhid;
     }
-    p->chan_rows = p->a_fdim > p->g_nch ? p->a_fdim : p->g_nch;
-    const int pw_fin = 2 * p->a_fdim;
-    p->pw_pair = pw_pair;
-    const int NNpad = (NN + 15) / 16 * 16;
-    int hq_floats = 0, h1m_floats = 0;
-    if (p->h_L) {
+    n.pw_fin = 2 * p.a_fdim;
+    n.fin_chained = p.a_fin.chain != 0;
+    n.hw_n = 1;
+    for (int l = 0; l < p.h_L; ++l) {
+        const HodgeLayerD& h = ccsd_hl(p, l);
         // (+1: the first layer's rows have an odd stride in k_xa -- bank-conflict-free reads in the dense pair loop)
-        for (int l = 0; l < p->h_L; ++l) { int v = ccsd_hl(*p, l).cin * E * (2 * ccsd_hl(*p, l).adim + (l == 0 ? 1 : 0)); if (v > hq_floats) hq_floats = v; }
-        for (int l = 0; l + 1 < p->h_L; ++l) { int v = ccsd_hl(*p, l).cout * E * E; if (v > h1m_floats) h1m_floats = v; }
-        if (E > NN) { pb.fail(CCSD_ERR_UNSUPPORTED, "E > N*N"); return 0; }
+        const int hq = h.cin * p.E * (2 * h.adim + (l == 0 ? 1 : 0)), h1m = l + 1 < p.h_L ? h.cout * p.E * p.E : 0;
+        if (hq > n.hq_floats) n.hq_floats = hq;
+        if (h1m > n.h1m_floats) n.h1m_floats = h1m;
+        if (h.matt.n > n.hw_n) n.hw_n = h.matt.n;
     }
-    // weight staging: largest section (X-network, one AttentionLayer, final MLP); only when it is small
-    int wst = 0;   // (weights are read in place from L2; the LDS-staged variant is gone)
-    // Candidate LDS budgets, best first: 4 workgroups/CU reading weights from L2 (32 waves/CU hide the latency of the
-    // ~45 barrier-separated phases best); 2/CU with the weights staged in LDS; 3/CU; then whatever fits in one CU.
-    // Within a budget take the largest channel group / chunk sizes.  CCSD_XA_PASS=<n> skips the first n candidates.
-    const int wst_full = wst;
-    const int NCAND = 4;
-    const int budgets_b[NCAND] = {40960, 53 * 1024, 79 * 1024, 152 * 1024};
-    const int stage_on[NCAND] = {0, 0, 0, 0};
-    int hw_n = 1;
-    for (int l = 0; l < p->h_L; ++l) if (ccsd_hl(*p, l).matt.n > hw_n) hw_n = ccsd_hl(*p, l).matt.n;
-    auto ld_of = [](int rows) { int r = (rows + 15) / 16 * 16; if (r % 32 == 0) r += 8; return r; };   // 2-way conflicts at worst
-    int best_total = -1;
-    // Large graphs (zinc250k: 46 channels x 38 x 38 = 266 KB): second round of candidates with the channel stack in the
-    // HBM workspace (L2-resident, one slab per graph) and only the per-layer working set in LDS.  CCSD_XA_GCH=1 forces it.
-    // Start at the budget that keeps ceil(batch / #CUs) workgroups co-resident per CU (batch_hint; unknown = 4 per CU, the
-    // qm9_CC B = 1024 case), then grow.  Within a budget the channel stack in LDS is tried before the HBM variant: with the
-    // residency the batch needs, more workgroups per CU buy nothing and the HBM stack costs.
-    const int gch_first = pb.xa_gch;
+    return n;
+}
+static inline int xa_chunk_ld(int rows) { int r = (rows + 15) / 16 * 16; if (r % 32 == 0) r += 8; return r; }   // 2-way conflicts at worst
+static inline int xa_carve(int& o, int v) { const int r = o; o += (v + 3) / 4 * 4; return r; }                // regions start on 16 bytes
+
+// ... the hodge branch's regions, carved at o behind the attention stack's (o_att .. o_xnext up to o_xnext_end, then o_vcat).  The branch
+// runs after the stack, whose regions are dead by then.  Returns the floats one row of HodgeBaselineLayer 0's chunk needs in the shared region
+static inline int xa_layout_hodge(const XaNeeds& n, PlanD* q, int o_xnext_end, int& o) {
+    const int E = q->E;
+    auto carve = [&](int v) { return xa_carve(o, v); };
+    // degree scratch of the dense hodge layers, three cases: (1) multi_channel's hidden layer; (2) two layers: a slot of its own when
+    // layer 1's degrees do not fit there, or when the Q | K scratch reaches into it; (3) more than two: always its own, for the largest
+    q->o_deg = q->o_vcat;
+    if (q->h_L) {
+        // the Q | K scratch re-uses [attention | node features | multi_channel hidden] when it fits
+        const int deg1 = q->h_L > 1 ? q->hl[1].cin * E : 0;
+        if (n.hq_floats <= o - q->o_att) {
+            q->o_hq = q->o_att;
+            if (q->h_L > 1 && (n.hq_floats > o_xnext_end - q->o_att || deg1 > n.mchid * q->ldn)) q->o_deg = carve(deg1);
+        } else {
+            q->o_hq = carve(n.hq_floats);
+            if (q->h_L > 1 && deg1 > n.mchid * q->ldn) q->o_deg = carve(deg1);
+        }
+        q->o_hd = carve(q->a_nch_hodge * E + (q->h_L > 1 ? 2 * E : 0));   // + [s fl | b fl] of P_1's composition (k_xa)
+        q->o_hw = carve((q->h_L > 2 ? q->h_L : 2) * n.hw_n * 72);
+        q->hw_stride = n.hw_n * 72;
+        if (q->h_L > 2) {
+            int degmax = 0, wcmax = 0;
+            for (int l = 1; l < q->h_L; ++l) {
+                if (ccsd_hl(*q, l).cin * E > degmax) degmax = ccsd_hl(*q, l).cin * E;
+                if (ccsd_hl(*q, l).wc > wcmax) wcmax = ccsd_hl(*q, l).wc;
+            }
+            q->o_deg = carve(degmax);
+            q->o_h2m = carve(n.h1m_floats);
+            q->o_hM = carve((q->h_L - 2) * E * E);
+            q->o_hX = carve(2 * E * wcmax);
+        }
+    }
+    if (!q->hb_L) return 0;
+    // HodgeBaselineLayers: layer 0's hidden rows re-use the same regions when they fit
+    const int g = q->hb[0].cin * E * q->hb[0].hid;
+    q->o_hbg = (g <= o - q->o_att) ? q->o_att : carve(g);
+    q->o_hbd = carve(q->hb_L > 1 ? q->hb[1].cin * E : 4);
+    q->o_hbw = carve(2 * CCSD_MAXLIN * (CCSD_FW * CCSD_FW + CCSD_FW));
+    q->o_hd = carve(q->a_nch_hodge * E);
+    // per row of the chunk: the symmetrised block outputs (mlp_hodge's input), layer 0's output, the next layer's hidden row
+    return q->hb_L > 1 ? q->hb[0].cin * E + q->hb[0].cout * (E + q->hb[1].hid) : 0;
+}
+
+// The layout (float offsets) of ONE candidate: `budget` floats of LDS, the channel stack [chan_rows][N*N] in LDS (gch = 0) or in the HBM
+// workspace (1), attention channels in groups of cg.  Writes the regions into *q, a copy of the plan, and returns whether they fit the
+// budget; cg, the chunk sizes, the shared region and xa_lds_floats are written only when they do.  Every aliasing rule k_xa relies on is here or in xa_layout_hodge.
+static inline bool xa_layout(const XaNeeds& n, int budget, int gch, int cg, PlanD* q) {
+    const int N = q->N, F = q->F, E = q->E, NN = N * N, NNpad = (NN + 15) / 16 * 16;
+    int o = 0;
+    auto carve = [&](int v) { return xa_carve(o, v); };
+    q->chan_global = gch;
+    q->o_flags = carve(N);
+    q->o_x = carve(N * F);
+    q->o_adj = carve(NN);
+    q->o_an = carve(gch ? n.cinmax * N : cg * N > N ? cg * N : N);      // D^-1/2 per channel of the group (HBM stack: of the layer)
+    q->o_edge = carve(E);
+    const int phase0 = o;
+    q->o_xcat = carve(q->x_fdim * q->ldn);                              // X-network phase ...
+    // hidden activations of the head: in registers when it is chained (then h1 only receives the F outputs)
+    q->o_h1 = carve(q->x_fin.chain ? (F > 4 ? F : 4) * q->ldn : 2 * q->x_fdim * q->ldn);
+    q->o_h2 = carve(q->x_fin.chain ? 4 : 2 * q->x_fdim * q->ldn);
+    const int xphase_end = o;
+    q->x_lds_floats = xphase_end + 64;                                  // (an X-network-only launch; GMH: the whole layout, below)
+    // ... aliased by the A-network phase -- unless ScoreNetworkX is GMH, which runs the attention-stack machinery itself: its regions stay clear
+    if (!q->x_gmh) o = phase0;
+    q->o_chan = gch ? 0 : carve(q->chan_rows * NN);
+    q->o_att = carve(n.cinmax * NN);                                    // attention of every input channel
+    q->o_xcur = carve(n.fmaxA * q->ldn);
+    q->o_xnext = carve(n.fmaxA * q->ldn);
+    const int o_after_xnext = o;
+    q->o_vcat = carve(n.mchid * q->ldn);                                // hidden layer of multi_channel
+    const int hb_rmin = xa_layout_hodge(n, q, o_after_xnext, o);
+    if (xphase_end > o) o = xphase_end;
+    // shared region R: GCN scratch of a channel group | hidden activations of the MLPs | dense hodge layer
+    // [channel][node][Q | K | V] of a group (the GCN's x W intermediate lives in registers)
+    int rmin = cg * N * n.colmax;
+    if (N * q->x_nhid > rmin) rmin = N * q->x_nhid;
+    if (n.h1m_floats > rmin) rmin = n.h1m_floats;
+    if (NN > rmin) rmin = NN;                                           // raw output of the chained final MLP
+    if (hb_rmin > rmin) rmin = hb_rmin;
+    if (o + rmin > budget) return false;
+    if (!n.fin_chained && o + 2 * n.pw_fin * 16 > budget) return false;
+    // within the budget the largest chunks of pairs for the MLPs that are not chained
+    int pch = 16, pchp = 16;
+    while (!n.fin_chained && pch + 16 <= NNpad && o + 2 * n.pw_fin * xa_chunk_ld(pch + 16) <= budget) pch += 16;
+    while (!n.pair_chained && pchp + 16 <= NNpad && o + 2 * n.pw_pair * xa_chunk_ld(pchp + 16) <= budget) pchp += 16;
+    int r = rmin > 64 ? rmin : 64;
+    if (!n.fin_chained && 2 * n.pw_fin * xa_chunk_ld(pch) > r) r = 2 * n.pw_fin * xa_chunk_ld(pch);
+    if (!n.pair_chained && 2 * n.pw_pair * xa_chunk_ld(pchp) > r) r = 2 * n.pw_pair * xa_chunk_ld(pchp);
+    q->cg = cg; q->pch = pch; q->ldp = xa_chunk_ld(pch); q->pchp = pchp; q->ldpp = xa_chunk_ld(pchp);
+    q->o_c0 = carve(r);
+    q->o_red = q->o_c0;                                                 // block reductions run when R is idle
+    if (hb_rmin) { q->hb_rows = r / hb_rmin; if (q->hb_rows > E) q->hb_rows = E; }
+    q->xa_lds_floats = o;
+    if (q->x_gmh) q->x_lds_floats = o;
+    return true;
+}
+
+// Searches k_xa's layout and settles the route where there is none.  Candidate LDS budgets: what leaves 4, 3, 2 workgroups and 1 on a CU
+// (32 waves/CU hide the latency of the ~45 barrier-separated phases best).  The search starts at the budget that keeps
+// ceil(batch / #CUs) workgroups co-resident per CU (batch_hint; unknown = 4 per CU, the qm9_CC B = 1024 case; CCSD_XA_PASS=<n> starts at
+// candidate n) and grows.  Within a budget the channel stack in LDS is tried before the stack in the HBM workspace (L2-resident, one slab
+// per graph -- large graphs, zinc250k: 46 channels x 38 x 38 = 266 KB; CCSD_XA_GCH=1 tries only that): with the residency the batch needs,
+// more workgroups per CU buy nothing and the HBM stack costs.  Within either, the largest channel group first.  The first fit is taken.
+#define CCSD_XA_NCAND 4
+static const int CCSD_XA_BUDGETS[CCSD_XA_NCAND] = {40960, 53 * 1024, 79 * 1024, 152 * 1024};   // bytes
+static inline void plan_xa_layout(const ccsd_config_t* c, PlanD* p, PlanBuilder& pb, const char* lg_reason) {
+    const int N = p->N, F = p->F;
+    const XaNeeds n = xa_needs(c, *p);
+    p->ldn = round_ld(N);
+    p->chan_rows = p->a_fdim > p->g_nch ? p->a_fdim : p->g_nch;
+    p->pw_pair = n.pw_pair;
     int need = c->batch_hint > 0 ? (c->batch_hint + 255) / 256 : 4;
     need = need < 1 ? 1 : need > 4 ? 4 : need;
-    for (int pass = pb.xa_pass >= 0 ? pb.xa_pass : 4 - need; pass < NCAND && best_total < 0; ++pass)
-    for (int gch = gch_first; gch < 2 && best_total < 0; ++gch) {
-        if (stage_on[pass] && (wst_full == 0 || gch)) continue;
-        p->chan_global = gch;
-        wst = stage_on[pass] ? wst_full : 0;
-        const int budget = budgets_b[pass] / 4;
-        for (int cg = cinmax; cg >= 1 && best_total < 0; --cg) {
-            int o = 0;
-            auto carve = [&](int n) { int r = o; o += (n + 3) / 4 * 4; return r; };
-            p->o_flags = carve(N);
-            p->o_x = carve(N * F);
-            p->o_adj = carve(NN);
-            p->o_an = carve(gch ? cinmax * N : cg * N > N ? cg * N : N);    // D^-1/2 per channel of the group (HBM stack: of the layer)
-            p->o_edge = carve(E);
-            const int phase0 = o;
-            p->o_xcat = carve(p->x_fdim * p->ldn);                          // X-network phase ...
-            // hidden activations of the head: in registers when it is chained (then h1 only receives the F outputs)
-            p->o_h1 = carve(p->x_fin.chain ? (F > 4 ? F : 4) * p->ldn : 2 * p->x_fdim * p->ldn);
-            p->o_h2 = carve(p->x_fin.chain ? 4 : 2 * p->x_fdim * p->ldn);
-            const int xphase_end = o;
-            p->x_lds_floats = xphase_end + 64;                              // (GMH: the whole layout, set below)
-            // (ScoreNetworkX_GMH runs the attention-stack machinery itself: its regions stay clear of the A-network phase's)
-            if (!p->x_gmh) o = phase0;                                      // ... aliased by the A-network phase
-            p->o_chan = gch ? 0 : carve(p->chan_rows * NN);
-            p->o_tmp = o;                                                   // (raw attention scratch: gone, symmetrisation is fused)
-            p->o_att = carve(cinmax * NN);                                  // attention of every input channel
-            p->o_xcur = carve(fmaxA * p->ldn);
-            p->o_xnext = carve(fmaxA * p->ldn);
-            const int o_after_xnext = o;
-            p->o_vcat = carve(mchid * p->ldn);                              // hidden layer of multi_channel
-            p->o_deg = p->o_vcat;
-            if (p->h_L) {
-                // the hodge branch runs after the attention stack: its Q|K scratch reuses [raw attention | attention]
-                // the hodge branch runs after the attention stack: its Q|K scratch reuses [attention | node features |
-                // multi_channel hidden] (all dead by then); the degree scratch then needs its own slot
-                if (hq_floats <= o - p->o_att) {
-                    p->o_hq = p->o_att;
-                    if (p->h_L > 1 && (hq_floats > o_after_xnext - p->o_att || p->hl[1].cin * E > mchid * p->ldn))
-                        p->o_deg = carve(p->hl[1].cin * E);
-                } else {
-                    p->o_hq = carve(hq_floats);
-                    if (p->h_L > 1 && p->hl[1].cin * E > mchid * p->ldn) p->o_deg = carve(p->hl[1].cin * E);
-                }
-                p->o_hd = carve(p->a_nch_hodge * E + (p->h_L > 1 ? 2 * E : 0));   // + [s fl | b fl] of P_1's composition (k_xa)
-                p->o_hw = carve((p->h_L > 2 ? p->h_L : 2) * hw_n * 72);
-                p->hw_stride = hw_n * 72;
-                if (p->h_L > 2) {
-                    int degmax = 0, wcmax = 0;
-                    for (int l = 1; l < p->h_L; ++l) {
-                        if (ccsd_hl(*p, l).cin * E > degmax) degmax = ccsd_hl(*p, l).cin * E;
-                        if (ccsd_hl(*p, l).wc > wcmax) wcmax = ccsd_hl(*p, l).wc;
-                    }
-                    p->o_deg = carve(degmax);
-                    p->o_h2m = carve(h1m_floats);
-                    p->o_hM = carve((p->h_L - 2) * E * E);
-                    p->o_hX = carve(2 * E * wcmax);
-                }
+    PlanD q = *p;
+    bool fits = false;
+    for (int pass = pb.xa_pass >= 0 ? pb.xa_pass : 4 - need; pass < CCSD_XA_NCAND && !fits; ++pass)
+        for (int gch = pb.xa_gch; gch < 2 && !fits; ++gch)
+            for (int cg = n.cinmax; cg >= 1 && !fits; --cg) {
+                q = *p;
+                fits = xa_layout(n, CCSD_XA_BUDGETS[pass] / 4, gch, cg, &q);
             }
-            int hb_rmin = 0;
-            if (p->hb_L) {
-                // the baseline hodge branch runs after the attention stack too
-                int g = p->hb[0].cin * E * p->hb[0].hid;
-                p->o_hbg = (g <= o - p->o_att) ? p->o_att : carve(g);
-                p->o_hbd = carve(p->hb_L > 1 ? p->hb[1].cin * E : 4);
-                p->o_hbw = carve(2 * CCSD_MAXLIN * (CCSD_FW * CCSD_FW + CCSD_FW));
-                p->o_hd = carve(p->a_nch_hodge * E);
-                // per row of the chunk: the symmetrised block outputs (mlp_hodge's input), layer 0's output, the next layer's hidden row
-                if (p->hb_L > 1) hb_rmin = p->hb[0].cin * E + p->hb[0].cout * (E + p->hb[1].hid);
-            }
-            if (xphase_end > o) o = xphase_end;
-            p->o_wst = carve(wst);
-            p->wst_floats = wst;
-            // shared region R: GCN scratch of a channel group | hidden activations of the MLPs | dense hodge layer
-            // [channel][node][Q | K | V] of a group (the GCN's x W intermediate lives in registers)
-            int rmin = cg * N * colmax;
-            if (N * c->x_nhid > rmin) rmin = N * c->x_nhid;
-            if (h1m_floats > rmin) rmin = h1m_floats;
-            if (NN > rmin) rmin = NN;                                       // raw output of the chained final MLP
-            if (hb_rmin > rmin) rmin = hb_rmin;
-            if (o + rmin > budget) continue;
-            const bool pair_chained = pair_chained_all;
-            const bool fin_chained = p->a_fin.chain != 0;
-            if (!fin_chained && o + 2 * pw_fin * 16 > budget) continue;
-            int pch = 16, pchp = 16;
-            while (!fin_chained && pch + 16 <= NNpad && o + 2 * pw_fin * ld_of(pch + 16) <= budget) pch += 16;
-            while (!pair_chained && pchp + 16 <= NNpad && o + 2 * pw_pair * ld_of(pchp + 16) <= budget) pchp += 16;
-            int r = rmin;
-            if (!fin_chained && 2 * pw_fin * ld_of(pch) > r) r = 2 * pw_fin * ld_of(pch);
-            if (!pair_chained && 2 * pw_pair * ld_of(pchp) > r) r = 2 * pw_pair * ld_of(pchp);
-            p->cg = cg; p->pch = pch; p->ldp = ld_of(pch); p->pchp = pchp; p->ldpp = ld_of(pchp);
-            p->o_c0 = carve(r > 64 ? r : 64); p->o_c1 = p->o_c0;
-            if (hb_rmin) { p->hb_rows = (r > 64 ? r : 64) / hb_rmin; if (p->hb_rows > E) p->hb_rows = E; }
-            p->o_red = p->o_c0;                                              // block reductions run when R is idle
-            p->xa_lds_floats = o;
-            if (p->x_gmh) p->x_lds_floats = o;
-            best_total = o;
-        }
-    }
+    // (a plan no candidate fits keeps the regions of the last one tried, as it always did: chan_global still sizes its workspace)
+    *p = q;
+    int total = fits ? p->xa_lds_floats : -1;
     // ScoreNetworkX late (k_xa): one wave runs it in stages inside the A-network's MLP-chain intervals, where that wave has
     // no tile.  Needs: the plain networks, chained MLPs, two AttentionLayers, at most three 16-pair tiles (E <= 48), node
     // tiles of 16, and room for its own [x_fdim + max(F, 4)][ldn] + 16 floats inside the budget the layout already fits.
-    p->x_late = 0; p->o_lx = 0;
-    if (best_total > 0 && !p->x_gmh && !p->hb_L && !p->chan_global && p->x_fin.chain && p->a_fin.chain && p->a_L >= 2 && N <= 16 && E <= 48 &&
+    if (fits && !p->x_gmh && !p->hb_L && !p->chan_global && p->x_fin.chain && p->a_fin.chain && p->a_L >= 2 && N <= 16 && p->E <= 48 &&
         p->al[0].mlp.chain && p->al[1].mlp.chain) {
         const int lx = (p->x_fdim + (F > 4 ? F : 4)) * p->ldn + 16;
         int cap = 160 * 1024 / 4;
-        for (int q = NCAND - 1; q >= 0; --q) if (best_total * 4 <= budgets_b[q]) cap = budgets_b[q] / 4;
-        if (best_total + lx <= cap) { p->x_late = 1; p->o_lx = best_total; best_total += lx; p->xa_lds_floats = best_total; if (p->x_gmh) p->x_lds_floats = best_total; }
+        for (int b = CCSD_XA_NCAND - 1; b >= 0; --b) if (total * 4 <= CCSD_XA_BUDGETS[b]) cap = CCSD_XA_BUDGETS[b] / 4;
+        if (total + lx <= cap) { p->x_late = 1; p->o_lx = total; total += lx; p->xa_lds_floats = total; }
     }
     if (pb.verbose)
-        fprintf(stderr, "[ccsd] k_xa LDS %d B (cg=%d pch=%d/%d pchp=%d/%d stage=%d floats, channel stack in %s)\n", best_total * 4, p->cg, p->pch, p->ldp, p->pchp, p->ldpp, p->wst_floats, p->chan_global ? "HBM" : "LDS");
-    if (best_total < 0 || (size_t)best_total * 4 > 160 * 1024) {
+        fprintf(stderr, "[ccsd] k_xa LDS %d B (cg=%d pch=%d/%d pchp=%d/%d, channel stack in %s)\n", total * 4, p->cg, p->pch, p->ldp, p->pchp, p->ldpp,
+                p->chan_global ? "HBM" : "LDS");
+    if (!fits || (size_t)total * 4 > 160 * 1024) {
         if (!lg_reason) pb.lg = 1;         // no k_xa layout: the tiled route serves the plan
         else pb.fail(CCSD_ERR_UNSUPPORTED, std::string("graph-network working set exceeds the 160 KB LDS of a CU, and the tiled graph-network route does not serve ") + lg_reason);
     }
+}
+
+// The route: the tiled graph-network kernels (ccsd_k_lg.h) when k_xa cannot place the plan or when forced; k_xa's layout otherwise
+static inline void plan_route(const ccsd_config_t* c, PlanD* p, PlanBuilder& pb) {
+    const char* lg_reason = ccsd_lg_ineligible(c, p, pb.h_wide);
+    // above 64 nodes k_xa's working set leaves one CU's LDS; its hodge branch is written for one or two HodgeBaselineLayers; its (and k_r2's)
+    // per-thread small_mlp is 8 wide
+    const char* need = c->N > CCSD_XA_MAXN ? "N > 64 needs" : p->hb_L > CCSD_MAXHL ? "more than 2 HodgeBaselineLayers need" :
+                       pb.h_wide ? "hodge MLPs wider than 8 need" : nullptr;
+    if (need) { plan_route_only(p, pb, lg_reason, need); return; }
+    // A dense HodgeBaselineLayer beyond E = 255 -- the envelope k_xa's dense hodge layers are built and tested in (ccsd_plan_create
+    // holds ScoreNetworkA_CC stacks to it; every shipped Base_CC geometry lies inside: E = 36 .. 190) -- takes the route where it is
+    // eligible: one workgroup per complex would walk the E^2 pairs alone (grid_small_Base_CC: E = 1176, a 148 KB k_xa layout).  So does
+    // a ScoreNetworkA_CC stack of two or more layers there: k_xa's pair table of the dense layer holds edge indices in bytes
+    if ((p->hb_L > 1 || p->h_L > 1) && p->E > 255 && !lg_reason) pb.lg = 1;
+    // (1 leaves combinatorial complexes on k_xa, as before the route served any of them: tests/golden/route_plans.json pins those plans)
+    if (pb.lg_force && !lg_reason && (!c->is_cc || pb.lg_force >= 2)) pb.lg = 1;
+    plan_xa_layout(c, p, pb, lg_reason);
     if (pb.lg) pb.route_copies(*p);
-    return nweights;
+}
+
+// Fills `p` (except the affine fold, which needs the weights) and pb's outputs; returns the blob size (0 where pb holds a failure).
+static inline size_t ccsd_build_plan(const ccsd_config_t* c, PlanD* p, PlanBuilder& pb) {
+    memset(p, 0, sizeof(*p));
+    if (!plan_geometry(c, p, pb) || !plan_xnet(c, p, pb) || !plan_anet_graph(c, p, pb) || !plan_anet_hodge(c, p, pb) || !plan_fnet(c, p, pb)) return 0;
+    const size_t nweights = (size_t)pb.cur;         // (the route reserves packed copies only)
+    plan_route(c, p, pb);
+    pb.npacked = (size_t)pb.pcur;
+    return pb.status == CCSD_OK ? nweights : 0;
 }
 
 // ScoreNetworkF block layout behind the weight blob (PlanD::f_blk): Linear q of layer l at (l * CCSD_MAXLIN + q) * 72

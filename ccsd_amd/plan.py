@@ -43,26 +43,22 @@ def _mlp_shapes(prefix: str, n: int, din: int, hid: int, dout: int) -> Shapes:
     return out
 
 
-def attn_layer_dims(p: dict):
+def stack_io(l: int, L: int, c_init: int, c_hid: int, c_final: int):
+    """(cin, cout) of layer l of a stack of L: c_init into the first, c_hid between the layers, c_final out of the last -- a single
+    layer counts as a first one and puts out c_hid (ccsd_plan.h: ccsd_stack_io)."""
+    return c_init if l == 0 else c_hid, c_final if (l == L - 1 and l != 0) else c_hid
+
+
+def attn_layer_dims(p: dict, layers_key: str = "num_layers"):
     """(cin, cout, fin, adim, fout) per AttentionLayer (ScoreNetwork_A.py:398-443)."""
-    L = p["num_layers"]
-    dims = []
-    for l in range(L):
-        first, last = l == 0, (l == L - 1 and l != 0)
-        dims.append((p["c_init"] if first else p["c_hid"], p["c_final"] if last else p["c_hid"],
-                     p["max_feat_num"] if first else p["nhid"], p["nhid"] if first else p["adim"], p["nhid"]))
-    return dims
+    L = p[layers_key]
+    return [stack_io(l, L, p["c_init"], p["c_hid"], p["c_final"]) +
+            ((p["max_feat_num"], p["nhid"], p["nhid"]) if l == 0 else (p["nhid"], p["adim"], p["nhid"])) for l in range(L)]
 
 
 def gmh_layer_dims(p: dict):
     """(cin, cout, fin, adim, fout) per AttentionLayer of ScoreNetworkX_GMH (ScoreNetwork_X.py:208-252)."""
-    L = p["depth"]
-    dims = []
-    for l in range(L):
-        first, last = l == 0, (l == L - 1 and l != 0)
-        dims.append((p["c_init"] if first else p["c_hid"], p["c_final"] if last else p["c_hid"],
-                     p["max_feat_num"] if first else p["nhid"], p["nhid"] if first else p["adim"], p["nhid"]))
-    return dims
+    return attn_layer_dims(p, "depth")
 
 
 def _attn_layer_shapes(l: int, cin: int, cout: int, fin: int, ad: int, fo: int, num_linears: int, conv: str = "GCN") -> Shapes:
@@ -82,32 +78,18 @@ def _attn_layer_shapes(l: int, cin: int, cout: int, fin: int, ad: int, fo: int, 
 def hodge_layer_dims(p: dict):
     """(cin, cout, adim) per HodgeAdjAttentionLayer (ScoreNetwork_A_CC.py:155-205)."""
     L = p["num_layers_h"]
-    dims = []
-    for l in range(L):
-        first, last = l == 0, (l == L - 1 and l != 0)
-        dims.append((p["c_init"] if first else p["c_hid_h"], p["c_final_h"] if last else p["c_hid_h"],
-                     p["nhid_h"] if first else p["adim_h"]))
-    return dims
+    return [stack_io(l, L, p["c_init"], p["c_hid_h"], p["c_final_h"]) + (p["adim_h"] if l else p["nhid_h"],) for l in range(L)]
 
 
 def hodge_base_dims(p: dict):
     """(cin, cout, hidden) per HodgeBaselineLayer (ScoreNetwork_A_Base_CC.py:153-195)."""
     L = p["num_layers_h"]
-    dims = []
-    for l in range(L):
-        first, last = l == 0, (l == L - 1 and l != 0)
-        dims.append((p["c_init"] if first else p["c_hid_h"], p["c_final_h"] if last else p["c_hid_h"],
-                     p["nhid_h"] if first else p["hidden_h"]))
-    return dims
+    return [stack_io(l, L, p["c_init"], p["c_hid_h"], p["c_final_h"]) + (p["hidden_h"] if l else p["nhid_h"],) for l in range(L)]
 
 
 def fnet_layer_dims(p: dict):
     L = p["num_layers"]
-    dims = []
-    for l in range(L):
-        first, last = l == 0, (l == L - 1 and l != 0)
-        dims.append((p["cnum"] if first else p["c_hid"], p["c_final"] if last else p["c_hid"]))
-    return dims
+    return [stack_io(l, L, p["cnum"], p["c_hid"], p["c_final"]) for l in range(L)]
 
 
 def state_dict_shapes(params: dict) -> Shapes:

@@ -1,14 +1,16 @@
-"""Regenerate ccsd_amd/csrc/ccsd_baked_qm9.h: the plan (PlanD) of the qm9_CC configuration at batch 1024 as a compile-time constant.
+"""Regenerate the baked plans ccsd_amd/csrc/ccsd_baked_{qm9,cs,z,enz}.h: the plan (PlanD) of the qm9_CC, community_small_CC, zinc250k
+and enzymes_small_CC configurations (TARGETS), each at its bench batch, as a compile-time constant.
 
     python tools/bake_plan.py            (CPU only: uses the host emulation of the kernel source, tests/emu)
 
-k_xa<false, XA_BAKED9> reads every plan field from this constant (index arithmetic, loop bounds and LDS offsets fold into
-immediates); the host selects that instance only for a plan whose architecture bytes (ccsd_plan_arch_bytes: the plan with the
-weight-derived affine fold zeroed) equal the baked ones, so any other configuration, batch or planner version simply runs the
-run-time-plan instances.  Re-run after changing PlanD or the planner (ccsd_plan.h); tests/test_gpu_parity.py checks that the
-headline plan really selects the baked instance and that it agrees bit for bit with the run-time-plan instance.
-The configuration is read from the shipped checkpoint's own config (tests/golden) with the sampler settings of
-config/sample_qm9_CC.yaml (bench.py WORKLOADS["qm9_CC"])."""
+The baked k_xa / k_r2 instances (XA_BAKED9, XA_BAKED20, XA_BAKED38, XA_BAKEDENZ) read every plan field from their constant (index
+arithmetic, loop bounds and LDS offsets fold into immediates); the host selects such an instance only for a plan whose architecture
+bytes (ccsd_plan_arch_bytes: the plan with the weight-derived affine fold zeroed) equal the baked ones, so any other configuration,
+batch or planner version simply runs the run-time-plan instances.  Re-run after changing PlanD or the planner (ccsd_plan.h): a
+header whose CCSD_BAKED_*_SIZE is not sizeof(PlanD) never matches.  tests/test_emu_parity.py checks that the committed headers are
+what the planner produces, tests/test_gpu_parity.py that the headline plan selects the baked instance and that it agrees bit for bit
+with the run-time-plan instance.  Each configuration is read from the shipped checkpoint's own config with the sampler settings of
+its bench workload (bench.py WORKLOADS)."""
 import os
 import sys
 
