@@ -29,7 +29,7 @@ EXPORTS = [
     "ccsd_eig_workspace_bytes", "ccsd_eigvalsh", "ccsd_spectral_workspace_bytes", "ccsd_spectral_hist",
     "ccsd_hodge_workspace_bytes", "ccsd_hodge_spectrum",
     "ccsd_nspdk_row_capacity", "ccsd_nspdk_workspace_bytes", "ccsd_nspdk_features", "ccsd_nspdk_mmd_workspace_bytes", "ccsd_nspdk_mmd",
-    "ccsd_lift",
+    "ccsd_lift", "ccsd_mol_correct",
 ]
 QUERIES = {"fused_r2": 0, "xa_variant": 1, "r2_lds_bytes": 2, "xa_lds_bytes": 3, "fused_loop": 4, "merged_r2": 5, "ew1": 6, "large_graph": 7,
            "r2_family": 8, "r2_instance": 9, "loop_form": 10, "h_full": 11, "hp_full": 12, "p0_narrow": 13, "tiled_fuse": 14, "ew1_fuse": 15,
@@ -73,6 +73,7 @@ CLUSTER_MAX_BINS, MMD_MAX_ROWS, MMD_MAX_BINS = 1024, 1 << 20, 1 << 16      # CCS
 ORBITS = 15                                                               # CCSD_ORBITS: ORCA's orbits of the graphlets on 2..4 nodes
 NSPDK_MAX_NODES, NSPDK_FEATURES = 64, 65537                               # CCSD_NSPDK_MAX_NODES, CCSD_NSPDK_FEATURES
 LIFT_PATHS, LIFT_CYCLES, LIFT_MAX_NODES = 0, 1, 64                         # CCSD_LIFT_PATHS, CCSD_LIFT_CYCLES; the node limit of ccsd_lift
+MOL_MAX_ATOMS, MOL_MAX_LABELS = 64, 16                                    # CCSD_MOL_MAX_ATOMS, CCSD_MOL_MAX_LABELS
 EIG_MAXN, EIG_MAX_SWEEPS = 512, 30                                        # CCSD_EIG_MAXN; the sweep cap of k_eigvalsh
 
 
@@ -87,6 +88,17 @@ FINISH_OUTPUTS = ("adj_int", "degree", "degree_hist", "edge_hist", "n_nodes", "x
 
 class FinishOut(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in FINISH_OUTPUTS]
+
+
+class MolDims(C.Structure):
+    _fields_ = [("B", C.c_int32), ("N", C.c_int32), ("L", C.c_int32), ("largest_fragment", C.c_int32)]
+
+
+MOL_OUTPUTS = ("mol_adj", "mol_labels", "mol_charge", "mol_no_correct", "mol_n_corrections", "mol_n_fragments", "mol_atoms")
+
+
+class MolOut(C.Structure):
+    _fields_ = [(n, C.c_void_p) for n in MOL_OUTPUTS]
 
 
 # ccsd_reduce_fn: int (*)(float* sums_dev, int32_t n, void* stream, void* user)
@@ -206,6 +218,8 @@ class Library:
         L.ccsd_nspdk_mmd.restype = C.c_int
         L.ccsd_lift.argtypes = [vp, i32, i32, i32, f32, i32, i32, u64, i32, i32, vp, vp, vp, vp, vp, vp, vp]
         L.ccsd_lift.restype = C.c_int
+        L.ccsd_mol_correct.argtypes = [P(MolDims), vp, vp, P(i32), P(i32), P(MolOut), vp]
+        L.ccsd_mol_correct.restype = C.c_int
 
     def __getattr__(self, name):
         return getattr(self.c, name)

@@ -1,6 +1,6 @@
 // ccsd_api_samples.h -- host side of the PLAN-FREE entry points of include/ccsd_hip.h: the operations on finished samples, which take
 // tensors and sizes and never a ccsd_plan_t (ccsd_quantize, ccsd_rank2_cells, ccsd_finish, ccsd_cluster_hist, ccsd_orbit_counts, ccsd_nspdk_features, ccsd_nspdk_mmd, ccsd_mmd, ccsd_eigvalsh,
-// ccsd_spectral_hist, ccsd_hodge_spectrum, ccsd_lift and their *_workspace_bytes).  Included by ccsd_api.h as its last line; of what stands above it
+// ccsd_spectral_hist, ccsd_hodge_spectrum, ccsd_lift, ccsd_mol_correct and their *_workspace_bytes).  Included by ccsd_api.h as its last line; of what stands above it
 // there, this file uses set_err, grid_for, RT_CHECK and LAUNCH_CHECK only.
 //
 // One definition per rule: check_batch (B, N, the quantiser), check_hist (bins, edges), check_scratch (workspace), no_bytes, quant_thr,
@@ -509,5 +509,57 @@ extern "C" int ccsd_lift(const float* adj, int32_t B, int32_t N, int32_t adj_mod
                     quant_thr(adj_mode, thr), tab, (int)d_min, K, W, (const unsigned long long*)cell_bits, rank2);
         LAUNCH_CHECK();
     }
+    return CCSD_OK;
+}
+
+// ---------------- molecule post-processing (ccsd_k_mol.h) ----------------
+static_assert(CCSD_MOL_MAX_ATOMS == CCSD_MOL_MAXN && CCSD_MOL_MAX_LABELS == CCSD_MOL_MAXL, "the header's limits are k_mol_correct's");
+#define CCSD_MOL_WAVES 4                                                 // molecules (waves) per workgroup of k_mol_correct
+// ccsd_mol_correct: construct_mol, correct_mol and the largest fragment (utils/mol_utils.py:144-326) of every molecule: k_mol_check_labels,
+// whose flag is read back -- the one host round trip --, then k_mol_correct
+extern "C" int ccsd_mol_correct(const ccsd_mol_dims_t* d, const float* adj, const int32_t* labels, const int32_t* max_valence,
+                                const int32_t* charge_base, const ccsd_mol_out_t* out, void* stream) {
+    if (!d || !out) return set_err(CCSD_ERR_INVALID, "ccsd_mol_correct: NULL argument");
+    const int B = d->B, N = d->N, L = d->L;
+    if (B == 0) return CCSD_OK;
+    if (B < 0) return set_err(CCSD_ERR_INVALID, "ccsd_mol_correct: B must be >= 0");
+    if (N < 1 || N > CCSD_MOL_MAXN)
+        return set_err(CCSD_ERR_INVALID, "ccsd_mol_correct: N = " + std::to_string(N) + " outside 1.." + std::to_string(CCSD_MOL_MAXN) +
+                                             ": lane i of a wave owns atom slot i");
+    if (L < 1 || L > CCSD_MOL_MAXL)
+        return set_err(CCSD_ERR_INVALID, "ccsd_mol_correct: L = " + std::to_string(L) + " outside 1.." + std::to_string(CCSD_MOL_MAXL));
+    if (!adj || !labels || !max_valence || !charge_base || !out->mol_adj || !out->mol_labels || !out->mol_charge || !out->no_correct ||
+        !out->n_corrections || !out->n_fragments || !out->atoms)
+        return set_err(CCSD_ERR_INVALID, "ccsd_mol_correct: NULL argument");
+    MolTab tab;
+    memset(&tab, 0, sizeof tab);
+    tab.L = L;
+    for (int i = 0; i < L; ++i) {
+        for (int c = 0; c < 2; ++c) {
+            // (an atom over-valent without a bond would have nothing to lower; 255 bounds the sums of 63 triple bonds from above)
+            if (max_valence[2 * i + c] < 0 || max_valence[2 * i + c] > 255)
+                return set_err(CCSD_ERR_INVALID, "ccsd_mol_correct: max_valence of label " + std::to_string(i) + " outside 0..255");
+            tab.maxv[i][c] = max_valence[2 * i + c];
+        }
+        if (charge_base[i] < 0 || charge_base[i] > 255)
+            return set_err(CCSD_ERR_INVALID, "ccsd_mol_correct: charge_base of label " + std::to_string(i) + " outside 0..255");
+        tab.cbase[i] = charge_base[i];
+    }
+    // a label >= L has no row in the table: the flag is raised in out->atoms[0], which k_mol_correct then overwrites
+    int* flag = (int*)out->atoms;
+    int bad = 0;
+    RT_CHECK(rt_memset_async(flag, 0, 4, stream));
+    const int64_t n = (int64_t)B * N;
+    CCSD_LAUNCH(k_mol_check_labels, dim3(n < 256 * 1024 ? grid_for(n, 256) : 1024), dim3(CCSD_NTHREADS), 0, stream, (const int*)labels,
+                (long long)n, L, flag);
+    LAUNCH_CHECK();
+    RT_CHECK(rt_d2h_sync(&bad, flag, 4, stream));
+    if (bad) return set_err(CCSD_ERR_INVALID, "ccsd_mol_correct: a label is >= L = " + std::to_string(L));
+    const int waves = CCSD_NTHREADS == 1 ? 1 : CCSD_MOL_WAVES;
+    CCSD_LAUNCH(k_mol_correct, dim3((B + waves - 1) / waves), dim3(CCSD_NTHREADS == 1 ? 1 : 64 * waves), (size_t)waves * mol_lds_bytes(N), stream,
+                adj, (const int*)labels, B, N, tab, (int)(d->largest_fragment != 0), (unsigned char*)out->mol_adj, (int*)out->mol_labels,
+                (signed char*)out->mol_charge, (unsigned char*)out->no_correct, (int*)out->n_corrections, (int*)out->n_fragments,
+                (int*)out->atoms);
+    LAUNCH_CHECK();
     return CCSD_OK;
 }

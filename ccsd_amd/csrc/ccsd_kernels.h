@@ -33,7 +33,7 @@
 //                    plan_anet_hodge, plan_fnet, plan_route (k_xa's LDS layout: xa_layout per candidate, plan_xa_layout the search);
 //                    the packers and table builders of plan creation (ccsd_pack_*, ccsd_edge_table, ccsd_cell_table, ccsd_hodge_pairs)
 //   ccsd_api.h       host side of the C ABI: plan, route, workspace, launchers, the sampler loop; its last line includes
-//   ccsd_api_samples.h   the host side of the plan-free entry points (ccsd_quantize .. ccsd_lift: operations on finished samples)
+//   ccsd_api_samples.h   the host side of the plan-free entry points (ccsd_quantize .. ccsd_mol_correct: operations on finished samples)
 // The product library is built from several translation units compiled in parallel (ccsd_hip.hip: C ABI + the small kernels;
 // ccsd_r2*.hip / ccsd_xa.hip: the explicit instantiations of the two big kernel templates); the host emulation used by the
 // CPU tests includes everything in one unit.  Reference file:line citations sit next to each restated formula.
@@ -50,4 +50,5 @@
 #include "ccsd_k_nspdk.h"
 #include "ccsd_k_eig.h"
 #include "ccsd_k_lift.h"
+#include "ccsd_k_mol.h"
 #include "ccsd_k_lg.h"

@@ -42,6 +42,7 @@ static inline rtError_t rt_malloc(void** p, size_t n) { *p = calloc(n ? n : 1, 1
 static inline rtError_t rt_free(void* p) { free(p); return 0; }
 static inline rtError_t rt_h2d(void* d, const void* h, size_t n) { memcpy(d, h, n); return 0; }
 static inline rtError_t rt_d2d_async(void* d, const void* s, size_t n, void*) { memcpy(d, s, n); return 0; }
+static inline rtError_t rt_d2h_sync(void* h, const void* d, size_t n, void*) { memcpy(h, d, n); return 0; }
 static inline rtError_t rt_memset_async(void* d, int v, size_t n, void*) { memset(d, v, n); return 0; }
 static inline rtError_t rt_last_error() { return 0; }
 static inline const char* rt_error_string(rtError_t) { return "emu"; }
@@ -73,6 +74,11 @@ static inline rtError_t rt_free(void* p) { return hipFree(p); }
 static inline rtError_t rt_h2d(void* d, const void* h, size_t n) { return hipMemcpy(d, h, n, hipMemcpyHostToDevice); }
 static inline rtError_t rt_d2d_async(void* d, const void* s, size_t n, void* st) {
     return hipMemcpyAsync(d, s, n, hipMemcpyDeviceToDevice, (hipStream_t)st);
+}
+// device -> host behind everything queued on the stream; returns when the bytes have arrived
+static inline rtError_t rt_d2h_sync(void* h, const void* d, size_t n, void* st) {
+    const rtError_t e = hipMemcpyAsync(h, d, n, hipMemcpyDeviceToHost, (hipStream_t)st);
+    return e != hipSuccess ? e : hipStreamSynchronize((hipStream_t)st);
 }
 static inline rtError_t rt_memset_async(void* d, int v, size_t n, void* st) { return hipMemsetAsync(d, v, n, (hipStream_t)st); }
 static inline rtError_t rt_last_error() { return hipGetLastError(); }

@@ -13,6 +13,8 @@ needs no external program:
                                                                                         -> SampleOps.nspdk_features / nspdk_mmd
   convert_graphs_to_CCs with path_based (path_length 3) / cycles  (cc_utils.py:816-880, 1644-1754) -> SampleOps.lift (ccsd_lift); opt-in:
                                                                   describe(lift=), eval_CC_batch(lift=), lift_settings
+  gen_mol: construct_mol, correct_mol, the largest fragment       (utils/mol_utils.py:144-326)   -> SampleOps.mol_correct (ccsd_mol_correct)
+                                                                  with MOL_TABLES; opt-in: Sampler.molecules, Sampler.evaluate(correct=True)
 
 The reference builds networkx graphs / toponetx complexes on the host and solves one pyemd linear program per pair of histograms.
 Here a sample set is a dict of per-sample integer DESCRIPTORS on the device -- `describe()`: the descriptor outputs of
@@ -22,9 +24,9 @@ solver (ccsd_eigvalsh, a batched Jacobi iteration on the device) and cost O(N^3)
 opt-in, `spectra=True`.  The orbit score counts 4-node graphlets per graph on the device where the reference starts the orca program
 once per graph; its cost grows with the triangles of a graph, so it is opt-in as well, `orbits=True`.  The NSPDK score -- the one
 graph score the reference prints for molecule runs -- hashes neighbourhood pairs per graph on the device and is opt-in, `nspdk=True`;
-it takes INTEGER node labels (mol_labels) and scores the quantised samples AS SAMPLED: the reference scores molecules after rdkit's
-valency correction and largest-fragment selection, which this build does not have (a user with rdkit can pass corrected adj / labels),
-and labels atoms with symbol strings, whose Python hash differs from process to process.  There is no CPU fallback:
+it takes INTEGER node labels (mol_labels) where the reference labels atoms with symbol strings, whose Python hash differs from process
+to process.  The reference scores molecules after valency correction and largest-fragment selection (gen_mol): SampleOps.mol_correct
+does that on the device with the valence data of MOL_TABLES, Sampler.evaluate(correct=True) scores its result.  There is no CPU fallback:
 methods that need an external program raise NotImplementedError (UNSUPPORTED); their histograms, computed elsewhere, can still be
 scored through compute_mmd.
 """
@@ -291,6 +293,29 @@ def mol_labels(x) -> torch.Tensor:
     return torch.where(on.any(-1), first, torch.full_like(first, -1)).to(torch.int32)
 
 
+def _mol_table(atomic_num_list):
+    # element -> (largest permitted valence when neutral, with charge +1, the reference's ATOM_VALENCY entry if it may take the charge)
+    elements = {6: (4, 4, 0), 7: (3, 4, 3), 8: (2, 3, 2), 9: (1, 1, 0), 15: (7, 7, 0), 16: (6, 6, 2), 17: (1, 1, 0), 35: (1, 1, 0), 53: (5, 5, 0)}
+    return {"atomic_num_list": list(atomic_num_list), "max_valence": [list(elements[z][:2]) for z in atomic_num_list],
+            "charge_base": [elements[z][2] for z in atomic_num_list]}
+
+
+MOL_TABLES = {"QM9": _mol_table([6, 7, 8, 9]), "ZINC250k": _mol_table([6, 7, 8, 9, 15, 16, 17, 35, 53])}
+"""The valence data of SampleOps.mol_correct per molecule data set -- the one place it lives.  A row per node label, in the order of the
+reference's atomic_num_list (gen_mol, utils/mol_utils.py:212-215; the label is mol_labels' channel index):
+  atomic_num_list   QM9 [6, 7, 8, 9] = C N O F; ZINC250k [6, 7, 8, 9, 15, 16, 17, 35, 53] = C N O F P S Cl Br I
+  max_valence       [neutral, charge +1]: the bond-order sum above which rdkit's SanitizeMol(SANITIZE_PROPERTIES) refuses the atom, i.e. the
+                    largest entry of rdkit's permitted-valence list.  Neutral: C 4, N 3, O 2, F 1, P 7, S 6, Cl 1, Br 1, I 5.  With
+                    charge +1 rdkit takes the list of the isoelectronic element: N 4, O 3.  Only N and O are ever charged with these
+                    tables (S at 3 is not over-valent, so construct_mol never charges it); the other labels repeat their neutral entry,
+                    which is never read.
+  charge_base       the reference's ATOM_VALENCY entry (mol_utils.py:24) of the labels construct_mol may charge (mol_utils.py:186): N 3,
+                    O 2, S 2; 0 for every other label.
+rdkit is not installed where this project is built and tested, so NOBODY HAS CHECKED THESE MAXIMA AGAINST RDKIT: they are restated from
+rdkit's element table.  That is why they are data and an argument of mol_correct (max_valence=, charge_base=), not constants of the
+kernel."""
+
+
 def nspdk_rows(obj, kw) -> Dict[str, torch.Tensor]:
     """The NSPDK feature rows of a side (CSR: NSPDK_KEYS): taken from a dict that holds them, computed from its `adj` with the labels
     `nspdk_labels`, or mol_labels(x) of its `x` in mol mode, or label 0 (a raw batch has label 0 in every slot)."""
@@ -312,8 +337,8 @@ def nspdk_rows(obj, kw) -> Dict[str, torch.Tensor]:
 def nspdk_stats(ref, pred, **kw) -> float:
     """nspdk_stats (stats.py:438-467): the MMD of the two sets' NSPDK feature rows under the linear kernel -- it takes no kernel
     argument.  ref / pred: adjacency batches (label 0 in every slot) or dicts (the three nspdk_* keys, or adj plus nspdk_labels or x).
-    Predicted graphs without a node are left out, as in the reference.  The score is of the quantised samples as sampled, with integer
-    labels: see the module docstring for what the reference does differently for molecules."""
+    Predicted graphs without a node are left out, as in the reference.  The score is of the sets as given, with integer labels: for
+    molecules the reference corrects the predicted set first (SampleOps.mol_correct; see the module docstring)."""
     a, b = nspdk_rows(ref, kw), nspdk_rows(pred, kw)
     eng = _ops(kw.get("device") if kw.get("device") is not None else (a["nspdk_indptr"].device if a["nspdk_indptr"].device.type == "cuda" else None), kw.get("lib"))
     return float(eng.nspdk_mmd(a, b)[3].item())

@@ -351,10 +351,31 @@ class Sampler:
             print("Sampling done.")
         return out
 
+    def molecules(self, result, largest_fragment: bool = True) -> Dict[str, torch.Tensor]:
+        """The molecules the reference scores (gen_mol, utils/mol_utils.py:191-229; Sampler_mol_*.sample calls it on every sample):
+        SampleOps.mol_correct -- formal charges, valency correction, the largest fragment, with the data set's row of
+        evaluation.MOL_TABLES -- of `result["adj"]` and evaluation.mol_labels(result["x"]).  `result`: what sample() returned (or any
+        dict with raw `adj` (B,N,N) and `x` (B,N,F)).  Returns mol_correct's outputs plus "validity_wo_correction" = mol_no_correct.sum()
+        / B, the first figure the reference prints for a molecule run.  Molecule samplers only: ValueError otherwise."""
+        from . import evaluation as ev
+
+        if not self.is_mol:
+            raise ValueError("molecules: valency correction applies to molecule samplers (data.data QM9 or ZINC250k) only")
+        name = _get(_get(self.config, "data"), "data")
+        if name not in ev.MOL_TABLES:
+            raise ValueError(f"molecules: no valence table for data.data = {name!r}; evaluation.MOL_TABLES has {sorted(ev.MOL_TABLES)}")
+        missing = [k for k in ("adj", "x") if k not in result]
+        if missing:
+            raise KeyError(f"molecules: the result lacks {missing}")
+        adj = torch.as_tensor(result["adj"]).to(device=self.device0, dtype=torch.float32)
+        labels = ev.mol_labels(torch.as_tensor(result["x"])).to(self.device0)
+        out = SampleOps(self.device0, self.extra.get("lib")).mol_correct(adj, labels, dataset=name, largest_fragment=largest_fragment)
+        out["validity_wo_correction"] = float(out["mol_no_correct"].sum().item()) / max(adj.shape[0], 1)
+        return out
 
     def evaluate(self, result, ref, methods: Optional[List[str]] = None, cc_methods: Optional[List[str]] = None, bins: int = 100,
                  cc_nb_eval: Optional[int] = 1000, spectra: bool = False, orbits: bool = False, nspdk: bool = False,
-                 lift: bool = False) -> Dict[str, float]:
+                 lift: bool = False, correct: bool = False) -> Dict[str, float]:
         """Score a finished run against a held-out set on the GPU (ccsd_amd/evaluation.py): what the reference prints after
         sampling from eval_graph_list and eval_CC_list (sampler.py:253-262, 565-583), for the methods this build computes.
         `result`: what sample() returned.  `ref`: an adjacency batch (B, N, N) of the held-out graphs, a descriptor dict
@@ -368,9 +389,13 @@ class Sampler:
         reference gets from the external orca program), computed from `adj` of each side.  nspdk=True adds "nspdk", the graph score the
         reference prints for molecule runs (nspdk_stats; not rounded, as in the reference), computed from `adj` of each side (at most 64
         nodes) and integer node labels: for molecule samplers evaluation.mol_labels of the side's `x`, or its `nspdk_labels`
-        (KeyError when a side has neither), label 0 otherwise.  It scores the quantised samples AS SAMPLED: the reference scores
-        molecules after rdkit's valency correction and largest-fragment selection, which this build does not have -- pass corrected
-        `adj` / `nspdk_labels` to score those.  lift=True LIFTS graphs to complexes by the config's rule (data.lifting_procedure /
+        (KeyError when a side has neither), label 0 otherwise.  Without `correct` it scores the quantised samples AS SAMPLED.
+        correct=True (molecule samplers only, ValueError otherwise) first passes the PREDICTED side through molecules() -- the
+        reference's gen_mol: formal charges, valency correction, largest fragment -- and computes every score from its mol_adj /
+        mol_labels: "degree", "cluster", "nspdk" and, for complexes, "rank1_distrib" (the sampled rank-2 cells belong to the uncorrected
+        molecule and are not scored).  Predicted molecules left without an atom are left out; the held-out side holds real molecules and
+        is left as given, as in the reference.  The result gains "validity_wo_correction".
+        lift=True LIFTS graphs to complexes by the config's rule (data.lifting_procedure /
         lifting_procedure_kwargs with data.d_min / d_max; evaluation.lift_settings, SampleOps.lift, at most 64 nodes), as the reference's
         data generators and Sampler_Graph do (sampler.py:259-287): on a sampler of complexes a side that has `adj` but no rank-2
         descriptors -- normally the held-out graphs -- is lifted, so that "rank2_distrib" and, with spectra=True,
@@ -381,8 +406,19 @@ class Sampler:
         rank holds the gathered samples and rank 0 alone evaluates; the other ranks return {}."""
         from . import evaluation as ev
 
+        if correct and not self.is_mol:
+            raise ValueError("evaluate: correct=True applies to molecule samplers (data.data QM9 or ZINC250k) only")
         if self.rank != 0:
             return {}
+        validity = None
+        if correct:
+            if isinstance(result, (str, os.PathLike)):
+                with np.load(result) as z:
+                    result = {k: torch.from_numpy(z[k]) for k in ("adj", "x") if k in z.files}
+            mols = self.molecules(result)
+            validity = mols["validity_wo_correction"]
+            kept = mols["mol_atoms"] > 0
+            result = {"adj": mols["mol_adj"][kept].to(torch.float32), "nspdk_labels": mols["mol_labels"][kept], "n_nodes": mols["mol_atoms"][kept]}
         lib = self.extra.get("lib")
         kw = dict(device=self.device0, lib=lib)
         data = _get(self.config, "data")
@@ -440,6 +476,8 @@ class Sampler:
                     have.append("hodge_laplacian_spectrum")
             out.update(ev.eval_CC_batch(held, pred, wk, have if cc_methods is None else cc_methods, cc_nb_eval=cc_nb_eval, spectra=spectra,
                                         mol=self.is_mol, **kw))
+        if validity is not None:
+            out["validity_wo_correction"] = validity
         return out
 
 

@@ -390,6 +390,58 @@ class SampleOps:
                                           _ptr(res["rank2_nnz"]), _ptr(res["lift_dropped"]), _ptr(res.get("rank2")), self._stream()))
         return res
 
+    def mol_correct(self, adj: torch.Tensor, labels: torch.Tensor, *, dataset: str = "QM9", max_valence=None, charge_base=None,
+                    largest_fragment: bool = True) -> dict:
+        """Molecule post-processing (ccsd_mol_correct): what gen_mol of the reference (utils/mol_utils.py:191-229) does to every sample
+        of a molecule run before it is scored -- construct_mol's formal charges, correct_mol's lowering of over-valent bonds, the
+        largest fragment of valid_mol_can_with_seg -- on integer bond orders, without rdkit.  adj (B,N,N) float32 raw samples,
+        N <= 64, quantised with finish()'s molecule quantiser (bond orders 0..3); pair (i, j), i < j, is read from row i, as lift reads
+        it.  labels (B,N) integer, as evaluation.mol_labels gives them: -1 = no atom (bonds to such a slot are ignored).  `dataset`
+        names a row of evaluation.MOL_TABLES ("QM9", "ZINC250k"); max_valence (L,2) = [neutral, charge +1] and charge_base (L,)
+        replace its tables (integers 0..255, L <= 16).
+          mol_adj (B,N,N) uint8         symmetric bond orders, zero diagonal
+          mol_labels (B,N) int32, mol_charge (B,N) int8     -1 / 0 for a slot without an atom; slots are not compacted
+          mol_no_correct (B,) uint8     no atom was over-valent after construction (the reference's "validity w/o correction" counts these)
+          mol_n_corrections (B,) int32  the decrements of correct_mol
+          mol_n_fragments (B,) int32    connected components after correction, before selection
+          mol_atoms (B,) int32          the atoms kept
+        largest_fragment=True keeps the fragment with the most atoms (tie: the one holding the lowest slot) and drops every other
+        atom -- the reference compares the lengths of the fragments' SMILES strings instead; False keeps every fragment, as the
+        reference's largest_connected_comp=False.  Every output is written in full.  The call reads one flag back (a label >= L raises
+        ValueError): it synchronises the stream once."""
+        adj = self._adj("mol_correct", adj)
+        B, N = adj.shape[0], adj.shape[1]
+        if tuple(labels.shape) != (B, N) or labels.dtype.is_floating_point or labels.dtype == torch.bool or labels.device.type != self.device.type:
+            raise ValueError(f"mol_correct: labels must be integer of shape ({B}, {N}) on {self.device}, got {labels.dtype} {tuple(labels.shape)} {labels.device}")
+        labels = labels.to(torch.int32).contiguous()
+        if max_valence is None or charge_base is None:
+            from .evaluation import MOL_TABLES
+
+            if dataset not in MOL_TABLES:
+                raise ValueError(f"mol_correct: dataset must be one of {sorted(MOL_TABLES)}, got {dataset!r}")
+            max_valence = MOL_TABLES[dataset]["max_valence"] if max_valence is None else max_valence
+            charge_base = MOL_TABLES[dataset]["charge_base"] if charge_base is None else charge_base
+        tables = []
+        for name, t in (("max_valence", max_valence), ("charge_base", charge_base)):
+            t = np.asarray(t.detach().cpu() if isinstance(t, torch.Tensor) else t)
+            if t.dtype.kind not in "iu":
+                raise ValueError(f"mol_correct: {name} must hold integers, got {t.dtype}")
+            tables.append(np.ascontiguousarray(t, dtype=np.int32))
+        mv, cb = tables
+        if mv.ndim != 2 or mv.shape[1] != 2 or cb.shape != (mv.shape[0],):
+            raise ValueError(f"mol_correct: max_valence must be (L, 2) and charge_base (L,), got {mv.shape} and {cb.shape}")
+        dev = adj.device
+        shapes = {"mol_adj": ((B, N, N), torch.uint8), "mol_labels": ((B, N), torch.int32), "mol_charge": ((B, N), torch.int8),
+                  "mol_no_correct": ((B,), torch.uint8), "mol_n_corrections": ((B,), torch.int32), "mol_n_fragments": ((B,), torch.int32),
+                  "mol_atoms": ((B,), torch.int32)}
+        res = {k: torch.empty(shape, dtype=dt, device=dev) for k, (shape, dt) in shapes.items()}
+        dims = _lib.MolDims(B, N, mv.shape[0], int(bool(largest_fragment)))
+        out = _lib.MolOut(*[_ptr(res[n]) for n in _lib.MOL_OUTPUTS])
+        i32p = C.POINTER(C.c_int32)
+        self.lib.check(self.lib.ccsd_mol_correct(C.byref(dims), _ptr(adj), _ptr(labels), mv.ctypes.data_as(i32p), cb.ctypes.data_as(i32p),
+                                                 C.byref(out), self._stream()))
+        return res
+
 
 def cells_from_bits(bits_row, N: int, d_min: int, d_max: int):
     """Cell tuples of one complex from its bitmask row, in the reference's enumeration order (get_cells,

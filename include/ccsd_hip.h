@@ -53,6 +53,8 @@
  * ccsd_lift                    convert_graphs_to_CCs + CC_to_incidence_matrices for the two lifting rules the configs ship:
  *                              path_based_lift_CC with path_length 3 and cycles_lift_CC (cc_utils.py:816-880, 1644-1754, 265-330), as the
  *                              cell bitmask and descriptors ccsd_finish writes, and on request the dense rank-2 incidence tensor
+ * ccsd_mol_correct             gen_mol without rdkit: construct_mol's formal charges, correct_mol and the largest fragment of
+ *                              valid_mol_can_with_seg on integer bond orders (utils/mol_utils.py:144-326)
  */
 #ifndef CCSD_HIP_H
 #define CCSD_HIP_H
@@ -542,6 +544,47 @@ enum { CCSD_LIFT_PATHS = 0, CCSD_LIFT_CYCLES = 1 };
 int ccsd_lift(const float* adj_dev, int32_t B, int32_t N, int32_t adj_mode, float thr, int32_t procedure, int32_t path_length,
               uint64_t sources_mask, int32_t d_min, int32_t d_max, uint64_t* cell_bits_dev, int32_t* cell_count_dev,
               int32_t* cell_hist_dev, int32_t* nnz_dev, int32_t* dropped_dev, float* rank2_dev, void* stream);
+
+/* Molecule post-processing: what gen_mol (utils/mol_utils.py:191-229) does to every sample of a molecule run before it is scored, on
+ * integer bond orders and without rdkit.  adj_dev (B,N,N) fp32 raw samples, quantised here in CCSD_FINISH_ADJ_MOL mode (bond orders
+ * 0..3); pair (i, j), i < j, is read from row i, as ccsd_lift reads it -- for a symmetric adjacency the reference's adj[start, end],
+ * start > end.  labels_dev (B,N) int32: the label per atom slot, negative = no atom (bonds to such a slot are ignored).  HOST tables, read
+ * during the call: max_valence (L,2) int32, the largest permitted bond-order sum of a label's atom when neutral and with charge +1, and
+ * charge_base (L,) int32, the valence above which by exactly one the atom takes charge +1 (the reference's ATOM_VALENCY), 0 for a label
+ * that takes none.
+ *   construct_mol   bonds enter in ascending (larger index, smaller index) order, each with the next insertion number; after every bond
+ *                   the FIRST atom in slot order whose sum exceeds its maximum is looked up, and takes charge +1 when its sum is
+ *                   charge_base + 1 (an earlier atom that stays over-valent masks the later ones, as in the reference);
+ *                   no_correct = no atom is over-valent at the end
+ *   correct_mol     while an atom is over-valent: the first one; its bond of highest order, on a tie of lowest insertion number, drops by
+ *                   one; at 0 it is gone, otherwise it gets a fresh insertion number
+ *   fragments       connected components of the result; largest_fragment != 0 keeps the one with the most atoms (tie: the one holding
+ *                   the lowest slot) and drops every other atom.  DIFFERENCE from the reference, which keeps the fragment with the
+ *                   longest SMILES string.
+ * Outputs, every one required and fully written; slots are not compacted:
+ *   mol_adj (B,N,N) uint8 symmetric bond orders, zero diagonal; mol_labels (B,N) int32 (-1: no atom); mol_charge (B,N) int8;
+ *   no_correct (B,) uint8; n_corrections (B,) int32 decrements; n_fragments (B,) int32 after correction, before selection;
+ *   atoms (B,) int32 the atoms kept.
+ * The call reads one flag back from the device before its main launch (it synchronises the stream once).  B = 0 is a no-op.
+ * CCSD_ERR_INVALID: N outside 1..CCSD_MOL_MAX_ATOMS, L outside 1..CCSD_MOL_MAX_LABELS, a label >= L, a table entry outside 0..255. */
+#define CCSD_MOL_MAX_ATOMS 64
+#define CCSD_MOL_MAX_LABELS 16
+typedef struct {
+    int32_t B, N;              /* molecules, atom slots per molecule */
+    int32_t L;                 /* labels: rows of max_valence / charge_base */
+    int32_t largest_fragment;  /* 0: keep every fragment (gen_mol's largest_connected_comp=False) */
+} ccsd_mol_dims_t;
+typedef struct {
+    uint8_t* mol_adj;
+    int32_t* mol_labels;
+    int8_t* mol_charge;
+    uint8_t* no_correct;
+    int32_t* n_corrections;
+    int32_t* n_fragments;
+    int32_t* atoms;
+} ccsd_mol_out_t;
+int ccsd_mol_correct(const ccsd_mol_dims_t* dims, const float* adj_dev, const int32_t* labels_dev, const int32_t* max_valence,
+                     const int32_t* charge_base, const ccsd_mol_out_t* out, void* stream);
 
 /* Measurement hooks (bench.py): time every launch of selected kernels with HIP events on the launch stream.
  * kernel_id: 0 k_xa, 1 k_gemm_p, 2 k_hf_score, 3 k_gemm_h, 4 k_langevin_apply, 5 k_r2, 6 k_s4_apply, 7 k_ew1; each call adds one kernel to the
